@@ -3,8 +3,8 @@
 
 Default workload = config C3 of SURVEY.md 8(d) / BASELINE.json configs[2]: GRCh37-scale synthetic multi-genome (3.1 G forward
 characters -> 6.85 G BWT rows, 64-bit positions, 13.7 GB device index for the alignment kernels), 10 M x 100 bp reads per GPU, `align -n 3`.  Genome,
-index (the product's own host indexer) and reads are built inside the run and cached under --workdir (about 4 minutes on the
-GPU box's 256 cores the first time).
+index (the product's own host indexer) and reads are built once and cached under --workdir (about 4 minutes the first time); on
+a machine with a GPU, build() prepares the default run's inputs there, so that a benchmark run does not pay for them.
 
 One "step" = one pass of the hot path (kl_calc_d + one slice of kl_search, include/bwbble_hip.h) over one batch of
 `--reads` reads that is resident in HBM before the timed region starts: the read pool is cut into batches, each uploaded into
@@ -16,7 +16,11 @@ contiguous shards (rank r owns reads [r*pool, (r+1)*pool), stored as its own fil
 `--gpus N` without a launcher starts the N ranks itself (a child `python -m torch.distributed.run`, before anything touches
 the GPU).  See DESIGN.md "Measurement".
 
-  python bench.py [--gpus N --steps K --warmup W] [--genome-mb 3100 --pool 10000000 --reads 2500000 --ndiff 3]
+A plain run times the steps and prints the line.  --full adds everything else the benchmark measures and checks: the CPU baseline
+(the real reference, with its parity), end to end through the library and through the CLI, the rank micro-kernel, `-n 0`, and with
+--gpus N the cross-shard parity sample.  --dump-outputs DIR writes what the last timed step returned (see dump_outputs).
+
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR] [--genome-mb 3100 --pool 10000000 --reads 2500000 --ndiff 3]
 """
 import argparse
 import json
@@ -42,7 +46,24 @@ def rec_bytes_written(read_len):
 DEV_BYTES_PER_BUCKET = 128  # what the device layout fetches per rank visit (bwb_device.h)
 
 
-def parse_args():
+def default_workdir():
+    """where the generated workload is cached: BWB_BENCH_DIR, else the user's cache directory (build() fills it on a machine with a GPU)"""
+    return os.environ.get("BWB_BENCH_DIR") or os.path.join(os.path.expanduser("~"), ".cache", "bwbble_amd", "bench")
+
+
+def usable_cpus():
+    """CPUs this process can use: its affinity mask, bounded by a cgroup CPU quota (os.cpu_count() counts the whole machine)"""
+    n = len(os.sched_getaffinity(0))
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    return n
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -57,9 +78,14 @@ def parse_args():
     ap.add_argument("--ndiff", type=int, default=None, help="-n (the reference default is 0; reported next to it)")
     ap.add_argument("--read-len", type=int, default=None)
     ap.add_argument("--cpu-sample", type=int, default=int(os.environ.get("BWB_BENCH_CPU_SAMPLE", 0)), help="reads in the CPU baseline sample (0 = auto)")
-    ap.add_argument("--workdir", default=os.environ.get("BWB_BENCH_DIR", "/tmp/bwb_bench"))
-    ap.add_argument("--no-extras", action="store_true", help="skip cpu_baseline, also.n0, end_to_end and rank_micro (profiling runs)")
-    a = ap.parse_args()
+    ap.add_argument("--workdir", default=default_workdir(), help="cache of the generated genome, index and reads (BWB_BENCH_DIR)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure cpu_baseline, end_to_end, rank_micro, also.n0 and cli_end_to_end, and with --gpus N "
+                         "check a sample of every shard on a neighbouring GPU (a plain run only times the steps)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip cpu_baseline, also.n0, end_to_end, rank_micro and cli_end_to_end")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float32 / float64; rank 0's batch)")
+    a = ap.parse_args(argv)
     cfg = {"C2": dict(genome_mb=48.0, pool=4000000, reads=1000000, ndiff=3, read_len=100, indel="0.1", extra=[]),
            "C3": dict(genome_mb=3100.0, pool=10000000, reads=2500000, ndiff=3, read_len=100, indel="0.1", extra=[]),
            "C5": dict(genome_mb=3100.0, pool=8000000, reads=2000000, ndiff=5, read_len=150, indel="0.2",
@@ -99,9 +125,128 @@ T_PROCESS_START = time.time()
 
 
 def over_budget(need_s):
-    """the extras after the timed region are optional evidence: one that would take the run past BWB_BENCH_BUDGET_S (default 900 s from process start)
-    is skipped and says so"""
-    return time.time() - T_PROCESS_START + need_s > float(os.environ.get("BWB_BENCH_BUDGET_S", 900))
+    """the extras of --full after the timed region are optional evidence: one that would take the run past BWB_BENCH_BUDGET_S (default 540 s from
+    process start, so that a --full run ends within ten minutes) is skipped and says so"""
+    return time.time() - T_PROCESS_START + need_s > float(os.environ.get("BWB_BENCH_BUDGET_S", 540))
+
+
+def genome_path(a):
+    return os.path.join(a.workdir, f"genome_{int(a.genome_mb * 1e6)}.fa")
+
+
+def shard_path(a, r):
+    """shard r of the logical FASTQ"""
+    return os.path.join(a.workdir, f"reads_{int(a.genome_mb * 1e6)}_{a.pool}_{a.read_len}_i{a.indel_pct}_r{r}.fq")
+
+
+def build_genome(a, bw):
+    """the synthetic genome and its index (the product's own indexer), once per work directory"""
+    fa = genome_path(a)
+    ok = fa + ".bwt.ok"
+    if os.path.exists(ok):
+        return fa
+    n_fwd = int(a.genome_mb * 1e6)
+    os.makedirs(a.workdir, exist_ok=True)
+    n_rec = 1 if n_fwd <= 60_000_000 else 24
+    subprocess.run([bw.SYNTH_BIN, "genome", fa, str(n_fwd), str(n_rec), str(max(4, n_fwd // 2400)), "21"], check=True)
+    import resource
+    t_ix = time.time()
+    subprocess.run([bw.HOST_BIN, "index", fa], check=True, stdout=subprocess.DEVNULL)  # f3 (SURVEY 8f): the product's own index builder (host/index.c)
+    json.dump({"index_s": round(time.time() - t_ix, 1), "peak_rss_GB": round(resource.getrusage(resource.RUSAGE_CHILDREN).ru_maxrss / 1e6, 1),
+               "bwt_bytes": os.path.getsize(fa + ".bwt"), "cores": usable_cpus()}, open(fa + ".index_stats.json", "w"))
+    if os.path.exists(fa + ".ref"):
+        os.remove(fa + ".ref")  # 2 bytes per forward character that nothing here reads
+    open(ok, "w").write("ok\n")
+    return fa
+
+
+def build_shard(a, bw, r):
+    fq = shard_path(a, r)
+    if not os.path.exists(fq + ".ok"):
+        subprocess.run([bw.SYNTH_BIN, "reads", genome_path(a), fq, str(a.pool), str(a.read_len), str(1000 + r), "1.0", a.indel_pct, "0.0"], check=True)
+        open(fq + ".ok", "w").write("ok\n")
+    return fq
+
+
+def load_shard(fq, bw):
+    """the shard's reads as (codes, lengths): the FASTQ is parsed once (bw.load_fastq_codes) and its arrays kept next to it as .npy"""
+    import numpy as np
+    names = (fq + ".codes.npy", fq + ".lens.npy")
+    if os.path.exists(fq + ".npy.ok"):
+        return tuple(np.load(n) for n in names)
+    seqs, lens = bw.load_fastq_codes(fq)
+    for arr, name in zip((seqs, lens), names):
+        with open(name + ".tmp", "wb") as f:
+            np.save(f, arr)
+        os.replace(name + ".tmp", name)
+    open(fq + ".npy.ok", "w").write("ok\n")
+    return seqs, lens
+
+
+def mem_available_gb():
+    for ln in open("/proc/meminfo"):
+        if ln.startswith("MemAvailable:"):
+            return int(ln.split()[1]) / 1e6
+    return 0.0
+
+
+def prepare_default_workload():
+    """Called by build(): on a machine that can run the benchmark (a GPU, and the ~120 GB of host memory the indexer needs at GRCh37 scale) the
+    default run's genome, index and read shard are built into the work directory now, so that a benchmark run measures the benchmark and not
+    a one-off build of its inputs.  BWB_BENCH_PREPARE=0 skips this, =1 prepares on any machine."""
+    import bwbble_amd as bw
+    a = parse_args([])
+    want = os.environ.get("BWB_BENCH_PREPARE", "")
+    if want == "0":
+        return None
+    if want != "1":
+        if not os.path.exists("/dev/kfd"):
+            print("bench.py: no GPU on this machine, the benchmark's workload is not prepared")
+            return None
+        if mem_available_gb() < 120 * a.genome_mb / 3100:
+            print(f"bench.py: {mem_available_gb():.0f} GB of host memory available, the benchmark's workload is not prepared")
+            return None
+    a.pool = max(a.pool, a.reads)
+    t0 = time.time()
+    build_genome(a, bw)
+    load_shard(build_shard(a, bw, 0), bw)
+    print(f"bench.py: workload of the default run ready in {a.workdir} ({time.time() - t0:.0f} s)")
+    return a.workdir
+
+
+DUMP_SEED = 20251016
+DUMP_N_HITS_READS = 1 << 22  # per-read hit counts of a larger batch: a seeded sample of half as many reads
+DUMP_SAMPLE_READS = 50000    # reads whose hit records are written ...
+DUMP_MAX_HITS = 200000       # ... at most this many records (the sample's first reads in batch order that fit)
+
+
+def dump_outputs(d, off, alns):
+    """--dump-outputs: what the caller of the timed path receives for the batch of the last timed step (its slot_result: hit offsets + records),
+    as float .npy files, at most ~52 MB whatever the batch size:
+      n_hits.npy        float32, hits of every read of the batch (more than 4 M reads: of a seeded sample, listed in n_hits_reads.npy, float64)
+      hits.npy          float64, one row per hit of a seeded sample of reads: read index in the batch, L, U, score, num_mm, num_gapo,
+                        num_gape, aln_length, gap_run[0..7] (L and U stay exact: below 2^53)"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    n = len(off) - 1
+    off = off.astype(np.int64)
+    cnt_all = off[1:] - off[:-1]
+    if n <= DUMP_N_HITS_READS:
+        np.save(os.path.join(d, "n_hits.npy"), cnt_all.astype(np.float32))
+    else:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_N_HITS_READS // 2, replace=False))
+        np.save(os.path.join(d, "n_hits.npy"), cnt_all[pick].astype(np.float32))
+        np.save(os.path.join(d, "n_hits_reads.npy"), pick.astype(np.float64))
+    reads = np.sort(np.random.default_rng(DUMP_SEED + 1).choice(n, size=min(n, DUMP_SAMPLE_READS), replace=False))
+    cnt = cnt_all[reads]
+    keep = np.cumsum(cnt) <= DUMP_MAX_HITS
+    reads, cnt = reads[keep], cnt[keep]
+    first = np.cumsum(cnt) - cnt  # where each read's records start in the output
+    idx = np.repeat(off[reads], cnt) + np.arange(int(cnt.sum())) - np.repeat(first, cnt)
+    rec = alns[idx]
+    cols = [np.repeat(reads, cnt)] + [rec[f] for f in ("L", "U", "score", "num_mm", "num_gapo", "num_gape", "aln_length")]
+    cols += [rec["gap_run"][:, k] for k in range(8)]
+    np.save(os.path.join(d, "hits.npy"), np.stack([c.astype(np.float64) for c in cols], axis=1).reshape(len(idx), 16))
 
 
 def main():
@@ -116,31 +261,16 @@ def main():
 
     # ---- workload: synthetic genome + index (built once, by rank 0, with the product's own indexer) ----------
     n_fwd = int(a.genome_mb * 1e6)
-    os.makedirs(a.workdir, exist_ok=True)
-    fa = os.path.join(a.workdir, f"genome_{n_fwd}.fa")
-    ok = fa + ".bwt.ok"
+    fa = genome_path(a)
     t_build = time.time()
     if rank == 0:
         bw.build()
-        if not os.path.exists(ok):
-            n_rec = 1 if n_fwd <= 60_000_000 else 24
-            subprocess.run([bw.SYNTH_BIN, "genome", fa, str(n_fwd), str(n_rec), str(max(4, n_fwd // 2400)), "21"], check=True)
-            import resource
-            t_ix = time.time()
-            subprocess.run([bw.HOST_BIN, "index", fa], check=True, stdout=subprocess.DEVNULL)  # f3: the product's own index builder (host/index.c)
-            json.dump({"index_s": round(time.time() - t_ix, 1), "peak_rss_GB": round(resource.getrusage(resource.RUSAGE_CHILDREN).ru_maxrss / 1e6, 1),
-                       "bwt_bytes": os.path.getsize(fa + ".bwt"), "cores": os.cpu_count()}, open(fa + ".index_stats.json", "w"))
-            if os.path.exists(fa + ".ref"):
-                os.remove(fa + ".ref")  # 2 bytes per forward character that nothing here reads
-            open(ok, "w").write("ok\n")
+        build_genome(a, bw)
     else:
-        wait_for(ok, "rank 0 to build the index")
+        wait_for(fa + ".bwt.ok", "rank 0 to build the index")
     a.pool = max(a.pool, a.reads)
-    shard = lambda r: os.path.join(a.workdir, f"reads_{n_fwd}_{a.pool}_{a.read_len}_i{a.indel_pct}_r{r}.fq")
-    fq = shard(rank)  # shard `rank` of the logical FASTQ
-    if not os.path.exists(fq + ".ok"):
-        subprocess.run([bw.SYNTH_BIN, "reads", fa, fq, str(a.pool), str(a.read_len), str(1000 + rank), "1.0", a.indel_pct, "0.0"], check=True)
-        open(fq + ".ok", "w").write("ok\n")
+    shard = lambda r: shard_path(a, r)
+    fq = build_shard(a, bw, rank)  # shard `rank` of the logical FASTQ
     t_build = time.time() - t_build
 
     import torch  # plumbing only (device census, barrier, max-over-ranks)
@@ -155,7 +285,7 @@ def main():
     for r in range(world):  # every shard exists before anybody needs a neighbour's
         wait_for(shard(r) + ".ok", f"rank {r}'s FASTQ shard")
 
-    seqs, lens = bw.load_fastq_codes(fq)
+    seqs, lens = load_shard(fq, bw)
     flags = ["-n", str(a.ndiff)] + a.extra_flags
     p = bw.params(flags)
     bwt = bw.BwtFile(fa + ".bwt")
@@ -186,6 +316,7 @@ def main():
     ctx.reset_stats()
     barrier()
     torch.cuda.synchronize() if torch.cuda.is_available() else None
+    t_to_timed = time.time() - T_PROCESS_START
     t0 = time.perf_counter()
     run_steps(a.steps)  # ends with a flush: the library's streams are idle when it returns
     torch.cuda.synchronize() if torch.cuda.is_available() else None
@@ -200,10 +331,13 @@ def main():
     rank_rates = [v[0] for v in gathered]  # every rank's own reads/s (its own clock between the barriers)
     rank_ctx_ms = [v[1] for v in gathered]  # every rank's .bwt -> HBM time (the ranks map one file: its pages are shared)
     off0, alns0 = ctx.slot_result(0)  # hits of batch 0 = the first B reads of this shard
+    if a.dump_outputs and rank == 0:
+        last = (a.steps - 1) % ns  # the slot the last timed step ran
+        dump_outputs(a.dump_outputs, *((off0, alns0) if last == 0 else ctx.slot_result(last)))
 
-    # every rank re-aligns a sample of its right neighbour's shard: the bytes must not depend on which GPU did the work
+    # --full: every rank re-aligns a sample of its right neighbour's shard: the bytes must not depend on which GPU did the work
     shard_check = None
-    if world > 1:
+    if world > 1 and a.full:
         nbr = (rank + 1) % world
         n_chk = min(2000, B)  # (its own name: `ns` is the number of resident slots and goes into the line)
         nseqs, nlens = bw.load_fastq_codes(shard(nbr), max_reads=n_chk)
@@ -273,7 +407,7 @@ def main():
                                   "(bit-identical records; DESIGN.md 3.4): `visits` stay the reference's count, the buckets of those steps are not fetched - kl_calc_d's device bytes and "
                                   "`device_frac` count what it really moves; built once per context, outside the timed region"),
         "hits_batch0": int(off0[-1]), "rerun_reads": int(st.n_overflow_reads), "kernel_ms_of_step_ms": round(kern_ms / (dt * 1e3), 4),
-        "setup_s": {"genome_index_reads": round(t_build, 1), "index_to_hbm": round(t_ctx, 1),
+        "setup_s": {"genome_index_reads": round(t_build, 1), "index_to_hbm": round(t_ctx, 1), "process_start_to_timed_steps": round(t_to_timed, 1),
                     "index": (json.load(open(fa + ".index_stats.json")) if os.path.exists(fa + ".index_stats.json") else None)},
     }
     if shard_check is not None:
@@ -285,14 +419,17 @@ def main():
         if n1:
             out["efficiency_vs_stored_n1"] = {"value": round(value / world / n1["value"], 4), "n1_reads_per_s": n1["value"], "n1_source": n1["source"],
                                               "note": "informational: this run's reads/s per GPU over a stored 1-GPU line of the same workload (the driver computes the official curve)"}
-    if world == 1 and not a.no_extras:
-        out["cpu_baseline"] = cpu_baseline(a, fa, fq, flags, off0, alns0, bw)
-        out["end_to_end"] = end_to_end(ctx, p, batch, ns, B, value)
-        out["rank_micro"] = rank_micro(ctx, index_mb)
+    if world == 1 and a.full and not a.no_extras:
+        skipped = {"skipped": "time budget (BWB_BENCH_BUDGET_S)"}
+        step_s = dt / a.steps
+        out["cpu_baseline"] = cpu_baseline(a, fa, fq, flags, off0, alns0, bw) if not over_budget(120) else skipped
+        out["end_to_end"] = end_to_end(ctx, p, batch, ns, B, value) if not over_budget(1.2 * (ns + 2) * step_s + 5) else skipped
+        out["rank_micro"] = rank_micro(ctx, index_mb) if not over_budget(15) else skipped
         if a.ndiff != 0:
-            out["also"] = {"n0": also_n0(ctx, bw, batch, nb, B)}
+            out["also"] = {"n0": also_n0(ctx, bw, batch, nb, B) if not over_budget(20) else skipped}
         ctx.flush()
-        out["cli_end_to_end"] = cli_end_to_end(a, fa, fq, flags, value, ctx, bw)  # (last: it closes this process's context)
+        # (last: it closes this process's context)
+        out["cli_end_to_end"] = cli_end_to_end(a, fa, fq, flags, value, ctx, bw) if not over_budget(10 + 1.5 * a.pool / value) else skipped
     print(json.dumps(out))
     grp.close()
 
@@ -440,7 +577,7 @@ def cli_end_to_end(a, fa, fq, flags, value, ctx, bw):
         hb = subprocess.run([bw.HOST_BIN, "hostbench", fq, kept], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, check=True)
         hj = json.loads(hb.stdout.strip().splitlines()[-1])
         res["host_pipeline"] = {"parse_reads_per_s": hj["parse_reads_per_s"], "write_records_per_s": hj.get("write_records_per_s"), "reads": hj["parse_reads"],
-                                "parse_stages_s": hj.get("parse_stages_s"), "cores": os.cpu_count(), "openmp_team": "at most 32 threads per region (bwb_host.h)", "what": "FASTQ record scan (parallel, verified against the sequential scan) + base encoding; .aln record serialisation of the run above"}
+                                "parse_stages_s": hj.get("parse_stages_s"), "cores": usable_cpus(), "openmp_team": "at most 32 threads per region (bwb_host.h)", "what": "FASTQ record scan (parallel, verified against the sequential scan) + base encoding; .aln record serialisation of the run above"}
     except Exception as e:  # noqa: BLE001
         res["host_pipeline"] = {"error": str(e)[-200:]}
     # f1: `bwbble aln2sam` on the same records - SA(L) of every mapped read by the invPsi walk on the GPU (k_locate: up to 31
@@ -552,7 +689,7 @@ def cpu_baseline(a, fa, fq, flags, off, alns, bw):
     So: a sweep of -t over {cores/4, cores/2, cores} at 64 reads per thread, then the best -t again at >= 200 reads per
     thread; the load (index + FASTQ) is timed with a 1-read FASTQ at the same -t and subtracted.  value = the best rate."""
     import oracle_lib
-    cores = os.cpu_count() or 1
+    cores = usable_cpus()
     ref_bin = os.path.join(ROOT, "oracle", "_ref", "bwbble")
     res = {"cores": cores, "unit": "reads/s"}
     def head_fastq(n_reads, path):

@@ -97,3 +97,45 @@ def test_pmc_summary_prices_every_dispatch_on_its_own(tmp_path):
     assert [q["hbm_bytes"] for q in pl["launches"]] == want
     assert pl["slice"]["hbm_bytes_per_launch"] == (want[0] + want[1]) / 2 and pl["drain"]["hbm_bytes_per_launch"] == want[2]
     assert pl["launches"][0]["device_bytes"] == 1000 * 128 + 30 * 16 + 30 * 16
+
+
+def test_a_plain_run_only_times_the_steps(monkeypatch):
+    """the extras (cpu_baseline, end_to_end, rank_micro, also.n0, cli_end_to_end, the cross-shard sample) run only with --full"""
+    a = parse([], monkeypatch)
+    assert not a.full and not a.no_extras and a.dump_outputs is None
+    a = parse(["--full", "--dump-outputs", "out", "--steps", "7"], monkeypatch)
+    assert a.full and a.dump_outputs == "out" and a.steps == 7
+
+
+def test_dumped_outputs_are_float_bounded_and_repeatable(tmp_path):
+    """--dump-outputs: per-read hit counts and a seeded sample of hit records, float32 / float64, at most 64 MB whatever the batch size,
+    the same files for the same result"""
+    import numpy as np
+    import bench
+    import bwbble_amd as bw
+    rng = np.random.default_rng(1)
+    for n in (5, 300_000, 5_000_000):
+        cnt = rng.poisson(1.2, n)
+        off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.uint64)
+        alns = np.zeros(int(off[-1]), dtype=bw.ALN_DTYPE)
+        alns["L"] = rng.integers(0, 6_850_000_000, len(alns))
+        alns["U"] = alns["L"] + rng.integers(0, 5, len(alns))
+        alns["score"] = rng.integers(0, 40, len(alns))
+        alns["gap_run"] = 0xFFFF
+        d1, d2 = tmp_path / f"a{n}", tmp_path / f"b{n}"
+        bench.dump_outputs(str(d1), off, alns)
+        bench.dump_outputs(str(d2), off, alns)
+        names = sorted(os.listdir(d1))
+        assert names == sorted(os.listdir(d2)) and "hits.npy" in names and "n_hits.npy" in names
+        assert sum(os.path.getsize(d1 / f) for f in names) <= 64 << 20
+        for f in names:
+            x = np.load(d1 / f)
+            assert x.dtype in (np.float32, np.float64) and np.array_equal(x, np.load(d2 / f))
+        hits = np.load(d1 / "hits.npy")
+        assert hits.shape[1] == 16 and len(hits) > 0
+        if n <= bench.DUMP_N_HITS_READS:
+            assert np.array_equal(np.load(d1 / "n_hits.npy"), cnt.astype(np.float32))
+        for r in np.unique(hits[:, 0].astype(np.int64))[:50]:  # every sampled read's records, whole and in order
+            lo, hi = int(off[r]), int(off[r + 1])
+            rows = hits[hits[:, 0] == r]
+            assert np.array_equal(rows[:, 1], alns["L"][lo:hi].astype(np.float64)) and np.array_equal(rows[:, 2], alns["U"][lo:hi].astype(np.float64))

@@ -14,12 +14,13 @@ import time
 import numpy as np
 import pytest
 
+import bench
 import bwbble_amd as bw
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_FWD = int(os.environ.get("BWB_TEST_GRCH37_FWD", 3_100_000_000))
-WORK = os.environ.get("BWB_BENCH_DIR", "/tmp/bwb_bench")
+WORK = bench.default_workdir()
 BUILD_BUDGET_S = int(os.environ.get("BWB_TEST_GRCH37_BUILD_BUDGET_S", 600))
 REF_BIN = os.path.join(ROOT, "oracle", "_ref", "bwbble")
 

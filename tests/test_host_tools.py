@@ -265,7 +265,7 @@ def test_bench_ranks_shard_one_fastq(built, tmp_path, ranks):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BWB_BENCH_SHARE_DEVICE="1", BWB_POOL_GB="2", BWB_BENCH_DIR=str(tmp_path), BWB_BLOCKS_PER_CU="1", BWB_CALCD_BLOCKS_PER_CU="1")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--genome-mb", "2", "--pool", "24000", "--reads", "6000",
-                        "--steps", "3", "--warmup", "1", "--no-extras"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1200)
+                        "--steps", "3", "--warmup", "1", "--full", "--no-extras"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1])
     assert line["shard_sample_parity"] is True and line["config"]["reads_per_gpu_per_step"] == 6000 and line["value"] > 0

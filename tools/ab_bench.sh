@@ -1,6 +1,6 @@
 #!/bin/bash
 # Developer tool: A/B of library builds on one workload in ONE GPU session (the genome, index and reads are built once and
-# cached in /tmp/bwb_bench).  Replaces the one-shot tools/r2_probe*.sh of round 2: every profiles/r3_* A/B table names the
+# cached in bench.py's work directory).  Replaces the one-shot tools/r2_probe*.sh of round 2: every profiles/r3_* A/B table names the
 # command line of this script that produced it.
 #
 #   tools/ab_bench.sh <out-dir-name> "<bench.py args>" <variant> [<variant> ...]

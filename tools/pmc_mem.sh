@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; export GRAFT_REPO_ROOT=$R
 [ -f "$R/bench.py" ] || { echo "pmc_mem.sh: $R/bench.py not found"; exit 2; }
 MB=${1:-48}; POOL=${2:-4000000}; READS=${3:-1000000}; ND=${4:-3}
-python3 $R/bench.py --genome-mb $MB --pool $POOL --reads $READS --ndiff $ND --steps 1 --warmup 0 --no-extras > /dev/null 2>&1   # leaves genome/index/reads in /tmp/bwb_bench
+python3 $R/bench.py --genome-mb $MB --pool $POOL --reads $READS --ndiff $ND --steps 1 --warmup 0 --no-extras > /dev/null 2>&1   # leaves genome/index/reads in bench.py's work directory
 python3 $R/tools/prof_bench.py $MB $POOL $READS $ND 3
 i=0
 ONLY=${PMC_SETS:-1 2 3 4 5 6 7 8}   # PMC_SETS="5 6 7": only those counter groups (the SQ ones)

@@ -20,7 +20,7 @@ cd /tmp && export TMPDIR=/tmp
 RD="TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_BUBBLE_sum TCC_EA0_RDREQ_DRAM_sum"
 make -s -C $R/bwbble_amd gather_bench > /dev/null 2>&1
 timeout 600 rocprofv3 --pmc $RD --output-format csv -d $OUT/calib -o run -- $R/bwbble_amd/tools_exp/gather_bench 7168 7168 meta > $OUT/calib.log 2>&1 || echo "calibration pass failed"
-timeout 1800 python3 $R/bench.py "$@" --steps 1 --warmup 0 --no-extras > /dev/null 2>&1   # builds genome/index/reads once (cached in /tmp/bwb_bench)
+timeout 1800 python3 $R/bench.py "$@" --steps 1 --warmup 0 --no-extras > /dev/null 2>&1   # builds genome/index/reads once (cached in bench.py's work directory)
 # (round 6) PMC_STEPS steps per pass (default 8: eight slices and the draining launch), and the library's own launch log next to the counters
 # (BWB_LAUNCH_LOG: buckets, heap entries and records of every launch), so that the summary prices every dispatch on its own and
 # bench.py can put a run's traffic together as (its slices) x (a slice's bytes) + (its draining launches) x (a drain's bytes)

@@ -5,7 +5,8 @@ import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bwbble_amd as bw
-work = os.environ.get("BWB_BENCH_DIR", "/tmp/bwb_bench")
+from bench import default_workdir
+work = default_workdir()
 n_fwd, pool, B, nd = int(float(sys.argv[1]) * 1e6), int(sys.argv[2]), int(sys.argv[3]), sys.argv[4]
 steps = int(sys.argv[5]) if len(sys.argv) > 5 else 3
 fa, fq = f"{work}/genome_{n_fwd}.fa", f"{work}/reads_{n_fwd}_{pool}_100_i0.1_r0.fq"

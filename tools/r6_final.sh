@@ -17,7 +17,7 @@ if [ $PRC -ne 0 ]; then tail -40 $O/pytest.log; echo "GPU tests failed: no evide
 python3 -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee $O/smoke.txt
 cd /tmp && export TMPDIR=/tmp
 bash $R/tools/pmc_traffic.sh r6_c3 > $O/pmc_c3.log 2>&1; tail -4 $O/pmc_c3.log; cp $R/gpurun_out/r6_c3_pmc.json $R/profiles/r6_c3_pmc.json 2>/dev/null   # (so that the bench line below can quote it)
-( export BWB_BENCH_BUDGET_S=5000; time timeout 3000 python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 ) > $O/bench_driver_args.log 2> $O/bench_driver_args.err
+( export BWB_BENCH_BUDGET_S=5000; time timeout 3000 python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full ) > $O/bench_driver_args.log 2> $O/bench_driver_args.err
 grep '^{"metric"' $O/bench_driver_args.log > $O/r6_bench_line_driver_args.json; tail -3 $O/bench_driver_args.err | cut -c1-200
 python3 $R/tools/ab_show.py c3_driver_args < $O/r6_bench_line_driver_args.json
 ( time timeout 900 python3 $R/tools/cli_check.py /tmp/bwb_bench/genome_3100000000.fa /tmp/bwb_bench/reads_3100000000_10000000_100_i0.1_r0.fq 5000 -n 3 ) > $O/r6_cli_c3.txt 2>&1; tail -7 $O/r6_cli_c3.txt

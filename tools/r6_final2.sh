@@ -11,7 +11,7 @@ if [ $PRC -ne 0 ]; then tail -40 $O/pytest.log; exit 1; fi
 python3 -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee $O/smoke.txt
 cd /tmp && export TMPDIR=/tmp
 bash $R/tools/pmc_traffic.sh r6_c3 > $O/pmc_c3.log 2>&1; tail -3 $O/pmc_c3.log; cp $R/gpurun_out/r6_c3_pmc.json $R/profiles/r6_c3_pmc.json 2>/dev/null
-( export BWB_BENCH_BUDGET_S=5000; time timeout 3000 python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 ) > $O/bench_driver_args.log 2> $O/bench_driver_args.err
+( export BWB_BENCH_BUDGET_S=5000; time timeout 3000 python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full ) > $O/bench_driver_args.log 2> $O/bench_driver_args.err
 grep '^{"metric"' $O/bench_driver_args.log > $O/r6_bench_line_driver_args.json; python3 $R/tools/ab_show.py c3_driver_args < $O/r6_bench_line_driver_args.json
 timeout 1500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python3 $R/bench.py --steps 3 --warmup 1 --no-extras > $O/r6_bench_line_under_rocprof.json 2> $O/trace.log
 cp $O/trace/run_kernel_stats.csv $O/r6_c3_kernel_stats.csv 2>/dev/null || cp $O/trace/*/run_kernel_stats.csv $O/r6_c3_kernel_stats.csv; head -3 $O/r6_c3_kernel_stats.csv | cut -c1-200
