@@ -22,6 +22,7 @@ EXPORTS = [
     "bwb_hip_calc_d", "bwb_hip_rank16", "bwb_hip_rank_bench", "bwb_hip_rank_bench_lane", "bwb_hip_set_sa", "bwb_hip_locate", "bwb_hip_locate_stats",
     "bwb_hip_reset_stats", "bwb_hip_slot_upload", "bwb_hip_slot_submit", "bwb_hip_slot_wait", "bwb_hip_slot_result", "bwb_hip_flush", "bwb_hip_abi_version", "bwb_hip_ctx_create_streamed", "bwb_hip_device_numa_node",
     "bwb_hip_ctx_create_async", "bwb_hip_ctx_index_wait", "bwb_hip_setup_times", "bwb_hip_dtab_info",
+    "bwb_hip_slot_place", "bwb_hip_batch_place", "bwb_hip_place_stats",
 ]
 ABI_VERSION = 3  # BWB_HIP_ABI_VERSION (include/bwbble_hip.h)
 MAX_SLOTS = 8  # BWB_MAX_SLOTS
@@ -51,6 +52,12 @@ class Stats(C.Structure):
 ALN_DTYPE = np.dtype([("L", "<u8"), ("U", "<u8"), ("score", "<u2"), ("num_mm", "u1"), ("num_gapo", "u1"),
                       ("num_gape", "u1"), ("reserved", "u1"), ("aln_length", "<u2"), ("gap_run", "<u2", (8,)), ("reserved2", "<u8")])
 assert ALN_DTYPE.itemsize == 48
+# bwb_place: what eval_aln + mapq make of one read's hits (kernel k_place); flags bit 0 = mapped, bit 1 = reverse strand
+PLACE_DTYPE = np.dtype([("pos", "<u8"), ("top1", "<i4"), ("top2", "<i4"), ("score", "<u2"), ("mapq", "u1"), ("flags", "u1"),
+                        ("num_mm", "u1"), ("num_gapo", "u1"), ("num_gape", "u1"), ("reserved", "u1"), ("aln_length", "<u2"),
+                        ("ref_len", "<u2"), ("reserved2", "<u4"), ("gap_run", "<u2", (8,))])
+assert PLACE_DTYPE.itemsize == 48
+PLACE_MAPPED, PLACE_REVERSE = 1, 2
 
 _FLAG = {"-M": "mm_score", "-O": "gapo_score", "-E": "gape_score", "-n": "max_diff", "-k": "max_diff_seed",
          "-o": "max_gapo", "-e": "max_gape", "-l": "seed_length", "-m": "max_entries", "-t": "n_threads"}
@@ -98,6 +105,9 @@ def lib():
         L.bwb_hip_dtab_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
         L.bwb_hip_setup_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
         L.bwb_hip_locate_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.bwb_hip_slot_place.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
+        L.bwb_hip_batch_place.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
+        L.bwb_hip_place_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -266,6 +276,29 @@ class Context:
         out = np.zeros(len(rows), dtype=np.uint64)
         _chk(lib().bwb_hip_locate(self._h, rows.ctypes.data, len(rows), out.ctypes.data))
         return out
+
+    # -- placement records: eval_aln + mapq on the GPU (needs set_sa) ----------------------------------------------
+    @staticmethod
+    def _places(ptr, n):
+        return np.frombuffer(C.string_at(ptr, n * PLACE_DTYPE.itemsize), dtype=PLACE_DTYPE).copy() if n else np.zeros(0, dtype=PLACE_DTYPE)
+
+    def slot_place(self, slot, max_mm=6):
+        """one PLACE_DTYPE record per read of the slot, in read order (max_mm: mapq's, aln2sam's -n)"""
+        ptr, n = C.c_void_p(), C.c_uint32()
+        _chk(lib().bwb_hip_slot_place(self._h, slot, max_mm, C.byref(ptr), C.byref(n)))
+        return self._places(ptr, n.value)
+
+    def place(self, max_mm=6):
+        """the same for the one-batch interface (after run() / align())"""
+        ptr, n = C.c_void_p(), C.c_uint32()
+        _chk(lib().bwb_hip_batch_place(self._h, max_mm, C.byref(ptr), C.byref(n)))
+        return self._places(ptr, n.value)
+
+    def place_stats(self):
+        """(reads, invPsi steps = rank-block visits, kernel ms) of the last place call"""
+        n, st, ms = C.c_uint64(), C.c_uint64(), C.c_double()
+        _chk(lib().bwb_hip_place_stats(self._h, C.byref(n), C.byref(st), C.byref(ms)))
+        return n.value, st.value, ms.value
 
     def dtab_info(self):
         """the context's calculate_d table: {K (0: none), build seconds, bytes}"""

@@ -21,6 +21,7 @@
 #include <time.h>
 #include <algorithm>
 #include <cctype>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -104,6 +105,9 @@ struct Slot {
 	std::vector<uint32_t> h_src;
 	uint64_t log_cap = 0;
 	PinMem h_reads, h_lens, h_cnt, h_off, h_log, h_ctl;
+	DevMem d_place;               /* bwb_hip_slot_place: one bwb_place per read */
+	PinMem h_place;
+	int placed_mm = -1;           /* h_place holds the records for this max_mm (-1: none) */
 	std::vector<uint8_t> h_status;
 	std::vector<uint64_t> h_aln_off;
 	std::vector<bwb_aln> h_alns;
@@ -147,6 +151,8 @@ struct bwb_hip_ctx {
 	std::vector<hipEvent_t> free_events;
 	uint32_t slice_iters = 0;           /* BWB_SLICE_ITERS: test knob, time-sliced launches */
 	double locate_ms = 0; uint64_t locate_steps = 0, locate_rows = 0; /* the last bwb_hip_locate call */
+	DevMem d_qtab;                      /* k_place: 256 bytes (int)(4.343 * log(n) + 0.5), then its step counter */
+	double place_ms = 0; uint64_t place_steps = 0, place_reads = 0;   /* the last place call */
 	bool force_slices = false;          /* BWB_FORCE_SLICES: the one-batch API parks and resumes too (tests) */
 	bool dbg = false, dbg_iters = false;
 	const char *launch_log = nullptr;   /* BWB_LAUNCH_LOG=<file>: one JSON line per class-0 kernel launch (synchronises after every launch: a profiling aid) */
@@ -688,7 +694,7 @@ extern "C" int bwb_hip_slot_upload(bwb_hip_ctx *c, int si, const bwb_params *p, 
 	/* (pageable source: the runtime stages it before returning, so h_descs may change again right away) */
 	HIPCHK(hipMemcpyAsync(c->d_descs.as<SlotDesc>() + si, &d, sizeof(SlotDesc), hipMemcpyHostToDevice, c->cstream));
 	HIPCHK(hipEventRecord(s.ev_up.e, c->cstream));
-	s.uploaded = true; s.submitted = false; s.complete = false; s.fetched = false;
+	s.uploaded = true; s.submitted = false; s.complete = false; s.fetched = false; s.placed_mm = -1;
 	return ensure_class(c, 0);
 }
 
@@ -952,7 +958,7 @@ static int submit(bwb_hip_ctx *c, int si, bool suspend) {
 		HIPCHK(hipStreamWaitEvent(c->stream, s.ev_calcd.e, 0));
 	}
 	HIPCHK(hipMemsetAsync(s.d_ctl.p, 0, 256, c->stream));
-	s.submitted = true; s.complete = false; s.fetched = false; s.launch = 0;
+	s.submitted = true; s.complete = false; s.fetched = false; s.placed_mm = -1; s.launch = 0;
 	if (s.n_reads == 0) { s.complete = true; s.launch = c->n_launches; return BWB_OK; }
 	HIPCHK(hipMemsetAsync(s.d_n.p, 0, (size_t)s.n_reads * 4, c->stream));
 	if (!ahead) {
@@ -1411,9 +1417,12 @@ extern "C" int bwb_hip_rank_bench_lane(bwb_hip_ctx *c, size_t n, int iters, uint
 extern "C" int bwb_hip_set_sa(bwb_hip_ctx *c, const uint64_t *SA, uint64_t num_sa) {
 	if (!c || !SA || num_sa != (c->ix.length + 31) / 32) return fail(BWB_E_ARG, "set_sa: bad argument");
 	HIPCHK(hipSetDevice(c->device));
+	/* (on the result stream, which only the caller's thread uses: after ctx_create_async the context's upload thread is still queueing
+	 * the index on the kernel stream, and neither waits for the other.  `bwbble map` calls this before its first slot_upload, so that
+	 * the chunk pool is sized from what is free with the SA resident) */
 	HIPCHK(c->d_SA.alloc(num_sa * 8));
-	HIPCHK(hipMemcpyAsync(c->d_SA.p, SA, num_sa * 8, hipMemcpyHostToDevice, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
+	HIPCHK(hipMemcpyAsync(c->d_SA.p, SA, num_sa * 8, hipMemcpyHostToDevice, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream));
 	c->num_sa = num_sa;
 	return BWB_OK;
 }
@@ -1458,6 +1467,83 @@ extern "C" int bwb_hip_locate_stats(bwb_hip_ctx *c, uint64_t *rows, uint64_t *st
 	if (rows) *rows = c->locate_rows;
 	if (steps) *steps = c->locate_steps;
 	if (kernel_ms) *kernel_ms = c->locate_ms;
+	return BWB_OK;
+}
+
+/* ---- placement records: eval_aln + mapq on the GPU (k_place) ------------------------------------------------------ */
+static_assert(sizeof(bwb_place) == 48, "bwb_place is three 16-byte words (k_place)");
+extern "C" int bwb_hip_slot_place(bwb_hip_ctx *c, int si, int max_mm, const bwb_place **out, uint32_t *n_reads) {
+	if (!c || !out || !n_reads || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_place: bad argument");
+	HIPCHK(hipSetDevice(c->device));
+	Slot &s = c->slots[si];
+	if (!c->d_SA.p) return fail(BWB_E_STATE, "slot_place: sampled SA not uploaded (bwb_hip_set_sa)");
+	if (!s.submitted) return fail(BWB_E_STATE, "slot_place: the slot has not been submitted");
+	int rc = slot_wait(c, si);
+	if (rc) return rc;
+	const uint32_t n = s.n_reads;
+	if (s.placed_mm != max_mm || !n) {
+		if (!c->d_qtab.p) { /* the only floating point of mapq (align.c:744), with the host's own expression */
+			uint8_t tab[256 + 8] = { 0 };
+			for (int k = 1; k < 256; k++) tab[k] = (uint8_t)(int)(4.343 * log((double)k) + 0.5);
+			HIPCHK(c->d_qtab.alloc(sizeof(tab)));
+			HIPCHK(hipMemcpyAsync(c->d_qtab.p, tab, sizeof(tab), hipMemcpyHostToDevice, c->rstream));
+			HIPCHK(hipStreamSynchronize(c->rstream));
+		}
+		c->place_ms = 0; c->place_steps = 0; c->place_reads = n;
+		HIPCHK(s.h_place.reserve((size_t)n * sizeof(bwb_place)));
+		if (n) {
+			HIPCHK(s.d_place.reserve((size_t)n * sizeof(bwb_place)));
+			/* On the result stream: the kernel stream may hold slices of later slots, seconds each, and this call must not wait for them.
+			 * The slot's reads are done (slot_wait) and were published with a system-scope release; the host reads the same memory on
+			 * this stream in slot_result. */
+			hipEvent_t e0 = get_event(c), e1 = get_event(c);
+			struct EvGuard {
+				bwb_hip_ctx *c; hipEvent_t a, b;
+				~EvGuard() { if (a) c->free_events.push_back(a); if (b) c->free_events.push_back(b); }
+			} evg{ c, e0, e1 };
+			if (!e0 || !e1) return fail(BWB_E_HIP, "hipEventCreate failed");
+			unsigned long long *steps = (unsigned long long *)(c->d_qtab.as<unsigned char>() + 256);
+			HIPCHK(hipMemsetAsync(steps, 0, 8, c->rstream));
+			HIPCHK(hipMemcpyAsync(s.h_ctl.p, s.ctl_count(), 8, hipMemcpyDeviceToHost, c->rstream));
+			HIPCHK(hipStreamSynchronize(c->rstream));
+			const uint64_t log_n = std::min<unsigned long long>(*s.h_ctl.as<unsigned long long>(), s.log_cap);
+			const unsigned grid = (unsigned)std::min<size_t>(((size_t)n + BWB_OCTS_PER_BLOCK - 1) / BWB_OCTS_PER_BLOCK, (size_t)c->num_cu * 8);
+			HIPCHK(hipEventRecord(e0, c->rstream));
+			hipLaunchKernelGGL(k_place, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, c->ix, c->d_SA.as<uint64_t>(), c->sa0_index, s.d_log.as<uint4>(), log_n,
+			                   s.d_off.as<uint64_t>(), s.d_n.as<uint32_t>(), n, max_mm, c->d_qtab.as<uint8_t>(), s.d_place.as<uint4>(), steps);
+			HIPCHK(hipGetLastError());
+			HIPCHK(hipEventRecord(e1, c->rstream));
+			HIPCHK(hipMemcpyAsync(s.h_place.p, s.d_place.p, (size_t)n * sizeof(bwb_place), hipMemcpyDeviceToHost, c->rstream));
+			unsigned long long hsteps = 0;
+			HIPCHK(hipMemcpyAsync(&hsteps, steps, 8, hipMemcpyDeviceToHost, c->rstream));
+			HIPCHK(hipStreamSynchronize(c->rstream));
+			float ms = 0;
+			HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+			c->place_ms = ms; c->place_steps = hsteps;
+			const bwb_place *hp = s.h_place.as<bwb_place>();
+			for (uint32_t i = 0; i < n; i++)
+				if (hp[i].flags & PLACE_F_BAD) return fail(BWB_E_STATE, "slot_place: a read's hits lie outside the hit log or the index");
+		}
+		s.placed_mm = max_mm;
+	}
+	*out = s.h_place.as<bwb_place>();
+	*n_reads = n;
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_batch_place(bwb_hip_ctx *c, int max_mm, const bwb_place **out, uint32_t *n_reads) {
+	if (!c || !out || !n_reads) return fail(BWB_E_ARG, "batch_place: null argument");
+	if (!c->d_SA.p) return fail(BWB_E_STATE, "batch_place: sampled SA not uploaded (bwb_hip_set_sa)");
+	if (!c->slots[0].submitted || !c->slots[0].complete) return fail(BWB_E_STATE, "batch_place: batch_run has not completed");
+	return bwb_hip_slot_place(c, 0, max_mm, out, n_reads);
+}
+
+/* the last place call: reads, invPsi steps and the kernel's HIP-event time */
+extern "C" int bwb_hip_place_stats(bwb_hip_ctx *c, uint64_t *reads, uint64_t *steps, double *kernel_ms) {
+	if (!c) return fail(BWB_E_ARG, "place_stats: null context");
+	if (reads) *reads = c->place_reads;
+	if (steps) *steps = c->place_steps;
+	if (kernel_ms) *kernel_ms = c->place_ms;
 	return BWB_OK;
 }
 

@@ -6,6 +6,7 @@
  *   k_rank_bench random-position rank micro-benchmark (octet-cooperative rank)
  *   k_locate     SA[row] by the invPsi walk (aln2sam)
  *   k_gather     per-read hit lists -> read order
+ *   k_place      eval_aln + mapq for every read of a slot (`bwbble map`): one 48-byte placement record per read
  * The alignment kernels themselves (kl_calc_d, kl_search: one read per lane) are in bwb_lane.h.
  */
 #pragma once
@@ -279,32 +280,145 @@ __global__ void k_dseed_inherit(Batch b, const uint32_t *src, uint32_t n) {
 	for (int k = -2; k < lr; k++) rec_put(rr, rec_count((uint32_t)lr), 8, k, rec_get(rq, 8, k + lq - lr));
 }
 
-/* SA[row] by the invPsi walk (bwt.c:311-329): one octet per row */
+/* The invPsi walk from row i to the next sampled row (bwt.c:311-329, SA_INTERVAL = 32, bwt.h:16), by one octet: returns that row and adds
+ * the steps taken to j (each one rank-block visit, the step through the sentinel row included).  SA[i0] = (SA[row >> 5] + j) % length.
+ * Shared by k_locate and k_place. */
+__device__ __forceinline__ uint64_t sa_walk(const DevIndex &ix, const uint64_t *s_base, uint64_t sa0_index, uint64_t i, int lane, int ol, uint64_t &j) {
+	while ((i & 31) != 0) {
+		if (i == sa0_index) { i = 0; j++; continue; } /* invPsi bwt.c:312-314 */
+		RankReq<uint64_t> ra;
+		rank_issue<uint64_t>(ix.buckets, ix.length - 1, i, ol, ra);
+		/* B(i), bwt.c:337-345: bit (i&31) of the planes held by lane 4 + ((i&63)>>5) */
+		const uint4 cq = ra.regular ? ra.q : ix.buckets[(i >> BKT_SHIFT) * 8 + ol]; /* i == length-1 is not ranked via its bucket */
+		const int off = (int)(i & BKT_MASK), srcl = (lane & ~7) + 4 + (off >> 5), bit = off & 31;
+		const uint32_t code_here = ((cq.x >> bit) & 1u) | (((cq.y >> bit) & 1u) << 1) | (((cq.z >> bit) & 1u) << 2) | (((cq.w >> bit) & 1u) << 3);
+		const uint32_t code = oct_bcast(code_here, srcl);
+		uint64_t v0, v1;
+		rank_finish<uint64_t, false>(ra, s_base, ol, lane, v0, v1);
+		/* C[c] + O(c,i): held by lane c>>1.  The sentinel row is stored as code 0 but is not a '$' (bwt.c:364) */
+		const uint64_t mine = (code & 1u) ? v1 : v0;
+		uint64_t nxt = oct_bcast(mine, (lane & ~7) + (int)(code >> 1));
+		if (code == 0 && ra.regular && sa0_index >= (i & ~127ull) && sa0_index <= i) nxt--;
+		i = nxt;
+		j++;
+	}
+	return i;
+}
+
+/* SA[row] by the invPsi walk: one octet per row */
 __global__ __launch_bounds__(BWB_BLOCK) void k_locate(DevIndex ix, const uint64_t *SA, uint64_t sa0_index, const uint64_t *rows, uint64_t n, uint64_t *out, unsigned long long *stats) {
 	__shared__ uint64_t s_base[BWB_BASE_ROWS * 16];
 	load_base<uint64_t>(s_base, ix);
 	const int lane = threadIdx.x & 63, ol = lane & 7;
 	const uint64_t noct = (uint64_t)gridDim.x * BWB_OCTS_PER_BLOCK;
 	for (uint64_t q = (uint64_t)blockIdx.x * BWB_OCTS_PER_BLOCK + (threadIdx.x >> 3); q < n; q += noct) {
-		uint64_t i = rows[q], j = 0;
-		while ((i & 31) != 0) { /* SA_INTERVAL = 32, bwt.h:16 */
-			if (i == sa0_index) { i = 0; j++; continue; } /* invPsi bwt.c:312-314 */
-			RankReq<uint64_t> ra;
-			rank_issue<uint64_t>(ix.buckets, ix.length - 1, i, ol, ra);
-			/* B(i), bwt.c:337-345: bit (i&31) of the planes held by lane 4 + ((i&63)>>5) */
-			const uint4 cq = ra.regular ? ra.q : ix.buckets[(i >> BKT_SHIFT) * 8 + ol]; /* i == length-1 is not ranked via its bucket */
-			const int off = (int)(i & BKT_MASK), srcl = (lane & ~7) + 4 + (off >> 5), bit = off & 31;
-			const uint32_t code_here = ((cq.x >> bit) & 1u) | (((cq.y >> bit) & 1u) << 1) | (((cq.z >> bit) & 1u) << 2) | (((cq.w >> bit) & 1u) << 3);
-			const uint32_t code = oct_bcast(code_here, srcl);
-			uint64_t v0, v1;
-			rank_finish<uint64_t, false>(ra, s_base, ol, lane, v0, v1);
-			/* C[c] + O(c,i): held by lane c>>1.  The sentinel row is stored as code 0 but is not a '$' (bwt.c:364) */
-			const uint64_t mine = (code & 1u) ? v1 : v0;
-			uint64_t nxt = oct_bcast(mine, (lane & ~7) + (int)(code >> 1));
-			if (code == 0 && ra.regular && sa0_index >= (i & ~127ull) && sa0_index <= i) nxt--;
-			i = nxt;
-			j++;
-		}
+		uint64_t j = 0;
+		const uint64_t i = sa_walk(ix, s_base, sa0_index, rows[q], lane, ol, j);
 		if (ol == 0) { out[q] = (SA[i >> 5] + j) % ix.length; if (j) atomicAdd(&stats[STAT_LOCATE_STEPS], (unsigned long long)j); } /* (j: invPsi steps = rank-block visits, the step through the sentinel row included) */
+	}
+}
+
+/* eval_aln + mapq (align.c:738-812) for every read of a slot, where its hits lie: one octet per read -> one 48-byte bwb_place record
+ * (include/bwbble_hip.h) in read order.  log/off/n are the slot's hit log (bwb_aln: three uint4 per hit, a read's hits contiguous and in
+ * discovery order).  All integer: qtab[n] = (int)(4.343 * log(n) + 0.5), tabulated by the host (the only floating point of mapq). */
+#define PLACE_F_MAPPED 1u
+#define PLACE_F_REVERSE 2u
+#define PLACE_F_BAD 0x80u  /* the read's hits lie outside the log / its row outside the index: nothing was read (the host reports it) */
+__global__ __launch_bounds__(BWB_BLOCK) void k_place(DevIndex ix, const uint64_t *SA, uint64_t sa0_index, const uint4 *log, uint64_t log_n, const uint64_t *off, const uint32_t *n,
+                                                      uint32_t n_reads, int max_mm, const uint8_t *qtab, uint4 *out, unsigned long long *steps) {
+	__shared__ uint64_t s_base[BWB_BASE_ROWS * 16];
+	load_base<uint64_t>(s_base, ix);
+	const int lane = threadIdx.x & 63, ol = lane & 7;
+	const uint32_t noct = gridDim.x * BWB_OCTS_PER_BLOCK;
+	for (uint32_t r = blockIdx.x * BWB_OCTS_PER_BLOCK + (threadIdx.x >> 3); r < n_reads; r += noct) {
+		const uint32_t ne = n[r];
+		const uint64_t o = ne ? off[r] : 0;
+		uint4 w0 = make_uint4(0u, 0u, 0u, 0u), w1 = w0, w2 = w0; /* n == 0: unmapped, everything zero */
+		if (ne && (o > log_n || ne > log_n - o)) w1.x = PLACE_F_BAD << 24;
+		else if (ne) {
+			const uint4 *e = log + o * 3;
+			const uint4 e0 = e[0], e1 = e[1], e2 = e[2]; /* L, U | score16 mm go | ge - alen16 | runs 0..3 | runs 4..7, - */
+			const uint32_t best = e1.x & 0xFFFFu;
+			/* top1 / top2 (align.c:771-779): the octet strides over the hits; 32-bit sums like read_t's ints */
+			uint32_t t1 = 0, t2 = 0;
+			for (uint32_t t = (uint32_t)ol; t < ne; t += 8) {
+				const uint4 a = e[(size_t)t * 3], b = e[(size_t)t * 3 + 1];
+				const uint32_t w = a.z - a.x + 1u; /* (int)(U - L + 1) */
+				if ((b.x & 0xFFFFu) > best) t2 += w; else t1 += w;
+			}
+			t1 += __shfl_xor(t1, 1); t1 += __shfl_xor(t1, 2); t1 += __shfl_xor(t1, 4);
+			t2 += __shfl_xor(t2, 1); t2 += __shfl_xor(t2, 2); t2 += __shfl_xor(t2, 4);
+			const uint64_t L = (uint64_t)e0.x | ((uint64_t)e0.y << 32);
+			const uint32_t num_mm = (e1.x >> 16) & 0xFFu, alen = e1.y >> 16;
+			/* get_aln_length (align.c:748-757): path positions below aln_length that are insertions.  The runs are applied in order like
+			 * aln_path_bytes does (a later run overwrites an earlier one), on a 256-bit map: aln_length is 8-bit wrapped */
+			uint64_t ins[4] = { 0, 0, 0, 0 };
+			const uint32_t rw[4] = { e1.z, e1.w, e2.x, e2.y };
+#pragma unroll
+			for (int k = 0; k < 8; k++) {
+				const uint32_t run = (rw[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu;
+				if (run == 0xFFFFu) continue;
+				const uint32_t start = run & 0xFFu, len = (run >> 8) & 0x7Fu, del = run >> 15;
+#pragma unroll
+				for (int q = 0; q < 4; q++) {
+					const int lo = (int)start - 64 * q, hi = lo + (int)len; /* bits [lo, hi) of word q */
+					const int a = lo < 0 ? 0 : lo, b = hi > 64 ? 64 : hi;
+					if (a >= b) continue;
+					const uint64_t m = (b - a == 64 ? ~0ull : ((1ull << (b - a)) - 1ull)) << a;
+					ins[q] = del ? (ins[q] & ~m) : (ins[q] | m);
+				}
+			}
+			uint32_t n_ins = 0;
+#pragma unroll
+			for (int q = 0; q < 4; q++) {
+				const int top = (int)alen - 64 * q;
+				if (top <= 0) continue;
+				n_ins += (uint32_t)__popcll(top >= 64 ? ins[q] : (ins[q] & ((1ull << top) - 1ull)));
+			}
+			const uint32_t ref_len = alen - n_ins;
+			/* The gap runs as aln2sam sees them: the .aln file holds the path from its end to its start (align.c:363-373) and the loader
+			 * fills it in that order (align.c:466-476), so eval_aln and the CIGAR code work on the align-time path REVERSED.  A run
+			 * (start, len) of a path of alen positions becomes (alen - start - len, len); ascending by start, unused runs last. */
+			uint32_t rr[8];
+#pragma unroll
+			for (int k = 0; k < 8; k++) {
+				const uint32_t run = (rw[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu;
+				rr[k] = run == 0xFFFFu ? 0xFFFFu : (((alen - (run & 0xFFu) - ((run >> 8) & 0x7Fu)) & 0xFFu) | (run & 0xFF00u));
+			}
+			if ((rw[0] & rw[1] & rw[2] & rw[3]) != 0xFFFFFFFFu) { /* (a sorting network of 19 exchanges; most hits have no gap at all) */
+#define PLACE_CE(a, b) { const uint32_t ka = rr[a] == 0xFFFFu ? 0x1FFu : (rr[a] & 0xFFu), kb = rr[b] == 0xFFFFu ? 0x1FFu : (rr[b] & 0xFFu); if (ka > kb) { const uint32_t t = rr[a]; rr[a] = rr[b]; rr[b] = t; } }
+				PLACE_CE(0, 2) PLACE_CE(1, 3) PLACE_CE(4, 6) PLACE_CE(5, 7) PLACE_CE(0, 4) PLACE_CE(1, 5) PLACE_CE(2, 6) PLACE_CE(3, 7)
+				PLACE_CE(0, 1) PLACE_CE(2, 3) PLACE_CE(4, 5) PLACE_CE(6, 7) PLACE_CE(2, 4) PLACE_CE(3, 5) PLACE_CE(1, 4) PLACE_CE(3, 6)
+				PLACE_CE(1, 2) PLACE_CE(3, 4) PLACE_CE(5, 6)
+#undef PLACE_CE
+			}
+			if (L >= ix.length) w1.x = PLACE_F_BAD << 24;
+			else {
+				uint64_t j = 0;
+				const uint64_t i = sa_walk(ix, s_base, sa0_index, L, lane, ol, j);
+				const uint64_t rp = (SA[i >> 5] + j) % ix.length;
+				if (ol == 0 && j) atomicAdd(steps, (unsigned long long)j);
+				/* strand and text position, align.c:790-799 */
+				uint32_t flags = PLACE_F_MAPPED;
+				uint64_t pos;
+				if (rp > (ix.length - 1) / 2) pos = ((ix.length - 1) - rp - 1) - (uint64_t)ref_len + 1;
+				else { flags |= PLACE_F_REVERSE; pos = rp; }
+				/* mapq, align.c:738-746 */
+				uint32_t mq;
+				const int top1 = (int)t1, top2 = (int)t2;
+				if (top1 == 0) mq = 23;
+				else if (top1 > 1) mq = 0;
+				else if ((int)num_mm == max_mm) mq = 25;
+				else if (top2 == 0) mq = 37;
+				else { const uint32_t q = qtab[top2 >= 255 ? 255 : (top2 < 0 ? 0 : top2)]; mq = 23 < q ? 0 : 23 - q; }
+				w0 = make_uint4((uint32_t)pos, (uint32_t)(pos >> 32), t1, t2);
+				w1 = make_uint4(best | (mq << 16) | (flags << 24), (e1.x >> 16) | ((e1.y & 0xFFu) << 16), alen | (ref_len << 16), 0u);
+				w2 = make_uint4(rr[0] | (rr[1] << 16), rr[2] | (rr[3] << 16), rr[4] | (rr[5] << 16), rr[6] | (rr[7] << 16));
+			}
+		}
+		uint4 *dst = out + (size_t)r * 3;
+		if (ol == 0) dst[0] = w0;
+		else if (ol == 1) dst[1] = w1;
+		else if (ol == 2) dst[2] = w2;
 	}
 }

@@ -7,6 +7,10 @@
  * The FM-index is replicated on every GPU; reads are cut into contiguous chunks that the per-GPU host threads
  * pull from a shared queue (the per-read work is heavy-tailed) and a writer emits them in order.
  * No collective is involved.  There is NO CPU alignment path: without a GPU this exits with an error.
+ *
+ * `bwbble map` (map_reads) is the same pipeline with another last stage: a finished chunk is not copied back hit by hit and serialised as
+ * .aln records, its reads are evaluated on the GPU (bwb_hip_slot_place: eval_aln + mapq, one 48-byte record per read) and the worker's
+ * team formats the chunk's SAM text (sam.c) - the bytes `align` + `aln2sam` write, from one process, one index load and no .aln file.
  */
 #define _GNU_SOURCE
 #include <pthread.h>
@@ -35,9 +39,14 @@ typedef struct chunk {
 	fq_chunk_t fq;                 /* the reads (freed once the chunk is uploaded) */
 	uint8_t *carry; uint32_t carry_len; /* the last read before the chunk that computes a D_seed (NULL: none), a copy */
 	unsigned char *buf; size_t buf_len; uint32_t n; /* the chunk's .aln records, serialised by the worker that received its hits */
+	char **sam; size_t *sam_len; size_t n_sam;      /* map: the chunk's SAM text instead, in blocks of SAM_BLOCK_READS reads */
+	size_t first_read;                              /* number of the chunk's first read in the file */
 	int ready;
 	struct chunk *next;            /* production order */
 } chunk_t;
+
+/* what `map` adds to the pipeline (NULL: align) */
+typedef struct { int max_mm; const fasta_annotations_t *ann; int ann_sorted; } map_t;
 
 typedef struct {
 	pthread_mutex_t mu;
@@ -52,6 +61,8 @@ typedef struct {
 	const aln_params_t *params;
 	uint32_t chunk_reads;
 	double t_first_chunk;
+	const map_t *map;
+	fq_stream *fs;                 /* map: the open stream - the chunks' names and qualities point into its mapping of the FASTQ */
 } pipe_t;
 
 typedef struct {
@@ -63,6 +74,7 @@ typedef struct {
 	double kernel_ms, t_ctx, t_pool, t_first_submit; /* index upload; the chunk pool's hipMalloc; worker start to the first slice queued */
 	unsigned long long pool_bytes;
 	unsigned long long n_reads; /* reads of the chunks this worker took */
+	double place_ms; unsigned long long place_steps; /* map: k_place, summed over the chunks */
 } worker_t;
 
 /* The reader: chunk k+1 is parsed (record boundaries by one sequential scan, bases encoded by all cores: reads.c) while chunk k is on
@@ -71,7 +83,7 @@ typedef struct {
  * look-back has no bound: the read is carried along as a copy). */
 static void *reader_thread(void *arg) {
 	pipe_t *pp = (pipe_t *)arg;
-	fq_stream *fs = fq_open(pp->readsFname);
+	fq_stream *fs = pp->map ? fq_open_text(pp->readsFname) : fq_open(pp->readsFname);
 	uint8_t *last_src = NULL; uint32_t last_len = 0;
 	const aln_params_t *params = pp->params;
 	const double t0 = wall();
@@ -91,6 +103,7 @@ static void *reader_thread(void *arg) {
 		}
 		pthread_mutex_lock(&pp->mu);
 		c->idx = pp->n_parsed++;
+		c->first_read = pp->n_reads;
 		pp->n_reads += c->fq.n;
 		if (c->idx == 0) pp->t_first_chunk = wall() - t0;
 		if (pp->last) pp->last->next = c; else pp->first = c;
@@ -105,7 +118,8 @@ static void *reader_thread(void *arg) {
 	pthread_cond_broadcast(&pp->cv_done);
 	pthread_mutex_unlock(&pp->mu);
 	free(last_src);
-	fq_close(fs);
+	if (pp->map) pp->fs = fs; /* (closed by the writer's thread after the last chunk's text is formatted) */
+	else fq_close(fs);
 	return NULL;
 }
 
@@ -115,6 +129,33 @@ static void retire(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c) {
 	if (bwb_hip_slot_result(ctx, slot, &r)) bwb_die("align_reads_inexact_gpu: GPU %d: %s", w->gpu, bwb_hip_last_error());
 	c->n = r.n_reads;
 	c->buf = alns2alnf_buf(r.alns, r.aln_off, r.n_reads, &c->buf_len); /* (with all cores; the library's result buffers stay valid until the slot is uploaded again) */
+	pthread_mutex_lock(&w->pp->mu);
+	c->ready = 1;
+	pthread_cond_broadcast(&w->pp->cv_done);
+	pthread_mutex_unlock(&w->pp->mu);
+}
+
+/* map: the same hand-over with the chunk's SAM text.  The reads are evaluated where their hits lie (kernel k_place); what comes back is one
+ * placement record per read, and the worker's team formats the text. */
+static void retire_map(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c) {
+	const map_t *m = w->pp->map;
+	const bwb_place *pl = NULL;
+	uint32_t n = 0;
+	if (bwb_hip_slot_place(ctx, slot, m->max_mm, &pl, &n)) bwb_die("map_reads: GPU %d: %s", w->gpu, bwb_hip_last_error());
+	{ uint64_t st = 0; double ms = 0; bwb_hip_place_stats(ctx, NULL, &st, &ms); w->place_ms += ms; w->place_steps += st; }
+	const sam_reads_t rd = { .pl = pl, .seq = c->fq.seq, .stride = c->fq.stride, .len = c->fq.len, .text = c->fq.text,
+	                         .name_off = c->fq.name_off, .qual_off = c->fq.qual_off, .name_len = c->fq.name_len, .first = c->first_read };
+	c->n = n;
+	c->n_sam = ((size_t)n + SAM_BLOCK_READS - 1) / SAM_BLOCK_READS;
+	c->sam = (char **)calloc(c->n_sam ? c->n_sam : 1, sizeof(char *));
+	c->sam_len = (size_t *)calloc(c->n_sam ? c->n_sam : 1, sizeof(size_t));
+#pragma omp parallel for schedule(dynamic, 1) num_threads(bwb_host_team())
+	for (long bi = 0; bi < (long)c->n_sam; bi++) {
+		const size_t r0 = (size_t)bi * SAM_BLOCK_READS, r1 = r0 + SAM_BLOCK_READS < n ? r0 + SAM_BLOCK_READS : n;
+		c->sam[bi] = sam_format_reads(&rd, r0, r1, m->ann, m->ann_sorted, &c->sam_len[bi]);
+	}
+	free(c->fq.seq); free(c->fq.len); free(c->fq.name_off); free(c->fq.qual_off); free(c->fq.name_len);
+	c->fq.seq = NULL; c->fq.len = NULL; c->fq.name_off = NULL; c->fq.qual_off = NULL; c->fq.name_len = NULL;
 	pthread_mutex_lock(&w->pp->mu);
 	c->ready = 1;
 	pthread_cond_broadcast(&w->pp->cv_done);
@@ -165,6 +206,15 @@ static void *gpu_worker(void *arg) {
 	if ((sync_create ? bwb_hip_ctx_create_streamed : bwb_hip_ctx_create_async)(w->device, hdr, w->BWT->C, w->BWT->bwt, w->BWT->O, w->BWT->loader ? &w->BWT->blocks_ready : NULL, &ctx))
 		bwb_die("align_reads_inexact_gpu: GPU %d: %s", w->device, bwb_hip_last_error());
 	if (dbg) fprintf(stderr, "[bwb host] worker %d: context created at +%.3f s (%s)\n", w->gpu, wall() - tq, sync_create ? "index uploaded" : "index upload under way");
+	if (pp->map) {
+		/* The sampled SA (length / 32 x 8 bytes: 1.7 GB at GRCh37 scale) goes to HBM BEFORE the first slot_upload sizes the chunk pool from
+		 * what is free - the loader reads it first (bwt_io.c) - and while the library's thread uploads the index: set_sa uses a stream of
+		 * its own for that (bwb_hip.hip). */
+		while (!__atomic_load_n(&w->BWT->sa_ready, __ATOMIC_ACQUIRE)) { struct timespec ts = { 0, 200000 }; nanosleep(&ts, NULL); }
+		if (bwb_hip_set_sa(ctx, w->BWT->SA, w->BWT->num_sa)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
+		if (dbg) fprintf(stderr, "[bwb host] worker %d: sampled SA resident at +%.3f s\n", w->gpu, wall() - tq);
+	}
+	void (*const hand_over)(worker_t *, bwb_hip_ctx *, int, chunk_t *) = pp->map ? retire_map : retire;
 	enum { NS = BWB_MAX_SLOTS }; /* chunks in flight: the heaviest reads of a chunk take several slices' time (they are parked and resumed), and
 	                                a slot can be uploaded again only when its chunk is complete */
 	chunk_t *in_slot[NS];
@@ -179,12 +229,12 @@ static void *gpu_worker(void *arg) {
 		const int done = !c && pp->reader_done;
 		pthread_mutex_unlock(&pp->mu);
 		if (!c) {
-			if (retired < j) { retire(w, ctx, (int)(retired % NS), in_slot[retired % NS]); retired++; continue; }
+			if (retired < j) { hand_over(w, ctx, (int)(retired % NS), in_slot[retired % NS]); retired++; continue; }
 			if (done) break;
 			continue;
 		}
 		const int slot = (int)(j % NS);
-		if (j >= NS && retired + NS <= j) { retire(w, ctx, slot, in_slot[slot]); retired++; } /* the slot's previous chunk: NS - 1 slices stay queued while the host waits */
+		if (j >= NS && retired + NS <= j) { hand_over(w, ctx, slot, in_slot[slot]); retired++; } /* the slot's previous chunk: NS - 1 slices stay queued while the host waits */
 		if (bwb_hip_slot_upload(ctx, slot, w->params, c->fq.seq, c->fq.len, c->fq.n, c->fq.stride, c->carry, c->carry_len))
 			bwb_die("align_reads_inexact_gpu: GPU %d: %s", w->device, bwb_hip_last_error());
 		if (j == 0) { /* the first chunk is staged, scratch and pool exist: now the index must be complete */
@@ -198,7 +248,8 @@ static void *gpu_worker(void *arg) {
 		if (bwb_hip_slot_submit(ctx, slot))
 			bwb_die("align_reads_inexact_gpu: GPU %d: %s", w->device, bwb_hip_last_error());
 		if (j == 0) w->t_first_submit = wall() - tq;
-		free(c->fq.seq); free(c->fq.len); free(c->carry); c->fq.seq = NULL; c->fq.len = NULL; c->carry = NULL; /* (staged by the library: the caller's buffers are free) */
+		if (!pp->map) { free(c->fq.seq); free(c->fq.len); c->fq.seq = NULL; c->fq.len = NULL; } /* (staged by the library: the caller's buffers are free; map prints the bases) */
+		free(c->carry); c->carry = NULL;
 		in_slot[slot] = c;
 		w->n_reads += c->fq.n;
 		j++;
@@ -216,10 +267,16 @@ static void *gpu_worker(void *arg) {
 /* The GPU replacement for align_reads_inexact_parallel, as a pipeline: reader thread (FASTQ -> chunks) | one worker per GPU | this
  * thread (ordered writer, inexact_match.c:154-162).  `reads` is the FASTQ's NAME: the file is streamed, not loaded (the reference's
  * reads_t holds the whole file in memory before the first read is aligned). */
+static int run_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, FILE *alnFile, const char *alnFname, int n_gpus, const map_t *map);
 int align_reads_inexact_gpu_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, char *alnFname, int n_gpus) {
 	printf("BWBBLE Inexact Alignment (MI355X)...\n");
 	FILE *alnFile = fopen(alnFname, "a+b");                                   /* inexact_match.c:94 */
 	if (!alnFile) { perror(alnFname); bwb_die("align_reads_inexact: Cannot open ALN file: %s!", alnFname); }
+	return run_stream(BWT, readsFname, params, alnFile, alnFname, n_gpus, NULL);
+}
+
+/* the pipeline; alnFile is the open output (.aln records, or with `map` the SAM file after its header lines) and is closed here */
+static int run_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, FILE *alnFile, const char *alnFname, int n_gpus, const map_t *map) {
 	if (bwb_hip_abi_version() != BWB_HIP_ABI_VERSION) bwb_die("align_reads_inexact_gpu: libbwbble_hip.so implements C-ABI version %d, this binary was compiled against %d", bwb_hip_abi_version(), BWB_HIP_ABI_VERSION);
 	const int ndev = bwb_hip_device_count();
 	if (ndev < 1) bwb_die("align_reads_inexact_gpu: no HIP device found (this build has no CPU alignment path)");
@@ -244,7 +301,7 @@ int align_reads_inexact_gpu_stream(bwt_t *BWT, const char *readsFname, aln_param
 	memset(&pp, 0, sizeof(pp));
 	pthread_mutex_init(&pp.mu, NULL);
 	pthread_cond_init(&pp.cv_work, NULL); pthread_cond_init(&pp.cv_done, NULL); pthread_cond_init(&pp.cv_space, NULL);
-	pp.readsFname = readsFname; pp.params = params;
+	pp.readsFname = readsFname; pp.params = params; pp.map = map;
 	pp.chunk_reads = GPU_CHUNK_DEFAULT;
 	if (getenv("BWB_CHUNK")) pp.chunk_reads = (uint32_t)strtoul(getenv("BWB_CHUNK"), NULL, 10);
 	if (pp.chunk_reads < 1) pp.chunk_reads = 1;
@@ -269,6 +326,11 @@ int align_reads_inexact_gpu_stream(bwt_t *BWT, const char *readsFname, aln_param
 		pthread_mutex_unlock(&pp.mu);
 		if (!c) break;
 		if (c->buf_len && fwrite(c->buf, 1, c->buf_len, alnFile) != c->buf_len) bwb_die("align_reads_inexact: Cannot write to the ALN file: %s!", alnFname);
+		for (size_t bi = 0; bi < c->n_sam; bi++) {
+			if (c->sam_len[bi] && fwrite(c->sam[bi], 1, c->sam_len[bi], alnFile) != c->sam_len[bi]) bwb_die("map_reads: Cannot write to the SAM file: %s!", alnFname);
+			free(c->sam[bi]);
+		}
+		free(c->sam); free(c->sam_len);
 		processed += c->n;
 		printf("Processed %zu reads. Elapsed: %.2f sec\n", processed, wall() - t0);
 		if (dbg) fprintf(stderr, "[bwb host] writer: chunk %zu written at +%.3f s\n", c->idx, wall() - t0);
@@ -279,6 +341,7 @@ int align_reads_inexact_gpu_stream(bwt_t *BWT, const char *readsFname, aln_param
 		pthread_mutex_unlock(&pp.mu);
 	}
 	pthread_join(rth, NULL);
+	if (pp.fs) fq_close(pp.fs);
 	bwb_stats tot; memset(&tot, 0, sizeof(tot));
 	double kms = 0, tctx = 0, tpool = 0, tfirst = 0;
 	unsigned long long pool_bytes = 0;
@@ -300,6 +363,11 @@ int align_reads_inexact_gpu_stream(bwt_t *BWT, const char *readsFname, aln_param
 	printf("GPUs: %d  reads: %llu  wall: %.3f sec (%.0f reads/s incl. index upload)  kernel: %.1f ms  index to HBM: %.2f sec  first chunk parsed after: %.2f sec  rank-block visits: %llu  hits: %llu  re-run reads: %llu\n",
 	       n_gpus, (unsigned long long)pp.n_reads, dt, pp.n_reads / (dt > 0 ? dt : 1), kms, tctx, pp.t_first_chunk, (unsigned long long)(tot.visits_single + tot.visits_alphabet),
 	       (unsigned long long)tot.n_alignments, (unsigned long long)tot.n_overflow_reads);
+	if (map) {
+		double pms = 0; unsigned long long pst = 0;
+		for (int g = 0; g < n_gpus; g++) { pst += ws[g].place_steps; if (ws[g].place_ms > pms) pms = ws[g].place_ms; }
+		printf("placements on the GPU: reads %llu  rank-block visits %llu  kernel %.3f ms\n", (unsigned long long)pp.n_reads, pst, pms);
+	}
 	/* where the start-up went (the three overlap): the .bwt file in memory | the index in HBM | the chunk pool's hipMalloc | first slice queued */
 	printf("start-up: .bwt read %.2f sec | index to HBM %.2f sec | chunk pool %.1f GB in %.2f sec | first slice queued after %.2f sec\n",
 	       bwt_load_seconds(BWT), tctx, (double)pool_bytes / (1u << 30), tpool, tfirst);
@@ -341,5 +409,46 @@ int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_
 	printf("Total read alignment time (index and read loading overlapped): %.2f sec\n", wall() - t);
 	free_bwt(BWT);
 	free(bwtFname);
+	return 0;
+}
+
+/* `bwbble map`: align_reads + alns2sam in one pass.  The .bwt is loaded once, with its SA; the SAM header is written before the first chunk. */
+int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int n_gpus) {
+	printf("**** BWBBLE Read Mapping (align + aln2sam in one pass) ****\n");
+	/* before anything is created: without a GPU no SAM file is left behind */
+	if (bwb_hip_device_count() < 1) bwb_die("align_reads_inexact_gpu: no HIP device found (this build has no CPU alignment path)");
+	size_t L = strlen(fastaFname) + 8;
+	char *bwtFname = (char *)malloc(L), *annFname = (char *)malloc(L);
+	snprintf(bwtFname, L, "%s.bwt", fastaFname);
+	snprintf(annFname, L, "%s.ann", fastaFname);
+	double t = wall();
+	bwt_t *BWT = load_bwt_start(bwtFname, 1);
+	fasta_annotations_t *ann = annf2ann(annFname);
+	if (params->use_precalc) { /* as in align_reads (align.c:59-65) */
+		char *preFname = (char *)malloc(L);
+		snprintf(preFname, L, "%s.pre", fastaFname);
+		FILE *pf = fopen(preFname, "r");
+		if (pf) {
+			fclose(pf);
+			if (check_precalc_file(preFname)) fprintf(stderr, "warning: %s is not a complete table of 16777216 interval lists (a run of the reference would fail on it): delete it to have it rebuilt\n", preFname);
+		} else {
+			load_bwt_wait(BWT);
+			printf("Total BWT loading time: %.2f sec\n", wall() - t);
+			t = wall();
+			precalc_sa_intervals(BWT, params, preFname);
+			printf("Total pre-calculated intervals time: %.2f sec\n", wall() - t);
+		}
+		free(preFname);
+	}
+	FILE *sam = fopen(samFname, "w");
+	if (!sam) { perror(samFname); bwb_die("map_reads: Cannot open SAM file: %s!", samFname); }
+	sam_write_header(sam, ann);
+	const map_t m = { .max_mm = max_mm, .ann = ann, .ann_sorted = sam_ann_sorted(ann) };
+	t = wall();
+	printf("BWBBLE Inexact Alignment (MI355X)...\n");
+	run_stream(BWT, readsFname, params, sam, samFname, n_gpus, &m);
+	printf("Total read mapping time (index and read loading overlapped): %.2f sec\n", wall() - t);
+	free_bwt(BWT); free_ann(ann);
+	free(bwtFname); free(annFname);
 	return 0;
 }

@@ -38,6 +38,7 @@ typedef struct {
 	volatile uint64_t blocks_ready;   /* leading 128-character blocks whose bwt words and O rows are in memory (release/acquire) */
 	void *loader;                     /* opaque: the loader threads (NULL: everything is loaded) */
 	double load_seconds;              /* load_bwt_start to the last byte of the file in memory */
+	volatile int sa_ready;            /* loadSA: SA is in memory (release/acquire; the loader reads it first - `map` uploads it before the chunk pool is sized) */
 } bwt_t;
 
 /* reads_t/read_t (io.h:151-194) in structure-of-arrays form: codes are read->seq (A0 G1 C2 T3 N4) */
@@ -92,8 +93,14 @@ typedef struct {
 	uint32_t n, stride, max_len;  /* reads in the chunk; bytes per read in seq (the chunk's longest read, at least 1) */
 	uint8_t *seq;                 /* [n][stride] read->seq codes (A0 G1 C2 T3 N4), malloc'ed: the consumer frees it */
 	uint16_t *len;                /* [n], malloc'ed */
+	/* only from a stream opened with fq_open_text (`map`; NULL otherwise): where each read's name and qualities lie in `text`, the stream's
+	 * mapping of the FASTQ - valid until fq_close, so the stream stays open until the last chunk's SAM text is formatted */
+	const char *text;
+	size_t *name_off, *qual_off;  /* [n], malloc'ed */
+	uint16_t *name_len;           /* [n], malloc'ed (at most MAX_SEQ_NAME_LEN, io.c:439) */
 } fq_chunk_t;
 fq_stream *fq_open(const char *readsFname);
+fq_stream *fq_open_text(const char *readsFname);                       /* the same; its chunks also carry name / quality offsets */
 int fq_next_chunk(fq_stream *s, uint32_t max_reads, fq_chunk_t *out); /* 0 at the end of the file */
 void fq_close(fq_stream *s);
 
@@ -108,6 +115,7 @@ int aln_path_bytes(const bwb_aln *a, unsigned char *path /* >= 272 bytes */); /*
 void set_default_aln_params(aln_params_t *params);                     /* align.c:22-38 */
 int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_t *params, int n_gpus); /* align.c:40-87 */
 int align_reads_inexact_gpu_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, char *alnFname, int n_gpus); /* the GPU's align_reads_inexact_parallel (inexact_match.h:40) over a streamed FASTQ */
+int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int n_gpus); /* `bwbble map`: align + aln2sam in one pass, the hits evaluated on the GPU */
 
 /* precalc.c */
 void precalc_sa_intervals(bwt_t *BWT, const aln_params_t *params, const char *preFname); /* align.c:200-224: writes <fasta>.pre */
@@ -115,6 +123,20 @@ int check_precalc_file(const char *preFname); /* the walk of load_precalc_sa_int
 
 /* sam.c */
 void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus); /* align.c:494-556 */
+/* the two halves of alns2sam: eval_aln of one read on the host, and the text of a block of reads from placement records (which `map` gets
+ * from the GPU instead, bwb_hip_slot_place) */
+#define SAM_BLOCK_READS ((size_t)1 << 14)                              /* reads formatted by one thread at a time */
+typedef struct {
+	const bwb_place *pl;                                               /* [n] */
+	const uint8_t *seq; uint32_t stride; const uint16_t *len;          /* read->seq codes */
+	const char *text; const size_t *name_off, *qual_off; const uint16_t *name_len; /* names and qualities: offsets into text */
+	size_t first;                                                      /* number of read 0 in the file (error messages) */
+} sam_reads_t;
+void place_from_alns(const bwb_aln *e, uint64_t ne, uint64_t ref_pos, uint64_t bwt_length, int max_mm, bwb_place *out);
+void sam_write_header(FILE *sam, const fasta_annotations_t *ann);
+int sam_ann_sorted(const fasta_annotations_t *ann);
+char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_annotations_t *ann, int ann_sorted, size_t *out_len);
+void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname); /* developer command: records from a file */
 
 
 /* The OpenMP teams of the host stages of `align` / `aln2sam` (base encoding, .aln serialisation, SAM text) have at most 32 threads unless

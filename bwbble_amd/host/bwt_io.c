@@ -67,12 +67,17 @@ static void *bwt_loader_thread(void *arg) {
 	bwt_t *B = L->B;
 	for (;;) {
 		pthread_mutex_lock(&L->mu);
-		const uint64_t u = L->next_unit++;
-		int do_sa = 0;
-		if (u >= L->n_units && L->load_sa && !L->sa_done) { L->sa_done = 1; do_sa = 1; }
+		/* the sampled SA first, by one thread: `map` uploads it before its first batch sizes the chunk pool from what is free */
+		const int do_sa = L->load_sa && !L->sa_done;
+		if (do_sa) L->sa_done = 1;
+		const uint64_t u = do_sa ? 0 : L->next_unit++;
 		pthread_mutex_unlock(&L->mu);
+		if (do_sa) {
+			pread_all(L->fd, B->SA, B->num_sa * sizeof(bwtint_t), L->off_SA, L->fname);
+			__atomic_store_n(&B->sa_ready, 1, __ATOMIC_RELEASE);
+			continue;
+		}
 		if (u >= L->n_units) {
-			if (do_sa) pread_all(L->fd, B->SA, B->num_sa * sizeof(bwtint_t), L->off_SA, L->fname);
 			{ /* (the last thread to get here names the moment the file was in memory) */
 				struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts);
 				const double now = ts.tv_sec + 1e-9 * ts.tv_nsec - L->t0;

@@ -1,5 +1,5 @@
 /* main.c - `bwbble` command line, same commands and flags as the reference (mg-aligner/main.c:38-160),
- * plus -g <n_gpus> on align / aln2sam. */
+ * plus -g <n_gpus> on align / aln2sam, and `map` = align + aln2sam in one pass. */
 #define _GNU_SOURCE
 #include <getopt.h>
 #include <time.h>
@@ -11,6 +11,7 @@ static int usage(void) {
 	printf("Usage:   bwbble command [options] \n");
 	printf("Command: index    index sequences in the FASTA format\n");
 	printf("         align    exact or inexact read alignment (MI355X)\n");
+	printf("         map      align + aln2sam in one pass: FASTQ to SAM (MI355X)\n");
 	printf("         fasta2ref    constructs a single linear reference from the input file \n");
 	printf("         aln2sam  convert alignment results to SAM file format for single-end mapping\n\n");
 	return 1;
@@ -25,6 +26,34 @@ static int align_usage(void) {
 	printf("         g    number of GPUs to use (default: 1; more than are present is an error)\n");
 	printf("         S    align with a single-genome reference\n         P    use pre-calculated partial alignment results (the GPU computes them per read; <fasta>.pre is written like the reference does when it is missing, and only checked for completeness when present)\n\n");
 	return 1;
+}
+
+static int map_usage(void) {
+	printf("Usage: bwbble map [align options] [-Q <int>] [-g <gpus>] <seq_fasta> <reads_fastq> <out_sam> \n");
+	printf("         writes the SAM file that `bwbble align [align options]` followed by `bwbble aln2sam [-n <Q>]` writes, without the .aln file\n");
+	printf("Options: the options of align, and\n");
+	printf("         Q    the mismatch count at which a unique hit gets MAPQ 25 (aln2sam's -n; default: 6)\n\n");
+	return 1;
+}
+
+/* the options `align` and `map` share; 0 = not one of them */
+static int align_option(int c, aln_params_t *params, int *n_gpus) {
+	switch (c) {
+	case 'M': params->mm_score = atoi(optarg); return 1;
+	case 'O': params->gapo_score = atoi(optarg); return 1;
+	case 'E': params->gape_score = atoi(optarg); return 1;
+	case 'n': params->max_diff = atoi(optarg); return 1;
+	case 'k': params->max_diff_seed = atoi(optarg); return 1;
+	case 'o': params->max_gapo = atoi(optarg); return 1;
+	case 'e': params->max_gape = atoi(optarg); return 1;
+	case 'l': params->seed_length = atoi(optarg); return 1;
+	case 'm': params->max_entries = atoi(optarg); return 1;
+	case 't': params->n_threads = atoi(optarg); return 1;
+	case 'g': *n_gpus = atoi(optarg); return 1;
+	case 'S': params->is_multiref = 0; return 1;
+	case 'P': params->use_precalc = 1; return 1;
+	}
+	return 0;
 }
 
 int main(int argc, char *argv[]) {
@@ -43,26 +72,29 @@ int main(int argc, char *argv[]) {
 		set_default_aln_params(&params);
 		int c, n_gpus = 1;
 		while ((c = getopt(argc - 1, argv + 1, "M:O:E:n:k:o:e:l:m:t:g:SP")) >= 0) {
-			switch (c) {
-			case 'M': params.mm_score = atoi(optarg); break;
-			case 'O': params.gapo_score = atoi(optarg); break;
-			case 'E': params.gape_score = atoi(optarg); break;
-			case 'n': params.max_diff = atoi(optarg); break;
-			case 'k': params.max_diff_seed = atoi(optarg); break;
-			case 'o': params.max_gapo = atoi(optarg); break;
-			case 'e': params.max_gape = atoi(optarg); break;
-			case 'l': params.seed_length = atoi(optarg); break;
-			case 'm': params.max_entries = atoi(optarg); break;
-			case 't': params.n_threads = atoi(optarg); break;
-			case 'g': n_gpus = atoi(optarg); break;
-			case 'S': params.is_multiref = 0; break;
-			case 'P': params.use_precalc = 1; break;
-			case '?': align_usage(); return 1;
-			default: return 1;
-			}
+			if (align_option(c, &params, &n_gpus)) continue;
+			if (c == '?') { align_usage(); return 1; }
+			return 1;
 		}
 		if (argc - 1 - optind < 3) { align_usage(); exit(1); }
 		align_reads(argv[optind + 1], argv[optind + 2], argv[optind + 3], &params, n_gpus);
+	} else if (strcmp(argv[1], "map") == 0) {
+		if (argc < 5) { map_usage(); exit(1); }
+		aln_params_t params;
+		set_default_aln_params(&params);
+		int c, n_gpus = 1, max_mm = 6; /* (aln2sam's default, mg-aligner/main.c:142) */
+		while ((c = getopt(argc - 1, argv + 1, "M:O:E:n:k:o:e:l:m:t:g:SPQ:")) >= 0) {
+			if (align_option(c, &params, &n_gpus)) continue;
+			if (c == 'Q') { max_mm = atoi(optarg); continue; }
+			if (c == '?') { map_usage(); return 1; }
+			return 1;
+		}
+		if (argc - 1 - optind < 3) { map_usage(); exit(1); }
+		map_reads(argv[optind + 1], argv[optind + 2], argv[optind + 3], &params, max_mm, n_gpus);
+	} else if (strcmp(argv[1], "places2sam") == 0) {
+		/* developer command (CPU only, used by the tests): placement records (bwb_place, include/bwbble_hip.h) from a file -> SAM text */
+		if (argc < 6) { printf("Usage: bwbble places2sam <seq_fasta> <reads_fastq> <places_bin> <out_sam> \n"); exit(1); }
+		places2sam(argv[2], argv[3], argv[4], argv[5]);
 	} else if (strcmp(argv[1], "fasta2ref") == 0) {
 		if (argc < 3) { printf("Usage: bwbble fasta2ref <seq_fasta> \n"); exit(1); }
 		size_t L = strlen(argv[2]) + 8;
@@ -88,18 +120,26 @@ int main(int argc, char *argv[]) {
 		alns2sam(argv[optind + 1], argv[optind + 2], argv[optind + 3], argv[optind + 4], is_multiref, max_diff, n_gpus);
 	} else if (strcmp(argv[1], "dumpreads") == 0) {
 		/* developer command (CPU only, used by the tests): what fastq2reads made of a FASTQ - per read "name<TAB>codes<TAB>quality" */
-		if (argc < 4) { printf("Usage: bwbble dumpreads <reads_fastq> <out_tsv> [chunk_reads] \n"); exit(1); }
+		if (argc < 4) { printf("Usage: bwbble dumpreads <reads_fastq> <out_tsv> [chunk_reads [text]] \n"); exit(1); }
 		if (argc >= 5) { /* the streaming reader of `align` (fq_next_chunk), chunk by chunk: "codes" per read */
-			fq_stream *fs = fq_open(argv[2]);
+			/* (a sixth argument `text`: the stream of `map`, fq_open_text - "name<TAB>codes<TAB>quality" like the whole-file form) */
+			const int text = argc >= 6 && strcmp(argv[5], "text") == 0;
+			fq_stream *fs = text ? fq_open_text(argv[2]) : fq_open(argv[2]);
 			FILE *g = fopen(argv[3], "w");
 			if (!g) { perror(argv[3]); return 1; }
 			fq_chunk_t ch;
 			while (fq_next_chunk(fs, (uint32_t)atoi(argv[4]), &ch)) {
 				for (uint32_t r = 0; r < ch.n; r++) {
+					if (text) {
+						fprintf(g, "%.*s\t", (int)ch.name_len[r], ch.text + ch.name_off[r]);
+						for (uint32_t i = 0; i < ch.len[r]; i++) fputc('0' + ch.seq[(size_t)r * ch.stride + i], g);
+						fprintf(g, "\t%.*s\n", (int)ch.len[r], ch.text + ch.qual_off[r]);
+						continue;
+					}
 					for (uint32_t i = 0; i < ch.stride; i++) if (i < ch.len[r]) fputc('0' + ch.seq[(size_t)r * ch.stride + i], g); else if (ch.seq[(size_t)r * ch.stride + i] != 4) fputc('!', g);
 					fputc('\n', g);
 				}
-				free(ch.seq); free(ch.len);
+				free(ch.seq); free(ch.len); free(ch.name_off); free(ch.qual_off); free(ch.name_len);
 			}
 			fclose(g);
 			fq_close(fs);

@@ -117,6 +117,7 @@ struct fq_stream {
 	size_t *soff; uint16_t *rlen; size_t n_rec, next_rec, cap; /* records found and not yet handed out: [next_rec, n_rec) */
 	uint64_t count;
 	int threads; long region;
+	int want_text; /* fq_open_text: chunks carry name / quality offsets */
 };
 
 /* next_record without the exits (a speculative scan may start in the middle of nowhere): 1 = a record, 0 = no '@' left, -1 = malformed */
@@ -201,6 +202,12 @@ fq_stream *fq_open(const char *readsFname) {
 	if (s->threads > 64) s->threads = 64;
 	s->region = getenv("BWB_FQ_REGION") ? atol(getenv("BWB_FQ_REGION")) : (256l << 20); /* (BWB_FQ_REGION: a test knob - regions of a few hundred bytes put a part boundary into every record) */
 	if (s->region < 1) s->region = 1;
+	return s;
+}
+
+fq_stream *fq_open_text(const char *readsFname) {
+	fq_stream *s = fq_open(readsFname);
+	s->want_text = 1;
 	return s;
 }
 
@@ -297,6 +304,31 @@ int fq_next_chunk(fq_stream *s, uint32_t max_reads, fq_chunk_t *out) {
 		for (; k < (int)stride; k++) d[k] = 4;
 	}
 	fq_prof_s[2] += now_s() - t0;
+	if (s->want_text) {
+		/* Where the scanner found the record's name and quality lines (next_record: io.c:430-498), from where it found the sequence line.  The
+		 * scanner comes from the end of the previous record's quality line - or the start of the file - and takes the first '@' it meets; the
+		 * line that holds it is the name line, the next one the sequence line.  So the name starts after the first '@' of the line before the
+		 * sequence line.  After the sequence: on to the next '+', the rest of that line, the quality line. */
+		out->text = raw;
+		out->name_off = (size_t *)malloc((size_t)n * sizeof(size_t));
+		out->qual_off = (size_t *)malloc((size_t)n * sizeof(size_t));
+		out->name_len = (uint16_t *)malloc((size_t)n * sizeof(uint16_t));
+		const long sz = s->sz;
+#pragma omp parallel for schedule(static) num_threads(bwb_host_team())
+		for (long i = 0; i < (long)n; i++) {
+			const long ss = (long)soff[i], ne = ss - 1; /* raw[ne] is the name line's '\n' */
+			long ls = ne;
+			while (ls > 0 && raw[ls - 1] != '\n') ls--;
+			const char *at = (const char *)memchr(raw + ls, '@', (size_t)(ne - ls));
+			const long ns = at ? at - raw + 1 : ne; /* (there is one: the scanner stopped at it) */
+			long nl = ne - ns;
+			if (nl > MAX_SEQ_NAME_LEN) nl = MAX_SEQ_NAME_LEN; /* io.c:439 */
+			long p = ss + len[i];
+			{ const char *q = (const char *)memchr(raw + p, '+', (size_t)(sz - p)); p = q ? q - raw : sz; }
+			{ const char *q = p < sz ? (const char *)memchr(raw + p, '\n', (size_t)(sz - p)) : NULL; p = q ? q - raw + 1 : sz; }
+			out->name_off[i] = (size_t)ns; out->name_len[i] = (uint16_t)nl; out->qual_off[i] = (size_t)p;
+		}
+	}
 	s->next_rec += n;
 	out->n = n; out->stride = stride; out->max_len = max_len; out->seq = seq; out->len = len;
 	s->count += n;

@@ -5,6 +5,10 @@
  * The only index work here is SA(aln.L) for the reported hit of every mapped read (align.c:786), an invPsi
  * walk of up to 31 dependent rank queries (bwt.c:311-329).  It runs on the GPU for all reads at once
  * (bwb_hip_locate); MAPQ (the only floating point in the tool), CIGAR and text stay on the host.
+ *
+ * Two halves since `bwbble map`: place_from_alns (eval_aln of one read -> a bwb_place record) and sam_format_reads (records + names, bases,
+ * qualities, annotations -> text).  `map` gets its records from the GPU (kernel k_place) and shares the formatter; `places2sam` feeds it
+ * from a file for the CPU tests.
  */
 #include <math.h>
 #include <pthread.h>
@@ -23,6 +27,104 @@ static int mapq(int top1, int top2, int num_mm, int max_mm) { /* align.c:738-746
 	int n = top2 >= 255 ? 255 : top2;
 	int q = (int)(4.343 * log(n) + 0.5);
 	return 23 < q ? 0 : 23 - q;
+}
+
+/* eval_aln (align.c:760-812) on the host: the placement record of one read from its .aln hits and SA(e[0].L).  The same arithmetic as
+ * kernel k_place (`bwbble map` gets these records from the GPU, where the hits lie). */
+void place_from_alns(const bwb_aln *e, uint64_t ne, uint64_t ref_pos, uint64_t bwt_length, int max_mm, bwb_place *out) {
+	memset(out, 0, sizeof(*out));
+	if (ne == 0) return; /* unmapped */
+	int top1 = 0, top2 = 0;
+	const int best_score = e[0].score;
+	for (uint64_t i = 0; i < ne; i++) {
+		if (e[i].score > best_score) top2 += (int)(e[i].U - e[i].L + 1);
+		else top1 += (int)(e[i].U - e[i].L + 1);
+	}
+	unsigned char path[272];
+	const int alen = aln_path_bytes(&e[0], path);
+	int ref_len = alen;                                                          /* get_aln_length :748-757 */
+	for (int i = 0; i < alen; i++) if (path[i] == 1) ref_len--;
+	out->flags = BWB_PLACE_MAPPED;
+	if (ref_pos > (bwt_length - 1) / 2) out->pos = ((bwt_length - 1) - ref_pos - 1) - (uint64_t)ref_len + 1;
+	else { out->flags |= BWB_PLACE_REVERSE; out->pos = ref_pos; }
+	out->top1 = top1; out->top2 = top2;
+	out->score = e[0].score;
+	out->mapq = (uint8_t)mapq(top1, top2, e[0].num_mm, max_mm);
+	out->num_mm = e[0].num_mm; out->num_gapo = e[0].num_gapo; out->num_gape = e[0].num_gape;
+	out->aln_length = (uint16_t)alen; out->ref_len = (uint16_t)ref_len;
+	memcpy(out->gap_run, e[0].gap_run, sizeof(out->gap_run));
+}
+
+void sam_write_header(FILE *sam, const fasta_annotations_t *ann) {
+	for (int i = 0; i < ann->num_seq; i++)                                           /* align.c:522-525 */
+		fprintf(sam, "@SQ\tSN:%s\tLN:%d\n", ann->seq_anns[i].name, (int)(ann->seq_anns[i].end_index - ann->seq_anns[i].start_index + 1));
+	fprintf(sam, "@PG\tID:bwbble\tPN:bwbble\tVN:0.1-r01\n");
+}
+
+int sam_ann_sorted(const fasta_annotations_t *ann) { /* records as fasta2ref writes them: increasing, disjoint */
+	for (int i = 1; i < ann->num_seq; i++) if (ann->seq_anns[i].start_index <= ann->seq_anns[i - 1].end_index) return 0;
+	return 1;
+}
+
+/* print_aln2sam (align.c:562-652) for reads [r0, r1) of rd: placement records + names / bases / qualities + annotations -> SAM text in a
+ * malloc'ed buffer.  Shared by aln2sam (records from place_from_alns), map (records from the GPU) and places2sam (records from a file). */
+char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_annotations_t *ann, int ann_sorted, size_t *out_len) {
+	size_t cap = 0;
+	for (size_t r = r0; r < r1; r++) cap += (size_t)rd->name_len[r] + 2 * (size_t)rd->len[r] + MAX_SEQ_NAME_LEN + 160 + 8 * (size_t)rd->pl[r].num_gapo;
+	char *o = (char *)malloc(cap ? cap : 1), *o0 = o;
+	unsigned char path[272];
+	for (size_t r = r0; r < r1; r++) {
+		const bwb_place *pl = &rd->pl[r];
+		const int len = rd->len[r];
+		const uint8_t *seq = rd->seq + (size_t)r * rd->stride;
+		const char *name = rd->text + rd->name_off[r];
+		const char *qual = rd->text + rd->qual_off[r];
+		memcpy(o, name, rd->name_len[r]); o += rd->name_len[r];
+		if (!(pl->flags & BWB_PLACE_MAPPED)) { /* unmapped, align.c:629-651 (aln_strand is 0 for a read that was never evaluated) */
+			o += sprintf(o, "\t%d\t*\t0\t0\t*\t*\t0\t0\t", SAM_FSU);
+			for (int i = 0; i < len; i++) o[i] = "AGCTN"[seq[i]];
+			o += len; *o++ = '\t';
+			memcpy(o, qual, (size_t)len); o += len; *o++ = '\n';
+			continue;
+		}
+		bwb_aln e0;
+		memset(&e0, 0, sizeof(e0));
+		e0.aln_length = pl->aln_length;
+		memcpy(e0.gap_run, pl->gap_run, sizeof(e0.gap_run));
+		const int alen = aln_path_bytes(&e0, path);
+		const int strand = (pl->flags & BWB_PLACE_REVERSE) != 0;
+		const uint64_t aln_pos = pl->pos;
+		/* the record that contains aln_pos (align.c:796-801 scans linearly; a multi-genome has a record per bubble - 1.3 M at
+		 * GRCh37 scale - and the records are disjoint and in text order, so a binary search finds the same one) */
+		int seqid = -1;
+		if (ann_sorted) {
+			int lo = 0, hi = ann->num_seq - 1;
+			while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (ann->seq_anns[mid].start_index <= aln_pos) lo = mid; else hi = mid - 1; }
+			if (ann->num_seq > 0 && aln_pos >= ann->seq_anns[lo].start_index && aln_pos <= ann->seq_anns[lo].end_index) seqid = lo;
+		} else
+			for (int i = 0; i < ann->num_seq; i++)
+				if (aln_pos >= ann->seq_anns[i].start_index && aln_pos <= ann->seq_anns[i].end_index) { seqid = i; break; }
+		if (seqid < 0) bwb_die("alns2sam: read %zu maps outside every annotated sequence", rd->first + r); /* the reference indexes seq_anns[-1] here */
+		o += sprintf(o, "\t%d\t%s\t%d\t%d\t", strand ? SAM_FSR : 0, ann->seq_anns[seqid].name, (int)(aln_pos - ann->seq_anns[seqid].start_index + 1), (int)pl->mapq);
+		if (strand) for (int i = 0; i < alen >> 1; i++) { unsigned char t = path[alen - 1 - i]; path[alen - 1 - i] = path[i]; path[i] = t; }
+		/* CIGAR: runs of the path walked from its end to its start (align.c:588-609) */
+		int i = alen - 1;
+		while (i >= 0) {
+			int j = i;
+			while (j >= 0 && path[j] == path[i]) j--;
+			o += sprintf(o, "%d%c", i - j, "MID"[path[i]]);
+			i = j;
+		}
+		memcpy(o, "\t*\t0\t0\t", 7); o += 7;
+		if (strand) for (int k = 0; k < len; k++) { const int c = seq[len - 1 - k]; o[k] = "AGCTN"[c > 3 ? 4 : 3 - c]; } /* read->rc */
+		else for (int k = 0; k < len; k++) o[k] = "AGCTN"[seq[k]];
+		o += len; *o++ = '\t';
+		if (strand) for (int k = 0; k < len; k++) o[k] = qual[len - 1 - k];
+		else memcpy(o, qual, (size_t)len);
+		o += len; *o++ = '\n';
+	}
+	*out_len = (size_t)(o - o0);
+	return o0;
 }
 
 /* SA lookups of a contiguous share of the rows on one GPU (the index is replicated, like in align) */
@@ -52,9 +154,7 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 	reads_t *reads = fastq2reads(readsFname);
 	FILE *sam = fopen(samFname, "w");
 	if (!sam) { perror(samFname); bwb_die("alns2sam: Cannot open SAM file: %s!", samFname); }
-	for (int i = 0; i < ann->num_seq; i++)                                           /* align.c:522-525 */
-		fprintf(sam, "@SQ\tSN:%s\tLN:%d\n", ann->seq_anns[i].name, (int)(ann->seq_anns[i].end_index - ann->seq_anns[i].start_index + 1));
-	fprintf(sam, "@PG\tID:bwbble\tPN:bwbble\tVN:0.1-r01\n");
+	sam_write_header(sam, ann);
 
 	const size_t n = reads->count < alns->n_reads ? reads->count : alns->n_reads;    /* align.c:535-537 */
 	/* SA(aln.L) of the first entry of every mapped read, on the GPU */
@@ -84,12 +184,17 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 	}
 	uint64_t *ref_pos = (uint64_t *)calloc(n ? n : 1, 8);
 	for (size_t k = 0; k < nm; k++) ref_pos[which[k]] = pos[k];
-
-	int ann_sorted = 1; /* records as fasta2ref writes them: increasing, disjoint */
-	for (int i = 1; i < ann->num_seq; i++) if (ann->seq_anns[i].start_index <= ann->seq_anns[i - 1].end_index) ann_sorted = 0;
+	/* eval_aln for every read, then the text */
+	bwb_place *pl = (bwb_place *)malloc((n ? n : 1) * sizeof(bwb_place));
+#pragma omp parallel for schedule(static) num_threads(bwb_host_team())
+	for (long r = 0; r < (long)n; r++)
+		place_from_alns(alns->alns + alns->aln_off[r], alns->aln_off[r + 1] - alns->aln_off[r], ref_pos[r], BWT->length, max_diff, &pl[r]);
+	const sam_reads_t rd = { .pl = pl, .seq = reads->seq, .stride = reads->stride, .len = reads->len, .text = reads->raw,
+	                         .name_off = reads->name_off, .qual_off = reads->qual_off, .name_len = reads->name_len, .first = 0 };
+	const int ann_sorted = sam_ann_sorted(ann);
 	/* The text: blocks of reads are formatted into memory by all cores and written in order (round 5: one thread's fprintf calls were
 	 * the wall time of aln2sam on a 10 M-read file, not the SA lookups). */
-	const size_t BLK = 1u << 14;
+	const size_t BLK = SAM_BLOCK_READS;
 	const size_t nblk = (n + BLK - 1) / BLK;
 	const size_t WAVE = 64; /* blocks formatted before the writer writes them */
 	char **bufs = (char **)calloc(WAVE, sizeof(char *));
@@ -99,81 +204,50 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 #pragma omp parallel for schedule(dynamic, 1) num_threads(bwb_host_team())
 		for (long bi = 0; bi < (long)nb_; bi++) {
 			const size_t r0 = (b0 + (size_t)bi) * BLK, r1 = r0 + BLK < n ? r0 + BLK : n;
-			size_t cap = 0;
-			for (size_t r = r0; r < r1; r++) cap += (size_t)reads->name_len[r] + 2 * (size_t)reads->len[r] + MAX_SEQ_NAME_LEN + 160;
-			char *o = (char *)malloc(cap ? cap : 1), *o0 = o;
-			unsigned char path[272];
-			for (size_t r = r0; r < r1; r++) {
-				const bwb_aln *e = alns->alns + alns->aln_off[r];
-				const uint64_t ne = alns->aln_off[r + 1] - alns->aln_off[r];
-				const int len = reads->len[r];
-				const uint8_t *seq = reads->seq + (size_t)r * reads->stride;
-				const char *name = reads->raw + reads->name_off[r];
-				const char *qual = reads->raw + reads->qual_off[r];
-				memcpy(o, name, reads->name_len[r]); o += reads->name_len[r];
-				if (ne == 0) { /* unmapped, align.c:629-651 (aln_strand is 0 for a read that was never evaluated) */
-					o += sprintf(o, "\t%d\t*\t0\t0\t*\t*\t0\t0\t", SAM_FSU);
-					for (int i = 0; i < len; i++) o[i] = "AGCTN"[seq[i]];
-					o += len; *o++ = '\t';
-					memcpy(o, qual, (size_t)len); o += len; *o++ = '\n';
-					continue;
-				}
-				/* eval_aln, align.c:760-812 */
-				int top1 = 0, top2 = 0;
-				const int best_score = e[0].score;
-				for (uint64_t i = 0; i < ne; i++) {
-					if (e[i].score > best_score) top2 += (int)(e[i].U - e[i].L + 1);
-					else top1 += (int)(e[i].U - e[i].L + 1);
-				}
-				int alen = aln_path_bytes(&e[0], path);
-				int ref_len = alen;                                                          /* get_aln_length :748-757 */
-				for (int i = 0; i < alen; i++) if (path[i] == 1) ref_len--;
-				const uint64_t rp = ref_pos[r];
-				int strand;
-				uint64_t aln_pos;
-				if (rp > (BWT->length - 1) / 2) { strand = 0; aln_pos = ((BWT->length - 1) - rp - 1) - (uint64_t)ref_len + 1; }
-				else { strand = 1; aln_pos = rp; }
-				const int mq = mapq(top1, top2, e[0].num_mm, max_diff);
-				/* the record that contains aln_pos (align.c:796-801 scans linearly; a multi-genome has a record per bubble - 1.3 M at
-				 * GRCh37 scale - and the records are disjoint and in text order, so a binary search finds the same one) */
-				int seqid = -1;
-				if (ann_sorted) {
-					int lo = 0, hi = ann->num_seq - 1;
-					while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (ann->seq_anns[mid].start_index <= aln_pos) lo = mid; else hi = mid - 1; }
-					if (ann->num_seq > 0 && aln_pos >= ann->seq_anns[lo].start_index && aln_pos <= ann->seq_anns[lo].end_index) seqid = lo;
-				} else
-					for (int i = 0; i < ann->num_seq; i++)
-						if (aln_pos >= ann->seq_anns[i].start_index && aln_pos <= ann->seq_anns[i].end_index) { seqid = i; break; }
-				if (seqid < 0) bwb_die("alns2sam: read %zu maps outside every annotated sequence", r); /* the reference indexes seq_anns[-1] here */
-				o += sprintf(o, "\t%d\t%s\t%d\t%d\t", strand ? SAM_FSR : 0, ann->seq_anns[seqid].name, (int)(aln_pos - ann->seq_anns[seqid].start_index + 1), mq);
-				if (strand) for (int i = 0; i < alen >> 1; i++) { unsigned char t = path[alen - 1 - i]; path[alen - 1 - i] = path[i]; path[i] = t; }
-				/* CIGAR: runs of the path walked from its end to its start (align.c:588-609) */
-				int i = alen - 1;
-				while (i >= 0) {
-					int j = i;
-					while (j >= 0 && path[j] == path[i]) j--;
-					o += sprintf(o, "%d%c", i - j, "MID"[path[i]]);
-					i = j;
-				}
-				memcpy(o, "\t*\t0\t0\t", 7); o += 7;
-				if (strand) for (int k = 0; k < len; k++) { const int c = seq[len - 1 - k]; o[k] = "AGCTN"[c > 3 ? 4 : 3 - c]; } /* read->rc */
-				else for (int k = 0; k < len; k++) o[k] = "AGCTN"[seq[k]];
-				o += len; *o++ = '\t';
-				if (strand) for (int k = 0; k < len; k++) o[k] = qual[len - 1 - k];
-				else memcpy(o, qual, (size_t)len);
-				o += len; *o++ = '\n';
-			}
-			bufs[bi] = o0; lens[bi] = (size_t)(o - o0);
+			bufs[bi] = sam_format_reads(&rd, r0, r1, ann, ann_sorted, &lens[bi]);
 		}
 		for (size_t bi = 0; bi < nb_; bi++) {
 			if (lens[bi] && fwrite(bufs[bi], 1, lens[bi], sam) != lens[bi]) bwb_die("alns2sam: Cannot write to the SAM file: %s!", samFname);
 			free(bufs[bi]); bufs[bi] = NULL;
 		}
 	}
+	free(pl);
 	free(bufs); free(lens);
 	printf("Processed %zu reads.\n", n);
 	free(rows); free(pos); free(which); free(ref_pos);
 	free(bwtFname); free(annFname);
 	free_bwt(BWT); free_reads(reads); free_alns_batch(alns); free_ann(ann);
+	fclose(sam);
+}
+
+/* developer command (CPU only, for the tests): raw bwb_place records from a file through sam_format_reads - the formatter `map` uses, on a
+ * machine without a GPU */
+void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname) {
+	size_t Ln = strlen(fastaFname) + 8;
+	char *annFname = (char *)malloc(Ln);
+	snprintf(annFname, Ln, "%s.ann", fastaFname);
+	fasta_annotations_t *ann = annf2ann(annFname);
+	reads_t *reads = fastq2reads(readsFname);
+	FILE *pf = fopen(placesFname, "rb");
+	if (!pf) { perror(placesFname); bwb_die("places2sam: Cannot open the placements file: %s!", placesFname); }
+	bwb_place *pl = (bwb_place *)malloc(((size_t)reads->count ? reads->count : 1) * sizeof(bwb_place));
+	const size_t got = fread(pl, sizeof(bwb_place), reads->count, pf);
+	fclose(pf);
+	const size_t n = got < reads->count ? got : reads->count;
+	FILE *sam = fopen(samFname, "w");
+	if (!sam) { perror(samFname); bwb_die("places2sam: Cannot open SAM file: %s!", samFname); }
+	sam_write_header(sam, ann);
+	const sam_reads_t rd = { .pl = pl, .seq = reads->seq, .stride = reads->stride, .len = reads->len, .text = reads->raw,
+	                         .name_off = reads->name_off, .qual_off = reads->qual_off, .name_len = reads->name_len, .first = 0 };
+	const int ann_sorted = sam_ann_sorted(ann);
+	for (size_t r0 = 0; r0 < n; r0 += SAM_BLOCK_READS) {
+		size_t len = 0;
+		char *buf = sam_format_reads(&rd, r0, r0 + SAM_BLOCK_READS < n ? r0 + SAM_BLOCK_READS : n, ann, ann_sorted, &len);
+		if (len && fwrite(buf, 1, len, sam) != len) bwb_die("places2sam: Cannot write to the SAM file: %s!", samFname);
+		free(buf);
+	}
+	printf("Processed %zu reads.\n", n);
+	free(pl); free(annFname);
+	free_reads(reads); free_ann(ann);
 	fclose(sam);
 }

@@ -190,6 +190,33 @@ int bwb_hip_locate(bwb_hip_ctx *ctx, const uint64_t *rows, size_t n, uint64_t *o
  * kernel's HIP-event time - what `bwbble aln2sam` and bench.py report (any pointer may be NULL) */
 int bwb_hip_locate_stats(bwb_hip_ctx *ctx, uint64_t *rows, uint64_t *steps, double *kernel_ms);
 
+/* What eval_aln + mapq (align.c:738-812) make of one read's hits - everything print_aln2sam needs except the names - computed on the GPU
+ * where the hits lie (kernel k_place), so that a caller who wants SAM text copies 48 bytes per read instead of every hit.  An unmapped read
+ * (no hits) is all zero.  (Added without a version change, like ctx_create_async: no structure or existing entry point changed.) */
+#define BWB_PLACE_MAPPED 1     /* flags bit 0: the read has a hit */
+#define BWB_PLACE_REVERSE 2    /* flags bit 1: aln_strand == 1, printed as SAM flag 16 */
+typedef struct {
+	uint64_t pos;            /* read_t.aln_pos: 0-based position in the indexed text (align.c:790-795) */
+	int32_t top1, top2;      /* summed interval widths of the hits with the first hit's score or less / of the others (align.c:771-779) */
+	uint16_t score;          /* of the first hit, like everything below */
+	uint8_t mapq;
+	uint8_t flags;
+	uint8_t num_mm, num_gapo, num_gape, reserved;
+	uint16_t aln_length;
+	uint16_t ref_len;        /* aln_length minus the path's insertions (get_aln_length, align.c:748-757) */
+	uint32_t reserved2;
+	uint16_t gap_run[BWB_MAX_GAP_RUNS]; /* the first hit's gap runs (encoded like bwb_aln.gap_run) on the path AS aln2sam SEES IT: reversed, the way the
+	                            .aln loader rebuilds it (align.c:466-476) - the CIGAR; ascending by start, unused runs (0xFFFF) last */
+} bwb_place;
+
+/* slot_wait + k_place over the slot + D2H of n_reads records in read order into pinned memory of the slot, valid until the slot is uploaded
+ * again.  max_mm is mapq's (aln2sam's -n, default 6 - not align's).  Needs the sampled SA (bwb_hip_set_sa; BWB_E_STATE without).  Independent
+ * of slot_result: either, both, in any order.  The kernel runs on the context's result stream, not behind the slices queued on the kernel
+ * stream.  batch_place is the one-batch form (slot 0 after batch_run), place_stats reports the last place call. */
+int bwb_hip_slot_place(bwb_hip_ctx *ctx, int slot, int max_mm, const bwb_place **out, uint32_t *n_reads);
+int bwb_hip_batch_place(bwb_hip_ctx *ctx, int max_mm, const bwb_place **out, uint32_t *n_reads);
+int bwb_hip_place_stats(bwb_hip_ctx *ctx, uint64_t *reads, uint64_t *steps, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
