@@ -22,7 +22,7 @@ EXPORTS = [
     "bwb_hip_calc_d", "bwb_hip_rank16", "bwb_hip_rank_bench", "bwb_hip_rank_bench_lane", "bwb_hip_set_sa", "bwb_hip_locate", "bwb_hip_locate_stats",
     "bwb_hip_reset_stats", "bwb_hip_slot_upload", "bwb_hip_slot_submit", "bwb_hip_slot_wait", "bwb_hip_slot_result", "bwb_hip_flush", "bwb_hip_abi_version", "bwb_hip_ctx_create_streamed", "bwb_hip_device_numa_node",
     "bwb_hip_ctx_create_async", "bwb_hip_ctx_index_wait", "bwb_hip_setup_times", "bwb_hip_dtab_info",
-    "bwb_hip_slot_place", "bwb_hip_batch_place", "bwb_hip_place_stats",
+    "bwb_hip_slot_place", "bwb_hip_batch_place", "bwb_hip_place_stats", "bwb_hip_place_hits",
 ]
 ABI_VERSION = 3  # BWB_HIP_ABI_VERSION (include/bwbble_hip.h)
 MAX_SLOTS = 8  # BWB_MAX_SLOTS
@@ -108,6 +108,7 @@ def lib():
         L.bwb_hip_slot_place.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
         L.bwb_hip_batch_place.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
         L.bwb_hip_place_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.bwb_hip_place_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
         _lib = L
     return _lib
 
@@ -293,6 +294,16 @@ class Context:
         ptr, n = C.c_void_p(), C.c_uint32()
         _chk(lib().bwb_hip_batch_place(self._h, max_mm, C.byref(ptr), C.byref(n)))
         return self._places(ptr, n.value)
+
+    def place_hits(self, aln_off, alns, max_mm=6):
+        """the same kernel on a hit list of the caller's: read r owns alns[aln_off[r]:aln_off[r + 1]] (ALN_DTYPE, discovery order)"""
+        aln_off = np.ascontiguousarray(aln_off, dtype=np.uint64)
+        alns = np.ascontiguousarray(alns, dtype=ALN_DTYPE)
+        if len(aln_off) < 1 or (len(aln_off) > 1 and int(aln_off.max()) > len(alns)):
+            raise ValueError("aln_off must hold n_reads + 1 offsets into alns")
+        out = np.zeros(len(aln_off) - 1, dtype=PLACE_DTYPE)
+        _chk(lib().bwb_hip_place_hits(self._h, alns.ctypes.data, aln_off.ctypes.data, len(aln_off) - 1, max_mm, out.ctypes.data))
+        return out
 
     def place_stats(self):
         """(reads, invPsi steps = rank-block visits, kernel ms) of the last place call"""

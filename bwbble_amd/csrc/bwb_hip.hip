@@ -1472,6 +1472,46 @@ extern "C" int bwb_hip_locate_stats(bwb_hip_ctx *c, uint64_t *rows, uint64_t *st
 
 /* ---- placement records: eval_aln + mapq on the GPU (k_place) ------------------------------------------------------ */
 static_assert(sizeof(bwb_place) == 48, "bwb_place is three 16-byte words (k_place)");
+/* k_place over n reads whose hits are log[off[r] .. off[r] + cnt[r]) (all device memory, log_n hits in the log) -> n records in d_out, copied to
+ * h_out; sets the context's place_ms / place_steps.  On the result stream.  Shared by slot_place (the slot's hit log) and place_hits (a hit
+ * list of the caller's): the same kernel, the same launch. */
+static int place_launch(bwb_hip_ctx *c, const char *who, const uint4 *d_log, uint64_t log_n, const uint64_t *d_off, const uint32_t *d_cnt, uint32_t n, int max_mm,
+                        uint4 *d_out, bwb_place *h_out) {
+	if (!c->d_qtab.p) { /* the only floating point of mapq (align.c:744), with the host's own expression */
+		uint8_t tab[256 + 8] = { 0 };
+		for (int k = 1; k < 256; k++) tab[k] = (uint8_t)(int)(4.343 * log((double)k) + 0.5);
+		HIPCHK(c->d_qtab.alloc(sizeof(tab)));
+		HIPCHK(hipMemcpyAsync(c->d_qtab.p, tab, sizeof(tab), hipMemcpyHostToDevice, c->rstream));
+		HIPCHK(hipStreamSynchronize(c->rstream));
+	}
+	c->place_ms = 0; c->place_steps = 0; c->place_reads = n;
+	if (!n) return BWB_OK;
+	hipEvent_t e0 = get_event(c), e1 = get_event(c);
+	struct EvGuard {
+		bwb_hip_ctx *c; hipEvent_t a, b;
+		~EvGuard() { if (a) c->free_events.push_back(a); if (b) c->free_events.push_back(b); }
+	} evg{ c, e0, e1 };
+	if (!e0 || !e1) return fail(BWB_E_HIP, "hipEventCreate failed");
+	unsigned long long *steps = (unsigned long long *)(c->d_qtab.as<unsigned char>() + 256);
+	HIPCHK(hipMemsetAsync(steps, 0, 8, c->rstream));
+	const unsigned grid = (unsigned)std::min<size_t>(((size_t)n + BWB_OCTS_PER_BLOCK - 1) / BWB_OCTS_PER_BLOCK, (size_t)c->num_cu * 8);
+	HIPCHK(hipEventRecord(e0, c->rstream));
+	hipLaunchKernelGGL(k_place, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, c->ix, c->d_SA.as<uint64_t>(), c->sa0_index, d_log, log_n,
+	                   d_off, d_cnt, n, max_mm, c->d_qtab.as<uint8_t>(), d_out, steps);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(e1, c->rstream));
+	HIPCHK(hipMemcpyAsync(h_out, d_out, (size_t)n * sizeof(bwb_place), hipMemcpyDeviceToHost, c->rstream));
+	unsigned long long hsteps = 0;
+	HIPCHK(hipMemcpyAsync(&hsteps, steps, 8, hipMemcpyDeviceToHost, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	float ms = 0;
+	HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+	c->place_ms = ms; c->place_steps = hsteps;
+	for (uint32_t i = 0; i < n; i++)
+		if (h_out[i].flags & PLACE_F_BAD) return fail(BWB_E_STATE, std::string(who) + ": a read's hits lie outside the hit log or the index");
+	return BWB_OK;
+}
+
 extern "C" int bwb_hip_slot_place(bwb_hip_ctx *c, int si, int max_mm, const bwb_place **out, uint32_t *n_reads) {
 	if (!c || !out || !n_reads || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_place: bad argument");
 	HIPCHK(hipSetDevice(c->device));
@@ -1482,53 +1522,53 @@ extern "C" int bwb_hip_slot_place(bwb_hip_ctx *c, int si, int max_mm, const bwb_
 	if (rc) return rc;
 	const uint32_t n = s.n_reads;
 	if (s.placed_mm != max_mm || !n) {
-		if (!c->d_qtab.p) { /* the only floating point of mapq (align.c:744), with the host's own expression */
-			uint8_t tab[256 + 8] = { 0 };
-			for (int k = 1; k < 256; k++) tab[k] = (uint8_t)(int)(4.343 * log((double)k) + 0.5);
-			HIPCHK(c->d_qtab.alloc(sizeof(tab)));
-			HIPCHK(hipMemcpyAsync(c->d_qtab.p, tab, sizeof(tab), hipMemcpyHostToDevice, c->rstream));
-			HIPCHK(hipStreamSynchronize(c->rstream));
-		}
-		c->place_ms = 0; c->place_steps = 0; c->place_reads = n;
 		HIPCHK(s.h_place.reserve((size_t)n * sizeof(bwb_place)));
+		uint64_t log_n = 0;
 		if (n) {
 			HIPCHK(s.d_place.reserve((size_t)n * sizeof(bwb_place)));
 			/* On the result stream: the kernel stream may hold slices of later slots, seconds each, and this call must not wait for them.
 			 * The slot's reads are done (slot_wait) and were published with a system-scope release; the host reads the same memory on
 			 * this stream in slot_result. */
-			hipEvent_t e0 = get_event(c), e1 = get_event(c);
-			struct EvGuard {
-				bwb_hip_ctx *c; hipEvent_t a, b;
-				~EvGuard() { if (a) c->free_events.push_back(a); if (b) c->free_events.push_back(b); }
-			} evg{ c, e0, e1 };
-			if (!e0 || !e1) return fail(BWB_E_HIP, "hipEventCreate failed");
-			unsigned long long *steps = (unsigned long long *)(c->d_qtab.as<unsigned char>() + 256);
-			HIPCHK(hipMemsetAsync(steps, 0, 8, c->rstream));
-			HIPCHK(hipMemcpyAsync(s.h_ctl.p, s.ctl_count(), 8, hipMemcpyDeviceToHost, c->rstream));
-			HIPCHK(hipStreamSynchronize(c->rstream));
-			const uint64_t log_n = std::min<unsigned long long>(*s.h_ctl.as<unsigned long long>(), s.log_cap);
-			const unsigned grid = (unsigned)std::min<size_t>(((size_t)n + BWB_OCTS_PER_BLOCK - 1) / BWB_OCTS_PER_BLOCK, (size_t)c->num_cu * 8);
-			HIPCHK(hipEventRecord(e0, c->rstream));
-			hipLaunchKernelGGL(k_place, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, c->ix, c->d_SA.as<uint64_t>(), c->sa0_index, s.d_log.as<uint4>(), log_n,
-			                   s.d_off.as<uint64_t>(), s.d_n.as<uint32_t>(), n, max_mm, c->d_qtab.as<uint8_t>(), s.d_place.as<uint4>(), steps);
-			HIPCHK(hipGetLastError());
-			HIPCHK(hipEventRecord(e1, c->rstream));
-			HIPCHK(hipMemcpyAsync(s.h_place.p, s.d_place.p, (size_t)n * sizeof(bwb_place), hipMemcpyDeviceToHost, c->rstream));
-			unsigned long long hsteps = 0;
-			HIPCHK(hipMemcpyAsync(&hsteps, steps, 8, hipMemcpyDeviceToHost, c->rstream));
-			HIPCHK(hipStreamSynchronize(c->rstream));
-			float ms = 0;
-			HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-			c->place_ms = ms; c->place_steps = hsteps;
-			const bwb_place *hp = s.h_place.as<bwb_place>();
-			for (uint32_t i = 0; i < n; i++)
-				if (hp[i].flags & PLACE_F_BAD) return fail(BWB_E_STATE, "slot_place: a read's hits lie outside the hit log or the index");
+			rc = fetch(c, s.h_ctl.p, s.ctl_count(), 8);
+			if (rc) return rc;
+			log_n = std::min<unsigned long long>(*s.h_ctl.as<unsigned long long>(), s.log_cap);
 		}
+		rc = place_launch(c, "slot_place", s.d_log.as<uint4>(), log_n, s.d_off.as<uint64_t>(), s.d_n.as<uint32_t>(), n, max_mm, s.d_place.as<uint4>(), s.h_place.as<bwb_place>());
+		if (rc) return rc;
 		s.placed_mm = max_mm;
 	}
 	*out = s.h_place.as<bwb_place>();
 	*n_reads = n;
 	return BWB_OK;
+}
+
+/* k_place on a hit list of the caller's instead of a slot's hit log (for parity tests): read r owns alns[aln_off[r] .. aln_off[r + 1]) */
+extern "C" int bwb_hip_place_hits(bwb_hip_ctx *c, const bwb_aln *alns, const uint64_t *aln_off, uint32_t n_reads, int max_mm, bwb_place *out) {
+	if (!c || !aln_off || (n_reads && !out)) return fail(BWB_E_ARG, "place_hits: null argument");
+	if (!c->d_SA.p) return fail(BWB_E_STATE, "place_hits: sampled SA not uploaded (bwb_hip_set_sa)");
+	const uint64_t base = aln_off[0], total = aln_off[n_reads] - base;
+	std::vector<uint64_t> off(n_reads ? n_reads : 1);
+	std::vector<uint32_t> cnt(n_reads ? n_reads : 1);
+	for (uint32_t r = 0; r < n_reads; r++) {
+		if (aln_off[r + 1] < aln_off[r] || aln_off[r + 1] - aln_off[r] > 0xFFFFFFFFull) return fail(BWB_E_ARG, "place_hits: aln_off is not ascending");
+		off[r] = aln_off[r] - base; cnt[r] = (uint32_t)(aln_off[r + 1] - aln_off[r]);
+	}
+	if (total && !alns) return fail(BWB_E_ARG, "place_hits: null argument");
+	HIPCHK(hipSetDevice(c->device));
+	{ int rc = index_ready(c); if (rc) return rc; }
+	static_assert(sizeof(bwb_aln) == 48, "bwb_aln is the hit log's three 16-byte words");
+	DevMem d_log, d_off, d_cnt, d_out;
+	HIPCHK(d_log.alloc((size_t)total * sizeof(bwb_aln)));
+	HIPCHK(d_off.alloc((size_t)n_reads * 8));
+	HIPCHK(d_cnt.alloc((size_t)n_reads * 4));
+	HIPCHK(d_out.alloc((size_t)n_reads * sizeof(bwb_place)));
+	if (total) HIPCHK(hipMemcpyAsync(d_log.p, alns + base, (size_t)total * sizeof(bwb_aln), hipMemcpyHostToDevice, c->rstream));
+	if (n_reads) {
+		HIPCHK(hipMemcpyAsync(d_off.p, off.data(), (size_t)n_reads * 8, hipMemcpyHostToDevice, c->rstream));
+		HIPCHK(hipMemcpyAsync(d_cnt.p, cnt.data(), (size_t)n_reads * 4, hipMemcpyHostToDevice, c->rstream));
+		HIPCHK(hipStreamSynchronize(c->rstream)); /* (off / cnt are pageable memory of this call) */
+	}
+	return place_launch(c, "place_hits", d_log.as<uint4>(), total, d_off.as<uint64_t>(), d_cnt.as<uint32_t>(), n_reads, max_mm, d_out.as<uint4>(), out);
 }
 
 extern "C" int bwb_hip_batch_place(bwb_hip_ctx *c, int max_mm, const bwb_place **out, uint32_t *n_reads) {

@@ -197,7 +197,10 @@ int bwb_hip_locate_stats(bwb_hip_ctx *ctx, uint64_t *rows, uint64_t *steps, doub
 #define BWB_PLACE_REVERSE 2    /* flags bit 1: aln_strand == 1, printed as SAM flag 16 */
 typedef struct {
 	uint64_t pos;            /* read_t.aln_pos: 0-based position in the indexed text (align.c:790-795) */
-	int32_t top1, top2;      /* summed interval widths of the hits with the first hit's score or less / of the others (align.c:771-779) */
+	int32_t top1, top2;      /* summed interval widths of the hits with the first hit's score or less / of the others (align.c:771-779): each
+	                            64-bit width is added into an int there, so the sums wrap modulo 2^32 and may be zero or negative on a mapped read.
+	                            With top2 < 0 and top1 == 1 or < 0 the reference's MAPQ is undefined (log() of a negative number, NaN
+	                            converted to int, align.c:744); this library then reads its table at 0 */
 	uint16_t score;          /* of the first hit, like everything below */
 	uint8_t mapq;
 	uint8_t flags;
@@ -216,6 +219,11 @@ typedef struct {
 int bwb_hip_slot_place(bwb_hip_ctx *ctx, int slot, int max_mm, const bwb_place **out, uint32_t *n_reads);
 int bwb_hip_batch_place(bwb_hip_ctx *ctx, int max_mm, const bwb_place **out, uint32_t *n_reads);
 int bwb_hip_place_stats(bwb_hip_ctx *ctx, uint64_t *reads, uint64_t *steps, double *kernel_ms);
+/* The same kernel on a hit list of the caller's instead of a slot's hit log: read r owns alns[aln_off[r] .. aln_off[r + 1]) in discovery
+ * order (a bwb_aln is exactly one record of the log; only alns[aln_off[0] .. aln_off[n_reads]) is read); n_reads records go to out, place_stats reports the call.  Needs set_sa; touches no slot.
+ * BWB_E_ARG when aln_off does not ascend; BWB_E_STATE when a first hit's L is not a row of the index (nothing of that read is looked up).
+ * For parity tests, like calc_d and rank16.  (Added without a version change: no structure or existing entry point changed.) */
+int bwb_hip_place_hits(bwb_hip_ctx *ctx, const bwb_aln *alns, const uint64_t *aln_off, uint32_t n_reads, int max_mm, bwb_place *out);
 
 #ifdef __cplusplus
 }

@@ -4,13 +4,20 @@ gives - so from a golden .aln of the reference or from the oracle's bytes, never
 invPsi / SA (oracle/bwb_oracle.c)."""
 import ctypes as C
 import math
+import random
 
 import numpy as np
 
 import bwbble_amd as bw
 
 
-def mapq(top1, top2, num_mm, max_mm):  # align.c:738-746
+def wrap32(x):
+    """what a C int holds after `+=` of 64-bit interval widths (align.c:773,776: read_t.aln_top1_count / aln_top2_count are ints)"""
+    x &= 0xFFFFFFFF
+    return x - (1 << 32) if x >= (1 << 31) else x
+
+
+def mapq(top1, top2, num_mm, max_mm):  # align.c:738-746 (top2 < 0 with top1 == 1 or < 0: log() of a negative number there - undefined, an error here)
     if top1 == 0:
         return 23
     if top1 > 1:
@@ -37,15 +44,54 @@ def gap_runs(states):
     return runs + [0xFFFF] * (8 - len(runs))
 
 
-def sa_walk(orc, idx, row):
-    """(SA[row], steps): bwt.c:311-329 with the oracle's invPsi, until a row divisible by 32; the step through the sentinel row counts"""
+def aln_records(reads, permute=None):
+    """The inverse of gap_runs: hits in the form oracle_lib.parse_aln gives (paths in the .aln file's order) -> (aln_off, records of
+    bwbble_amd.ALN_DTYPE) as kl_search would have emitted them.  The search writes the path in align-time order, which the file holds from
+    its end to its start (align.c:363-373): a run (start, len) of the file's path is (aln_length - start - len, len) there.  permute: the
+    order of the runs inside gap_run[] - None: ascending by align-time start; "reverse": descending; a random.Random: shuffled by it."""
+    off = np.zeros(len(reads) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(ents) for ents in reads])
+    alns = np.zeros(int(off[-1]), dtype=bw.ALN_DTYPE)
+    k = 0
+    for ents in reads:
+        for e in ents:
+            alen = e["aln_length"]
+            runs = []
+            for run in gap_runs(e["states"]):
+                if run != 0xFFFF:
+                    start, ln = run & 0xFF, (run >> 8) & 0x7F
+                    assert 0 <= alen - start - ln <= 0xFF
+                    runs.append((alen - start - ln) | (run & 0xFF00))
+            runs.sort(key=lambda v: v & 0xFF)
+            if permute == "reverse":
+                runs.reverse()
+            elif isinstance(permute, random.Random):
+                permute.shuffle(runs)
+            else:
+                assert permute is None
+            rec = alns[k]
+            rec["L"], rec["U"], rec["score"] = e["L"], e["U"], e["score"]
+            rec["num_mm"], rec["num_gapo"], rec["num_gape"], rec["aln_length"] = e["mm"], e["gapo"], e["gape"], alen
+            rec["gap_run"] = runs + [0xFFFF] * (8 - len(runs))
+            k += 1
+    return off, alns
+
+
+def walk_rows(orc, idx, row):
+    """the rows the invPsi walk from `row` visits, the start and the sampled row it ends on included (bwt.c:311-329)"""
     orc.lib.bwb_or_invPsi.restype = C.c_uint64
     orc.lib.bwb_or_invPsi.argtypes = [C.c_void_p, C.c_uint64]
-    i, j = row, 0
-    while i % 32:
-        i = orc.lib.bwb_or_invPsi(idx, i)
-        j += 1
-    return (int(idx.contents.SA[i // 32]) + j) % int(idx.contents.length), j
+    rows = [row]
+    while rows[-1] % 32:
+        rows.append(int(orc.lib.bwb_or_invPsi(idx, rows[-1])))
+    return rows
+
+
+def sa_walk(orc, idx, row):
+    """(SA[row], steps): bwt.c:311-329 with the oracle's invPsi, until a row divisible by 32; the step through the sentinel row counts"""
+    rows = walk_rows(orc, idx, row)
+    j = len(rows) - 1
+    return (int(idx.contents.SA[rows[-1] // 32]) + j) % int(idx.contents.length), j
 
 
 def expected_places(orc, idx, reads, max_mm=6):
@@ -57,8 +103,8 @@ def expected_places(orc, idx, reads, max_mm=6):
         if not ents:
             continue
         e0 = ents[0]
-        top1 = sum(e["U"] - e["L"] + 1 for e in ents if e["score"] <= e0["score"])
-        top2 = sum(e["U"] - e["L"] + 1 for e in ents if e["score"] > e0["score"])
+        top1 = wrap32(sum(e["U"] - e["L"] + 1 for e in ents if e["score"] <= e0["score"]))  # sums of C ints, align.c:773,776
+        top2 = wrap32(sum(e["U"] - e["L"] + 1 for e in ents if e["score"] > e0["score"]))
         ref_len = e0["aln_length"] - sum(s >> 2 for s in e0["states"] if (s & 3) == 1)  # get_aln_length, align.c:748-757
         rp, j = sa_walk(orc, idx, e0["L"])
         steps += j

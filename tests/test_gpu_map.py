@@ -1,7 +1,8 @@
 """`bwbble map` on the GPU: kernel k_place through Context.place / slot_place against the Python restatement of eval_aln
 (tests/map_model.py) fed with the ORACLE's hits - never the library's own slot_result -, the streaming interface with parked and resumed
 reads, the state errors, the command line against the reference's golden .sam files and against this build's align + aln2sam, and the
-walk on the small-superblock test build."""
+walk on the small-superblock test build.  And k_place on hit lists the search would never hand it (Context.place_hits on the synth_hits
+fixture, whose judge is the reference's aln2sam): eight gap runs in every order, sums that wrap, special first rows, 200 000 reads."""
 import os
 import shutil
 import subprocess
@@ -138,6 +139,141 @@ def test_place_state_errors_leave_the_context_usable(built, golden, oracle):
         ctx.close()
 
 
+# ---- k_place on injected hit lists (tests/golden/synth_hits.*, made by tests/golden/make_golden_map.py with the reference as judge) ----------
+
+@pytest.fixture(scope="module")
+def synth(golden, oracle):
+    """the fixture's hit lists as bwb_aln records, and what eval_aln makes of them under aln2sam's -n 6 and -n 3 (records, invPsi steps)"""
+    import types
+    idx = oracle.load_index(os.path.join(golden, "rep.fa.bwt"), load_sa=True)
+    reads = oracle_lib.parse_aln(open(os.path.join(golden, "synth_hits.aln"), "rb").read())
+    off, alns = map_model.aln_records(reads)
+    return types.SimpleNamespace(reads=reads, off=off, alns=alns, want={mm: map_model.expected_places(oracle, idx, reads, mm) for mm in (6, 3)})
+
+
+@pytest.fixture(scope="module")
+def synth_text(tmp_path_factory):
+    """the fixture's text files (committed gzipped) as plain files: synth_hits.fq, synth_hits_n6.sam, synth_hits_n3.sam"""
+    from golden.make_golden_map import unpack_synth
+    return unpack_synth(tmp_path_factory.mktemp("synth"))
+
+
+@pytest.fixture()
+def rep_ctx(built, golden):
+    ctx = sa_context(os.path.join(golden, "rep.fa.bwt"))
+    yield ctx
+    ctx.close()
+
+
+def same_places(got, want, what=""):
+    assert map_model.first_difference(got, want) is None, (what, map_model.first_difference(got, want))
+    assert got.tobytes() == want.tobytes(), what
+
+
+def tiled(off, alns, times):
+    """the hit lists `times` times over"""
+    cnt = np.diff(off)
+    toff = np.zeros(len(cnt) * times + 1, dtype=np.uint64)
+    toff[1:] = np.cumsum(np.tile(cnt, times))
+    return toff, np.tile(alns, times)
+
+
+def compute_units():
+    """the device's CU count, asked in a child process (k_place's grid is min(ceil(n / 32), 8 * CUs) blocks)"""
+    r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.get_device_properties(0).multi_processor_count)"],
+                       check=True, stdout=subprocess.PIPE, text=True, timeout=300)
+    return int(r.stdout.split()[-1])
+
+
+@pytest.mark.parametrize("max_mm", [6, 3])
+def test_place_hits_equals_the_model_and_the_references_sam(rep_ctx, golden, synth, synth_text, tmp_path, max_mm):
+    """k_place on the synthetic hit lists == the model's records and step count; and the kernel's records through the formatter == the
+    SAM the REFERENCE wrote for these hit lists (no model in that loop)"""
+    want, steps = synth.want[max_mm]
+    got = rep_ctx.place_hits(synth.off, synth.alns, max_mm)
+    same_places(got, want)
+    n, st, ms = rep_ctx.place_stats()
+    assert (n, st) == (len(synth.reads), steps) and ms > 0
+    pf, out = tmp_path / "places.bin", tmp_path / "out.sam"
+    got.tofile(pf)
+    subprocess.run([bw.HOST_BIN, "places2sam", os.path.join(golden, "rep.fa"), os.path.join(synth_text, "synth_hits.fq"), str(pf), str(out)], check=True, stdout=subprocess.DEVNULL)
+    assert open(out, "rb").read() == open(os.path.join(synth_text, f"synth_hits_n{max_mm}.sam"), "rb").read()
+
+
+@pytest.mark.parametrize("order", ["reverse", "seed1", "seed2", "seed3"])
+def test_place_hits_does_not_depend_on_the_order_of_the_gap_runs(rep_ctx, synth, order):
+    """every hit's runs reversed / shuffled inside gap_run[]: the sorting network gets its eight live inputs in other orders, the insertion
+    map is built from disjoint runs - the records are the same"""
+    import random
+    off, alns = map_model.aln_records(synth.reads, "reverse" if order == "reverse" else random.Random(int(order[4:])))
+    changed = (alns["gap_run"] != synth.alns["gap_run"]).any(axis=1)
+    first = np.zeros(len(alns), dtype=bool)
+    first[off[:-1][np.diff(off) > 0].astype(np.int64)] = True
+    assert (changed & first).sum() >= 30  # first hits are the ones k_place sorts
+    same_places(rep_ctx.place_hits(off, alns, 6), synth.want[6][0], order)
+
+
+def test_place_hits_strides_over_more_reads_than_the_grid_has_octets(rep_ctx, synth):
+    """the production path of k_place's loop: more than twice 8 * CUs * 32 reads, so that every octet takes a third read"""
+    cus = compute_units()
+    times = max(200_000, 2 * 8 * cus * 32 + 1) // len(synth.reads) + 1
+    n = times * len(synth.reads)
+    assert n > 2 * 8 * cus * 32 and n >= 200_000
+    off, alns = tiled(synth.off, synth.alns, times)
+    want, steps = synth.want[6]
+    got = rep_ctx.place_hits(off, alns, 6)
+    same_places(got, np.tile(want, times), f"{n} reads on {cus} CUs")
+    assert rep_ctx.place_stats()[:2] == (n, steps * times)
+
+
+@pytest.mark.parametrize("n", [0, 1, 31, 32, 33])
+def test_place_hits_on_a_few_reads(rep_ctx, synth, n):
+    """less than a block, exactly one, one more; and none (no launch)"""
+    mapped = [r for r, e in enumerate(synth.reads) if e]
+    first = mapped[0]  # (so that one read is a read with hits)
+    want, _ = synth.want[6]
+    got = rep_ctx.place_hits(synth.off[first:first + n + 1], synth.alns, 6)
+    same_places(got, want[first:first + n], n)
+    assert len(got) == n and rep_ctx.place_stats()[0] == n
+    if n:
+        assert got["flags"][0] & bw.PLACE_MAPPED
+
+
+def test_place_hits_errors_leave_the_context_usable(built, golden, synth):
+    """hits the kernel must not follow (a first row outside the index) come back as a state error, a hit list that does not ascend is refused
+    on the host; after each the context places the fixture"""
+    b = bw.BwtFile(os.path.join(golden, "rep.fa.bwt"), load_sa=True)
+    ctx = bw.Context(b)
+    want, _ = synth.want[6]
+    try:
+        with pytest.raises(bw.BwbError, match="set_sa"):
+            ctx.place_hits(synth.off, synth.alns)
+        ctx.set_sa(b.SA)
+        target = int(synth.off[[r for r, e in enumerate(synth.reads) if e][5]])
+        for row in (b.length, 2**63):
+            alns = synth.alns.copy()
+            alns["L"][target], alns["U"][target] = row, row
+            with pytest.raises(bw.BwbError, match="error -4.*outside the hit log or the index"):
+                ctx.place_hits(synth.off, alns)
+            same_places(ctx.place_hits(synth.off, synth.alns), want, row)
+        off = synth.off.copy()
+        off[7], off[8] = off[8] + 1, off[7]
+        assert (np.diff(off.astype(np.int64)) < 0).any()
+        with pytest.raises(bw.BwbError, match="error -1.*not ascending"):
+            ctx.place_hits(off, synth.alns)
+        with pytest.raises(ValueError):
+            ctx.place_hits(synth.off, synth.alns[:-1])
+        same_places(ctx.place_hits(synth.off, synth.alns), want)
+        # and the slot interface is untouched by all this
+        seqs, lens = bw.encode_reads(bw.read_fastq(os.path.join(golden, "rep.fq")))
+        ctx.align(bw.params(["-n", "3"]), seqs, lens)
+        a = ctx.place().tobytes()
+        ctx.place_hits(synth.off, synth.alns, 3)
+        assert ctx.place().tobytes() == a and ctx.place_stats()[0] == len(synth.reads)
+    finally:
+        ctx.close()
+
+
 @pytest.fixture(scope="module")
 def map_dir(built, golden, tmp_path_factory):
     """the two golden indexes in a directory of the test's own (`-P` writes <fasta>.pre next to the index)"""
@@ -193,6 +329,14 @@ def test_cli_map_equals_align_then_aln2sam(map_dir, golden, tmp_path, name, fq, 
     cli(["aln2sam", fa, fqp, aln, two])
     assert open(one, "rb").read() == open(two, "rb").read()
     assert os.path.getsize(one) > 1000
+
+
+@pytest.mark.parametrize("max_mm", [6, 3])
+def test_cli_aln2sam_of_the_synthetic_hits_writes_the_reference_sam(map_dir, golden, synth_text, max_mm):
+    """the host's own eval_aln (place_from_alns) and the .aln loader on paths of eight runs and sums that wrap"""
+    out = map_dir / f"synth_aln2sam_{max_mm}.sam"
+    cli(["aln2sam"] + (["-n", "3"] if max_mm == 3 else []) + [map_dir / "rep.fa", os.path.join(synth_text, "synth_hits.fq"), os.path.join(golden, "synth_hits.aln"), out])
+    assert open(out, "rb").read() == open(os.path.join(synth_text, f"synth_hits_n{max_mm}.sam"), "rb").read()
 
 
 @pytest.fixture(scope="module")

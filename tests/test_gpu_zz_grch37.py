@@ -16,6 +16,8 @@ import pytest
 
 import bench
 import bwbble_amd as bw
+import map_model
+import oracle_lib
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -208,3 +210,91 @@ def test_c5_stream_and_rerun_paths_match_the_reference_at_grch37_size(grch37, or
     print(f"[grch37] C5 -o 2 with a 1 GB pool: {st2.n_overflow_reads} of {n2} reads re-run")
     assert got2 == want2, f"-o 2 (32-byte entries) differs from {who2}"
     ctx.close()
+
+
+def sam_body(path):
+    return [ln for ln in open(path, "rb").read().split(b"\n") if ln and not ln.startswith(b"@")]
+
+
+def test_map_and_place_match_the_reference_at_grch37_size(grch37, oracle, tmp_path):
+    """`bwbble map -n 3` and k_place on the GRCh37-scale index: 160 000 reads of 100 bases in one chunk (k_place's grid is at most 8 * CUs * 32
+    = 65 536 octets on a 256-CU part, so its loop strides), the SAM lines of the LAST 5 000 against the reference's `align -n 3` + `aln2sam`
+    on those reads alone (its aln2sam scans all ~1.3 M annotation records per read); where the reference's binary did not travel, against the
+    oracle's .aln -> the model (tests/map_model.py, the oracle's SA) -> `places2sam`.  Then in process: Context.place() of the tail reads ==
+    the model fed with the same reference hits; both strands, more than half of the reads mapped, and 64-bit rows and SA values.
+
+    The text of this index is (6.85 G - 1) / 2 = 3.43 G characters long, so no position in it reaches 2^32 = 4.29 G: what is 64 bits wide
+    here are the first hits' rows and their SA values (every forward-strand read's SA value lies above 3.43 G), from which k_place
+    computes the position; the test asserts those, and that pos is the model's for every read.
+
+    Times on an MI355X box when the test was added (it prints them): map of the 160 000 reads 10 s, the reference's aln2sam on 5 000 reads
+    4 s (0.4 s by the fall-back), the whole test 39 s beside the index build the module's tests share."""
+    fa = grch37
+    n_reads, n_tail = 160_000, 5_000
+    t_start = time.time()
+    fq, tail_fq = str(tmp_path / "map.fq"), str(tmp_path / "tail.fq")
+    subprocess.run([bw.SYNTH_BIN, "reads", fa, fq, str(n_reads), "100", "7171", "1.0", "0.1", "0.0"], check=True)
+    with open(fq) as f, open(tail_fq, "w") as g:
+        g.writelines(f.readlines()[-4 * n_tail:])
+    flags = ["-n", "3"]
+    # one pass on the GPU
+    t0 = time.time()
+    out = str(tmp_path / "map.sam")
+    r = subprocess.run([bw.HOST_BIN, "map"] + flags + [fa, fq, out], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1500)
+    assert r.returncode == 0, r.stdout[-3000:]
+    t_map = time.time() - t0
+    got = sam_body(out)
+    assert len(got) == n_reads
+    # the reference on the tail
+    want_aln, _, who = reference_bytes(fa, tail_fq, flags, str(tmp_path), oracle)
+    hits = oracle_lib.parse_aln(want_aln)
+    assert len(hits) == n_tail
+    idx = oracle.load_index(fa + ".bwt", load_sa=True)
+    want, steps = map_model.expected_places(oracle, idx, hits, 6)
+    ref_sam = str(tmp_path / "ref.sam")
+    t0 = time.time()
+    if who == "oracle/_ref/bwbble":
+        subprocess.run([REF_BIN, "aln2sam", fa, tail_fq, str(tmp_path / "ref.aln"), ref_sam], check=True, stdout=subprocess.DEVNULL, timeout=1500)
+        sam_by = "the reference's aln2sam"
+    else:
+        pf = tmp_path / "places.bin"
+        want.tofile(pf)
+        subprocess.run([bw.HOST_BIN, "places2sam", fa, tail_fq, str(pf), ref_sam], check=True, stdout=subprocess.DEVNULL, timeout=1500)
+        sam_by = "the oracle's hits -> model -> places2sam"
+    t_ref = time.time() - t0
+    print(f"[grch37] map of {n_reads} reads: {t_map:.1f} s; SAM of the last {n_tail} by {sam_by}: {t_ref:.1f} s")
+    ref = sam_body(ref_sam)
+    assert len(ref) == n_tail
+    bad = [k for k in range(n_tail) if got[n_reads - n_tail + k] != ref[k]]
+    assert not bad, (len(bad), got[n_reads - n_tail + bad[0]][:200], ref[bad[0]][:200])
+    # in process: k_place on the library's own hit log of these reads against eval_aln of the reference's hits
+    seqs, lens = bw.load_fastq_codes(tail_fq)
+    b = bw.BwtFile(fa + ".bwt", load_sa=True)
+    ctx = bw.Context(b)
+    try:
+        ctx.set_sa(b.SA)
+        ctx.align(bw.params(flags), seqs, lens)
+        places = ctx.place(6)
+        assert map_model.first_difference(places, want) is None, map_model.first_difference(places, want)
+        assert places.tobytes() == want.tobytes()
+        assert ctx.place_stats()[:2] == (n_tail, steps)
+        # and on the same hits handed in, tiled beyond twice the grid's octets
+        off, alns = map_model.aln_records(hits)
+        times = 150_000 // n_tail + 1
+        toff = np.zeros(n_tail * times + 1, dtype=np.uint64)
+        toff[1:] = np.cumsum(np.tile(np.diff(off), times))
+        assert ctx.place_hits(toff, np.tile(alns, times), 6).tobytes() == np.tile(want, times).tobytes()
+    finally:
+        ctx.close()
+    mapped = (want["flags"] & bw.PLACE_MAPPED) != 0
+    assert mapped.mean() > 0.5
+    rev = (want["flags"] & bw.PLACE_REVERSE) != 0
+    assert (mapped & rev).sum() > n_tail // 10 and (mapped & ~rev).sum() > n_tail // 10
+    length = int(idx.contents.length)
+    if N_FWD >= 2_000_000_000:  # (a smaller index, BWB_TEST_GRCH37_FWD, has nothing 64 bits wide)
+        rows = np.array([e[0]["L"] for e in hits if e], dtype=np.uint64)
+        sa = np.array([map_model.sa_walk(oracle, idx, int(v))[0] for v in rows[:500]], dtype=np.uint64)
+        assert (rows >= 2**32).any() and (rows < 2**32).any() and (sa >= 2**32).any() and (sa < 2**32).any()
+        # a text position of 2^32 and more exists only in a text that long: (6.85 G - 1) / 2 = 3.43 G characters at the default size
+        assert (want["pos"] >= 2**32).any() == ((length - 1) // 2 > 2**32 + 2**28)
+    print(f"[grch37] map + place test: {time.time() - t_start:.0f} s in all, {int(mapped.sum())} of {n_tail} reads mapped")

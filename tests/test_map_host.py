@@ -21,6 +21,9 @@ CASES = {
     "sim_chr21_N100_n2": ("toy.fa", "sim_chr21_N100.fastq", "sim_chr21_N100_n2.aln", "sim_chr21_N100_n2.sam", 6),
     "rep_n3": ("rep.fa", "rep.fq", "rep_n3.aln", "rep_n3.sam", 6),
     "rep_n3_q3": ("rep.fa", "rep.fq", "rep_n3.aln", "rep_n3_q3.sam", 3),
+    # hit lists nobody searched for, judged by the reference's aln2sam (tests/golden/make_golden_map.py): the model's sums wrap like its ints
+    "synth_hits_n6": ("rep.fa", "synth_hits.fq", "synth_hits.aln", "synth_hits_n6.sam", 6),
+    "synth_hits_n3": ("rep.fa", "synth_hits.fq", "synth_hits.aln", "synth_hits_n3.sam", 3),
 }
 
 
@@ -45,6 +48,10 @@ def test_place_record_layout_matches_the_header(built, tmp_path):
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_formatter_writes_the_reference_sam_from_placement_records(built, golden, oracle, tmp_path, name):
+    text = golden
+    if name.startswith("synth_hits"):  # (its text files are committed gzipped)
+        from golden.make_golden_map import unpack_synth
+        text = unpack_synth(tmp_path)
     """placement records computed HERE, in Python, from the reference's .aln and the oracle's SA -> `places2sam` (sam_format_reads, the
     formatter of `map`) -> the reference's .sam, byte for byte"""
     fa, fq, aln, sam, max_mm = CASES[name]
@@ -53,8 +60,8 @@ def test_formatter_writes_the_reference_sam_from_placement_records(built, golden
     places, _ = map_model.expected_places(oracle, idx, reads, max_mm)
     pf, out = tmp_path / "places.bin", tmp_path / "out.sam"
     places.tofile(pf)
-    subprocess.run([bw.HOST_BIN, "places2sam", os.path.join(golden, fa), os.path.join(golden, fq), str(pf), str(out)], check=True, stdout=subprocess.DEVNULL)
-    assert open(out, "rb").read() == open(os.path.join(golden, sam), "rb").read()
+    subprocess.run([bw.HOST_BIN, "places2sam", os.path.join(golden, fa), os.path.join(text, fq), str(pf), str(out)], check=True, stdout=subprocess.DEVNULL)
+    assert open(out, "rb").read() == open(os.path.join(text, sam), "rb").read()
 
 
 def test_repeat_fixture_reaches_every_mapq_outcome(golden):
@@ -75,6 +82,34 @@ def test_repeat_fixture_reaches_every_mapq_outcome(golden):
     assert any(e and e[0]["U"] > e[0]["L"] for e in reads)
     assert sum(1 for e in reads if len(e) > 1) >= 10
     assert any(sum(1 for x in e if x["score"] > e[0]["score"]) >= 2 for e in reads)  # top2 summed over several entries
+
+
+def test_synthetic_hits_fixture_holds_every_case_it_exists_for(golden, oracle):
+    """the committed synth_hits files: read lengths around 64 / 128 / 192, 0-8 gap runs across the words of k_place's insertion map in both
+    orientations, sums at the clamp and wrapped to 1, 0 and below, later hits below the first, 9 and 17 hits, first rows that are special
+    for the walk - every assertion of make_golden_map.check_synth, with the MAPQ values taken from the reference's SAM"""
+    from golden.make_golden_map import check_synth
+    idx = oracle.load_index(os.path.join(golden, "rep.fa.bwt"), load_sa=True)
+    check_synth(oracle, idx, golden)
+
+
+def test_model_sums_wrap_like_the_references_ints():
+    assert [map_model.wrap32(v) for v in (0, 1, 2**31 - 1, 2**31, 2**32 - 1, 2**32, 2**32 + 1, 3 * 2**31)] == [0, 1, 2**31 - 1, -2**31, -1, 0, 1, -2**31]
+
+
+@pytest.mark.parametrize("order", ["natural", "reverse", "shuffled"])
+def test_hit_records_rebuilt_from_the_aln_file_serialise_to_its_bytes(golden, order):
+    """map_model.aln_records (file order -> the bwb_aln records kl_search emits, align-time order) is the inverse of the serialiser: aln_bytes
+    of the rebuilt records == synth_hits.aln byte for byte, whatever the order of the runs inside gap_run[]; and the rep fixture's"""
+    import random
+    for name in ("synth_hits.aln", "rep_n3.aln", "ragged_n4gap.aln"):
+        data = open(os.path.join(golden, name), "rb").read()
+        permute = {"natural": None, "reverse": "reverse", "shuffled": random.Random(5)}[order]
+        off, alns = map_model.aln_records(oracle_lib.parse_aln(data), permute)
+        assert bw.aln_bytes(off, alns) == data, name
+        if name == "synth_hits.aln" and order != "natural":  # the order did change
+            nat = map_model.aln_records(oracle_lib.parse_aln(data))[1]
+            assert (alns["gap_run"] != nat["gap_run"]).any(axis=1).sum() > 50
 
 
 def test_mapq_table_fits_a_byte():
