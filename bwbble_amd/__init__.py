@@ -23,6 +23,7 @@ EXPORTS = [
     "bwb_hip_reset_stats", "bwb_hip_slot_upload", "bwb_hip_slot_submit", "bwb_hip_slot_wait", "bwb_hip_slot_result", "bwb_hip_flush", "bwb_hip_abi_version", "bwb_hip_ctx_create_streamed", "bwb_hip_device_numa_node",
     "bwb_hip_ctx_create_async", "bwb_hip_ctx_index_wait", "bwb_hip_setup_times", "bwb_hip_dtab_info",
     "bwb_hip_slot_place", "bwb_hip_batch_place", "bwb_hip_place_stats", "bwb_hip_place_hits",
+    "bwb_hip_slot_place_alt", "bwb_hip_batch_place_alt", "bwb_hip_place_alt_stats", "bwb_hip_place_hits_alt",
 ]
 ABI_VERSION = 3  # BWB_HIP_ABI_VERSION (include/bwbble_hip.h)
 MAX_SLOTS = 8  # BWB_MAX_SLOTS
@@ -58,6 +59,10 @@ PLACE_DTYPE = np.dtype([("pos", "<u8"), ("top1", "<i4"), ("top2", "<i4"), ("scor
                         ("ref_len", "<u2"), ("reserved2", "<u4"), ("gap_run", "<u2", (8,))])
 assert PLACE_DTYPE.itemsize == 48
 PLACE_MAPPED, PLACE_REVERSE = 1, 2
+# bwb_alt: one of a read's other placements (kernel k_place_alt); flags as in bwb_place
+ALT_DTYPE = np.dtype([("pos", "<u8"), ("flags", "u1"), ("hit", "u1"), ("num_mm", "u1"), ("num_gapo", "u1"), ("num_gape", "u1"),
+                      ("reserved", "u1"), ("aln_length", "<u2"), ("gap_run", "<u2", (8,))])
+assert ALT_DTYPE.itemsize == 32
 
 _FLAG = {"-M": "mm_score", "-O": "gapo_score", "-E": "gape_score", "-n": "max_diff", "-k": "max_diff_seed",
          "-o": "max_gapo", "-e": "max_gape", "-l": "seed_length", "-m": "max_entries", "-t": "n_threads"}
@@ -109,6 +114,10 @@ def lib():
         L.bwb_hip_batch_place.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
         L.bwb_hip_place_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         L.bwb_hip_place_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
+        L.bwb_hip_slot_place_alt.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
+        L.bwb_hip_batch_place_alt.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
+        L.bwb_hip_place_alt_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.bwb_hip_place_hits_alt.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         _lib = L
     return _lib
 
@@ -309,6 +318,44 @@ class Context:
         """(reads, invPsi steps = rank-block visits, kernel ms) of the last place call"""
         n, st, ms = C.c_uint64(), C.c_uint64(), C.c_double()
         _chk(lib().bwb_hip_place_stats(self._h, C.byref(n), C.byref(st), C.byref(ms)))
+        return n.value, st.value, ms.value
+
+    # -- a read's other placements (X0 / X1 / XA): the placement records, and one ALT_DTYPE record per item -------------------
+    @staticmethod
+    def _alts(n, off_ptr, alt_ptr):
+        off = np.frombuffer(C.string_at(off_ptr, (n + 1) * 8), dtype="<u8").copy()
+        total = int(off[n])
+        alts = np.frombuffer(C.string_at(alt_ptr, total * ALT_DTYPE.itemsize), dtype=ALT_DTYPE).copy() if total else np.zeros(0, dtype=ALT_DTYPE)
+        return off, alts
+
+    def slot_place_alt(self, slot, max_mm=6, max_alt=5):
+        """(places, alt_off, alts): slot_place's records, and read r's items alts[alt_off[r]:alt_off[r + 1]] (max_alt: map's -X, 1..255)"""
+        pp, po, pa, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint32()
+        _chk(lib().bwb_hip_slot_place_alt(self._h, slot, max_mm, max_alt, C.byref(pp), C.byref(po), C.byref(pa), C.byref(n)))
+        return (self._places(pp, n.value),) + self._alts(n.value, po, pa)
+
+    def place_alt(self, max_mm=6, max_alt=5):
+        """the same for the one-batch interface (after run() / align())"""
+        pp, po, pa, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint32()
+        _chk(lib().bwb_hip_batch_place_alt(self._h, max_mm, max_alt, C.byref(pp), C.byref(po), C.byref(pa), C.byref(n)))
+        return (self._places(pp, n.value),) + self._alts(n.value, po, pa)
+
+    def place_hits_alt(self, aln_off, alns, max_mm=6, max_alt=5):
+        """the same kernels on a hit list of the caller's (see place_hits)"""
+        aln_off = np.ascontiguousarray(aln_off, dtype=np.uint64)
+        alns = np.ascontiguousarray(alns, dtype=ALN_DTYPE)
+        if len(aln_off) < 1 or (len(aln_off) > 1 and int(aln_off.max()) > len(alns)):
+            raise ValueError("aln_off must hold n_reads + 1 offsets into alns")
+        n = len(aln_off) - 1
+        out = np.zeros(n, dtype=PLACE_DTYPE)
+        po, pa = C.c_void_p(), C.c_void_p()
+        _chk(lib().bwb_hip_place_hits_alt(self._h, alns.ctypes.data, aln_off.ctypes.data, n, max_mm, max_alt, out.ctypes.data, C.byref(po), C.byref(pa)))
+        return (out,) + self._alts(n, po, pa)
+
+    def place_alt_stats(self):
+        """(items, invPsi steps = rank-block visits, kernel ms) of the last place_alt call"""
+        n, st, ms = C.c_uint64(), C.c_uint64(), C.c_double()
+        _chk(lib().bwb_hip_place_alt_stats(self._h, C.byref(n), C.byref(st), C.byref(ms)))
         return n.value, st.value, ms.value
 
     def dtab_info(self):

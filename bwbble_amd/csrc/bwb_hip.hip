@@ -87,6 +87,12 @@ struct Event {
 	hipError_t create() { return e ? hipSuccess : hipEventCreate(&e); }
 };
 
+/* the buffers of one place_alt call: items per read, their exclusive scan, the scan's block sums, the bwb_alt records; and what the host gets */
+struct AltBufs {
+	DevMem d_cnt, d_off, d_bsum, d_alts;
+	PinMem h_off, h_alts;
+};
+
 /* per-lane scratch of one class (class 0 = every resident lane, classes 1/2 = fewer lanes with larger lists) */
 struct ScratchClass {
 	DevMem mem;
@@ -108,6 +114,8 @@ struct Slot {
 	DevMem d_place;               /* bwb_hip_slot_place: one bwb_place per read */
 	PinMem h_place;
 	int placed_mm = -1;           /* h_place holds the records for this max_mm (-1: none) */
+	AltBufs alt;                  /* bwb_hip_slot_place_alt: the items of the slot's reads */
+	int placed_alt = -1;          /* alt holds the items for this max_alt (-1: none) */
 	std::vector<uint8_t> h_status;
 	std::vector<uint64_t> h_aln_off;
 	std::vector<bwb_aln> h_alns;
@@ -153,6 +161,9 @@ struct bwb_hip_ctx {
 	double locate_ms = 0; uint64_t locate_steps = 0, locate_rows = 0; /* the last bwb_hip_locate call */
 	DevMem d_qtab;                      /* k_place: 256 bytes (int)(4.343 * log(n) + 0.5), then its step counter */
 	double place_ms = 0; uint64_t place_steps = 0, place_reads = 0;   /* the last place call */
+	DevMem d_altctl;                    /* k_place_alt: its step counter and its count of flagged items */
+	AltBufs hits_alt;                   /* bwb_hip_place_hits_alt: the items of the caller's hit list */
+	double alt_ms = 0; uint64_t alt_steps = 0, alt_items = 0;         /* the last place_alt call */
 	bool force_slices = false;          /* BWB_FORCE_SLICES: the one-batch API parks and resumes too (tests) */
 	bool dbg = false, dbg_iters = false;
 	const char *launch_log = nullptr;   /* BWB_LAUNCH_LOG=<file>: one JSON line per class-0 kernel launch (synchronises after every launch: a profiling aid) */
@@ -694,7 +705,7 @@ extern "C" int bwb_hip_slot_upload(bwb_hip_ctx *c, int si, const bwb_params *p, 
 	/* (pageable source: the runtime stages it before returning, so h_descs may change again right away) */
 	HIPCHK(hipMemcpyAsync(c->d_descs.as<SlotDesc>() + si, &d, sizeof(SlotDesc), hipMemcpyHostToDevice, c->cstream));
 	HIPCHK(hipEventRecord(s.ev_up.e, c->cstream));
-	s.uploaded = true; s.submitted = false; s.complete = false; s.fetched = false; s.placed_mm = -1;
+	s.uploaded = true; s.submitted = false; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1;
 	return ensure_class(c, 0);
 }
 
@@ -958,7 +969,7 @@ static int submit(bwb_hip_ctx *c, int si, bool suspend) {
 		HIPCHK(hipStreamWaitEvent(c->stream, s.ev_calcd.e, 0));
 	}
 	HIPCHK(hipMemsetAsync(s.d_ctl.p, 0, 256, c->stream));
-	s.submitted = true; s.complete = false; s.fetched = false; s.placed_mm = -1; s.launch = 0;
+	s.submitted = true; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.launch = 0;
 	if (s.n_reads == 0) { s.complete = true; s.launch = c->n_launches; return BWB_OK; }
 	HIPCHK(hipMemsetAsync(s.d_n.p, 0, (size_t)s.n_reads * 4, c->stream));
 	if (!ahead) {
@@ -1543,17 +1554,18 @@ extern "C" int bwb_hip_slot_place(bwb_hip_ctx *c, int si, int max_mm, const bwb_
 }
 
 /* k_place on a hit list of the caller's instead of a slot's hit log (for parity tests): read r owns alns[aln_off[r] .. aln_off[r + 1]) */
-extern "C" int bwb_hip_place_hits(bwb_hip_ctx *c, const bwb_aln *alns, const uint64_t *aln_off, uint32_t n_reads, int max_mm, bwb_place *out) {
-	if (!c || !aln_off || (n_reads && !out)) return fail(BWB_E_ARG, "place_hits: null argument");
-	if (!c->d_SA.p) return fail(BWB_E_STATE, "place_hits: sampled SA not uploaded (bwb_hip_set_sa)");
+static int alt_launch(bwb_hip_ctx *c, const char *who, const uint4 *d_log, uint64_t log_n, const uint64_t *d_off, const uint32_t *d_cnt, uint32_t n, int max_alt, AltBufs &ab);
+/* (max_alt 0: the placement records only; otherwise the items as well, into the context's hits_alt) */
+static int place_hits_impl(bwb_hip_ctx *c, const std::string &who, const bwb_aln *alns, const uint64_t *aln_off, uint32_t n_reads, int max_mm, int max_alt, bwb_place *out) {
+	if (!c->d_SA.p) return fail(BWB_E_STATE, who + ": sampled SA not uploaded (bwb_hip_set_sa)");
 	const uint64_t base = aln_off[0], total = aln_off[n_reads] - base;
 	std::vector<uint64_t> off(n_reads ? n_reads : 1);
 	std::vector<uint32_t> cnt(n_reads ? n_reads : 1);
 	for (uint32_t r = 0; r < n_reads; r++) {
-		if (aln_off[r + 1] < aln_off[r] || aln_off[r + 1] - aln_off[r] > 0xFFFFFFFFull) return fail(BWB_E_ARG, "place_hits: aln_off is not ascending");
+		if (aln_off[r + 1] < aln_off[r] || aln_off[r + 1] - aln_off[r] > 0xFFFFFFFFull) return fail(BWB_E_ARG, who + ": aln_off is not ascending");
 		off[r] = aln_off[r] - base; cnt[r] = (uint32_t)(aln_off[r + 1] - aln_off[r]);
 	}
-	if (total && !alns) return fail(BWB_E_ARG, "place_hits: null argument");
+	if (total && !alns) return fail(BWB_E_ARG, who + ": null argument");
 	HIPCHK(hipSetDevice(c->device));
 	{ int rc = index_ready(c); if (rc) return rc; }
 	static_assert(sizeof(bwb_aln) == 48, "bwb_aln is the hit log's three 16-byte words");
@@ -1568,7 +1580,25 @@ extern "C" int bwb_hip_place_hits(bwb_hip_ctx *c, const bwb_aln *alns, const uin
 		HIPCHK(hipMemcpyAsync(d_cnt.p, cnt.data(), (size_t)n_reads * 4, hipMemcpyHostToDevice, c->rstream));
 		HIPCHK(hipStreamSynchronize(c->rstream)); /* (off / cnt are pageable memory of this call) */
 	}
-	return place_launch(c, "place_hits", d_log.as<uint4>(), total, d_off.as<uint64_t>(), d_cnt.as<uint32_t>(), n_reads, max_mm, d_out.as<uint4>(), out);
+	const int rc = place_launch(c, who.c_str(), d_log.as<uint4>(), total, d_off.as<uint64_t>(), d_cnt.as<uint32_t>(), n_reads, max_mm, d_out.as<uint4>(), out);
+	if (rc || !max_alt) return rc;
+	return alt_launch(c, who.c_str(), d_log.as<uint4>(), total, d_off.as<uint64_t>(), d_cnt.as<uint32_t>(), n_reads, max_alt, c->hits_alt);
+}
+
+extern "C" int bwb_hip_place_hits(bwb_hip_ctx *c, const bwb_aln *alns, const uint64_t *aln_off, uint32_t n_reads, int max_mm, bwb_place *out) {
+	if (!c || !aln_off || (n_reads && !out)) return fail(BWB_E_ARG, "place_hits: null argument");
+	return place_hits_impl(c, "place_hits", alns, aln_off, n_reads, max_mm, 0, out);
+}
+
+extern "C" int bwb_hip_place_hits_alt(bwb_hip_ctx *c, const bwb_aln *alns, const uint64_t *aln_off, uint32_t n_reads, int max_mm, int max_alt, bwb_place *out,
+                                      const uint64_t **alt_off, const bwb_alt **alts) {
+	if (!c || !aln_off || (n_reads && !out) || !alt_off || !alts) return fail(BWB_E_ARG, "place_hits_alt: null argument");
+	if (max_alt < 1 || max_alt > 255) return fail(BWB_E_ARG, "place_hits_alt: max_alt must be 1..255");
+	const int rc = place_hits_impl(c, "place_hits_alt", alns, aln_off, n_reads, max_mm, max_alt, out);
+	if (rc) return rc;
+	*alt_off = c->hits_alt.h_off.as<uint64_t>();
+	*alts = c->hits_alt.h_alts.as<bwb_alt>();
+	return BWB_OK;
 }
 
 extern "C" int bwb_hip_batch_place(bwb_hip_ctx *c, int max_mm, const bwb_place **out, uint32_t *n_reads) {
@@ -1584,6 +1614,102 @@ extern "C" int bwb_hip_place_stats(bwb_hip_ctx *c, uint64_t *reads, uint64_t *st
 	if (reads) *reads = c->place_reads;
 	if (steps) *steps = c->place_steps;
 	if (kernel_ms) *kernel_ms = c->place_ms;
+	return BWB_OK;
+}
+
+/* ---- a read's other placements: bwb_alt records (k_alt_count, the scan, k_place_alt) ------------------------------------------ */
+static_assert(sizeof(bwb_alt) == 32, "bwb_alt is two 16-byte words (k_place_alt)");
+/* The three steps over n reads whose hits are log[off[r] .. off[r] + cnt[r]) -> ab.h_off[n + 1] and ab.h_alts[h_off[n]]; sets the context's
+ * alt_ms / alt_steps / alt_items.  On the result stream, like place_launch.  The only host round trip is the read of the total, which sizes
+ * the record buffers: they hold the items there are, never n * max_alt. */
+static int alt_launch(bwb_hip_ctx *c, const char *who, const uint4 *d_log, uint64_t log_n, const uint64_t *d_off, const uint32_t *d_cnt, uint32_t n, int max_alt, AltBufs &ab) {
+	c->alt_ms = 0; c->alt_steps = 0; c->alt_items = 0;
+	HIPCHK(ab.h_off.reserve(((size_t)n + 1) * 8));
+	ab.h_off.as<uint64_t>()[0] = 0;
+	if (!n) return BWB_OK;
+	const unsigned nblk = (unsigned)(((size_t)n + BWB_BLOCK - 1) / BWB_BLOCK);
+	HIPCHK(ab.d_cnt.reserve((size_t)n * 4));
+	HIPCHK(ab.d_off.reserve(((size_t)n + 1) * 8));
+	HIPCHK(ab.d_bsum.reserve((size_t)nblk * 8));
+	if (!c->d_altctl.p) HIPCHK(c->d_altctl.alloc(16));
+	hipEvent_t ev[4] = { get_event(c), get_event(c), get_event(c), get_event(c) };
+	struct EvGuard {
+		bwb_hip_ctx *c; hipEvent_t *e;
+		~EvGuard() { for (int k = 0; k < 4; k++) if (e[k]) c->free_events.push_back(e[k]); }
+	} evg{ c, ev };
+	if (!ev[0] || !ev[1] || !ev[2] || !ev[3]) return fail(BWB_E_HIP, "hipEventCreate failed");
+	unsigned long long *ctl = c->d_altctl.as<unsigned long long>();
+	uint64_t *d_altoff = ab.d_off.as<uint64_t>();
+	HIPCHK(hipMemsetAsync(ctl, 0, 16, c->rstream));
+	HIPCHK(hipEventRecord(ev[0], c->rstream));
+	hipLaunchKernelGGL(k_alt_count, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, d_log, log_n, d_off, d_cnt, n, (uint32_t)max_alt, ab.d_cnt.as<uint32_t>());
+	hipLaunchKernelGGL(k_scan_blocks, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, ab.d_cnt.as<uint32_t>(), n, d_altoff, ab.d_bsum.as<uint64_t>());
+	hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(BWB_BLOCK), 0, c->rstream, ab.d_bsum.as<uint64_t>(), (uint32_t)nblk, d_altoff + n);
+	hipLaunchKernelGGL(k_scan_add, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, d_altoff, n, ab.d_bsum.as<uint64_t>());
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(ev[1], c->rstream));
+	HIPCHK(hipMemcpyAsync(ab.h_off.p, d_altoff, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	const uint64_t total = ab.h_off.as<uint64_t>()[n];
+	float ms = 0, ms2 = 0;
+	HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+	unsigned long long hctl[2] = { 0, 0 };
+	if (total) {
+		HIPCHK(ab.d_alts.reserve((size_t)total * sizeof(bwb_alt)));
+		HIPCHK(ab.h_alts.reserve((size_t)total * sizeof(bwb_alt)));
+		const unsigned grid = (unsigned)std::min<uint64_t>((total + BWB_OCTS_PER_BLOCK - 1) / BWB_OCTS_PER_BLOCK, (uint64_t)c->num_cu * 8);
+		HIPCHK(hipEventRecord(ev[2], c->rstream));
+		hipLaunchKernelGGL(k_place_alt, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, c->ix, c->d_SA.as<uint64_t>(), c->sa0_index, d_log, log_n, d_off, d_cnt, n,
+		                   (const uint64_t *)d_altoff, total, ab.d_alts.as<uint4>(), ctl);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipEventRecord(ev[3], c->rstream));
+		HIPCHK(hipMemcpyAsync(ab.h_alts.p, ab.d_alts.p, (size_t)total * sizeof(bwb_alt), hipMemcpyDeviceToHost, c->rstream));
+		HIPCHK(hipMemcpyAsync(hctl, ctl, 16, hipMemcpyDeviceToHost, c->rstream));
+		HIPCHK(hipStreamSynchronize(c->rstream));
+		HIPCHK(hipEventElapsedTime(&ms2, ev[2], ev[3]));
+	}
+	c->alt_ms = (double)ms + ms2; c->alt_steps = hctl[0]; c->alt_items = total;
+	if (hctl[1]) return fail(BWB_E_STATE, std::string(who) + ": an alternative's hit lies outside the hit log or its row outside the index");
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_slot_place_alt(bwb_hip_ctx *c, int si, int max_mm, int max_alt, const bwb_place **places, const uint64_t **alt_off, const bwb_alt **alts, uint32_t *n_reads) {
+	if (!c || !places || !alt_off || !alts || !n_reads || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_place_alt: bad argument");
+	if (max_alt < 1 || max_alt > 255) return fail(BWB_E_ARG, "slot_place_alt: max_alt must be 1..255");
+	int rc = bwb_hip_slot_place(c, si, max_mm, places, n_reads); /* (waits for the slot; refuses what slot_place refuses) */
+	if (rc) return rc;
+	Slot &s = c->slots[si];
+	const uint32_t n = s.n_reads;
+	if (s.placed_alt != max_alt || !n) {
+		uint64_t log_n = 0;
+		if (n) {
+			rc = fetch(c, s.h_ctl.p, s.ctl_count(), 8);
+			if (rc) return rc;
+			log_n = std::min<unsigned long long>(*s.h_ctl.as<unsigned long long>(), s.log_cap);
+		}
+		rc = alt_launch(c, "slot_place_alt", s.d_log.as<uint4>(), log_n, s.d_off.as<uint64_t>(), s.d_n.as<uint32_t>(), n, max_alt, s.alt);
+		if (rc) return rc;
+		s.placed_alt = max_alt;
+	}
+	*alt_off = s.alt.h_off.as<uint64_t>();
+	*alts = s.alt.h_alts.as<bwb_alt>();
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_batch_place_alt(bwb_hip_ctx *c, int max_mm, int max_alt, const bwb_place **places, const uint64_t **alt_off, const bwb_alt **alts, uint32_t *n_reads) {
+	if (!c || !places || !alt_off || !alts || !n_reads) return fail(BWB_E_ARG, "batch_place_alt: null argument");
+	if (max_alt < 1 || max_alt > 255) return fail(BWB_E_ARG, "batch_place_alt: max_alt must be 1..255");
+	if (!c->d_SA.p) return fail(BWB_E_STATE, "batch_place_alt: sampled SA not uploaded (bwb_hip_set_sa)");
+	if (!c->slots[0].submitted || !c->slots[0].complete) return fail(BWB_E_STATE, "batch_place_alt: batch_run has not completed");
+	return bwb_hip_slot_place_alt(c, 0, max_mm, max_alt, places, alt_off, alts, n_reads);
+}
+
+/* the last place_alt call: items, invPsi steps and the HIP-event time of its kernels (count + scan + k_place_alt) */
+extern "C" int bwb_hip_place_alt_stats(bwb_hip_ctx *c, uint64_t *items, uint64_t *steps, double *kernel_ms) {
+	if (!c) return fail(BWB_E_ARG, "place_alt_stats: null context");
+	if (items) *items = c->alt_items;
+	if (steps) *steps = c->alt_steps;
+	if (kernel_ms) *kernel_ms = c->alt_ms;
 	return BWB_OK;
 }
 

@@ -318,6 +318,52 @@ __global__ __launch_bounds__(BWB_BLOCK) void k_locate(DevIndex ix, const uint64_
 	}
 }
 
+/* get_aln_length (align.c:748-757) of a hit from its gap runs rw[] (four words of two runs, as the hit log holds them): aln_length minus the
+ * path positions below aln_length that are insertions.  The runs are applied in order like aln_path_bytes does (a later run overwrites an
+ * earlier one), on a 256-bit map: aln_length is 8-bit wrapped.  Shared by k_place and k_place_alt. */
+__device__ __forceinline__ uint32_t place_ref_len(uint32_t alen, const uint32_t rw[4]) {
+	uint64_t ins[4] = { 0, 0, 0, 0 };
+#pragma unroll
+	for (int k = 0; k < 8; k++) {
+		const uint32_t run = (rw[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu;
+		if (run == 0xFFFFu) continue;
+		const uint32_t start = run & 0xFFu, len = (run >> 8) & 0x7Fu, del = run >> 15;
+#pragma unroll
+		for (int q = 0; q < 4; q++) {
+			const int lo = (int)start - 64 * q, hi = lo + (int)len; /* bits [lo, hi) of word q */
+			const int a = lo < 0 ? 0 : lo, b = hi > 64 ? 64 : hi;
+			if (a >= b) continue;
+			const uint64_t m = (b - a == 64 ? ~0ull : ((1ull << (b - a)) - 1ull)) << a;
+			ins[q] = del ? (ins[q] & ~m) : (ins[q] | m);
+		}
+	}
+	uint32_t n_ins = 0;
+#pragma unroll
+	for (int q = 0; q < 4; q++) {
+		const int top = (int)alen - 64 * q;
+		if (top <= 0) continue;
+		n_ins += (uint32_t)__popcll(top >= 64 ? ins[q] : (ins[q] & ((1ull << top) - 1ull)));
+	}
+	return alen - n_ins;
+}
+/* The gap runs as aln2sam sees them: the .aln file holds the path from its end to its start (align.c:363-373) and the loader
+ * fills it in that order (align.c:466-476), so eval_aln and the CIGAR code work on the align-time path REVERSED.  A run
+ * (start, len) of a path of alen positions becomes (alen - start - len, len); ascending by start, unused runs last. */
+__device__ __forceinline__ void place_runs(uint32_t alen, const uint32_t rw[4], uint32_t rr[8]) {
+#pragma unroll
+	for (int k = 0; k < 8; k++) {
+		const uint32_t run = (rw[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu;
+		rr[k] = run == 0xFFFFu ? 0xFFFFu : (((alen - (run & 0xFFu) - ((run >> 8) & 0x7Fu)) & 0xFFu) | (run & 0xFF00u));
+	}
+	if ((rw[0] & rw[1] & rw[2] & rw[3]) != 0xFFFFFFFFu) { /* (a sorting network of 19 exchanges; most hits have no gap at all) */
+#define PLACE_CE(a, b) { const uint32_t ka = rr[a] == 0xFFFFu ? 0x1FFu : (rr[a] & 0xFFu), kb = rr[b] == 0xFFFFu ? 0x1FFu : (rr[b] & 0xFFu); if (ka > kb) { const uint32_t t = rr[a]; rr[a] = rr[b]; rr[b] = t; } }
+		PLACE_CE(0, 2) PLACE_CE(1, 3) PLACE_CE(4, 6) PLACE_CE(5, 7) PLACE_CE(0, 4) PLACE_CE(1, 5) PLACE_CE(2, 6) PLACE_CE(3, 7)
+		PLACE_CE(0, 1) PLACE_CE(2, 3) PLACE_CE(4, 5) PLACE_CE(6, 7) PLACE_CE(2, 4) PLACE_CE(3, 5) PLACE_CE(1, 4) PLACE_CE(3, 6)
+		PLACE_CE(1, 2) PLACE_CE(3, 4) PLACE_CE(5, 6)
+#undef PLACE_CE
+	}
+}
+
 /* eval_aln + mapq (align.c:738-812) for every read of a slot, where its hits lie: one octet per read -> one 48-byte bwb_place record
  * (include/bwbble_hip.h) in read order.  log/off/n are the slot's hit log (bwb_aln: three uint4 per hit, a read's hits contiguous and in
  * discovery order).  All integer: qtab[n] = (int)(4.343 * log(n) + 0.5), tabulated by the host (the only floating point of mapq). */
@@ -350,48 +396,10 @@ __global__ __launch_bounds__(BWB_BLOCK) void k_place(DevIndex ix, const uint64_t
 			t2 += __shfl_xor(t2, 1); t2 += __shfl_xor(t2, 2); t2 += __shfl_xor(t2, 4);
 			const uint64_t L = (uint64_t)e0.x | ((uint64_t)e0.y << 32);
 			const uint32_t num_mm = (e1.x >> 16) & 0xFFu, alen = e1.y >> 16;
-			/* get_aln_length (align.c:748-757): path positions below aln_length that are insertions.  The runs are applied in order like
-			 * aln_path_bytes does (a later run overwrites an earlier one), on a 256-bit map: aln_length is 8-bit wrapped */
-			uint64_t ins[4] = { 0, 0, 0, 0 };
 			const uint32_t rw[4] = { e1.z, e1.w, e2.x, e2.y };
-#pragma unroll
-			for (int k = 0; k < 8; k++) {
-				const uint32_t run = (rw[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu;
-				if (run == 0xFFFFu) continue;
-				const uint32_t start = run & 0xFFu, len = (run >> 8) & 0x7Fu, del = run >> 15;
-#pragma unroll
-				for (int q = 0; q < 4; q++) {
-					const int lo = (int)start - 64 * q, hi = lo + (int)len; /* bits [lo, hi) of word q */
-					const int a = lo < 0 ? 0 : lo, b = hi > 64 ? 64 : hi;
-					if (a >= b) continue;
-					const uint64_t m = (b - a == 64 ? ~0ull : ((1ull << (b - a)) - 1ull)) << a;
-					ins[q] = del ? (ins[q] & ~m) : (ins[q] | m);
-				}
-			}
-			uint32_t n_ins = 0;
-#pragma unroll
-			for (int q = 0; q < 4; q++) {
-				const int top = (int)alen - 64 * q;
-				if (top <= 0) continue;
-				n_ins += (uint32_t)__popcll(top >= 64 ? ins[q] : (ins[q] & ((1ull << top) - 1ull)));
-			}
-			const uint32_t ref_len = alen - n_ins;
-			/* The gap runs as aln2sam sees them: the .aln file holds the path from its end to its start (align.c:363-373) and the loader
-			 * fills it in that order (align.c:466-476), so eval_aln and the CIGAR code work on the align-time path REVERSED.  A run
-			 * (start, len) of a path of alen positions becomes (alen - start - len, len); ascending by start, unused runs last. */
+			const uint32_t ref_len = place_ref_len(alen, rw);
 			uint32_t rr[8];
-#pragma unroll
-			for (int k = 0; k < 8; k++) {
-				const uint32_t run = (rw[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu;
-				rr[k] = run == 0xFFFFu ? 0xFFFFu : (((alen - (run & 0xFFu) - ((run >> 8) & 0x7Fu)) & 0xFFu) | (run & 0xFF00u));
-			}
-			if ((rw[0] & rw[1] & rw[2] & rw[3]) != 0xFFFFFFFFu) { /* (a sorting network of 19 exchanges; most hits have no gap at all) */
-#define PLACE_CE(a, b) { const uint32_t ka = rr[a] == 0xFFFFu ? 0x1FFu : (rr[a] & 0xFFu), kb = rr[b] == 0xFFFFu ? 0x1FFu : (rr[b] & 0xFFu); if (ka > kb) { const uint32_t t = rr[a]; rr[a] = rr[b]; rr[b] = t; } }
-				PLACE_CE(0, 2) PLACE_CE(1, 3) PLACE_CE(4, 6) PLACE_CE(5, 7) PLACE_CE(0, 4) PLACE_CE(1, 5) PLACE_CE(2, 6) PLACE_CE(3, 7)
-				PLACE_CE(0, 1) PLACE_CE(2, 3) PLACE_CE(4, 5) PLACE_CE(6, 7) PLACE_CE(2, 4) PLACE_CE(3, 5) PLACE_CE(1, 4) PLACE_CE(3, 6)
-				PLACE_CE(1, 2) PLACE_CE(3, 4) PLACE_CE(5, 6)
-#undef PLACE_CE
-			}
+			place_runs(alen, rw, rr);
 			if (L >= ix.length) w1.x = PLACE_F_BAD << 24;
 			else {
 				uint64_t j = 0;
@@ -420,5 +428,144 @@ __global__ __launch_bounds__(BWB_BLOCK) void k_place(DevIndex ix, const uint64_t
 		if (ol == 0) dst[0] = w0;
 		else if (ol == 1) dst[1] = w1;
 		else if (ol == 2) dst[2] = w2;
+	}
+}
+
+/* ---- a read's other placements (`map -X N`: the X0 / X1 / XA tags) -----------------------------------------------------------
+ * A read's PLACEMENTS are the rows e[0].L .. e[0].U, then e[1].L .. e[1].U, and so on through its hits in discovery order; placement 0 is
+ * what k_place reports.  T = the number of placements, 64-bit and saturating (a hit with U < L saturates it).  With 2 <= T <= N + 1 the read
+ * lists the placements 1 .. T - 1 as items (BWA's rule: too many placements, no list), one 32-byte bwb_alt record each
+ * (include/bwbble_hip.h).  The work is per item, not per read - most reads own none, a few own up to 255 - so: k_alt_count (items per
+ * read), an exclusive scan of the counts (k_scan_blocks / k_scan_sums / k_scan_add), and k_place_alt with one octet per ITEM. */
+
+/* cnt[r] = (2 <= T <= max_alt + 1) ? T - 1 : 0.  One thread per read; the sum stops as soon as it exceeds max_alt + 1, so a thread reads at
+ * most max_alt + 2 hits.  A read whose hits lie outside the log gets no items (k_place flags the read itself). */
+__global__ __launch_bounds__(BWB_BLOCK) void k_alt_count(const uint4 *log, uint64_t log_n, const uint64_t *off, const uint32_t *n, uint32_t n_reads, uint32_t max_alt, uint32_t *cnt) {
+	const uint32_t r = blockIdx.x * BWB_BLOCK + threadIdx.x;
+	if (r >= n_reads) return;
+	const uint32_t ne = n[r];
+	const uint64_t o = ne ? off[r] : 0;
+	uint64_t T = 0;
+	if (ne && !(o > log_n || ne > log_n - o)) {
+		const uint4 *e = log + o * 3;
+		for (uint32_t t = 0; t < ne && T <= (uint64_t)max_alt + 1; t++) {
+			const uint4 a = e[(size_t)t * 3];
+			const uint64_t L = (uint64_t)a.x | ((uint64_t)a.y << 32), U = (uint64_t)a.z | ((uint64_t)a.w << 32);
+			const uint64_t w = U - L + 1; /* (0 for the interval of every row: saturated as well) */
+			if (U < L || w == 0 || T + w < T) T = ~0ull; else T += w;
+		}
+	}
+	cnt[r] = (T >= 2 && T <= (uint64_t)max_alt + 1) ? (uint32_t)(T - 1) : 0u;
+}
+
+/* Exclusive scan of cnt[0 .. n) into off[0 .. n], off[n] = the total.  k_scan_blocks: every block scans BWB_BLOCK counts - inclusive scan
+ * of each wave by shuffles, the waves' sums through LDS - and leaves the block-local exclusive values in off[] and its sum in bsum[];
+ * k_scan_sums (one block) turns bsum[] into the blocks' offsets and writes the total; k_scan_add adds them.  No host round trip. */
+__global__ __launch_bounds__(BWB_BLOCK) void k_scan_blocks(const uint32_t *cnt, uint32_t n, uint64_t *off, uint64_t *bsum) {
+	__shared__ uint32_t s_wave[BWB_BLOCK / 64];
+	const uint32_t i = blockIdx.x * BWB_BLOCK + threadIdx.x;
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	const uint32_t v = i < n ? cnt[i] : 0u;
+	uint32_t inc = v; /* (a block's sum is at most 256 * 255) */
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(inc, d); if (lane >= d) inc += t; }
+	if (lane == 63) s_wave[wv] = inc;
+	__syncthreads();
+	uint32_t before = 0, total = 0;
+#pragma unroll
+	for (int k = 0; k < BWB_BLOCK / 64; k++) { if (k < wv) before += s_wave[k]; total += s_wave[k]; }
+	if (i < n) off[i] = (uint64_t)(before + inc - v);
+	if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+}
+__global__ __launch_bounds__(BWB_BLOCK) void k_scan_sums(uint64_t *bsum, uint32_t nblk, uint64_t *total_out) {
+	__shared__ uint64_t s_wave[BWB_BLOCK / 64];
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	uint64_t carry = 0;
+	for (uint32_t b0 = 0; b0 < nblk; b0 += BWB_BLOCK) { /* (every thread of the block takes every turn of this loop: the barriers are uniform) */
+		const uint32_t i = b0 + threadIdx.x;
+		const uint64_t v = i < nblk ? bsum[i] : 0ull;
+		uint64_t inc = v;
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) { const uint64_t t = __shfl_up(inc, d); if (lane >= d) inc += t; }
+		if (lane == 63) s_wave[wv] = inc;
+		__syncthreads();
+		uint64_t before = 0, total = 0;
+#pragma unroll
+		for (int k = 0; k < BWB_BLOCK / 64; k++) { if (k < wv) before += s_wave[k]; total += s_wave[k]; }
+		if (i < nblk) bsum[i] = carry + before + inc - v;
+		carry += total;
+		__syncthreads();
+	}
+	if (threadIdx.x == 0) *total_out = carry;
+}
+__global__ __launch_bounds__(BWB_BLOCK) void k_scan_add(uint64_t *off, uint32_t n, const uint64_t *bsum) {
+	const uint32_t i = blockIdx.x * BWB_BLOCK + threadIdx.x;
+	if (i < n) off[i] += bsum[blockIdx.x];
+}
+
+/* eval_aln (align.c:786-801) of item q = placement q - alt_off[r] + 1 of read r, the read found by binary search in alt_off[0 .. n_reads]:
+ * hit h and row L_h + d by a linear scan over the read's hits (at most max_alt + 1 of them come before the last placement), the same walk,
+ * strand rule and position formula as the primary's, that hit's ref_len and reversed gap runs.  One octet per item, grid-strided.  An item
+ * whose row is not a row of the index, or whose hit is not where the counts said, is flagged PLACE_F_BAD and counted in ctl[1]; nothing is
+ * looked up for it.  ctl[0]: invPsi steps, added once per wave. */
+__global__ __launch_bounds__(BWB_BLOCK) void k_place_alt(DevIndex ix, const uint64_t *SA, uint64_t sa0_index, const uint4 *log, uint64_t log_n, const uint64_t *off, const uint32_t *n,
+                                                          uint32_t n_reads, const uint64_t *alt_off, uint64_t n_items, uint4 *out, unsigned long long *ctl) {
+	__shared__ uint64_t s_base[BWB_BASE_ROWS * 16];
+	load_base<uint64_t>(s_base, ix);
+	const int lane = threadIdx.x & 63, ol = lane & 7;
+	const uint64_t noct = (uint64_t)gridDim.x * BWB_OCTS_PER_BLOCK;
+	unsigned long long my_steps = 0, my_bad = 0; /* of this octet's items (kept by its lane 0) */
+	for (uint64_t q = (uint64_t)blockIdx.x * BWB_OCTS_PER_BLOCK + (threadIdx.x >> 3); q < n_items; q += noct) {
+		/* the last read r with alt_off[r] <= q (reads without items share their successor's offset: the last one is the owner) */
+		uint32_t lo = 0, hi = n_reads - 1;
+		while (lo < hi) { const uint32_t mid = lo + ((hi - lo + 1) >> 1); if (alt_off[mid] <= q) lo = mid; else hi = mid - 1; }
+		const uint32_t r = lo, ne = n[r];
+		const uint64_t o = ne ? off[r] : 0;
+		uint64_t k = q - alt_off[r] + 1; /* the placement: the primary is skipped */
+		uint4 w0 = make_uint4(0u, 0u, PLACE_F_BAD, 0u), w1 = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+		bool found = false;
+		uint32_t h = 0;
+		uint64_t row = 0;
+		if (ne && !(o > log_n || ne > log_n - o)) {
+			const uint4 *e = log + o * 3;
+			for (; h < ne && h < 256; h++) {
+				const uint4 a = e[(size_t)h * 3];
+				const uint64_t L = (uint64_t)a.x | ((uint64_t)a.y << 32), U = (uint64_t)a.z | ((uint64_t)a.w << 32);
+				if (U < L) break;
+				const uint64_t w = U - L + 1;
+				if (w == 0 || k < w) { row = L + k; found = row >= L && row < ix.length; break; }
+				k -= w;
+			}
+		}
+		if (found) {
+			const uint4 *e = log + (o + h) * 3;
+			const uint4 e1 = e[1], e2 = e[2];
+			const uint32_t alen = e1.y >> 16;
+			const uint32_t rw[4] = { e1.z, e1.w, e2.x, e2.y };
+			const uint32_t ref_len = place_ref_len(alen, rw);
+			uint32_t rr[8];
+			place_runs(alen, rw, rr);
+			uint64_t j = 0;
+			const uint64_t i = sa_walk(ix, s_base, sa0_index, row, lane, ol, j);
+			const uint64_t rp = (SA[i >> 5] + j) % ix.length;
+			if (ol == 0) my_steps += j;
+			uint32_t flags = PLACE_F_MAPPED;
+			uint64_t pos;
+			if (rp > (ix.length - 1) / 2) pos = ((ix.length - 1) - rp - 1) - (uint64_t)ref_len + 1;
+			else { flags |= PLACE_F_REVERSE; pos = rp; }
+			/* pos | flags hit mm go | ge - alen16 || the runs */
+			w0 = make_uint4((uint32_t)pos, (uint32_t)(pos >> 32), flags | (h << 8) | (e1.x & 0xFFFF0000u), (e1.y & 0xFFu) | (alen << 16));
+			w1 = make_uint4(rr[0] | (rr[1] << 16), rr[2] | (rr[3] << 16), rr[4] | (rr[5] << 16), rr[6] | (rr[7] << 16));
+		} else if (ol == 0) my_bad++;
+		uint4 *dst = out + q * 2;
+		if (ol == 0) dst[0] = w0;
+		else if (ol == 1) dst[1] = w1;
+	}
+	/* one atomic per wave: the eight octets' counts (held by their lanes 0; the other lanes hold zeros) summed by shuffles */
+	my_steps += __shfl_xor(my_steps, 8); my_steps += __shfl_xor(my_steps, 16); my_steps += __shfl_xor(my_steps, 32);
+	my_bad += __shfl_xor(my_bad, 8); my_bad += __shfl_xor(my_bad, 16); my_bad += __shfl_xor(my_bad, 32);
+	if (lane == 0) {
+		if (my_steps) atomicAdd(&ctl[0], my_steps);
+		if (my_bad) atomicAdd(&ctl[1], my_bad);
 	}
 }

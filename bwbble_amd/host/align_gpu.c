@@ -46,7 +46,7 @@ typedef struct chunk {
 } chunk_t;
 
 /* what `map` adds to the pipeline (NULL: align) */
-typedef struct { int max_mm; const fasta_annotations_t *ann; int ann_sorted; } map_t;
+typedef struct { int max_mm; int max_alt /* -X (0: no tags) */; const fasta_annotations_t *ann; int ann_sorted; } map_t;
 
 typedef struct {
 	pthread_mutex_t mu;
@@ -75,6 +75,7 @@ typedef struct {
 	unsigned long long pool_bytes;
 	unsigned long long n_reads; /* reads of the chunks this worker took */
 	double place_ms; unsigned long long place_steps; /* map: k_place, summed over the chunks */
+	double alt_ms; unsigned long long alt_steps, alt_items; /* map -X: k_alt_count + scan + k_place_alt, summed over the chunks */
 } worker_t;
 
 /* The reader: chunk k+1 is parsed (record boundaries by one sequential scan, bases encoded by all cores: reads.c) while chunk k is on
@@ -141,10 +142,15 @@ static void retire_map(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c) {
 	const map_t *m = w->pp->map;
 	const bwb_place *pl = NULL;
 	uint32_t n = 0;
-	if (bwb_hip_slot_place(ctx, slot, m->max_mm, &pl, &n)) bwb_die("map_reads: GPU %d: %s", w->gpu, bwb_hip_last_error());
+	const uint64_t *alt_off = NULL;
+	const bwb_alt *alts = NULL;
+	if (m->max_alt ? bwb_hip_slot_place_alt(ctx, slot, m->max_mm, m->max_alt, &pl, &alt_off, &alts, &n) : bwb_hip_slot_place(ctx, slot, m->max_mm, &pl, &n))
+		bwb_die("map_reads: GPU %d: %s", w->gpu, bwb_hip_last_error());
 	{ uint64_t st = 0; double ms = 0; bwb_hip_place_stats(ctx, NULL, &st, &ms); w->place_ms += ms; w->place_steps += st; }
+	if (m->max_alt) { uint64_t it = 0, st = 0; double ms = 0; bwb_hip_place_alt_stats(ctx, &it, &st, &ms); w->alt_ms += ms; w->alt_steps += st; w->alt_items += it; }
 	const sam_reads_t rd = { .pl = pl, .seq = c->fq.seq, .stride = c->fq.stride, .len = c->fq.len, .text = c->fq.text,
-	                         .name_off = c->fq.name_off, .qual_off = c->fq.qual_off, .name_len = c->fq.name_len, .first = c->first_read };
+	                         .name_off = c->fq.name_off, .qual_off = c->fq.qual_off, .name_len = c->fq.name_len, .first = c->first_read,
+	                         .alt_off = alt_off, .alts = alts };
 	c->n = n;
 	c->n_sam = ((size_t)n + SAM_BLOCK_READS - 1) / SAM_BLOCK_READS;
 	c->sam = (char **)calloc(c->n_sam ? c->n_sam : 1, sizeof(char *));
@@ -367,6 +373,12 @@ static int run_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, 
 		double pms = 0; unsigned long long pst = 0;
 		for (int g = 0; g < n_gpus; g++) { pst += ws[g].place_steps; if (ws[g].place_ms > pms) pms = ws[g].place_ms; }
 		printf("placements on the GPU: reads %llu  rank-block visits %llu  kernel %.3f ms\n", (unsigned long long)pp.n_reads, pst, pms);
+		if (map->max_alt) {
+			double ams = 0; unsigned long long ast = 0, ait = 0;
+			for (int g = 0; g < n_gpus; g++) { ast += ws[g].alt_steps; ait += ws[g].alt_items; if (ws[g].alt_ms > ams) ams = ws[g].alt_ms; }
+			printf("other placements on the GPU (-X %d): items %llu (%.3f per read)  rank-block visits %llu  kernels %.3f ms\n", map->max_alt, ait,
+			       pp.n_reads ? (double)ait / (double)pp.n_reads : 0.0, ast, ams);
+		}
 	}
 	/* where the start-up went (the three overlap): the .bwt file in memory | the index in HBM | the chunk pool's hipMalloc | first slice queued */
 	printf("start-up: .bwt read %.2f sec | index to HBM %.2f sec | chunk pool %.1f GB in %.2f sec | first slice queued after %.2f sec\n",
@@ -413,7 +425,7 @@ int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_
 }
 
 /* `bwbble map`: align_reads + alns2sam in one pass.  The .bwt is loaded once, with its SA; the SAM header is written before the first chunk. */
-int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int n_gpus) {
+int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, int n_gpus) {
 	printf("**** BWBBLE Read Mapping (align + aln2sam in one pass) ****\n");
 	/* before anything is created: without a GPU no SAM file is left behind */
 	if (bwb_hip_device_count() < 1) bwb_die("align_reads_inexact_gpu: no HIP device found (this build has no CPU alignment path)");
@@ -443,7 +455,7 @@ int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *
 	FILE *sam = fopen(samFname, "w");
 	if (!sam) { perror(samFname); bwb_die("map_reads: Cannot open SAM file: %s!", samFname); }
 	sam_write_header(sam, ann);
-	const map_t m = { .max_mm = max_mm, .ann = ann, .ann_sorted = sam_ann_sorted(ann) };
+	const map_t m = { .max_mm = max_mm, .max_alt = max_alt, .ann = ann, .ann_sorted = sam_ann_sorted(ann) };
 	t = wall();
 	printf("BWBBLE Inexact Alignment (MI355X)...\n");
 	run_stream(BWT, readsFname, params, sam, samFname, n_gpus, &m);

@@ -115,14 +115,14 @@ int aln_path_bytes(const bwb_aln *a, unsigned char *path /* >= 272 bytes */); /*
 void set_default_aln_params(aln_params_t *params);                     /* align.c:22-38 */
 int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_t *params, int n_gpus); /* align.c:40-87 */
 int align_reads_inexact_gpu_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, char *alnFname, int n_gpus); /* the GPU's align_reads_inexact_parallel (inexact_match.h:40) over a streamed FASTQ */
-int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int n_gpus); /* `bwbble map`: align + aln2sam in one pass, the hits evaluated on the GPU */
+int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, int n_gpus); /* `bwbble map`: align + aln2sam in one pass, the hits evaluated on the GPU */
 
 /* precalc.c */
 void precalc_sa_intervals(bwt_t *BWT, const aln_params_t *params, const char *preFname); /* align.c:200-224: writes <fasta>.pre */
 int check_precalc_file(const char *preFname); /* the walk of load_precalc_sa_intervals (align.c:226-238) over an existing table: 0 = complete */
 
 /* sam.c */
-void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus); /* align.c:494-556 */
+void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt); /* align.c:494-556; max_alt: -X (0: no tags) */
 /* the two halves of alns2sam: eval_aln of one read on the host, and the text of a block of reads from placement records (which `map` gets
  * from the GPU instead, bwb_hip_slot_place) */
 #define SAM_BLOCK_READS ((size_t)1 << 14)                              /* reads formatted by one thread at a time */
@@ -131,12 +131,15 @@ typedef struct {
 	const uint8_t *seq; uint32_t stride; const uint16_t *len;          /* read->seq codes */
 	const char *text; const size_t *name_off, *qual_off; const uint16_t *name_len; /* names and qualities: offsets into text */
 	size_t first;                                                      /* number of read 0 in the file (error messages) */
+	const uint64_t *alt_off; const bwb_alt *alts;                      /* -X (NULL: no tags): read r's other placements are alts[alt_off[r] .. alt_off[r + 1]) */
 } sam_reads_t;
 void place_from_alns(const bwb_aln *e, uint64_t ne, uint64_t ref_pos, uint64_t bwt_length, int max_mm, bwb_place *out);
+void alt_from_aln(const bwb_aln *e, unsigned hit, uint64_t ref_pos, uint64_t bwt_length, bwb_alt *out); /* one of the other placements, from its hit and SA(its row) */
+uint64_t alt_placements(const bwb_aln *e, uint64_t ne);               /* the rows of all hits: 64-bit, saturating */
 void sam_write_header(FILE *sam, const fasta_annotations_t *ann);
 int sam_ann_sorted(const fasta_annotations_t *ann);
 char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_annotations_t *ann, int ann_sorted, size_t *out_len);
-void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname); /* developer command: records from a file */
+void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname); /* developer command: records from a file (altsFname: NULL or the items) */
 
 
 /* The OpenMP teams of the host stages of `align` / `aln2sam` (base encoding, .aln serialisation, SAM text) have at most 32 threads unless

@@ -29,11 +29,25 @@ static int align_usage(void) {
 }
 
 static int map_usage(void) {
-	printf("Usage: bwbble map [align options] [-Q <int>] [-g <gpus>] <seq_fasta> <reads_fastq> <out_sam> \n");
-	printf("         writes the SAM file that `bwbble align [align options]` followed by `bwbble aln2sam [-n <Q>]` writes, without the .aln file\n");
+	printf("Usage: bwbble map [align options] [-Q <int>] [-X <int>] [-g <gpus>] <seq_fasta> <reads_fastq> <out_sam> \n");
+	printf("         writes the SAM file that `bwbble align [align options]` followed by `bwbble aln2sam [-n <Q>] [-X <N>]` writes, without the .aln file\n");
 	printf("Options: the options of align, and\n");
-	printf("         Q    the mismatch count at which a unique hit gets MAPQ 25 (aln2sam's -n; default: 6)\n\n");
+	printf("         Q    the mismatch count at which a unique hit gets MAPQ 25 (aln2sam's -n; default: 6)\n");
+	printf("         X    1..255: mapped reads get the tags X0:i / X1:i, and a read with 2..X+1 placements lists the others as XA:Z:name,<+|->pos,CIGAR,NM; (default: no tags)\n\n");
 	return 1;
+}
+static int aln2sam_usage(void) {
+	printf("Usage: bwbble aln2sam [-S, -n, -g, -X] <seq_fasta> <reads_fastq> <alns_aln> <out_sam> \n");
+	printf("Options: n    the mismatch count at which a unique hit gets MAPQ 25 (default: 6)\n         g    number of GPUs for the SA lookups (default: 1)\n");
+	printf("         X    1..255: the tags X0:i / X1:i / XA:Z: of `bwbble map -X` (default: no tags)\n\n");
+	return 1;
+}
+/* -X's argument: 1..255, anything else is refused */
+static int alt_option(const char *arg) {
+	char *end;
+	const long v = strtol(arg, &end, 10);
+	if (*arg == 0 || *end != 0 || v < 1 || v > 255) { printf("Error: -X takes a number from 1 to 255 (got '%s')\n", arg); exit(1); }
+	return (int)v;
 }
 
 /* the options `align` and `map` share; 0 = not one of them */
@@ -82,19 +96,21 @@ int main(int argc, char *argv[]) {
 		if (argc < 5) { map_usage(); exit(1); }
 		aln_params_t params;
 		set_default_aln_params(&params);
-		int c, n_gpus = 1, max_mm = 6; /* (aln2sam's default, mg-aligner/main.c:142) */
-		while ((c = getopt(argc - 1, argv + 1, "M:O:E:n:k:o:e:l:m:t:g:SPQ:")) >= 0) {
+		int c, n_gpus = 1, max_mm = 6, max_alt = 0; /* (aln2sam's default, mg-aligner/main.c:142) */
+		while ((c = getopt(argc - 1, argv + 1, "M:O:E:n:k:o:e:l:m:t:g:SPQ:X:")) >= 0) {
 			if (align_option(c, &params, &n_gpus)) continue;
 			if (c == 'Q') { max_mm = atoi(optarg); continue; }
+			if (c == 'X') { max_alt = alt_option(optarg); continue; }
 			if (c == '?') { map_usage(); return 1; }
 			return 1;
 		}
 		if (argc - 1 - optind < 3) { map_usage(); exit(1); }
-		map_reads(argv[optind + 1], argv[optind + 2], argv[optind + 3], &params, max_mm, n_gpus);
+		map_reads(argv[optind + 1], argv[optind + 2], argv[optind + 3], &params, max_mm, max_alt, n_gpus);
 	} else if (strcmp(argv[1], "places2sam") == 0) {
 		/* developer command (CPU only, used by the tests): placement records (bwb_place, include/bwbble_hip.h) from a file -> SAM text */
-		if (argc < 6) { printf("Usage: bwbble places2sam <seq_fasta> <reads_fastq> <places_bin> <out_sam> \n"); exit(1); }
-		places2sam(argv[2], argv[3], argv[4], argv[5]);
+		/* (a sixth argument: u64 alt_off[n + 1] followed by the bwb_alt records - the X tags of `map -X`) */
+		if (argc < 6) { printf("Usage: bwbble places2sam <seq_fasta> <reads_fastq> <places_bin> <out_sam> [<alts_bin>] \n"); exit(1); }
+		places2sam(argv[2], argv[3], argv[4], argv[5], argc >= 7 ? argv[6] : NULL);
 	} else if (strcmp(argv[1], "fasta2ref") == 0) {
 		if (argc < 3) { printf("Usage: bwbble fasta2ref <seq_fasta> \n"); exit(1); }
 		size_t L = strlen(argv[2]) + 8;
@@ -106,10 +122,11 @@ int main(int argc, char *argv[]) {
 		fasta2ref(argv[2], refFname, annFname, &seq, &seqLen);
 		free(seq); free(refFname); free(annFname);
 	} else if (strcmp(argv[1], "aln2sam") == 0) {
-		if (argc < 6) { printf("Usage: bwbble aln2sam [-S, -n, -g] <seq_fasta> <reads_fastq> <alns_aln> <out_sam> \n"); exit(1); }
-		int is_multiref = 1, max_diff = 6, n_gpus = 1, c;
-		while ((c = getopt(argc - 1, argv + 1, "n:g:S")) >= 0) {
+		if (argc < 6) { aln2sam_usage(); exit(1); }
+		int is_multiref = 1, max_diff = 6, n_gpus = 1, max_alt = 0, c;
+		while ((c = getopt(argc - 1, argv + 1, "n:g:SX:")) >= 0) {
 			switch (c) {
+			case 'X': max_alt = alt_option(optarg); break;
 			case 'S': is_multiref = 0; break;
 			case 'n': max_diff = atoi(optarg); break;
 			case 'g': n_gpus = atoi(optarg); break;
@@ -117,7 +134,8 @@ int main(int argc, char *argv[]) {
 			default: return 1;
 			}
 		}
-		alns2sam(argv[optind + 1], argv[optind + 2], argv[optind + 3], argv[optind + 4], is_multiref, max_diff, n_gpus);
+		if (argc - 1 - optind < 4) { aln2sam_usage(); exit(1); }
+		alns2sam(argv[optind + 1], argv[optind + 2], argv[optind + 3], argv[optind + 4], is_multiref, max_diff, n_gpus, max_alt);
 	} else if (strcmp(argv[1], "dumpreads") == 0) {
 		/* developer command (CPU only, used by the tests): what fastq2reads made of a FASTQ - per read "name<TAB>codes<TAB>quality" */
 		if (argc < 4) { printf("Usage: bwbble dumpreads <reads_fastq> <out_tsv> [chunk_reads [text]] \n"); exit(1); }

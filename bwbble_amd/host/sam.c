@@ -55,6 +55,33 @@ void place_from_alns(const bwb_aln *e, uint64_t ne, uint64_t ref_pos, uint64_t b
 	memcpy(out->gap_run, e[0].gap_run, sizeof(out->gap_run));
 }
 
+/* the same for one of the read's other placements (`aln2sam -X`): hit number `hit` of the read and SA(its row), like kernel k_place_alt */
+void alt_from_aln(const bwb_aln *e, unsigned hit, uint64_t ref_pos, uint64_t bwt_length, bwb_alt *out) {
+	memset(out, 0, sizeof(*out));
+	unsigned char path[272];
+	const int alen = aln_path_bytes(e, path);
+	int ref_len = alen;
+	for (int i = 0; i < alen; i++) if (path[i] == 1) ref_len--;
+	out->flags = BWB_PLACE_MAPPED;
+	if (ref_pos > (bwt_length - 1) / 2) out->pos = ((bwt_length - 1) - ref_pos - 1) - (uint64_t)ref_len + 1;
+	else { out->flags |= BWB_PLACE_REVERSE; out->pos = ref_pos; }
+	out->hit = (uint8_t)hit;
+	out->num_mm = e->num_mm; out->num_gapo = e->num_gapo; out->num_gape = e->num_gape;
+	out->aln_length = (uint16_t)alen;
+	memcpy(out->gap_run, e->gap_run, sizeof(out->gap_run));
+}
+
+/* the number of a read's placements - the rows of all its hits - as the X tags count them: 64-bit and saturating, a hit with U < L saturates */
+uint64_t alt_placements(const bwb_aln *e, uint64_t ne) {
+	uint64_t T = 0;
+	for (uint64_t i = 0; i < ne; i++) {
+		const uint64_t w = e[i].U - e[i].L + 1;
+		if (e[i].U < e[i].L || w == 0 || T + w < T) return UINT64_MAX;
+		T += w;
+	}
+	return T;
+}
+
 void sam_write_header(FILE *sam, const fasta_annotations_t *ann) {
 	for (int i = 0; i < ann->num_seq; i++)                                           /* align.c:522-525 */
 		fprintf(sam, "@SQ\tSN:%s\tLN:%d\n", ann->seq_anns[i].name, (int)(ann->seq_anns[i].end_index - ann->seq_anns[i].start_index + 1));
@@ -66,13 +93,50 @@ int sam_ann_sorted(const fasta_annotations_t *ann) { /* records as fasta2ref wri
 	return 1;
 }
 
+/* the record that contains aln_pos, -1: none (align.c:796-801 scans linearly; a multi-genome has a record per bubble - 1.3 M at
+ * GRCh37 scale - and the records are disjoint and in text order, so a binary search finds the same one) */
+static int sam_find_record(const fasta_annotations_t *ann, int ann_sorted, uint64_t aln_pos) {
+	if (ann_sorted) {
+		int lo = 0, hi = ann->num_seq - 1;
+		while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (ann->seq_anns[mid].start_index <= aln_pos) lo = mid; else hi = mid - 1; }
+		if (ann->num_seq > 0 && aln_pos >= ann->seq_anns[lo].start_index && aln_pos <= ann->seq_anns[lo].end_index) return lo;
+		return -1;
+	}
+	for (int i = 0; i < ann->num_seq; i++)
+		if (aln_pos >= ann->seq_anns[i].start_index && aln_pos <= ann->seq_anns[i].end_index) return i;
+	return -1;
+}
+
+/* CIGAR of a path given by its length and gap runs (as bwb_place.gap_run), reversed for the reverse strand: runs of the path walked from
+ * its end to its start (align.c:588-609); returns the end of the text */
+static char *sam_put_cigar(char *o, uint16_t aln_length, const uint16_t *gap_run, int strand) {
+	unsigned char path[272];
+	bwb_aln e0;
+	memset(&e0, 0, sizeof(e0));
+	e0.aln_length = aln_length;
+	memcpy(e0.gap_run, gap_run, sizeof(e0.gap_run));
+	const int alen = aln_path_bytes(&e0, path);
+	if (strand) for (int i = 0; i < alen >> 1; i++) { unsigned char t = path[alen - 1 - i]; path[alen - 1 - i] = path[i]; path[i] = t; }
+	int i = alen - 1;
+	while (i >= 0) {
+		int j = i;
+		while (j >= 0 && path[j] == path[i]) j--;
+		o += sprintf(o, "%d%c", i - j, "MID"[path[i]]);
+		i = j;
+	}
+	return o;
+}
+
 /* print_aln2sam (align.c:562-652) for reads [r0, r1) of rd: placement records + names / bases / qualities + annotations -> SAM text in a
  * malloc'ed buffer.  Shared by aln2sam (records from place_from_alns), map (records from the GPU) and places2sam (records from a file). */
 char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_annotations_t *ann, int ann_sorted, size_t *out_len) {
 	size_t cap = 0;
 	for (size_t r = r0; r < r1; r++) cap += (size_t)rd->name_len[r] + 2 * (size_t)rd->len[r] + MAX_SEQ_NAME_LEN + 160 + 8 * (size_t)rd->pl[r].num_gapo;
+	if (rd->alt_off) { /* the tags: X0 and X1 (two ints), and per item a name, a position, a CIGAR of up to 17 runs and NM */
+		cap += (r1 - r0) * 48;
+		for (uint64_t k = rd->alt_off[r0]; k < rd->alt_off[r1]; k++) cap += MAX_SEQ_NAME_LEN + 64 + 8 * (size_t)rd->alts[k].num_gapo;
+	}
 	char *o = (char *)malloc(cap ? cap : 1), *o0 = o;
-	unsigned char path[272];
 	for (size_t r = r0; r < r1; r++) {
 		const bwb_place *pl = &rd->pl[r];
 		const int len = rd->len[r];
@@ -87,41 +151,32 @@ char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_
 			memcpy(o, qual, (size_t)len); o += len; *o++ = '\n';
 			continue;
 		}
-		bwb_aln e0;
-		memset(&e0, 0, sizeof(e0));
-		e0.aln_length = pl->aln_length;
-		memcpy(e0.gap_run, pl->gap_run, sizeof(e0.gap_run));
-		const int alen = aln_path_bytes(&e0, path);
 		const int strand = (pl->flags & BWB_PLACE_REVERSE) != 0;
 		const uint64_t aln_pos = pl->pos;
-		/* the record that contains aln_pos (align.c:796-801 scans linearly; a multi-genome has a record per bubble - 1.3 M at
-		 * GRCh37 scale - and the records are disjoint and in text order, so a binary search finds the same one) */
-		int seqid = -1;
-		if (ann_sorted) {
-			int lo = 0, hi = ann->num_seq - 1;
-			while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (ann->seq_anns[mid].start_index <= aln_pos) lo = mid; else hi = mid - 1; }
-			if (ann->num_seq > 0 && aln_pos >= ann->seq_anns[lo].start_index && aln_pos <= ann->seq_anns[lo].end_index) seqid = lo;
-		} else
-			for (int i = 0; i < ann->num_seq; i++)
-				if (aln_pos >= ann->seq_anns[i].start_index && aln_pos <= ann->seq_anns[i].end_index) { seqid = i; break; }
+		const int seqid = sam_find_record(ann, ann_sorted, aln_pos);
 		if (seqid < 0) bwb_die("alns2sam: read %zu maps outside every annotated sequence", rd->first + r); /* the reference indexes seq_anns[-1] here */
 		o += sprintf(o, "\t%d\t%s\t%d\t%d\t", strand ? SAM_FSR : 0, ann->seq_anns[seqid].name, (int)(aln_pos - ann->seq_anns[seqid].start_index + 1), (int)pl->mapq);
-		if (strand) for (int i = 0; i < alen >> 1; i++) { unsigned char t = path[alen - 1 - i]; path[alen - 1 - i] = path[i]; path[i] = t; }
-		/* CIGAR: runs of the path walked from its end to its start (align.c:588-609) */
-		int i = alen - 1;
-		while (i >= 0) {
-			int j = i;
-			while (j >= 0 && path[j] == path[i]) j--;
-			o += sprintf(o, "%d%c", i - j, "MID"[path[i]]);
-			i = j;
-		}
+		o = sam_put_cigar(o, pl->aln_length, pl->gap_run, strand);
 		memcpy(o, "\t*\t0\t0\t", 7); o += 7;
 		if (strand) for (int k = 0; k < len; k++) { const int c = seq[len - 1 - k]; o[k] = "AGCTN"[c > 3 ? 4 : 3 - c]; } /* read->rc */
 		else for (int k = 0; k < len; k++) o[k] = "AGCTN"[seq[k]];
 		o += len; *o++ = '\t';
 		if (strand) for (int k = 0; k < len; k++) o[k] = qual[len - 1 - k];
 		else memcpy(o, qual, (size_t)len);
-		o += len; *o++ = '\n';
+		o += len;
+		if (rd->alt_off) { /* -X: the two counters as they are, and the read's other placements (an item outside every record is left out) */
+			o += sprintf(o, "\tX0:i:%d\tX1:i:%d", (int)pl->top1, (int)pl->top2);
+			if (rd->alt_off[r + 1] > rd->alt_off[r]) { memcpy(o, "\tXA:Z:", 6); o += 6; }
+			for (uint64_t k = rd->alt_off[r]; k < rd->alt_off[r + 1]; k++) {
+				const bwb_alt *a = &rd->alts[k];
+				const int sid = sam_find_record(ann, ann_sorted, a->pos);
+				if (sid < 0) continue;
+				o += sprintf(o, "%s,%c%d,", ann->seq_anns[sid].name, (a->flags & BWB_PLACE_REVERSE) ? '-' : '+', (int)(a->pos - ann->seq_anns[sid].start_index + 1));
+				o = sam_put_cigar(o, a->aln_length, a->gap_run, (a->flags & BWB_PLACE_REVERSE) != 0);
+				o += sprintf(o, ",%d;", (int)a->num_mm + (int)a->num_gapo + (int)a->num_gape);
+			}
+		}
+		*o++ = '\n';
 	}
 	*out_len = (size_t)(o - o0);
 	return o0;
@@ -141,7 +196,7 @@ static void *locate_worker(void *arg) {
 	return NULL;
 }
 
-void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus) {
+void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt) {
 	(void)is_multiref;
 	printf("**** BWBBLE Alignment Evaluation/SAM File Generation ****\n");
 	size_t Ln = strlen(fastaFname) + 8;
@@ -158,11 +213,31 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 
 	const size_t n = reads->count < alns->n_reads ? reads->count : alns->n_reads;    /* align.c:535-537 */
 	/* SA(aln.L) of the first entry of every mapped read, on the GPU */
-	uint64_t *rows = (uint64_t *)malloc((n ? n : 1) * 8), *pos = (uint64_t *)malloc((n ? n : 1) * 8);
+	/* -X: the rows of the reads' other placements ride along behind the primaries' (the same rows kernel k_place_alt walks from for `map -X`) */
+	uint64_t *alt_off = NULL;
+	bwb_alt *alts = NULL;
+	if (max_alt) {
+		alt_off = (uint64_t *)calloc(n + 1, 8);
+		for (size_t r = 0; r < n; r++) {
+			const uint64_t T = alt_placements(alns->alns + alns->aln_off[r], alns->aln_off[r + 1] - alns->aln_off[r]);
+			alt_off[r + 1] = alt_off[r] + (T >= 2 && T <= (uint64_t)max_alt + 1 ? T - 1 : 0);
+		}
+		alts = (bwb_alt *)malloc((alt_off[n] ? alt_off[n] : 1) * sizeof(bwb_alt));
+	}
+	const size_t n_alt = max_alt ? (size_t)alt_off[n] : 0, n_rows = n + n_alt;
+	uint64_t *rows = (uint64_t *)malloc((n_rows ? n_rows : 1) * 8), *pos = (uint64_t *)malloc((n_rows ? n_rows : 1) * 8);
 	size_t *which = (size_t *)malloc((n ? n : 1) * sizeof(size_t));
 	size_t nm = 0;
 	for (size_t r = 0; r < n; r++)
 		if (alns->aln_off[r + 1] > alns->aln_off[r]) { rows[nm] = alns->alns[alns->aln_off[r]].L; which[nm] = r; nm++; }
+	const size_t n_prim = nm;
+	for (size_t r = 0; r < n && n_alt; r++) { /* placements 1 .. T - 1: the rest of the first hit's rows, then the later hits' */
+		if (alt_off[r + 1] == alt_off[r]) continue;
+		const bwb_aln *e = alns->alns + alns->aln_off[r];
+		uint64_t left = alt_off[r + 1] - alt_off[r];
+		for (uint64_t h = 0; left; h++)
+			for (uint64_t row = e[h].L + (h == 0); row <= e[h].U && left; row++, left--) rows[nm++] = row;
+	}
 	if (nm) {
 		const int ndev = bwb_hip_device_count();
 		if (ndev < 1) bwb_die("alns2sam: no HIP device found (SA lookups run on the GPU)");
@@ -183,14 +258,22 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 		printf("SA lookups on the GPU: rows %zu  rank-block visits %llu  kernel %.3f ms  (%.2f G visits/s)\n", nm, (unsigned long long)steps, kms, kms > 0 ? steps / kms / 1e6 : 0.0);
 	}
 	uint64_t *ref_pos = (uint64_t *)calloc(n ? n : 1, 8);
-	for (size_t k = 0; k < nm; k++) ref_pos[which[k]] = pos[k];
+	for (size_t k = 0; k < n_prim; k++) ref_pos[which[k]] = pos[k];
+	for (size_t r = 0, k = n_prim; r < n && n_alt; r++) { /* the items, beside place_from_alns below: the same walk over the same rows */
+		if (alt_off[r + 1] == alt_off[r]) continue;
+		const bwb_aln *e = alns->alns + alns->aln_off[r];
+		uint64_t q = alt_off[r];
+		for (uint64_t h = 0; q < alt_off[r + 1]; h++)
+			for (uint64_t row = e[h].L + (h == 0); row <= e[h].U && q < alt_off[r + 1]; row++, q++) alt_from_aln(&e[h], (unsigned)h, pos[k++], BWT->length, &alts[q]);
+	}
 	/* eval_aln for every read, then the text */
 	bwb_place *pl = (bwb_place *)malloc((n ? n : 1) * sizeof(bwb_place));
 #pragma omp parallel for schedule(static) num_threads(bwb_host_team())
 	for (long r = 0; r < (long)n; r++)
 		place_from_alns(alns->alns + alns->aln_off[r], alns->aln_off[r + 1] - alns->aln_off[r], ref_pos[r], BWT->length, max_diff, &pl[r]);
 	const sam_reads_t rd = { .pl = pl, .seq = reads->seq, .stride = reads->stride, .len = reads->len, .text = reads->raw,
-	                         .name_off = reads->name_off, .qual_off = reads->qual_off, .name_len = reads->name_len, .first = 0 };
+	                         .name_off = reads->name_off, .qual_off = reads->qual_off, .name_len = reads->name_len, .first = 0,
+	                         .alt_off = alt_off, .alts = alts };
 	const int ann_sorted = sam_ann_sorted(ann);
 	/* The text: blocks of reads are formatted into memory by all cores and written in order (round 5: one thread's fprintf calls were
 	 * the wall time of aln2sam on a 10 M-read file, not the SA lookups). */
@@ -211,7 +294,7 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 			free(bufs[bi]); bufs[bi] = NULL;
 		}
 	}
-	free(pl);
+	free(pl); free(alt_off); free(alts);
 	free(bufs); free(lens);
 	printf("Processed %zu reads.\n", n);
 	free(rows); free(pos); free(which); free(ref_pos);
@@ -222,7 +305,7 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 
 /* developer command (CPU only, for the tests): raw bwb_place records from a file through sam_format_reads - the formatter `map` uses, on a
  * machine without a GPU */
-void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname) {
+void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname) {
 	size_t Ln = strlen(fastaFname) + 8;
 	char *annFname = (char *)malloc(Ln);
 	snprintf(annFname, Ln, "%s.ann", fastaFname);
@@ -234,11 +317,25 @@ void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *sam
 	const size_t got = fread(pl, sizeof(bwb_place), reads->count, pf);
 	fclose(pf);
 	const size_t n = got < reads->count ? got : reads->count;
+	/* optional: u64 alt_off[n + 1], then alt_off[n] bwb_alt records (what slot_place_alt returns) - the X tags */
+	uint64_t *alt_off = NULL;
+	bwb_alt *alts = NULL;
+	if (altsFname) {
+		FILE *af = fopen(altsFname, "rb");
+		if (!af) { perror(altsFname); bwb_die("places2sam: Cannot open the alternatives file: %s!", altsFname); }
+		alt_off = (uint64_t *)malloc((n + 1) * 8);
+		if (fread(alt_off, 8, n + 1, af) != n + 1) bwb_die("places2sam: %s is shorter than %zu + 1 offsets", altsFname, n);
+		for (size_t r = 0; r < n; r++) if (alt_off[r + 1] < alt_off[r]) bwb_die("places2sam: %s: the offsets do not ascend", altsFname);
+		alts = (bwb_alt *)malloc((alt_off[n] ? alt_off[n] : 1) * sizeof(bwb_alt));
+		if (alt_off[0] != 0 || fread(alts, sizeof(bwb_alt), alt_off[n], af) != alt_off[n]) bwb_die("places2sam: %s does not hold the records its offsets name", altsFname);
+		fclose(af);
+	}
 	FILE *sam = fopen(samFname, "w");
 	if (!sam) { perror(samFname); bwb_die("places2sam: Cannot open SAM file: %s!", samFname); }
 	sam_write_header(sam, ann);
 	const sam_reads_t rd = { .pl = pl, .seq = reads->seq, .stride = reads->stride, .len = reads->len, .text = reads->raw,
-	                         .name_off = reads->name_off, .qual_off = reads->qual_off, .name_len = reads->name_len, .first = 0 };
+	                         .name_off = reads->name_off, .qual_off = reads->qual_off, .name_len = reads->name_len, .first = 0,
+	                         .alt_off = alt_off, .alts = alts };
 	const int ann_sorted = sam_ann_sorted(ann);
 	for (size_t r0 = 0; r0 < n; r0 += SAM_BLOCK_READS) {
 		size_t len = 0;
@@ -247,7 +344,7 @@ void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *sam
 		free(buf);
 	}
 	printf("Processed %zu reads.\n", n);
-	free(pl); free(annFname);
+	free(pl); free(annFname); free(alt_off); free(alts);
 	free_reads(reads); free_ann(ann);
 	fclose(sam);
 }

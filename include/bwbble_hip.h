@@ -225,6 +225,34 @@ int bwb_hip_place_stats(bwb_hip_ctx *ctx, uint64_t *reads, uint64_t *steps, doub
  * For parity tests, like calc_d and rank16.  (Added without a version change: no structure or existing entry point changed.) */
 int bwb_hip_place_hits(bwb_hip_ctx *ctx, const bwb_aln *alns, const uint64_t *aln_off, uint32_t n_reads, int max_mm, bwb_place *out);
 
+/* A read's OTHER placements (`bwbble map -X N`: the X0 / X1 / XA tags).  A read's placements are the rows L .. U of its first hit, then of its
+ * second, and so on in discovery order; placement 0 is the one bwb_place describes.  T = their number (64-bit, saturating; a hit with U < L
+ * saturates it).  With 2 <= T <= max_alt + 1 the read owns the T - 1 items alts[alt_off[r] .. alt_off[r + 1]), placements 1 .. T - 1 in that
+ * order; otherwise none (BWA's rule: too many placements, no list).  Every item is evaluated like the primary (align.c:786-801) from its own
+ * hit and row.  Computed on the GPU per ITEM, not per read: kernels k_alt_count, an exclusive scan, k_place_alt - the buffers hold the items
+ * there are, never n_reads * max_alt.  (Added without a version change: no structure or existing entry point changed.) */
+typedef struct {            /* 32 bytes */
+	uint64_t pos;           /* as bwb_place.pos */
+	uint8_t flags;          /* BWB_PLACE_MAPPED | BWB_PLACE_REVERSE */
+	uint8_t hit;            /* index of the hit in the read's list */
+	uint8_t num_mm, num_gapo, num_gape, reserved;
+	uint16_t aln_length;
+	uint16_t gap_run[BWB_MAX_GAP_RUNS]; /* as bwb_place.gap_run */
+} bwb_alt;
+/* slot_place, then the items of the slot's reads: places as slot_place gives them, alt_off[n_reads + 1] and the items in pinned memory of the
+ * slot, valid until the slot is uploaded again.  max_alt outside 1..255: BWB_E_ARG; no sampled SA: BWB_E_STATE; an item whose row is not a
+ * row of the index: BWB_E_STATE (nothing is looked up for it).  The context stays usable after each.  batch_place_alt is the one-batch form,
+ * place_alt_stats reports the last place_alt call: items, invPsi steps, kernel milliseconds (count + scan + k_place_alt). */
+int bwb_hip_slot_place_alt(bwb_hip_ctx *ctx, int slot, int max_mm, int max_alt, const bwb_place **places, const uint64_t **alt_off,
+                           const bwb_alt **alts, uint32_t *n_reads);
+int bwb_hip_batch_place_alt(bwb_hip_ctx *ctx, int max_mm, int max_alt, const bwb_place **places, const uint64_t **alt_off,
+                            const bwb_alt **alts, uint32_t *n_reads);
+int bwb_hip_place_alt_stats(bwb_hip_ctx *ctx, uint64_t *items, uint64_t *steps, double *kernel_ms);
+/* The same on a hit list of the caller's (see place_hits): n_reads records go to out; alt_off and alts point into memory of the context, valid
+ * until the next place_hits_alt call on it.  For parity tests. */
+int bwb_hip_place_hits_alt(bwb_hip_ctx *ctx, const bwb_aln *alns, const uint64_t *aln_off, uint32_t n_reads, int max_mm, int max_alt,
+                           bwb_place *out, const uint64_t **alt_off, const bwb_alt **alts);
+
 #ifdef __cplusplus
 }
 #endif
