@@ -1068,19 +1068,19 @@ static int rerun_overflows(bwb_hip_ctx *c, int si) {
 		if (k == 1) c->stats.n_overflow_reads += todo.size(); /* (class 2 re-runs a subset of these) */
 		rc = ensure_class(c, k);
 		if (rc) return rc;
-		if (!dids.empty()) { /* calculate_d first: it leaves ST_OK, or ST_D_OVF again (then the next class tries) */
+		if (!dids.empty()) { /* calculate_d first: it leaves ST_OK, or ST_D_OVF again (then the next class tries); ST_D_WAIT reads only need the inheritance */
 			rc = put_worklist(dids);
 			if (rc) return rc;
 			rc = launch_calc_d(c, k, si, s.d_worklist.as<uint32_t>(), (uint32_t)dids.size(), s.ctl_counter2(), nullptr, nullptr);
 			if (rc) return rc;
-			rc = launch_inherit(c, si); /* sources that were late are there now (a read whose source still is not stays ST_D_OVF) */
+			rc = launch_inherit(c, si); /* sources that were late are there now (a read whose source still is not stays ST_D_WAIT) */
 			if (rc) return rc;
 			HIPCHK(hipStreamSynchronize(c->stream));
 			rc = load_status();
 			if (rc) return rc;
 		}
 		list.clear();
-		for (uint32_t i : todo) if (s.h_status[i] != ST_D_OVF) list.push_back(i);
+		for (uint32_t i : todo) if (s.h_status[i] < ST_D_OVF) list.push_back(i);
 		for (int guard = 0; !list.empty(); guard++) {
 			if (guard == 40) return fail(BWB_E_OVERFLOW, "hit log kept overflowing");
 			bool out_ovf = false;

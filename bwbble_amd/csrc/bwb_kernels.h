@@ -20,6 +20,7 @@
 #define ST_SCRATCH_OVF 1  /* heap arena / interval list / hit list too small: re-run in a bigger class */
 #define ST_OUT_OVF 2      /* the slot's hit log is full: host grows it and re-runs the read */
 #define ST_D_OVF 3        /* kl_calc_d: SA-interval list too small; kl_search leaves the read to the re-run of both kernels in a bigger class */
+#define ST_D_WAIT 4       /* k_dseed_inherit: the read's own calculate_d is done, the read its D_seed comes from is ST_D_OVF; kl_search leaves it too */
 
 struct KParams {
 	int max_diff, max_gapo, max_gape, max_entries;
@@ -272,12 +273,14 @@ __global__ void k_dseed_inherit(Batch b, const uint32_t *src, uint32_t n) {
 	if (r >= n) return;
 	const uint32_t q = src[r];
 	if (q == NONE32) return;
-	if (b.status[q] == ST_D_OVF) { b.status[r] = ST_D_OVF; return; } /* its source waits for a larger scratch class: so does this read */
+	/* its source waits for a larger scratch class: so does this read (its own calculate_d is not repeated, unless that overflowed as well) */
+	if (b.status[q] == ST_D_OVF) { if (b.status[r] != ST_D_OVF) b.status[r] = ST_D_WAIT; return; }
 	const int lr = b.lens[r], lq = b.lens[q];
 	uint8_t *rr = b.dbuf + (size_t)r * b.dstride;
 	const uint8_t *rq = b.dbuf + (size_t)q * b.dstride;
 	/* DS of read r at position k (of r) = DS of read q at position k + len_q - len_r (of q): the same seed index */
 	for (int k = -2; k < lr; k++) rec_put(rr, rec_count((uint32_t)lr), 8, k, rec_get(rq, 8, k + lq - lr));
+	if (b.status[r] == ST_D_WAIT) b.status[r] = ST_OK; /* (a re-run class has made the source fit: the search may have the read now) */
 }
 
 /* The invPsi walk from row i to the next sampled row (bwt.c:311-329, SA_INTERVAL = 32, bwt.h:16), by one octet: returns that row and adds

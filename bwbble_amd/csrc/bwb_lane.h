@@ -1388,8 +1388,9 @@ __global__ __launch_bounds__(LANE_BLOCK, LANE_WAVES_PER_SIMD) void kl_search(Dev
 				h.reset(); /* heap_reset :540-546 (bucket states were cleared when the previous read finished) */
 				n_alns = 0; exact_mode = false; active = true;
 				bool ovf0 = false;
-				/* a read whose calculate_d overflowed its scratch class waits for the re-run of both kernels in a larger class */
-				const bool dfail = b.status[rid] == ST_D_OVF;
+				/* a read whose calculate_d overflowed its scratch class - or that of the read its D_seed comes from: ST_D_WAIT - waits for the
+				 * re-run in a larger class */
+				const bool dfail = b.status[rid] >= ST_D_OVF;
 				/* (an EMPTY read is searched like any other: its root entry is a hit with the whole index as its interval, :331-344) */
 				bool skip = cntN > kq.max_diff || unrep || dfail; /* inexact_match.c:260-266 */
 				seeding = false;
