@@ -19,7 +19,7 @@ SYNTH_BIN = os.path.join(HERE, "bin", "bwb_synth")
 EXPORTS = [
     "bwb_hip_device_count", "bwb_hip_last_error", "bwb_default_params", "bwb_hip_ctx_create", "bwb_hip_ctx_destroy",
     "bwb_hip_align_batch", "bwb_hip_batch_upload", "bwb_hip_batch_run", "bwb_hip_batch_result", "bwb_hip_get_stats",
-    "bwb_hip_calc_d", "bwb_hip_rank16", "bwb_hip_rank_bench", "bwb_hip_rank_bench_lane", "bwb_hip_set_sa", "bwb_hip_locate", "bwb_hip_locate_stats",
+    "bwb_hip_calc_d", "bwb_hip_rank16", "bwb_hip_children", "bwb_hip_rank_bench", "bwb_hip_rank_bench_lane", "bwb_hip_set_sa", "bwb_hip_locate", "bwb_hip_locate_stats",
     "bwb_hip_reset_stats", "bwb_hip_slot_upload", "bwb_hip_slot_submit", "bwb_hip_slot_wait", "bwb_hip_slot_result", "bwb_hip_flush", "bwb_hip_abi_version", "bwb_hip_ctx_create_streamed", "bwb_hip_device_numa_node",
     "bwb_hip_ctx_create_async", "bwb_hip_ctx_index_wait", "bwb_hip_setup_times", "bwb_hip_dtab_info",
     "bwb_hip_slot_place", "bwb_hip_batch_place", "bwb_hip_place_stats", "bwb_hip_place_hits",
@@ -97,6 +97,7 @@ def lib():
         L.bwb_hip_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
         L.bwb_hip_calc_d.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.bwb_hip_rank16.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
+        L.bwb_hip_children.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         L.bwb_hip_rank_bench.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
         L.bwb_hip_rank_bench_lane.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
         L.bwb_hip_reset_stats.argtypes = [C.c_void_p]
@@ -269,6 +270,21 @@ class Context:
         out = np.zeros((len(pos), 16), dtype=np.uint64)
         _chk(lib().bwb_hip_rank16(self._h, pos.ctypes.data, len(pos), inc, int(exact), out.ctypes.data))
         return out
+
+    def children(self, iL, iU, need=True, alpha=False):
+        """wave_children by itself: (L, U) as (n, 16) uint64 with column j = child j (column 0 is zero) and the non-empty mask (n,) uint32.
+        Pair q runs as lane q % 64 of wave q / 64: the order of the pairs composes the waves."""
+        iL = np.ascontiguousarray(iL, dtype=np.uint64)
+        iU = np.ascontiguousarray(iU, dtype=np.uint64)
+        n = len(iL)
+        flags = np.ascontiguousarray(np.broadcast_to(np.asarray(need, dtype=bool), (n,)).astype(np.uint8)
+                                     | (np.broadcast_to(np.asarray(alpha, dtype=bool), (n,)).astype(np.uint8) << 1))
+        if len(iU) != n:
+            raise ValueError("iL and iU must have one entry per pair")
+        oL, oU, mask = np.zeros((n, 15), dtype=np.uint64), np.zeros((n, 15), dtype=np.uint64), np.zeros(n, dtype=np.uint32)
+        _chk(lib().bwb_hip_children(self._h, iL.ctypes.data, iU.ctypes.data, flags.ctypes.data, n, oL.ctypes.data, oU.ctypes.data, mask.ctypes.data))
+        z = np.zeros((n, 1), dtype=np.uint64)
+        return np.hstack([z, oL]), np.hstack([z, oU]), mask
 
     def rank_bench(self, n, iters=5, seed=1, lane=False):
         """Random Occ16 micro-benchmark: octet layout (8 lanes share a bucket) or the alignment kernels' lane layout."""

@@ -245,6 +245,10 @@ extern "C" int bwb_hip_ctx_create(int device, const uint64_t hdr[5], const uint6
 	return bwb_hip_ctx_create_streamed(device, hdr, C, bwt, O, nullptr, out);
 }
 
+#ifndef BWB_IDX_CHUNK_SHIFT
+#define BWB_IDX_CHUNK_SHIFT 20          /* blocks per upload chunk = 2^20 (the test build `make testlib` uses 10, so that a few-M-row index is uploaded in
+                                           dozens of chunks - both staging sets, a partial last chunk, superblock starts inside chunks - like a GRCh37-scale one) */
+#endif
 /* the upload: re-layout on the GPU, chunk by chunk behind the caller's loader (runs on the creating thread, or on the context's own
  * thread after bwb_hip_ctx_create_async) */
 static int index_upload(bwb_hip_ctx *c, uint64_t num_words, uint64_t sa0, const uint64_t *C, const uint32_t *bwt, const uint64_t *O, const volatile uint64_t *blocks_ready) {
@@ -257,7 +261,7 @@ static int index_upload(bwb_hip_ctx *c, uint64_t num_words, uint64_t sa0, const 
 	/* 2^20 blocks (128 M characters) per chunk: reference arrays -> 128-character buckets in a staging
 	 * buffer (k_relayout) -> the index's 64-character buckets (k_relayout64); the two staging sets alternate so that the copy
 	 * of chunk k+1 overlaps the kernels of chunk k */
-	const uint64_t CH = 1ull << 20;
+	const uint64_t CH = 1ull << BWB_IDX_CHUNK_SHIFT;
 	DevMem d_bwt[2], d_O[2], d_b128[2], d_sbc;
 	Event ev_k[2];
 	for (int t = 0; t < 2; t++) {
@@ -1377,6 +1381,31 @@ extern "C" int bwb_hip_rank16(bwb_hip_ctx *c, const uint64_t *pos, size_t n, int
 	hipLaunchKernelGGL(k_rank16, dim3(grid), dim3(BWB_BLOCK), 0, c->stream, c->ix, dp.as<uint64_t>(), (uint64_t)n, inc, exact, dout.as<uint64_t>());
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(out, dout.p, n * 128, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	return BWB_OK;
+}
+
+/* wave_children by itself, for parity tests: pair q runs as lane q % 64 of wave q / 64 (kl_children, bwb_lane.h) */
+extern "C" int bwb_hip_children(bwb_hip_ctx *c, const uint64_t *iL, const uint64_t *iU, const uint8_t *flags, size_t n, uint64_t *out_L, uint64_t *out_U, uint32_t *out_mask) {
+	if (!c || (n && (!iL || !iU || !flags || !out_L || !out_U || !out_mask))) return fail(BWB_E_ARG, "children: null argument");
+	if (n == 0) return BWB_OK;
+	for (size_t i = 0; i < n; i++) /* iL - 1 and iU are positions: -1 (iL == 0) .. length - 1 */
+		if (iL[i] > c->ix.length || iU[i] >= c->ix.length || (flags[i] & ~3u)) return fail(BWB_E_ARG, "children: interval out of range or unknown flag");
+	HIPCHK(hipSetDevice(c->device));
+	{ int rc = index_ready(c); if (rc) return rc; }
+	DevMem dL, dU, df, doL, doU, dm;
+	HIPCHK(dL.alloc(n * 8)); HIPCHK(dU.alloc(n * 8)); HIPCHK(df.alloc(n));
+	HIPCHK(doL.alloc(n * 15 * 8)); HIPCHK(doU.alloc(n * 15 * 8)); HIPCHK(dm.alloc(n * 4));
+	HIPCHK(hipMemcpyAsync(dL.p, iL, n * 8, hipMemcpyHostToDevice, c->stream));
+	HIPCHK(hipMemcpyAsync(dU.p, iU, n * 8, hipMemcpyHostToDevice, c->stream));
+	HIPCHK(hipMemcpyAsync(df.p, flags, n, hipMemcpyHostToDevice, c->stream));
+	const unsigned grid = (unsigned)std::min<size_t>((n + LANE_BLOCK - 1) / LANE_BLOCK, (size_t)c->num_cu * 8);
+	if (c->pos32) hipLaunchKernelGGL(kl_children<uint32_t>, dim3(grid), dim3(LANE_BLOCK), 0, c->stream, c->ix, dL.as<uint64_t>(), dU.as<uint64_t>(), df.as<uint8_t>(), (uint64_t)n, doL.as<uint64_t>(), doU.as<uint64_t>(), dm.as<uint32_t>());
+	else hipLaunchKernelGGL(kl_children<uint64_t>, dim3(grid), dim3(LANE_BLOCK), 0, c->stream, c->ix, dL.as<uint64_t>(), dU.as<uint64_t>(), df.as<uint8_t>(), (uint64_t)n, doL.as<uint64_t>(), doU.as<uint64_t>(), dm.as<uint32_t>());
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(out_L, doL.p, n * 15 * 8, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(out_U, doU.p, n * 15 * 8, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(out_mask, dm.p, n * 4, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
 	return BWB_OK;
 }

@@ -2126,3 +2126,40 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_rank_bench_lane(DevIndex ix, uin
 	for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
 	if ((threadIdx.x & 63u) == 0 && acc) atomicAdd(checksum, acc);
 }
+
+/* wave_children by itself (bwb_hip_children, for parity tests): pair q is lane q % 64 of wave q / 64, so a caller composes the waves - which
+ * lanes share a bucket, how many fetch a U row of their own, which are idle.  LDS as in k_rank_bench_lane, with both base tables (load_base2:
+ * alpha lanes read the second) - the layout kl_search gives wave_children, and its template arguments.  Every lane of a wave that holds a
+ * pair calls wave_children, the padding of the last wave with need = false; the fifteen children are read with kid_get. */
+template <typename P>
+__global__ __launch_bounds__(LANE_BLOCK) void kl_children(DevIndex ix, const uint64_t *iL, const uint64_t *iU, const uint8_t *flags, uint64_t n,
+                                                          uint64_t *outL, uint64_t *outU, uint32_t *outMask) {
+	__shared__ P s_base[(BWB_BASE_ROWS + BWB_NSB_MAX) * 16];
+	__shared__ __align__(128) u32x4 s_zero[8];
+	__shared__ __align__(128) u32x4 s_stage[LANE_BLOCK / 64][WAVE_LDS_BYTES / 16]; /* rows + exchange array (rows 128-byte aligned: RowRef) */
+	if (threadIdx.x < 32) ((Lds<uint32_t>)&s_zero[0])[threadIdx.x] = 0u;
+	load_base2<P>(s_base, ix);
+	const uint64_t nl = (uint64_t)gridDim.x * LANE_BLOCK;
+	const int lane = (int)(threadIdx.x & 63u);
+	Lds<u32x4> stage = (Lds<u32x4>)&s_stage[threadIdx.x >> 6][0], zero_row = (Lds<u32x4>)&s_zero[0];
+	const Lds<P> sb = (Lds<P>)&s_base[0];
+	const P last_row = (P)(ix.length - 1);
+	for (uint64_t q = (uint64_t)blockIdx.x * LANE_BLOCK + threadIdx.x; (q & ~63ull) < n; q += nl) { /* whole waves iterate together */
+		const bool in = q < n;
+		const uint32_t f = in ? flags[q] : 0u;
+		const P pL = in ? (P)iL[q] : (P)0, pU = in ? (P)iU[q] : (P)0;
+		uint32_t nbk = 0;
+		KidCtx<P> kc;
+		const uint32_t ne = wave_children<P>(ix.buckets, last_row, (f & 1u) != 0, pL, pU, (f & 2u) != 0, sb, stage, zero_row, lane, nbk, kc);
+		if (in) {
+			outMask[q] = ne;
+#pragma unroll 1
+			for (int j = 1; j < 16; j++) {
+				P L = 0, U = 0;
+				if (f & 1u) kid_get<P>(kc, sb, j, L, U);
+				outL[q * 15 + (j - 1)] = (uint64_t)L; outU[q * 15 + (j - 1)] = (uint64_t)U;
+			}
+		}
+		__builtin_amdgcn_wave_barrier(); /* (the rows are read before the next iteration's gather overwrites them) */
+	}
+}

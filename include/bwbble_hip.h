@@ -175,6 +175,17 @@ int bwb_hip_calc_d(bwb_hip_ctx *ctx, int32_t *out_D, int32_t *out_Dseed);
  * (== C[j] + O(j,pos) + inc, bwt.c:348-372) when exact!=0. out[q][0] is 0. pos may be (uint64_t)-1. */
 int bwb_hip_rank16(bwb_hip_ctx *ctx, const uint64_t *pos, size_t n, int inc, int exact, uint64_t *out);
 
+/* The children of n SA intervals [iL[q], iU[q]] as the alignment kernels compute them (wave_children, bwb_lane.h): child j = 1..15 is
+ * [C[j] + Occ(j, iL - 1) + 1, C[j] + Occ(j, iU)], out_L[q][j - 1] / out_U[q][j - 1]; out_mask[q] has bit j set when child j is not empty (L <= U).
+ * flags[q] bit 0 = need: the lane asks for its children (clear: an idle lane of a busy wave - mask 0, L and U 0); bit 1 = alpha: Occ as O_alphabet
+ * sees it (bwt.c:374-438: the codes 5, 9, 11, 13 of a regular position are C[j] - [first character of the block == j]), exact otherwise.
+ * iL <= length (iL - 1 is a position, -1 for iL == 0), iU < length: the root interval is (0, length - 1).
+ * LANE ORDER: pair q runs as lane q % 64 of wave q / 64 - a wave gathers the buckets of its 64 pairs together, so the caller decides which pairs
+ * share a bucket, how many need a second one (more than 24 take further gather rounds) and which lanes are idle; the last wave is padded with
+ * idle lanes.  For parity tests, like calc_d and rank16.  (Added without a version change: no structure or existing entry point changed.) */
+int bwb_hip_children(bwb_hip_ctx *ctx, const uint64_t *iL, const uint64_t *iU, const uint8_t *flags, size_t n,
+                     uint64_t *out_L, uint64_t *out_U, uint32_t *out_mask);
+
 /* Rank micro-benchmark: `n` pseudo-random Occ16 queries (seeded), repeated `iters` times with
  * everything resident; returns kernel milliseconds per iteration and a checksum of the results. */
 int bwb_hip_rank_bench(bwb_hip_ctx *ctx, size_t n, int iters, uint64_t seed, double *ms_per_iter, uint64_t *checksum);
