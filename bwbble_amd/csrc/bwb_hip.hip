@@ -148,7 +148,7 @@ struct bwb_hip_ctx {
 	SlotDesc h_descs[BWB_MAX_SLOTS]{};
 	ScratchClass cls[3];
 	DevMem d_pool, d_pool_bump;         /* heap chunk pool, POOL_REGIONS equal regions (the re-run classes use it after a drain); bump counters (two sets) */
-	uint32_t keep = 256;                /* chunks of a lane's private run (BWB_KEEP) */
+	uint32_t keep = 256;                /* chunks of a lane's private run */
 	int bpc_search = LANE_WAVES_PER_SIMD, bpc_calcd = LANE_WAVES_PER_SIMD; /* blocks of four waves per CU = waves per SIMD */
 	bool wide = false;                  /* 32-byte heap entries (max_gapo > 1: more than one gap run per path) */
 	bool parked = false;                /* reads may be parked in the class-0 save area (the last class-0 launch was a non-draining slice) */
@@ -487,7 +487,6 @@ static int ensure_class(bwb_hip_ctx *c, int k) {
 			                                        the stationary heaps of 196 608 reads with -n 5 on 150 bp reads fill 60 % of the pool; rounds 3-5 ran two blocks there) */
 			c->bpc_calcd = CALCD_WAVES_PER_SIMD;
 			if (getenv("BWB_BLOCKS_PER_CU")) c->bpc_search = std::max(1, atoi(getenv("BWB_BLOCKS_PER_CU")));
-			if (getenv("BWB_KEEP")) c->keep = (uint32_t)std::max(0, atoi(getenv("BWB_KEEP")));
 			if (getenv("BWB_CALCD_BLOCKS_PER_CU")) c->bpc_calcd = std::max(1, atoi(getenv("BWB_CALCD_BLOCKS_PER_CU")));
 			/* A slice's blocks must all be resident at once: a parked read only moves while its block runs, and a block that had to
 			 * wait for another one to leave would find the cursor exhausted and park again at once.  So never more blocks per CU than

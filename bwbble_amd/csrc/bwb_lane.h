@@ -35,9 +35,7 @@
  * 52.6 KB of LDS per block.  Round 2 ran two (256 registers, 66 KB): the waves spent half their time waiting on memory with the
  * SIMDs' issue slots a third used; the third wave is what the round-3 register and LDS diet (rank from LDS, children in relative
  * form, list selector, window mask of the non-empty buckets, statistics straight to memory) is for. */
-#ifndef LANE_WAVES_PER_SIMD
 #define LANE_WAVES_PER_SIMD 3
-#endif
 /* lane-private LDS columns: explicit LDS address space, so they compile to ds_read/ds_write (a generic or volatile
  * pointer here turns every access into a flat_* instruction with 64-bit addresses and full waits) */
 template <typename P> using Lds = __attribute__((address_space(3))) P *;
@@ -91,9 +89,7 @@ struct LaneScratch {
  *   [11 KB, 11.5 KB) the exchange array of the gather
  * A rank is computed straight from the LDS rows, one 32-character sub-block at a time (four plane words in registers, not the
  * 2 x 32 words of both buckets as in round 2: the two kernels' register budgets are what allows three waves per SIMD). */
-#ifndef NU_MAX
 #define NU_MAX 24 /* compacted U rows per round (a multiple of 8, at most 32: the exchange array holds four per column) */
-#endif
 /* (the number of U rows is a template parameter of the gather: kl_search and kl_calc_d choose their own, CALCD_NU below) */
 #define WAVE_XCH_OFF_NU(nu) ((64 * 8 + (nu) * 8) * 16)
 #define WAVE_LDS_BYTES_NU(nu) (WAVE_XCH_OFF_NU(nu) + 512)
@@ -115,12 +111,8 @@ static_assert(3 * (((LDS_WAVES_OFF + 4 * WAVE_LDS_BYTES + 128 + 256 + LDS_GRANUL
 
 /* kl_calc_d has its own LDS map: the first base table only (exact counts), the zero row, then its waves' areas with CALCD_NU compacted U rows.
  * CALCD_WAVES_PER_SIMD = 4 needs at most 40 960 bytes per block (32 granules): 1 408 + 4 x 9 728 = 40 320 with 8 U rows. */
-#ifndef CALCD_NU
 #define CALCD_NU NU_MAX
-#endif
-#ifndef CALCD_WAVES_PER_SIMD
 #define CALCD_WAVES_PER_SIMD LANE_WAVES_PER_SIMD
-#endif
 #define CALCD_ZERO_OFF (BWB_BASE_ROWS * 16 * 8)
 #define CALCD_WAVES_OFF (CALCD_ZERO_OFF + 128)
 #define LDS_ALIGN_SLACK 128 /* the kernels align their dynamic LDS to 128 bytes themselves */
@@ -129,11 +121,6 @@ static_assert(CALCD_WAVES_PER_SIMD * (((CALCD_LDS_BYTES + LDS_GRANULE - 1) / LDS
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4))); /* (a plain vector: HIP's uint4 class has no LDS-address-space operators) */
 typedef __attribute__((address_space(3))) unsigned char *LdsBytes;
 
-/* cache policy of the bucket loads (aux operand: 1 = sc0, 2 = nt, 16 = sc1).  A non-temporal policy, meant to keep the per-lane
- * metadata in L2, measured 2 % slower at 884 M rows (round 2): left at the default. */
-#ifndef BWB_GATHER_AUX
-#define BWB_GATHER_AUX 0
-#endif
 #define QUIRK_CODES 0x2A20u /* codes 5, 9, 11, 13: not counted by O_alphabet (bwt.c:718-726) */
 
 template <typename P> __device__ __forceinline__ bool pi_regular(P last_row, P pos) { return !(pos == (P)~(P)0 || pos == last_row); }
@@ -201,11 +188,12 @@ __device__ __forceinline__ void wave_gather(const uint4 *__restrict__ buckets, c
 	/* slice of instruction r = p ^ rot(8 r + sub) = p ^ ((sub >> 1) + 4 (r & 1)) = p ^ (sub >> 1) ^ 4 (r & 1): two values, for even and for odd r */
 	const uint32_t sl0 = (uint32_t)(p ^ (sub >> 1)), sl1 = sl0 ^ 4u;
 	const uint32_t oL[8] = { a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w };
+	/* (the loads' cache policy, the last operand, is the default: non-temporal measured 2 % slower, round 2) */
 	if (first == 0) {
 #pragma unroll
 		for (int r = 0; r < 8; r++) {
 			const uint32_t slice = (r & 1) ? sl1 : sl0;
-			__builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)(buckets + (size_t)(oL[r] + slice)), (void __attribute__((address_space(3))) *)(uintptr_t)(sbase + 1024u * r), 16, 0, BWB_GATHER_AUX);
+			__builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)(buckets + (size_t)(oL[r] + slice)), (void __attribute__((address_space(3))) *)(uintptr_t)(sbase + 1024u * r), 16, 0, 0);
 		}
 	}
 	const uint32_t oU[4] = { b0.x, b0.y, b0.z, b0.w };
@@ -213,7 +201,7 @@ __device__ __forceinline__ void wave_gather(const uint4 *__restrict__ buckets, c
 #pragma unroll
 	for (int r = 0; r < NU / 8; r++) {
 		const uint32_t slice = (r & 1) ? sl1 : sl0;
-		if (nU_here > 8 * r) __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)(buckets + (size_t)(oU[r] + slice)), (void __attribute__((address_space(3))) *)(uintptr_t)(sbase + 8192u + 1024u * r), 16, 0, BWB_GATHER_AUX);
+		if (nU_here > 8 * r) __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)(buckets + (size_t)(oU[r] + slice)), (void __attribute__((address_space(3))) *)(uintptr_t)(sbase + 8192u + 1024u * r), 16, 0, 0);
 	}
 	/* (Tried, session 12: the loads as structured-buffer loads - record = slice, idle owners out of range, no exec mask, three instructions
 	 * a load instead of nine.  Correct on every test index and wrong at GRCh37 size: without swizzling the range check works on bytes,
@@ -1242,10 +1230,8 @@ __global__ __launch_bounds__(LANE_BLOCK, LANE_WAVES_PER_SIMD) void kl_search(Dev
 	 * (tools/bbprof.py), each a round trip to the scalar cache in the path of a whole wave.  A value it cannot see through is kept, or parked
 	 * in a VGPR lane and fetched with one v_readlane. */
 	KParams kq = kp;
-#ifndef BWB_NO_KQ
 	asm volatile("" : "+s"(kq.max_diff), "+s"(kq.max_gapo), "+s"(kq.max_gape), "+s"(kq.max_entries), "+s"(kq.mm_score), "+s"(kq.gapo_score), "+s"(kq.gape_score));
 	asm volatile("" : "+s"(kq.seed_length), "+s"(kq.max_diff_seed), "+s"(kq.max_best), "+s"(kq.no_indel_length), "+s"(kq.num_buckets), "+s"(kq.use_precalc));
-#endif
 	const int nb = kq.num_buckets;
 	const uint4 *__restrict__ buckets = ix.buckets;
 	const P last_row = (P)(ix.length - 1);
@@ -1260,11 +1246,7 @@ __global__ __launch_bounds__(LANE_BLOCK, LANE_WAVES_PER_SIMD) void kl_search(Dev
 	h.pXv = h.pX; h.pGov = h.pGo; h.pGev = h.pGe; h.nbkv = nb;
 	if (!WIDE) asm volatile("" : "+v"(h.pXv), "+v"(h.pGov), "+v"(h.pGev), "+v"(h.nbkv)); /* (the 32-byte-entry kernels have no registers to spare: there these stay scalars) */
 	h.far = WIDE && (kq.mm_score > 63 || kq.gapo_score > 63 || kq.gape_score > 63);
-#ifdef BWB_NO_PHANTOM /* (A/B: the round-5 behaviour - every pushed entry is stored) */
-	const bool ph_ok = false;
-#else
 	const bool ph_ok = nb <= 256 && !h.far; /* count-only pushes (see the expansion); wave-uniform */
-#endif
 	h.fhead = NONE32;
 	h.reset();
 
@@ -1455,12 +1437,6 @@ __global__ __launch_bounds__(LANE_BLOCK, LANE_WAVES_PER_SIMD) void kl_search(Dev
 		if (!wany(active)) __builtin_amdgcn_s_sleep(64); /* a wave whose lanes all wait for admission */
 
 		bool finish = false, ovf = false, from_pop = false, need_rank = false, alpha = false, is_group = false;
-#ifdef BWB_PERTURB_VALU /* measurement only: what does the loop pay for 128 more vector instructions per iteration? (profiles/r4_ab_steps.txt) */
-		asm volatile(".rept 128\n\tv_nop\n\t.endr");
-#endif
-#ifdef BWB_PERTURB_SALU
-		asm volatile(".rept 128\n\ts_nop 0\n\t.endr");
-#endif
 		uint32_t ld_cnt = 0; /* heap entries this lane fetches from memory in this iteration */
 		uint32_t pf_top = NONE32, pf_hdr = NONE32, pf_free = NONE32; /* what LHeap::pop wants fetched ahead of the gather; the chunk it emptied */
 		P iL = 0, iU = 0;
@@ -1610,11 +1586,7 @@ __global__ __launch_bounds__(LANE_BLOCK, LANE_WAVES_PER_SIMD) void kl_search(Dev
 			const int g_run = (int)((e.f >> 16) & 255u) - 1;                 /* the run the group's gap belongs to: the children's num_gapo - 1 */
 			const int g_sh = 16 * (g_run & 3) + 15;
 			const bool g_hi = WIDE && g_run >= 4;
-#ifdef BWB_NO_GAP_COMBINE
-			const bool comb = false;
-#else
 			const bool comb = (((g_hi ? gr2 : gr) >> g_sh) & 1ull) == 0ull;
-#endif
 			const int n = __popc(ne) + (comb ? 1 : 0);
 			const uint32_t cst_old = h.cst;
 			const uint32_t st0 = h.reserve(cst_old, n, ovf, xs);
@@ -1716,16 +1688,12 @@ __global__ __launch_bounds__(LANE_BLOCK, LANE_WAVES_PER_SIMD) void kl_search(Dev
 			const int nDel = ph_g ? 0 : nDel_c, nIns = ph_g ? 0 : nIns_c;
 			const uint32_t mism = ph_x ? 0u : mism_c;
 			const int nX = ph_x ? 0 : nX_c;
-#ifdef BWB_NO_GAP_COMBINE /* (A/B: the insertion as its own entry next to the deletion group = rounds 3-5) */
-			const int nG = nIns + (nDel ? 1 : 0);   /* gap entries stored: the deletions as one group (STATE_GROUP) */
-#else
 			/* gap entries stored: ONE.  An expansion that opens gaps pushes the insertion and then the deletions onto the same bucket (:438-463;
 			 * both or neither: `ins_ok` and `del_ok` are the same condition for a STATE_M parent), and all of them derive from the parent's
 			 * interval - so the insertion rides in the deletion group (round 6: a COMBINED group, told by the clear deletion bit of the run it
 			 * opens) and is put in place, below the deletion children, when the group reaches the top of its bucket.  Gap entries were two
 			 * thirds of all entries the round-5 kernel stored at GRCh37 scale, almost none of them ever popped. */
 			const int nG = (nIns | nDel) ? 1 : 0;
-#endif
 #ifdef BWB_HIST
 			{ const int nne = __popc(ne);
 			  HIST(H_NE0, nne == 0); HIST(H_NE1, nne == 1); HIST(H_NE2, nne == 2); HIST(H_NE3_4, nne == 3 || nne == 4); HIST(H_NE5_8, nne >= 5 && nne <= 8); HIST(H_NE9, nne >= 9);
@@ -1788,16 +1756,10 @@ __global__ __launch_bounds__(LANE_BLOCK, LANE_WAVES_PER_SIMD) void kl_search(Dev
 				   * holds the parent's interval (a single deletion child is stored as itself) */
 					uint32_t sg = tG == 0 ? s0 : (tG == 1 ? s1 : s2);
 					const uint32_t fd = f_gap | (uint32_t)(e_i & 255);
-#ifdef BWB_NO_GAP_COMBINE
-					if (nIns) emit(sg, e.L, e.U, f_gap | (uint32_t)((e_i - 1) & 255), (uint32_t)STATE_I | (alen1 << 2), gruns_i, gruns2);
-					if (nDel == 1) { P cl, cu; kid(__ffs((int)delm) - 1, cl, cu); emit(sg, cl, cu, fd, (uint32_t)STATE_D | (alen1 << 2), gruns_d, gruns2_d); }
-					else if (nDel) emit(sg, e.L, e.U, fd, (uint32_t)STATE_GROUP | (alen1 << 2), gruns_d, gruns2_d);
-#else
 					if (nIns && nDel) emit(sg, e.L, e.U, fd, (uint32_t)STATE_GROUP | (alen1 << 2), gruns_i, gruns2); /* combined: the INSERTION's runs (deletion bit clear) */
 					else if (nIns) emit(sg, e.L, e.U, f_gap | (uint32_t)((e_i - 1) & 255), (uint32_t)STATE_I | (alen1 << 2), gruns_i, gruns2);
 					else if (nDel == 1) { P cl, cu; kid(__ffs((int)delm) - 1, cl, cu); emit(sg, cl, cu, fd, (uint32_t)STATE_D | (alen1 << 2), gruns_d, gruns2_d); }
 					else if (nDel) emit(sg, e.L, e.U, fd, (uint32_t)STATE_GROUP | (alen1 << 2), gruns_d, gruns2_d);
-#endif
 					if (tG == 0) s0 = sg; else if (tG == 1) s1 = sg; else s2 = sg;
 				}
 				STAMP(12);

@@ -24,18 +24,21 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "bwbble_amd", "csrc", "bwb_hip.hip")
+# the hipcc command line of the library for every tool that compiles it here (tools/isa_stats.py too); a caller appends `-o <file>` and its own flags
+# (bwbble_amd/Makefile holds the other copy, HIPFLAGS: a flag that changes there changes here)
+HIPCC_CMD = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-function", "-Wno-unused-value", "--save-temps", SRC]
+ASM_NAME = "bwb_hip-hip-amdgcn-amd-amdhsa-gfx950.s"
 
 
 def compile_isa(flags, remarks=None):
     """compiles the library with --save-temps; returns the path of the gfx950 assembly.  remarks: a dict that receives, per kernel symbol,
     the compiler's resource-usage remarks (VGPRs, ScratchSize, SGPRs Spill, VGPRs Spill, Occupancy)"""
     d = tempfile.mkdtemp(prefix="isa_")
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-function", "-Wno-unused-value",
-           "--save-temps", "-Rpass-analysis=kernel-resource-usage", "-o", os.path.join(d, "lib.so"), SRC] + flags
+    cmd = HIPCC_CMD + ["-Rpass-analysis=kernel-resource-usage", "-o", os.path.join(d, "lib.so")] + flags
     r = subprocess.run(cmd, cwd=d, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
     if remarks is not None:
         parse_remarks(r.stderr, remarks)
-    return os.path.join(d, "bwb_hip-hip-amdgcn-amd-amdhsa-gfx950.s")
+    return os.path.join(d, ASM_NAME)
 
 
 def parse_remarks(text, remarks):

@@ -19,17 +19,16 @@ import subprocess
 import sys
 import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "bwbble_amd", "csrc", "bwb_hip.hip")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from check_prefetch_regs import ASM_NAME, HIPCC_CMD, ROOT  # the library's hipcc command line: one list for both tools
 INSTR = re.compile(r"\s+((v|s|ds|global|buffer|flat|scratch)_\w+)")
 
 
 def compile_isa(flags, lines=False):
     d = tempfile.mkdtemp(prefix="isa_")
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-function", "-Wno-unused-value",
-           "--save-temps", "-o", os.path.join(d, "lib.so"), SRC] + flags + (["-gline-tables-only"] if lines else [])
+    cmd = HIPCC_CMD + ["-o", os.path.join(d, "lib.so")] + flags + (["-gline-tables-only"] if lines else [])
     subprocess.run(cmd, cwd=d, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    return os.path.join(d, "bwb_hip-hip-amdgcn-amd-amdhsa-gfx950.s")
+    return os.path.join(d, ASM_NAME)
 
 
 def kernels(path):
