@@ -128,6 +128,24 @@ def _chk(rc):
         raise BwbError(f"bwbble_hip error {rc}: {lib().bwb_hip_last_error().decode()}")
 
 
+def _read_arrays(seqs, lens):
+    """the read codes and lengths as the C-ABI takes them: (n_reads, stride) uint8 rows, one uint16 length per row"""
+    seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+    lens = np.ascontiguousarray(lens, dtype=np.uint16)
+    if seqs.ndim != 2 or len(lens) != seqs.shape[0]:
+        raise ValueError("seqs must be (n_reads, stride) uint8 with one length per row")
+    return seqs, lens
+
+
+def _hit_arrays(aln_off, alns):
+    """a caller's hit list as the C-ABI takes it: n_reads + 1 uint64 offsets into ALN_DTYPE records"""
+    aln_off = np.ascontiguousarray(aln_off, dtype=np.uint64)
+    alns = np.ascontiguousarray(alns, dtype=ALN_DTYPE)
+    if len(aln_off) < 1 or (len(aln_off) > 1 and int(aln_off.max()) > len(alns)):
+        raise ValueError("aln_off must hold n_reads + 1 offsets into alns")
+    return aln_off, alns
+
+
 def device_count():
     return lib().bwb_hip_device_count()
 
@@ -194,10 +212,7 @@ class Context:
 
     # -- batch API ------------------------------------------------------------------------------
     def upload(self, p, seqs, lens):
-        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
-        lens = np.ascontiguousarray(lens, dtype=np.uint16)
-        if seqs.ndim != 2 or len(lens) != seqs.shape[0]:
-            raise ValueError("seqs must be (n_reads, stride) uint8 with one length per row")
+        seqs, lens = _read_arrays(seqs, lens)
         self._keep = (seqs, lens)
         _chk(lib().bwb_hip_batch_upload(self._h, C.byref(p), seqs.ctypes.data, lens.ctypes.data, seqs.shape[0], max(seqs.shape[1], 1)))
 
@@ -207,10 +222,7 @@ class Context:
     # -- streaming API: up to MAX_SLOTS batches resident, slices that park instead of draining ---------------------
     def slot_upload(self, slot, p, seqs, lens, carry=None):
         """carry: codes of the last read longer than the seed that precedes this batch in the file (D_seed of leading short reads)"""
-        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
-        lens = np.ascontiguousarray(lens, dtype=np.uint16)
-        if seqs.ndim != 2 or len(lens) != seqs.shape[0]:
-            raise ValueError("seqs must be (n_reads, stride) uint8 with one length per row")
+        seqs, lens = _read_arrays(seqs, lens)
         carry = None if carry is None else np.ascontiguousarray(carry, dtype=np.uint8)
         _chk(lib().bwb_hip_slot_upload(self._h, slot, C.byref(p), seqs.ctypes.data, lens.ctypes.data, seqs.shape[0], max(seqs.shape[1], 1),
                                        None if carry is None else carry.ctypes.data, 0 if carry is None else len(carry)))
@@ -303,6 +315,12 @@ class Context:
         _chk(lib().bwb_hip_locate(self._h, rows.ctypes.data, len(rows), out.ctypes.data))
         return out
 
+    def _count_steps_ms(self, getter):
+        """(count, steps, kernel ms) of the last call of one kind: locate_stats, place_stats, place_alt_stats"""
+        n, st, ms = C.c_uint64(), C.c_uint64(), C.c_double()
+        _chk(getter(self._h, C.byref(n), C.byref(st), C.byref(ms)))
+        return n.value, st.value, ms.value
+
     # -- placement records: eval_aln + mapq on the GPU (needs set_sa) ----------------------------------------------
     @staticmethod
     def _places(ptr, n):
@@ -322,19 +340,14 @@ class Context:
 
     def place_hits(self, aln_off, alns, max_mm=6):
         """the same kernel on a hit list of the caller's: read r owns alns[aln_off[r]:aln_off[r + 1]] (ALN_DTYPE, discovery order)"""
-        aln_off = np.ascontiguousarray(aln_off, dtype=np.uint64)
-        alns = np.ascontiguousarray(alns, dtype=ALN_DTYPE)
-        if len(aln_off) < 1 or (len(aln_off) > 1 and int(aln_off.max()) > len(alns)):
-            raise ValueError("aln_off must hold n_reads + 1 offsets into alns")
+        aln_off, alns = _hit_arrays(aln_off, alns)
         out = np.zeros(len(aln_off) - 1, dtype=PLACE_DTYPE)
         _chk(lib().bwb_hip_place_hits(self._h, alns.ctypes.data, aln_off.ctypes.data, len(aln_off) - 1, max_mm, out.ctypes.data))
         return out
 
     def place_stats(self):
         """(reads, invPsi steps = rank-block visits, kernel ms) of the last place call"""
-        n, st, ms = C.c_uint64(), C.c_uint64(), C.c_double()
-        _chk(lib().bwb_hip_place_stats(self._h, C.byref(n), C.byref(st), C.byref(ms)))
-        return n.value, st.value, ms.value
+        return self._count_steps_ms(lib().bwb_hip_place_stats)
 
     # -- a read's other placements (X0 / X1 / XA): the placement records, and one ALT_DTYPE record per item -------------------
     @staticmethod
@@ -358,10 +371,7 @@ class Context:
 
     def place_hits_alt(self, aln_off, alns, max_mm=6, max_alt=5):
         """the same kernels on a hit list of the caller's (see place_hits)"""
-        aln_off = np.ascontiguousarray(aln_off, dtype=np.uint64)
-        alns = np.ascontiguousarray(alns, dtype=ALN_DTYPE)
-        if len(aln_off) < 1 or (len(aln_off) > 1 and int(aln_off.max()) > len(alns)):
-            raise ValueError("aln_off must hold n_reads + 1 offsets into alns")
+        aln_off, alns = _hit_arrays(aln_off, alns)
         n = len(aln_off) - 1
         out = np.zeros(n, dtype=PLACE_DTYPE)
         po, pa = C.c_void_p(), C.c_void_p()
@@ -370,9 +380,7 @@ class Context:
 
     def place_alt_stats(self):
         """(items, invPsi steps = rank-block visits, kernel ms) of the last place_alt call"""
-        n, st, ms = C.c_uint64(), C.c_uint64(), C.c_double()
-        _chk(lib().bwb_hip_place_alt_stats(self._h, C.byref(n), C.byref(st), C.byref(ms)))
-        return n.value, st.value, ms.value
+        return self._count_steps_ms(lib().bwb_hip_place_alt_stats)
 
     def dtab_info(self):
         """the context's calculate_d table: {K (0: none), build seconds, bytes}"""
@@ -382,24 +390,22 @@ class Context:
 
     def locate_stats(self):
         """(rows, invPsi steps = rank-block visits, kernel ms) of the last locate()"""
-        n, st, ms = C.c_uint64(), C.c_uint64(), C.c_double()
-        _chk(lib().bwb_hip_locate_stats(self._h, C.byref(n), C.byref(st), C.byref(ms)))
-        return n.value, st.value, ms.value
+        return self._count_steps_ms(lib().bwb_hip_locate_stats)
 
 
 # -- formats ------------------------------------------------------------------------------------
 
+_BASE_LUT = np.full(256, 4, dtype=np.uint8)  # ASCII -> read->seq code (io.h:112-130): A0 G1 C2 T3 in either case, anything else 4
+_BASE_LUT[np.frombuffer(b"AGCTagct", dtype=np.uint8)] = np.arange(8) % 4
+
+
 def encode_reads(ascii_reads):
     """read->seq codes of fastq2reads (io.c:467; io.h:112-130): A0 G1 C2 T3, anything else 4."""
-    lut = np.full(256, 4, dtype=np.uint8)
-    for ch, v in (("A", 0), ("G", 1), ("C", 2), ("T", 3)):
-        lut[ord(ch)] = v
-        lut[ord(ch.lower())] = v
     lens = np.array([len(r) for r in ascii_reads], dtype=np.uint16)
     stride = int(lens.max()) if len(lens) else 1
     seqs = np.full((len(ascii_reads), max(stride, 1)), 4, dtype=np.uint8)
     for i, r in enumerate(ascii_reads):
-        seqs[i, :len(r)] = lut[np.frombuffer(r.encode(), dtype=np.uint8)]
+        seqs[i, :len(r)] = _BASE_LUT[np.frombuffer(r.encode(), dtype=np.uint8)]
     return seqs, lens
 
 
@@ -419,17 +425,13 @@ def load_fastq_codes(path, max_reads=0, chunk=500000):
     s0 = nl[0:4 * n:4] + 1
     lens = (e0 - s0).astype(np.uint16)
     stride = int(lens.max())
-    lut = np.full(256, 4, dtype=np.uint8)
-    for ch, v in (("A", 0), ("G", 1), ("C", 2), ("T", 3)):
-        lut[ord(ch)] = v
-        lut[ord(ch.lower())] = v
     seqs = np.empty((n, stride), dtype=np.uint8)
     cols = np.arange(stride)[None, :]
     for a in range(0, n, chunk):
         b = min(n, a + chunk)
         idx = s0[a:b, None] + cols
         valid = cols < lens[a:b, None]
-        seqs[a:b] = np.where(valid, lut[data[np.minimum(idx, len(data) - 1)]], 4)
+        seqs[a:b] = np.where(valid, _BASE_LUT[data[np.minimum(idx, len(data) - 1)]], 4)
     return seqs, lens
 
 

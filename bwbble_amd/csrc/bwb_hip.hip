@@ -28,6 +28,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 #include "../../include/bwbble_hip.h"
 #include "bwb_kernels.h"
@@ -40,6 +41,12 @@ static int fail(int code, const std::string &m) { g_err = m; return code; }
 	do {                                                                                                  \
 		hipError_t e_ = (x);                                                                              \
 		if (e_ != hipSuccess) return fail(BWB_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_));  \
+	} while (0)
+/* the same for this file's own functions: BWB_OK, or the error code of a call that has set the message */
+#define RC(x)                    \
+	do {                         \
+		const int rc_ = (x);     \
+		if (rc_) return rc_;     \
 	} while (0)
 
 /* device / pinned-host allocations that free themselves: an early error return leaks nothing */
@@ -194,6 +201,13 @@ struct bwb_hip_ctx {
 		if (dstream) (void)hipStreamDestroy(dstream);
 	}
 };
+
+/* The run-time choices among a kernel's instantiations, so that a launch is written once: f(uint32_t{}) or f(uint64_t{}) by the context's
+ * position width, f(std::true_type{}) or f(std::false_type{}) by a flag; f is a generic lambda that names decltype(p) / decltype(b)::value. */
+template <typename F> static auto with_pos(const bwb_hip_ctx *c, F &&f) { return c->pos32 ? f(uint32_t{}) : f(uint64_t{}); }
+template <typename F> static auto with_flag(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+/* grid of a kernel that works in octets of lanes, one item per octet (k_rank16, k_locate, k_place, k_place_alt) */
+static unsigned oct_grid(const bwb_hip_ctx *c, size_t n) { return (unsigned)std::min<size_t>((n + BWB_OCTS_PER_BLOCK - 1) / BWB_OCTS_PER_BLOCK, (size_t)c->num_cu * 8); }
 
 extern "C" const char *bwb_hip_last_error(void) { return g_err.c_str(); }
 static_assert(sizeof(bwb_aln) == 16 * ALN_U4, "bwb_aln is ALN_U4 16-byte words (bwb_lane.h)");
@@ -356,8 +370,7 @@ static int ctx_create(int device, const uint64_t hdr[5], const uint64_t C[17], c
 	c->sa0_index = hdr[4];
 	c->pos32 = length < 0xFFFFFFFFull && !getenv("BWB_FORCE_POS64");
 	if (!async) {
-		int rc = index_upload(c.get(), num_words, hdr[4], C, bwt, O, blocks_ready);
-		if (rc) return rc;
+		RC(index_upload(c.get(), num_words, hdr[4], C, bwt, O, blocks_ready));
 	} else {
 		bwb_hip_ctx *cp = c.get();
 		const uint64_t sa0 = hdr[4];
@@ -382,8 +395,7 @@ extern "C" int bwb_hip_ctx_create_async(int device, const uint64_t hdr[5], const
 
 extern "C" int bwb_hip_ctx_index_wait(bwb_hip_ctx *c, double *seconds) {
 	if (!c) return fail(BWB_E_ARG, "ctx_index_wait: null context");
-	int rc = index_ready(c);
-	if (rc) return rc;
+	RC(index_ready(c));
 	if (seconds) *seconds = c->idx_seconds;
 	return BWB_OK;
 }
@@ -499,14 +511,15 @@ static int ensure_class(bwb_hip_ctx *c, int k) {
 				const size_t need = ((fa.sharedSizeBytes + dyn + LDS_GRANULE - 1) / LDS_GRANULE) * LDS_GRANULE;
 				return (int)std::max<size_t>(1, LDS_CU_BYTES / need);
 			};
-			const void *kf = c->pos32 ? (c->wide ? (const void *)kl_search<uint32_t, true, true> : (const void *)kl_search<uint32_t, false, true>)
-			                          : (c->wide ? (const void *)kl_search<uint64_t, true, true> : (const void *)kl_search<uint64_t, false, true>); /* (the -S instantiations need no more) */
+			const void *kf = with_pos(c, [&](auto p) { /* (the -S instantiations need no more) */
+				return with_flag(c->wide, [](auto w) { return (const void *)kl_search<decltype(p), decltype(w)::value, true>; });
+			});
 			if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kf, LANE_BLOCK, lane_lds(c)) == hipSuccess && occ >= 1) {
 				if (c->dbg && !s.ready) fprintf(stderr, "[bwb] kl_search: %d block(s) of %d threads fit a CU\n", occ, LANE_BLOCK);
 				c->bpc_search = std::min(c->bpc_search, std::min(occ, lds_fit(kf, lane_lds(c))));
 				if (c->dbg && !s.ready && lds_fit(kf, lane_lds(c)) < occ) fprintf(stderr, "[bwb] kl_search: only %d block(s) per CU by LDS granules\n", lds_fit(kf, lane_lds(c)));
 			}
-			const void *kd = c->pos32 ? (const void *)kl_calc_d<uint32_t> : (const void *)kl_calc_d<uint64_t>;
+			const void *kd = with_pos(c, [](auto p) { return (const void *)kl_calc_d<decltype(p)>; });
 			if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kd, LANE_BLOCK, calcd_lds()) == hipSuccess && occ >= 1) {
 				c->bpc_calcd = std::min(c->bpc_calcd, std::min(occ, lds_fit(kd, calcd_lds())));
 				if (c->dbg && !s.ready) fprintf(stderr, "[bwb] kl_calc_d: %d block(s) per CU (occupancy query %d, LDS granules %d)\n", c->bpc_calcd, occ, lds_fit(kd, calcd_lds()));
@@ -560,6 +573,29 @@ static hipEvent_t get_event(bwb_hip_ctx *c) {
 	return e;
 }
 
+/* One timed region of a stream: two events of the context's pool, recorded around it.  Both go back to the pool on every way out (one
+ * alone too, when the other could not be created) - unless the span has been handed to c->pending, whose events resolve_times returns
+ * once the launch has finished. */
+struct Timed {
+	bwb_hip_ctx *c;
+	hipStream_t st;
+	hipEvent_t e0 = nullptr, e1 = nullptr;
+	bool own = true;
+	Timed(bwb_hip_ctx *c_, hipStream_t st_) : c(c_), st(st_) {}
+	Timed(const Timed &) = delete;
+	Timed &operator=(const Timed &) = delete;
+	~Timed() { if (own && e0) c->free_events.push_back(e0); if (own && e1) c->free_events.push_back(e1); }
+	int begin() {
+		e0 = get_event(c); e1 = get_event(c);
+		if (!e0 || !e1) return fail(BWB_E_HIP, "hipEventCreate failed");
+		HIPCHK(hipEventRecord(e0, st));
+		return BWB_OK;
+	}
+	int end() { HIPCHK(hipEventRecord(e1, st)); return BWB_OK; }
+	int ms(float *out) const { HIPCHK(hipEventElapsedTime(out, e0, e1)); return BWB_OK; } /* (after the stream, or e1, has been waited for) */
+	void defer(int kind) { c->pending.push_back(PendingTime{ e0, e1, kind }); own = false; } /* kind: PendingTime */
+};
+
 /* adds the HIP-event time of every finished launch to the statistics (all of them when `all`: the stream must be idle then) */
 static int resolve_times(bwb_hip_ctx *c, bool all) {
 	size_t w = 0;
@@ -602,7 +638,7 @@ extern "C" int bwb_hip_flush(bwb_hip_ctx *c) {
 	if (!c) return fail(BWB_E_ARG, "flush: null context");
 	HIPCHK(hipSetDevice(c->device));
 	for (int s = 0; s < BWB_MAX_SLOTS; s++)
-		if (c->slots[s].submitted && !c->slots[s].complete) { int rc = slot_wait(c, s); if (rc) return rc; }
+		if (c->slots[s].submitted && !c->slots[s].complete) RC(slot_wait(c, s));
 	HIPCHK(hipStreamSynchronize(c->stream));
 	return resolve_times(c, true);
 }
@@ -611,20 +647,19 @@ extern "C" int bwb_hip_slot_upload(bwb_hip_ctx *c, int si, const bwb_params *p, 
                                    uint32_t n_reads, uint32_t stride, const uint8_t *carry_seq, uint32_t carry_len) {
 	if (!c || !p || si < 0 || si >= BWB_MAX_SLOTS || (n_reads && (!reads_fwd || !lens)) || stride == 0) return fail(BWB_E_ARG, "slot_upload: bad argument");
 	int nb = 0;
-	int rc = check_params(p, &nb);
-	if (rc) return rc;
+	RC(check_params(p, &nb));
 	HIPCHK(hipSetDevice(c->device));
 	Slot &s = c->slots[si];
-	if (s.submitted && !s.complete) { rc = slot_wait(c, si); if (rc) return rc; } /* the slot is being reused */
+	if (s.submitted && !s.complete) RC(slot_wait(c, si)); /* the slot is being reused */
 	if (s.uploaded) HIPCHK(hipEventSynchronize(s.ev_up.e)); /* its previous H2D copy has left the pinned staging buffers */
 	if (s.calcd_queued && !s.submitted) HIPCHK(hipStreamSynchronize(c->dstream)); /* (uploaded, its kl_calc_d queued ahead, never submitted: that kernel reads the buffers) */
 	s.calcd_queued = false;
 	/* every slot in flight runs under the same parameters (they are launch arguments) */
-	if (c->have_params && memcmp(&c->p, p, sizeof(*p)) != 0 && (any_in_flight(c) || c->parked)) { rc = bwb_hip_flush(c); if (rc) return rc; }
+	if (c->have_params && memcmp(&c->p, p, sizeof(*p)) != 0 && (any_in_flight(c) || c->parked)) RC(bwb_hip_flush(c));
 	/* 32-byte heap entries: more than one gap run per path - and penalties above 63, whose buckets can lie beyond the 64-bucket window of
 	 * the non-empty buckets: only these kernels carry the code for that (LHeap::far) */
 	const bool wide = p->max_gapo > 1 || p->mm_score > 63 || p->gapo_score > 63 || p->gape_score > 63;
-	if (c->cls[0].ready && wide != c->wide && c->parked) { rc = bwb_hip_flush(c); if (rc) return rc; }
+	if (c->cls[0].ready && wide != c->wide && c->parked) RC(bwb_hip_flush(c));
 	c->p = *p; c->have_params = true;
 	c->kp = KParams{ p->max_diff, p->max_gapo, p->max_gape, p->max_entries, p->mm_score, p->gapo_score, p->gape_score,
 	                 p->seed_length, p->max_diff_seed, p->max_best, p->no_indel_length, nb, p->use_precalc ? 1 : 0, p->is_multiref ? 1 : 0 };
@@ -770,12 +805,10 @@ template <typename P> static int build_dtab_t(bwb_hip_ctx *c, int K) {
 		                   (const Intv<P> *)pool_of[(k - 1) & 1], ent_of[k & 1]->template as<uint4>(), (Intv<P> *)pool_of[k & 1], bump.as<unsigned long long>(), cap, sc.sc);
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipStreamSynchronize(c->stream)); /* (the level is complete: its interval count) */
-		int rc = fetch(c, &total, bump.p, 8);
-		if (rc) return rc;
+		RC(fetch(c, &total, bump.p, 8));
 		if (k == 1) { /* the first step's summed width by base: what a lookup after a restart compares the restart's width with */
 			uint4 e1[8];
-			rc = fetch(c, e1, ent_of[1]->p, sizeof(e1));
-			if (rc) return rc;
+			RC(fetch(c, e1, ent_of[1]->p, sizeof(e1)));
 			for (int j = 0; j < 4; j++) c->dtab_nm1[j] = e1[2 * j].z;
 		}
 		if (total > cap) {
@@ -806,18 +839,17 @@ static int ensure_dtab(bwb_hip_ctx *c, uint32_t n_reads) {
 	int K = DTAB_KMAX;
 	if (getenv("BWB_DTAB_K")) K = std::max(1, std::min(DTAB_KMAX, atoi(getenv("BWB_DTAB_K"))));
 	if (c->dtab_K) { c->d_dtab_ent.release(); c->d_dtab_pool.release(); c->dtab_K = 0; } /* (another alphabet) */
-	return c->pos32 ? build_dtab_t<uint32_t>(c, K) : build_dtab_t<uint64_t>(c, K);
+	return with_pos(c, [&](auto p) { return build_dtab_t<decltype(p)>(c, K); });
 }
 
 /* BWB_LAUNCH_LOG: what ONE launch did - its HIP-event time and the counters it added (buckets fetched, heap entries stored / loaded, records
  * loaded) - so that per-dispatch PMC counters (tools/pmc_traffic.sh) can be priced launch by launch, slices and the draining launch apart */
-static int log_launch(bwb_hip_ctx *c, const char *kernel, int k, int si, bool drains, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
-	HIPCHK(hipStreamSynchronize(st));
+static int log_launch(bwb_hip_ctx *c, const char *kernel, int k, int si, bool drains, const Timed &t) {
+	HIPCHK(hipStreamSynchronize(t.st));
 	float ms = 0;
-	HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+	RC(t.ms(&ms));
 	unsigned long long cur[16];
-	int rc = fetch(c, cur, c->d_stats.p, sizeof(cur));
-	if (rc) return rc;
+	RC(fetch(c, cur, c->d_stats.p, sizeof(cur)));
 	if (FILE *f = fopen(c->launch_log, "a")) {
 		auto d = [&](int i) { return cur[i] - c->log_prev[i]; };
 		fprintf(f, "{\"kernel\": \"%s\", \"class\": %d, \"slot\": %d, \"drains\": %s, \"ms\": %.3f, \"buckets\": %llu, \"entries_stored\": %llu, \"entries_loaded\": %llu, \"records_loaded\": %llu}\n",
@@ -837,25 +869,22 @@ static int launch_calc_d(bwb_hip_ctx *c, int k, int si, const uint32_t *wl, uint
 	const uint32_t maxb = k == 0 ? (uint32_t)(c->num_cu * c->bpc_calcd) : sc.blocks;
 	const uint32_t grid = std::max<uint32_t>(1, std::min<uint32_t>(maxb, (n_work + LANE_BLOCK - 1) / LANE_BLOCK));
 	const size_t lds = calcd_lds();
-	hipEvent_t e0 = get_event(c), e1 = get_event(c);
-	if (!e0 || !e1) return fail(BWB_E_HIP, "hipEventCreate failed");
-	c->pending.push_back(PendingTime{ e0, e1, 0 });
-	HIPCHK(hipEventRecord(e0, st));
-	if (c->pos32)
-		hipLaunchKernelGGL(kl_calc_d<uint32_t>, dim3(grid), dim3(LANE_BLOCK), lds, st, c->ix, c->h_descs[si].b, wk, c->kp, sc.sc, dbgD, dbgDs,
-		                   s.maxlen + 1, (uint32_t)c->kp.seed_length + 1, c->d_stats.as<unsigned long long>(), dtab_of<uint32_t>(c));
-	else
-		hipLaunchKernelGGL(kl_calc_d<uint64_t>, dim3(grid), dim3(LANE_BLOCK), lds, st, c->ix, c->h_descs[si].b, wk, c->kp, sc.sc, dbgD, dbgDs,
-		                   s.maxlen + 1, (uint32_t)c->kp.seed_length + 1, c->d_stats.as<unsigned long long>(), dtab_of<uint64_t>(c));
+	Timed t(c, st);
+	RC(t.begin());
+	with_pos(c, [&](auto p) {
+		hipLaunchKernelGGL(kl_calc_d<decltype(p)>, dim3(grid), dim3(LANE_BLOCK), lds, st, c->ix, c->h_descs[si].b, wk, c->kp, sc.sc, dbgD, dbgDs,
+		                   s.maxlen + 1, (uint32_t)c->kp.seed_length + 1, c->d_stats.as<unsigned long long>(), dtab_of<decltype(p)>(c));
+	});
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(e1, st));
+	RC(t.end());
+	t.defer(0);
 	if (c->dbg) {
 		HIPCHK(hipStreamSynchronize(st));
 		float ms = 0;
-		HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+		RC(t.ms(&ms));
 		fprintf(stderr, "[bwb] kl_calc_d class %d slot %d: %u reads, grid %u, %.3f ms\n", k, si, n_work, grid, ms);
 	}
-	if (c->launch_log) return log_launch(c, "kl_calc_d", k, si, false, st, e0, e1);
+	if (c->launch_log) return log_launch(c, "kl_calc_d", k, si, false, t);
 	return BWB_OK;
 }
 
@@ -894,21 +923,17 @@ static int launch_search(bwb_hip_ctx *c, int k, int si, const uint32_t *wl, uint
 		const uint32_t lanes = (grid + s.sc.n_regions - 1) / s.sc.n_regions * LANE_BLOCK;
 		s.sc.keep = std::min<uint32_t>(c->keep, s.sc.pool_cap / 4 * 3 / lanes);
 	}
-	hipEvent_t e0 = get_event(c), e1 = get_event(c);
-	if (!e0 || !e1) return fail(BWB_E_HIP, "hipEventCreate failed");
-	c->pending.push_back(PendingTime{ e0, e1, 1 });
-	HIPCHK(hipEventRecord(e0, c->stream));
+	Timed t(c, c->stream);
+	RC(t.begin());
 	const SlotDesc *descs = c->d_descs.as<SlotDesc>();
 	unsigned long long *st = c->d_stats.as<unsigned long long>();
-#define LAUNCH_SEARCH(PT, W, M) hipLaunchKernelGGL((kl_search<PT, W, M>), dim3(grid), dim3(LANE_BLOCK), lds, c->stream, c->ix, descs, wk, c->kp, s.sc, st)
-	const bool multi = c->kp.multiref != 0;
-	if (c->pos32 && !c->wide) { if (multi) LAUNCH_SEARCH(uint32_t, false, true); else LAUNCH_SEARCH(uint32_t, false, false); }
-	else if (c->pos32) { if (multi) LAUNCH_SEARCH(uint32_t, true, true); else LAUNCH_SEARCH(uint32_t, true, false); }
-	else if (!c->wide) { if (multi) LAUNCH_SEARCH(uint64_t, false, true); else LAUNCH_SEARCH(uint64_t, false, false); }
-	else { if (multi) LAUNCH_SEARCH(uint64_t, true, true); else LAUNCH_SEARCH(uint64_t, true, false); }
-#undef LAUNCH_SEARCH
+	/* position width x 32-byte entries x the IUPAC alphabet: the one place that picks among the eight instantiations */
+	with_pos(c, [&](auto p) { with_flag(c->wide, [&](auto w) { with_flag(c->kp.multiref != 0, [&](auto m) {
+		hipLaunchKernelGGL((kl_search<decltype(p), decltype(w)::value, decltype(m)::value>), dim3(grid), dim3(LANE_BLOCK), lds, c->stream, c->ix, descs, wk, c->kp, s.sc, st);
+	}); }); });
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(e1, c->stream));
+	RC(t.end());
+	t.defer(1);
 	if (k == 0) {
 		c->parked = suspend || slice_iters != 0;
 		hipEvent_t le = get_event(c);
@@ -926,17 +951,16 @@ static int launch_search(bwb_hip_ctx *c, int k, int si, const uint32_t *wl, uint
 	if (c->dbg) {
 		HIPCHK(hipStreamSynchronize(c->stream));
 		float ms = 0;
-		HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+		RC(t.ms(&ms));
 		unsigned int hb[POOL_REGIONS * 16], used_max = 0;
 		unsigned long long used = 0;
-		int rc = fetch(c, hb, bump, sizeof(hb));
-		if (rc) return rc;
+		RC(fetch(c, hb, bump, sizeof(hb)));
 		const uint32_t priv = (grid + s.sc.n_regions - 1) / s.sc.n_regions * LANE_BLOCK * s.sc.keep;
 		for (uint32_t r = 0; r < s.sc.n_regions; r++) { used += std::min(priv + hb[r * 16], s.sc.pool_cap); used_max = std::max(used_max, priv + hb[r * 16]); }
 		fprintf(stderr, "[bwb] kl_search class %d slot %d: %u new reads, grid %u, %s%s, %.3f ms, pool chunks used %llu of %d x %u (fullest region asked for %u; %u private per lane)\n",
 		        k, si, n_work, grid, suspend ? "slice (parks)" : "drains", resume ? ", resumes parked reads" : "", ms, used, (int)s.sc.n_regions, s.sc.pool_cap, used_max, s.sc.keep);
 	}
-	if (c->launch_log) return log_launch(c, "kl_search", k, si, !(suspend || slice_iters != 0), c->stream, e0, e1);
+	if (c->launch_log) return log_launch(c, "kl_search", k, si, !(suspend || slice_iters != 0), t);
 	return BWB_OK;
 }
 
@@ -946,10 +970,8 @@ static int queue_calc_d(bwb_hip_ctx *c, int si) {
 	HIPCHK(s.ev_calcd.create());
 	HIPCHK(hipStreamWaitEvent(c->dstream, s.ev_up.e, 0));
 	HIPCHK(hipMemsetAsync(s.d_status.p, 0, (size_t)s.n_tot, c->dstream));
-	int rc = launch_calc_d(c, 0, si, nullptr, s.n_tot, s.ctl_counter(), nullptr, nullptr, c->dstream);
-	if (rc) return rc;
-	rc = launch_inherit(c, si, c->dstream);
-	if (rc) return rc;
+	RC(launch_calc_d(c, 0, si, nullptr, s.n_tot, s.ctl_counter(), nullptr, nullptr, c->dstream));
+	RC(launch_inherit(c, si, c->dstream));
 	HIPCHK(hipEventRecord(s.ev_calcd.e, c->dstream));
 	s.calcd_queued = true;
 	return BWB_OK;
@@ -959,16 +981,13 @@ static int submit(bwb_hip_ctx *c, int si, bool suspend) {
 	Slot &s = c->slots[si];
 	if (!s.uploaded) return fail(BWB_E_STATE, "slot_submit: nothing uploaded into this slot");
 	if (s.submitted && !s.complete) return fail(BWB_E_STATE, "slot_submit: the slot is still in flight");
-	int rc = index_ready(c); /* (a context created with bwb_hip_ctx_create_async: its index upload may still be running) */
-	if (rc) return rc;
-	rc = ensure_class(c, 0);
-	if (rc) return rc;
-	rc = ensure_dtab(c, s.n_reads);
-	if (rc) return rc;
+	RC(index_ready(c)); /* (a context created with bwb_hip_ctx_create_async: its index upload may still be running) */
+	RC(ensure_class(c, 0));
+	RC(ensure_dtab(c, s.n_reads));
 	HIPCHK(hipStreamWaitEvent(c->stream, s.ev_up.e, 0));
 	const bool ahead = c->calcd_ahead > 0 && s.n_reads != 0;
 	if (ahead) { /* kl_calc_d of this batch runs (or has run) on the second kernel stream: the search waits for it (the slot's cursor is its cursor too) */
-		if (!s.calcd_queued) { rc = queue_calc_d(c, si); if (rc) return rc; }
+		if (!s.calcd_queued) RC(queue_calc_d(c, si));
 		HIPCHK(hipStreamWaitEvent(c->stream, s.ev_calcd.e, 0));
 	}
 	HIPCHK(hipMemsetAsync(s.d_ctl.p, 0, 256, c->stream));
@@ -977,13 +996,10 @@ static int submit(bwb_hip_ctx *c, int si, bool suspend) {
 	HIPCHK(hipMemsetAsync(s.d_n.p, 0, (size_t)s.n_reads * 4, c->stream));
 	if (!ahead) {
 		HIPCHK(hipMemsetAsync(s.d_status.p, 0, (size_t)s.n_tot, c->stream));
-		rc = launch_calc_d(c, 0, si, nullptr, s.n_tot, s.ctl_counter(), nullptr, nullptr);
-		if (rc) return rc;
-		rc = launch_inherit(c, si);
-		if (rc) return rc;
+		RC(launch_calc_d(c, 0, si, nullptr, s.n_tot, s.ctl_counter(), nullptr, nullptr));
+		RC(launch_inherit(c, si));
 	}
-	rc = launch_search(c, 0, si, nullptr, s.n_reads, s.ctl_counter(), suspend);
-	if (rc) return rc;
+	RC(launch_search(c, 0, si, nullptr, s.n_reads, s.ctl_counter(), suspend));
 	s.launch = c->n_launches;
 	/* the batches the caller has uploaded beyond this one (slots are used round-robin): their kl_calc_d is queued NOW, on the second
 	 * stream, where it runs beside the search slices instead of in front of its own (the two calls are independent per read,
@@ -991,7 +1007,7 @@ static int submit(bwb_hip_ctx *c, int si, bool suspend) {
 	for (int k = 1; ahead && k <= c->calcd_ahead; k++) {
 		const int sj = (si + k) % BWB_MAX_SLOTS;
 		Slot &t = c->slots[sj];
-		if (t.uploaded && !t.submitted && !t.calcd_queued && t.n_reads) { rc = queue_calc_d(c, sj); if (rc) return rc; }
+		if (t.uploaded && !t.submitted && !t.calcd_queued && t.n_reads) RC(queue_calc_d(c, sj));
 	}
 	return BWB_OK;
 }
@@ -1002,26 +1018,33 @@ extern "C" int bwb_hip_slot_submit(bwb_hip_ctx *c, int si) {
 	return submit(c, si, true);
 }
 
+/* the first n status bytes of the slot -> s.h_status (n_reads, or n_tot: a carried read that rides along for its D_seed can overflow
+ * calculate_d too; it is never searched) */
+static int load_status(bwb_hip_ctx *c, Slot &s, uint32_t n) {
+	s.h_status.resize(n);
+	return fetch(c, s.h_status.data(), s.d_status.p, n);
+}
+
+/* ids -> the slot's device worklist; there when this returns */
+static int put_worklist(bwb_hip_ctx *c, Slot &s, const std::vector<uint32_t> &ids) {
+	HIPCHK(hipMemcpyAsync(s.d_worklist.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	return BWB_OK;
+}
+
 /* reads of the slot whose status == want -> the slot's device worklist */
 static int collect(bwb_hip_ctx *c, Slot &s, uint8_t want, std::vector<uint32_t> &ids) {
-	s.h_status.resize(s.n_reads);
-	int rc = fetch(c, s.h_status.data(), s.d_status.p, s.n_reads);
-	if (rc) return rc;
+	RC(load_status(c, s, s.n_reads));
 	ids.clear();
 	for (uint32_t i = 0; i < s.n_reads; i++) if (s.h_status[i] == want) ids.push_back(i);
-	if (!ids.empty()) {
-		HIPCHK(hipMemcpyAsync(s.d_worklist.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, c->stream));
-		HIPCHK(hipStreamSynchronize(c->stream));
-	}
-	return BWB_OK;
+	return ids.empty() ? BWB_OK : put_worklist(c, s, ids);
 }
 
 /* grows the slot's hit log (keeping what is in it) */
 static int grow_log(bwb_hip_ctx *c, int si) {
 	Slot &s = c->slots[si];
 	unsigned long long cnt = 0;
-	int rc = fetch(c, &cnt, s.ctl_count(), 8);
-	if (rc) return rc;
+	RC(fetch(c, &cnt, s.ctl_count(), 8));
 	const uint64_t valid = std::min<uint64_t>(cnt, s.log_cap);
 	const uint64_t ncap = s.log_cap * 4;
 	DevMem nl;
@@ -1048,20 +1071,11 @@ static int rerun_overflows(bwb_hip_ctx *c, int si) {
 	 * its share and in class 2 a five-hundredth of the pool to itself).  So whatever is parked must finish first: one draining
 	 * launch (fed from this slot's exhausted cursor) completes the parked reads of every slot. */
 	if (c->parked) {
-		int rc = launch_search(c, 0, si, nullptr, s.n_reads, s.ctl_counter(), false, false, true);
-		if (rc) return rc;
+		RC(launch_search(c, 0, si, nullptr, s.n_reads, s.ctl_counter(), false, false, true));
 		HIPCHK(hipStreamSynchronize(c->stream));
 	}
-	/* (n_tot: a carried read that rides along for its D_seed can overflow calculate_d too; it is never searched) */
-	auto load_status = [&]() { s.h_status.resize(s.n_tot); return fetch(c, s.h_status.data(), s.d_status.p, s.n_tot); };
-	auto put_worklist = [&](const std::vector<uint32_t> &v) -> int {
-		HIPCHK(hipMemcpyAsync(s.d_worklist.p, v.data(), v.size() * 4, hipMemcpyHostToDevice, c->stream));
-		HIPCHK(hipStreamSynchronize(c->stream));
-		return BWB_OK;
-	};
 	for (int k = 1; k <= 2; k++) {
-		int rc = load_status();
-		if (rc) return rc;
+		RC(load_status(c, s, s.n_tot));
 		todo.clear(); dids.clear();
 		for (uint32_t i = 0; i < s.n_tot; i++) {
 			if (s.h_status[i] != ST_OK && i < s.n_reads) todo.push_back(i);
@@ -1069,18 +1083,13 @@ static int rerun_overflows(bwb_hip_ctx *c, int si) {
 		}
 		if (todo.empty()) return BWB_OK;
 		if (k == 1) c->stats.n_overflow_reads += todo.size(); /* (class 2 re-runs a subset of these) */
-		rc = ensure_class(c, k);
-		if (rc) return rc;
+		RC(ensure_class(c, k));
 		if (!dids.empty()) { /* calculate_d first: it leaves ST_OK, or ST_D_OVF again (then the next class tries); ST_D_WAIT reads only need the inheritance */
-			rc = put_worklist(dids);
-			if (rc) return rc;
-			rc = launch_calc_d(c, k, si, s.d_worklist.as<uint32_t>(), (uint32_t)dids.size(), s.ctl_counter2(), nullptr, nullptr);
-			if (rc) return rc;
-			rc = launch_inherit(c, si); /* sources that were late are there now (a read whose source still is not stays ST_D_WAIT) */
-			if (rc) return rc;
+			RC(put_worklist(c, s, dids));
+			RC(launch_calc_d(c, k, si, s.d_worklist.as<uint32_t>(), (uint32_t)dids.size(), s.ctl_counter2(), nullptr, nullptr));
+			RC(launch_inherit(c, si)); /* sources that were late are there now (a read whose source still is not stays ST_D_WAIT) */
 			HIPCHK(hipStreamSynchronize(c->stream));
-			rc = load_status();
-			if (rc) return rc;
+			RC(load_status(c, s, s.n_tot));
 		}
 		list.clear();
 		for (uint32_t i : todo) if (s.h_status[i] < ST_D_OVF) list.push_back(i);
@@ -1088,22 +1097,18 @@ static int rerun_overflows(bwb_hip_ctx *c, int si) {
 			if (guard == 40) return fail(BWB_E_OVERFLOW, "hit log kept overflowing");
 			bool out_ovf = false;
 			for (uint32_t i : list) out_ovf |= s.h_status[i] == ST_OUT_OVF;
-			if (out_ovf) { rc = grow_log(c, si); if (rc) return rc; }
-			rc = put_worklist(list);
-			if (rc) return rc;
-			rc = launch_search(c, k, si, s.d_worklist.as<uint32_t>(), (uint32_t)list.size(), s.ctl_counter2(), false);
-			if (rc) return rc;
+			if (out_ovf) RC(grow_log(c, si));
+			RC(put_worklist(c, s, list));
+			RC(launch_search(c, k, si, s.d_worklist.as<uint32_t>(), (uint32_t)list.size(), s.ctl_counter2(), false));
 			HIPCHK(hipStreamSynchronize(c->stream));
-			rc = load_status();
-			if (rc) return rc;
+			RC(load_status(c, s, s.n_tot));
 			/* only reads the hit log had no room for are repeated within a class (the log grows x4 each time) */
 			std::vector<uint32_t> again;
 			for (uint32_t i : list) if (s.h_status[i] == ST_OUT_OVF) again.push_back(i);
 			list.swap(again);
 		}
 	}
-	int rc = load_status();
-	if (rc) return rc;
+	RC(load_status(c, s, s.n_tot));
 	for (uint32_t i = 0; i < s.n_tot; i++)
 		if (s.h_status[i] != ST_OK) return fail(BWB_E_OVERFLOW, "a read exceeded the largest per-read scratch class");
 	return BWB_OK;
@@ -1120,24 +1125,19 @@ static int slot_wait(bwb_hip_ctx *c, int si) {
 	for (;;) {
 		HIPCHK(hipEventSynchronize(c->launch_ev[L - 1 - c->ev_base]));
 		unsigned int done = 0;
-		int rc = fetch(c, &done, s.ctl_done(), 4);
-		if (rc) return rc;
+		RC(fetch(c, &done, s.ctl_done(), 4));
 		if (done >= s.n_reads) break;
 		if (L < c->n_launches) { L++; continue; }
 		/* (the slot's cursor is where the slices left it: normally exhausted, so only parked reads run) */
-		rc = launch_search(c, 0, si, nullptr, s.n_reads, s.ctl_counter(), false, false);
-		if (rc) return rc;
+		RC(launch_search(c, 0, si, nullptr, s.n_reads, s.ctl_counter(), false, false));
 		L = c->n_launches;
 	}
-	int rc = resolve_times(c, false);
-	if (rc) return rc;
+	RC(resolve_times(c, false));
 	/* anything that needs a larger scratch class?  (one byte per read; almost always all zero) */
-	s.h_status.resize(s.n_tot);
-	rc = fetch(c, s.h_status.data(), s.d_status.p, s.n_tot);
-	if (rc) return rc;
+	RC(load_status(c, s, s.n_tot));
 	bool clean = true;
 	for (uint32_t i = 0; i < s.n_tot && clean; i++) clean = s.h_status[i] == ST_OK;
-	if (!clean) { rc = rerun_overflows(c, si); if (rc) return rc; }
+	if (!clean) RC(rerun_overflows(c, si));
 	s.complete = true;
 	if (!any_in_flight(c)) c->parked = false; /* every read of every submitted slot is done: nothing can be parked any more */
 	return BWB_OK;
@@ -1154,8 +1154,7 @@ extern "C" int bwb_hip_slot_result(bwb_hip_ctx *c, int si, bwb_result *out) {
 	HIPCHK(hipSetDevice(c->device));
 	Slot &s = c->slots[si];
 	if (!s.submitted) return fail(BWB_E_STATE, "slot_result: the slot has not been submitted");
-	int rc = slot_wait(c, si);
-	if (rc) return rc;
+	RC(slot_wait(c, si));
 	const uint32_t n = s.n_reads;
 	if (!s.fetched) {
 		/* per-read counts and offsets into the hit log, and the log itself, on the result stream (the kernel stream keeps running) */
@@ -1199,10 +1198,8 @@ extern "C" int bwb_hip_slot_result(bwb_hip_ctx *c, int si, bwb_result *out) {
 extern "C" int bwb_hip_batch_upload(bwb_hip_ctx *c, const bwb_params *p, const uint8_t *reads_fwd, const uint16_t *lens,
                                     uint32_t n_reads, uint32_t stride) {
 	if (!c) return fail(BWB_E_ARG, "batch_upload: null context");
-	int rc = bwb_hip_flush(c); /* this interface owns the context: nothing else may be in flight */
-	if (rc) return rc;
-	rc = bwb_hip_slot_upload(c, 0, p, reads_fwd, lens, n_reads, stride, nullptr, 0);
-	if (rc) return rc;
+	RC(bwb_hip_flush(c)); /* this interface owns the context: nothing else may be in flight */
+	RC(bwb_hip_slot_upload(c, 0, p, reads_fwd, lens, n_reads, stride, nullptr, 0));
 	HIPCHK(hipStreamSynchronize(c->cstream));
 	HIPCHK(hipStreamSynchronize(c->stream));
 	return BWB_OK;
@@ -1210,8 +1207,7 @@ extern "C" int bwb_hip_batch_upload(bwb_hip_ctx *c, const bwb_params *p, const u
 
 static int read_device_stats(bwb_hip_ctx *c) {
 	unsigned long long st[STAT_WORDS];
-	int rc = fetch(c, st, c->d_stats.p, sizeof(st));
-	if (rc) return rc;
+	RC(fetch(c, st, c->d_stats.p, sizeof(st)));
 	c->stats.visits_single = st[STAT_VIS_SINGLE]; c->stats.visits_alphabet = st[STAT_VIS_ALPHA]; c->stats.visits_calc_d = st[STAT_VIS_CALCD];
 	c->stats.heap_pops = st[STAT_POPS]; c->stats.heap_pushes = st[STAT_PUSHES]; c->stats.n_alignments = st[STAT_ALNS];
 	c->stats.bucket_loads_search = st[STAT_BKT_SEARCH]; c->stats.bucket_loads_calc_d = st[STAT_BKT_CALCD];
@@ -1258,8 +1254,7 @@ static int read_device_stats(bwb_hip_ctx *c) {
 extern "C" int bwb_hip_reset_stats(bwb_hip_ctx *c) {
 	if (!c) return fail(BWB_E_ARG, "reset_stats: null context");
 	HIPCHK(hipSetDevice(c->device));
-	int rc = resolve_times(c, false);
-	if (rc) return rc;
+	RC(resolve_times(c, false));
 	memset(&c->stats, 0, sizeof(c->stats));
 	memset(c->log_prev, 0, sizeof(c->log_prev));
 	HIPCHK(hipMemsetAsync(c->d_stats.p, 0, sizeof(unsigned long long) * STAT_WORDS, c->stream));
@@ -1270,19 +1265,14 @@ extern "C" int bwb_hip_reset_stats(bwb_hip_ctx *c) {
 extern "C" int bwb_hip_batch_run(bwb_hip_ctx *c) {
 	if (!c || !c->slots[0].uploaded) return fail(BWB_E_STATE, "batch_run: no batch uploaded");
 	HIPCHK(hipSetDevice(c->device));
-	int rc = bwb_hip_flush(c);
-	if (rc) return rc;
-	rc = bwb_hip_reset_stats(c);
-	if (rc) return rc;
+	RC(bwb_hip_flush(c));
+	RC(bwb_hip_reset_stats(c));
 	const double t0 = wall_s();
-	rc = submit(c, 0, c->force_slices);
-	if (rc) return rc;
-	rc = slot_wait(c, 0);
-	if (rc) return rc;
+	RC(submit(c, 0, c->force_slices));
+	RC(slot_wait(c, 0));
 	HIPCHK(hipStreamSynchronize(c->stream));
 	c->stats.ms_total = (wall_s() - t0) * 1e3;
-	rc = resolve_times(c, true);
-	if (rc) return rc;
+	RC(resolve_times(c, true));
 	return read_device_stats(c);
 }
 
@@ -1290,10 +1280,8 @@ extern "C" int bwb_hip_batch_run(bwb_hip_ctx *c) {
 extern "C" int bwb_hip_get_stats(bwb_hip_ctx *c, bwb_stats *out) {
 	if (!c || !out) return fail(BWB_E_ARG, "get_stats: null argument");
 	HIPCHK(hipSetDevice(c->device));
-	int rc = resolve_times(c, false);
-	if (rc) return rc;
-	rc = read_device_stats(c);
-	if (rc) return rc;
+	RC(resolve_times(c, false));
+	RC(read_device_stats(c));
 	*out = c->stats;
 	return BWB_OK;
 }
@@ -1308,13 +1296,11 @@ extern "C" int bwb_hip_align_batch(bwb_hip_ctx *c, const bwb_params *p, const ui
                                    uint32_t n_reads, uint32_t stride, bwb_result *out) {
 	if (!c) return fail(BWB_E_ARG, "align_batch: null context");
 	double t0 = wall_s();
-	int rc = bwb_hip_batch_upload(c, p, reads_fwd, lens, n_reads, stride);
-	if (rc) return rc;
+	RC(bwb_hip_batch_upload(c, p, reads_fwd, lens, n_reads, stride));
 	const double t1 = wall_s();
-	rc = bwb_hip_batch_run(c);
-	if (rc) return rc;
+	RC(bwb_hip_batch_run(c));
 	const double t2 = wall_s();
-	rc = bwb_hip_batch_result(c, out);
+	const int rc = bwb_hip_batch_result(c, out);
 	if (c->dbg) fprintf(stderr, "[bwb] align_batch: upload %.3f s, run %.3f s, result %.3f s\n", t1 - t0, t2 - t1, wall_s() - t2);
 	return rc;
 }
@@ -1324,44 +1310,35 @@ extern "C" int bwb_hip_calc_d(bwb_hip_ctx *c, int32_t *out_D, int32_t *out_Dseed
 	Slot &s = c->slots[0];
 	if (!s.uploaded) return fail(BWB_E_STATE, "calc_d: no batch uploaded");
 	HIPCHK(hipSetDevice(c->device));
-	int rc = bwb_hip_flush(c);
-	if (rc) return rc;
-	rc = index_ready(c);
-	if (rc) return rc;
+	RC(bwb_hip_flush(c));
+	RC(index_ready(c));
 	const size_t nD = (size_t)s.n_reads * (s.maxlen + 1) * 2, nS = (size_t)s.n_reads * (c->kp.seed_length + 1) * 2;
 	DevMem dD, dS;
 	HIPCHK(dD.alloc((nD ? nD : 1) * 4));
 	HIPCHK(dS.alloc((nS ? nS : 1) * 4));
 	HIPCHK(hipMemsetAsync(dD.p, 0, (nD ? nD : 1) * 4, c->stream));
 	HIPCHK(hipMemsetAsync(dS.p, 0, (nS ? nS : 1) * 4, c->stream));
-	rc = bwb_hip_reset_stats(c);
-	if (rc) return rc;
+	RC(bwb_hip_reset_stats(c));
 	if (s.n_reads) {
 		HIPCHK(hipStreamWaitEvent(c->stream, s.ev_up.e, 0));
 		HIPCHK(hipMemsetAsync(s.d_status.p, 0, s.n_reads, c->stream));
-		rc = launch_calc_d(c, 0, 0, nullptr, s.n_reads, s.ctl_counter(), dD.as<int32_t>(), dS.as<int32_t>());
-		if (rc) return rc;
+		RC(launch_calc_d(c, 0, 0, nullptr, s.n_reads, s.ctl_counter(), dD.as<int32_t>(), dS.as<int32_t>()));
 		HIPCHK(hipStreamSynchronize(c->stream));
 		std::vector<uint32_t> ids;
 		for (int k = 1; k <= 2; k++) {
-			rc = collect(c, s, ST_D_OVF, ids);
-			if (rc) return rc;
+			RC(collect(c, s, ST_D_OVF, ids));
 			if (ids.empty()) break;
-			rc = ensure_class(c, k);
-			if (rc) return rc;
-			rc = launch_calc_d(c, k, 0, s.d_worklist.as<uint32_t>(), (uint32_t)ids.size(), s.ctl_counter2(), dD.as<int32_t>(), dS.as<int32_t>());
-			if (rc) return rc;
+			RC(ensure_class(c, k));
+			RC(launch_calc_d(c, k, 0, s.d_worklist.as<uint32_t>(), (uint32_t)ids.size(), s.ctl_counter2(), dD.as<int32_t>(), dS.as<int32_t>()));
 			HIPCHK(hipStreamSynchronize(c->stream));
 		}
-		rc = collect(c, s, ST_D_OVF, ids);
-		if (rc) return rc;
+		RC(collect(c, s, ST_D_OVF, ids));
 		if (!ids.empty()) return fail(BWB_E_OVERFLOW, "calculate_d: SA-interval list exceeded the largest scratch class");
 	}
 	HIPCHK(hipMemcpyAsync(out_D, dD.p, nD * 4, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipMemcpyAsync(out_Dseed, dS.p, nS * 4, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
-	rc = resolve_times(c, true);
-	if (rc) return rc;
+	RC(resolve_times(c, true));
 	return read_device_stats(c);
 }
 
@@ -1371,12 +1348,12 @@ extern "C" int bwb_hip_rank16(bwb_hip_ctx *c, const uint64_t *pos, size_t n, int
 	for (size_t i = 0; i < n; i++)
 		if (pos[i] != ~0ull && pos[i] >= c->ix.length) return fail(BWB_E_ARG, "rank16: position out of range");
 	HIPCHK(hipSetDevice(c->device));
-	{ int rc = index_ready(c); if (rc) return rc; }
+	RC(index_ready(c));
 	DevMem dp, dout;
 	HIPCHK(dp.alloc(n * 8));
 	HIPCHK(dout.alloc(n * 128));
 	HIPCHK(hipMemcpyAsync(dp.p, pos, n * 8, hipMemcpyHostToDevice, c->stream));
-	const unsigned grid = (unsigned)std::min<size_t>((n + BWB_OCTS_PER_BLOCK - 1) / BWB_OCTS_PER_BLOCK, (size_t)c->num_cu * 8);
+	const unsigned grid = oct_grid(c, n);
 	hipLaunchKernelGGL(k_rank16, dim3(grid), dim3(BWB_BLOCK), 0, c->stream, c->ix, dp.as<uint64_t>(), (uint64_t)n, inc, exact, dout.as<uint64_t>());
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(out, dout.p, n * 128, hipMemcpyDeviceToHost, c->stream));
@@ -1391,7 +1368,7 @@ extern "C" int bwb_hip_children(bwb_hip_ctx *c, const uint64_t *iL, const uint64
 	for (size_t i = 0; i < n; i++) /* iL - 1 and iU are positions: -1 (iL == 0) .. length - 1 */
 		if (iL[i] > c->ix.length || iU[i] >= c->ix.length || (flags[i] & ~3u)) return fail(BWB_E_ARG, "children: interval out of range or unknown flag");
 	HIPCHK(hipSetDevice(c->device));
-	{ int rc = index_ready(c); if (rc) return rc; }
+	RC(index_ready(c));
 	DevMem dL, dU, df, doL, doU, dm;
 	HIPCHK(dL.alloc(n * 8)); HIPCHK(dU.alloc(n * 8)); HIPCHK(df.alloc(n));
 	HIPCHK(doL.alloc(n * 15 * 8)); HIPCHK(doU.alloc(n * 15 * 8)); HIPCHK(dm.alloc(n * 4));
@@ -1399,8 +1376,9 @@ extern "C" int bwb_hip_children(bwb_hip_ctx *c, const uint64_t *iL, const uint64
 	HIPCHK(hipMemcpyAsync(dU.p, iU, n * 8, hipMemcpyHostToDevice, c->stream));
 	HIPCHK(hipMemcpyAsync(df.p, flags, n, hipMemcpyHostToDevice, c->stream));
 	const unsigned grid = (unsigned)std::min<size_t>((n + LANE_BLOCK - 1) / LANE_BLOCK, (size_t)c->num_cu * 8);
-	if (c->pos32) hipLaunchKernelGGL(kl_children<uint32_t>, dim3(grid), dim3(LANE_BLOCK), 0, c->stream, c->ix, dL.as<uint64_t>(), dU.as<uint64_t>(), df.as<uint8_t>(), (uint64_t)n, doL.as<uint64_t>(), doU.as<uint64_t>(), dm.as<uint32_t>());
-	else hipLaunchKernelGGL(kl_children<uint64_t>, dim3(grid), dim3(LANE_BLOCK), 0, c->stream, c->ix, dL.as<uint64_t>(), dU.as<uint64_t>(), df.as<uint8_t>(), (uint64_t)n, doL.as<uint64_t>(), doU.as<uint64_t>(), dm.as<uint32_t>());
+	with_pos(c, [&](auto p) {
+		hipLaunchKernelGGL(kl_children<decltype(p)>, dim3(grid), dim3(LANE_BLOCK), 0, c->stream, c->ix, dL.as<uint64_t>(), dU.as<uint64_t>(), df.as<uint8_t>(), (uint64_t)n, doL.as<uint64_t>(), doU.as<uint64_t>(), dm.as<uint32_t>());
+	});
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(out_L, doL.p, n * 15 * 8, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipMemcpyAsync(out_U, doU.p, n * 15 * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1414,34 +1392,29 @@ static int rank_bench(bwb_hip_ctx *c, int layout, size_t n, int iters, uint64_t 
 	if (!c || n < 4 || iters < 1) return fail(BWB_E_ARG, "rank_bench: bad argument");
 	n &= ~(size_t)3;
 	HIPCHK(hipSetDevice(c->device));
-	{ int rc = index_ready(c); if (rc) return rc; }
+	RC(index_ready(c));
 	unsigned long long *cs = c->d_misc.as<unsigned long long>();
 	HIPCHK(hipMemsetAsync(cs, 0, 8, c->stream));
 	const unsigned grid = (unsigned)(c->num_cu * 8);
 	auto launch = [&](uint64_t sd) {
-		if (layout == 0) {
-			if (c->pos32) hipLaunchKernelGGL(k_rank_bench<uint32_t>, dim3(grid), dim3(BWB_BLOCK), 0, c->stream, c->ix, (uint64_t)n, sd, cs);
-			else hipLaunchKernelGGL(k_rank_bench<uint64_t>, dim3(grid), dim3(BWB_BLOCK), 0, c->stream, c->ix, (uint64_t)n, sd, cs);
-		} else {
-			if (c->pos32) hipLaunchKernelGGL(k_rank_bench_lane<uint32_t>, dim3(grid), dim3(LANE_BLOCK), 0, c->stream, c->ix, (uint64_t)n, sd, cs);
-			else hipLaunchKernelGGL(k_rank_bench_lane<uint64_t>, dim3(grid), dim3(LANE_BLOCK), 0, c->stream, c->ix, (uint64_t)n, sd, cs);
-		}
+		with_pos(c, [&](auto p) {
+			if (layout == 0) hipLaunchKernelGGL(k_rank_bench<decltype(p)>, dim3(grid), dim3(BWB_BLOCK), 0, c->stream, c->ix, (uint64_t)n, sd, cs);
+			else hipLaunchKernelGGL(k_rank_bench_lane<decltype(p)>, dim3(grid), dim3(LANE_BLOCK), 0, c->stream, c->ix, (uint64_t)n, sd, cs);
+		});
 	};
-	Event e0, e1;
-	HIPCHK(e0.create()); HIPCHK(e1.create());
+	Timed t(c, c->stream);
 	launch(seed); /* warm-up */
 	HIPCHK(hipMemsetAsync(cs, 0, 8, c->stream));
-	HIPCHK(hipEventRecord(e0.e, c->stream));
+	RC(t.begin());
 	for (int i = 0; i < iters; i++)
 		launch(seed + i);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(e1.e, c->stream));
+	RC(t.end());
 	HIPCHK(hipStreamSynchronize(c->stream));
 	float ms = 0;
-	HIPCHK(hipEventElapsedTime(&ms, e0.e, e1.e));
+	RC(t.ms(&ms));
 	unsigned long long v = 0;
-	int rc = fetch(c, &v, cs, 8);
-	if (rc) return rc;
+	RC(fetch(c, &v, cs, 8));
 	if (ms_per_iter) *ms_per_iter = ms / iters;
 	if (checksum) *checksum = v;
 	return BWB_OK;
@@ -1472,30 +1445,25 @@ extern "C" int bwb_hip_locate(bwb_hip_ctx *c, const uint64_t *rows, size_t n, ui
 	if (n == 0) { c->locate_ms = 0; c->locate_steps = 0; c->locate_rows = 0; return BWB_OK; } /* (locate_stats reports THIS call) */
 	for (size_t i = 0; i < n; i++) if (rows[i] >= c->ix.length) return fail(BWB_E_ARG, "locate: row out of range");
 	HIPCHK(hipSetDevice(c->device));
-	{ int rc = index_ready(c); if (rc) return rc; }
+	RC(index_ready(c));
 	DevMem dr, dout;
 	HIPCHK(dr.alloc(n * 8));
 	HIPCHK(dout.alloc(n * 8));
 	HIPCHK(hipMemcpyAsync(dr.p, rows, n * 8, hipMemcpyHostToDevice, c->stream));
-	const unsigned grid = (unsigned)std::min<size_t>((n + BWB_OCTS_PER_BLOCK - 1) / BWB_OCTS_PER_BLOCK, (size_t)c->num_cu * 8);
-	hipEvent_t e0 = get_event(c), e1 = get_event(c);
-	struct EvGuard { /* the two events go back to the context's free list on every way out (an error path used to leak them) */
-		bwb_hip_ctx *c; hipEvent_t a, b;
-		~EvGuard() { if (a) c->free_events.push_back(a); if (b) c->free_events.push_back(b); }
-	} evg{ c, e0, e1 };
-	if (!e0 || !e1) return fail(BWB_E_HIP, "hipEventCreate failed");
+	const unsigned grid = oct_grid(c, n);
+	Timed t(c, c->stream);
 	unsigned long long *steps = c->d_stats.as<unsigned long long>() + STAT_LOCATE_STEPS;
 	HIPCHK(hipMemsetAsync(steps, 0, 8, c->stream));
-	HIPCHK(hipEventRecord(e0, c->stream));
+	RC(t.begin());
 	hipLaunchKernelGGL(k_locate, dim3(grid), dim3(BWB_BLOCK), 0, c->stream, c->ix, c->d_SA.as<uint64_t>(), c->sa0_index, dr.as<uint64_t>(), (uint64_t)n, dout.as<uint64_t>(), c->d_stats.as<unsigned long long>());
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(e1, c->stream));
+	RC(t.end());
 	HIPCHK(hipMemcpyAsync(out_pos, dout.p, n * 8, hipMemcpyDeviceToHost, c->stream));
 	unsigned long long hsteps = 0;
 	HIPCHK(hipMemcpyAsync(&hsteps, steps, 8, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
 	float ms = 0;
-	HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+	RC(t.ms(&ms));
 	c->locate_ms = ms; c->locate_steps = hsteps; c->locate_rows = n;
 	return BWB_OK;
 }
@@ -1525,29 +1493,33 @@ static int place_launch(bwb_hip_ctx *c, const char *who, const uint4 *d_log, uin
 	}
 	c->place_ms = 0; c->place_steps = 0; c->place_reads = n;
 	if (!n) return BWB_OK;
-	hipEvent_t e0 = get_event(c), e1 = get_event(c);
-	struct EvGuard {
-		bwb_hip_ctx *c; hipEvent_t a, b;
-		~EvGuard() { if (a) c->free_events.push_back(a); if (b) c->free_events.push_back(b); }
-	} evg{ c, e0, e1 };
-	if (!e0 || !e1) return fail(BWB_E_HIP, "hipEventCreate failed");
+	Timed t(c, c->rstream);
 	unsigned long long *steps = (unsigned long long *)(c->d_qtab.as<unsigned char>() + 256);
 	HIPCHK(hipMemsetAsync(steps, 0, 8, c->rstream));
-	const unsigned grid = (unsigned)std::min<size_t>(((size_t)n + BWB_OCTS_PER_BLOCK - 1) / BWB_OCTS_PER_BLOCK, (size_t)c->num_cu * 8);
-	HIPCHK(hipEventRecord(e0, c->rstream));
+	const unsigned grid = oct_grid(c, n);
+	RC(t.begin());
 	hipLaunchKernelGGL(k_place, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, c->ix, c->d_SA.as<uint64_t>(), c->sa0_index, d_log, log_n,
 	                   d_off, d_cnt, n, max_mm, c->d_qtab.as<uint8_t>(), d_out, steps);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(e1, c->rstream));
+	RC(t.end());
 	HIPCHK(hipMemcpyAsync(h_out, d_out, (size_t)n * sizeof(bwb_place), hipMemcpyDeviceToHost, c->rstream));
 	unsigned long long hsteps = 0;
 	HIPCHK(hipMemcpyAsync(&hsteps, steps, 8, hipMemcpyDeviceToHost, c->rstream));
 	HIPCHK(hipStreamSynchronize(c->rstream));
 	float ms = 0;
-	HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+	RC(t.ms(&ms));
 	c->place_ms = ms; c->place_steps = hsteps;
 	for (uint32_t i = 0; i < n; i++)
 		if (h_out[i].flags & PLACE_F_BAD) return fail(BWB_E_STATE, std::string(who) + ": a read's hits lie outside the hit log or the index");
+	return BWB_OK;
+}
+
+/* How many hits the log of a finished slot holds.  On the result stream: the kernel stream may hold slices of later slots, seconds each,
+ * and the place calls must not wait for them.  The slot's reads are done (slot_wait) and were published with a system-scope release; the
+ * host reads the same memory on this stream in slot_result. */
+static int slot_log_n(bwb_hip_ctx *c, Slot &s, uint64_t *log_n) {
+	RC(fetch(c, s.h_ctl.p, s.ctl_count(), 8));
+	*log_n = std::min<unsigned long long>(*s.h_ctl.as<unsigned long long>(), s.log_cap);
 	return BWB_OK;
 }
 
@@ -1557,23 +1529,16 @@ extern "C" int bwb_hip_slot_place(bwb_hip_ctx *c, int si, int max_mm, const bwb_
 	Slot &s = c->slots[si];
 	if (!c->d_SA.p) return fail(BWB_E_STATE, "slot_place: sampled SA not uploaded (bwb_hip_set_sa)");
 	if (!s.submitted) return fail(BWB_E_STATE, "slot_place: the slot has not been submitted");
-	int rc = slot_wait(c, si);
-	if (rc) return rc;
+	RC(slot_wait(c, si));
 	const uint32_t n = s.n_reads;
 	if (s.placed_mm != max_mm || !n) {
 		HIPCHK(s.h_place.reserve((size_t)n * sizeof(bwb_place)));
 		uint64_t log_n = 0;
 		if (n) {
 			HIPCHK(s.d_place.reserve((size_t)n * sizeof(bwb_place)));
-			/* On the result stream: the kernel stream may hold slices of later slots, seconds each, and this call must not wait for them.
-			 * The slot's reads are done (slot_wait) and were published with a system-scope release; the host reads the same memory on
-			 * this stream in slot_result. */
-			rc = fetch(c, s.h_ctl.p, s.ctl_count(), 8);
-			if (rc) return rc;
-			log_n = std::min<unsigned long long>(*s.h_ctl.as<unsigned long long>(), s.log_cap);
+			RC(slot_log_n(c, s, &log_n));
 		}
-		rc = place_launch(c, "slot_place", s.d_log.as<uint4>(), log_n, s.d_off.as<uint64_t>(), s.d_n.as<uint32_t>(), n, max_mm, s.d_place.as<uint4>(), s.h_place.as<bwb_place>());
-		if (rc) return rc;
+		RC(place_launch(c, "slot_place", s.d_log.as<uint4>(), log_n, s.d_off.as<uint64_t>(), s.d_n.as<uint32_t>(), n, max_mm, s.d_place.as<uint4>(), s.h_place.as<bwb_place>()));
 		s.placed_mm = max_mm;
 	}
 	*out = s.h_place.as<bwb_place>();
@@ -1595,7 +1560,7 @@ static int place_hits_impl(bwb_hip_ctx *c, const std::string &who, const bwb_aln
 	}
 	if (total && !alns) return fail(BWB_E_ARG, who + ": null argument");
 	HIPCHK(hipSetDevice(c->device));
-	{ int rc = index_ready(c); if (rc) return rc; }
+	RC(index_ready(c));
 	static_assert(sizeof(bwb_aln) == 48, "bwb_aln is the hit log's three 16-byte words");
 	DevMem d_log, d_off, d_cnt, d_out;
 	HIPCHK(d_log.alloc((size_t)total * sizeof(bwb_aln)));
@@ -1622,8 +1587,7 @@ extern "C" int bwb_hip_place_hits_alt(bwb_hip_ctx *c, const bwb_aln *alns, const
                                       const uint64_t **alt_off, const bwb_alt **alts) {
 	if (!c || !aln_off || (n_reads && !out) || !alt_off || !alts) return fail(BWB_E_ARG, "place_hits_alt: null argument");
 	if (max_alt < 1 || max_alt > 255) return fail(BWB_E_ARG, "place_hits_alt: max_alt must be 1..255");
-	const int rc = place_hits_impl(c, "place_hits_alt", alns, aln_off, n_reads, max_mm, max_alt, out);
-	if (rc) return rc;
+	RC(place_hits_impl(c, "place_hits_alt", alns, aln_off, n_reads, max_mm, max_alt, out));
 	*alt_off = c->hits_alt.h_off.as<uint64_t>();
 	*alts = c->hits_alt.h_alts.as<bwb_alt>();
 	return BWB_OK;
@@ -1660,41 +1624,36 @@ static int alt_launch(bwb_hip_ctx *c, const char *who, const uint4 *d_log, uint6
 	HIPCHK(ab.d_off.reserve(((size_t)n + 1) * 8));
 	HIPCHK(ab.d_bsum.reserve((size_t)nblk * 8));
 	if (!c->d_altctl.p) HIPCHK(c->d_altctl.alloc(16));
-	hipEvent_t ev[4] = { get_event(c), get_event(c), get_event(c), get_event(c) };
-	struct EvGuard {
-		bwb_hip_ctx *c; hipEvent_t *e;
-		~EvGuard() { for (int k = 0; k < 4; k++) if (e[k]) c->free_events.push_back(e[k]); }
-	} evg{ c, ev };
-	if (!ev[0] || !ev[1] || !ev[2] || !ev[3]) return fail(BWB_E_HIP, "hipEventCreate failed");
+	Timed t_count(c, c->rstream), t_place(c, c->rstream); /* k_alt_count and the scan; k_place_alt */
 	unsigned long long *ctl = c->d_altctl.as<unsigned long long>();
 	uint64_t *d_altoff = ab.d_off.as<uint64_t>();
 	HIPCHK(hipMemsetAsync(ctl, 0, 16, c->rstream));
-	HIPCHK(hipEventRecord(ev[0], c->rstream));
+	RC(t_count.begin());
 	hipLaunchKernelGGL(k_alt_count, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, d_log, log_n, d_off, d_cnt, n, (uint32_t)max_alt, ab.d_cnt.as<uint32_t>());
 	hipLaunchKernelGGL(k_scan_blocks, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, ab.d_cnt.as<uint32_t>(), n, d_altoff, ab.d_bsum.as<uint64_t>());
 	hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(BWB_BLOCK), 0, c->rstream, ab.d_bsum.as<uint64_t>(), (uint32_t)nblk, d_altoff + n);
 	hipLaunchKernelGGL(k_scan_add, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, d_altoff, n, ab.d_bsum.as<uint64_t>());
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(ev[1], c->rstream));
+	RC(t_count.end());
 	HIPCHK(hipMemcpyAsync(ab.h_off.p, d_altoff, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, c->rstream));
 	HIPCHK(hipStreamSynchronize(c->rstream));
 	const uint64_t total = ab.h_off.as<uint64_t>()[n];
 	float ms = 0, ms2 = 0;
-	HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+	RC(t_count.ms(&ms));
 	unsigned long long hctl[2] = { 0, 0 };
 	if (total) {
 		HIPCHK(ab.d_alts.reserve((size_t)total * sizeof(bwb_alt)));
 		HIPCHK(ab.h_alts.reserve((size_t)total * sizeof(bwb_alt)));
-		const unsigned grid = (unsigned)std::min<uint64_t>((total + BWB_OCTS_PER_BLOCK - 1) / BWB_OCTS_PER_BLOCK, (uint64_t)c->num_cu * 8);
-		HIPCHK(hipEventRecord(ev[2], c->rstream));
+		const unsigned grid = oct_grid(c, total);
+		RC(t_place.begin());
 		hipLaunchKernelGGL(k_place_alt, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, c->ix, c->d_SA.as<uint64_t>(), c->sa0_index, d_log, log_n, d_off, d_cnt, n,
 		                   (const uint64_t *)d_altoff, total, ab.d_alts.as<uint4>(), ctl);
 		HIPCHK(hipGetLastError());
-		HIPCHK(hipEventRecord(ev[3], c->rstream));
+		RC(t_place.end());
 		HIPCHK(hipMemcpyAsync(ab.h_alts.p, ab.d_alts.p, (size_t)total * sizeof(bwb_alt), hipMemcpyDeviceToHost, c->rstream));
 		HIPCHK(hipMemcpyAsync(hctl, ctl, 16, hipMemcpyDeviceToHost, c->rstream));
 		HIPCHK(hipStreamSynchronize(c->rstream));
-		HIPCHK(hipEventElapsedTime(&ms2, ev[2], ev[3]));
+		RC(t_place.ms(&ms2));
 	}
 	c->alt_ms = (double)ms + ms2; c->alt_steps = hctl[0]; c->alt_items = total;
 	if (hctl[1]) return fail(BWB_E_STATE, std::string(who) + ": an alternative's hit lies outside the hit log or its row outside the index");
@@ -1704,19 +1663,13 @@ static int alt_launch(bwb_hip_ctx *c, const char *who, const uint4 *d_log, uint6
 extern "C" int bwb_hip_slot_place_alt(bwb_hip_ctx *c, int si, int max_mm, int max_alt, const bwb_place **places, const uint64_t **alt_off, const bwb_alt **alts, uint32_t *n_reads) {
 	if (!c || !places || !alt_off || !alts || !n_reads || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_place_alt: bad argument");
 	if (max_alt < 1 || max_alt > 255) return fail(BWB_E_ARG, "slot_place_alt: max_alt must be 1..255");
-	int rc = bwb_hip_slot_place(c, si, max_mm, places, n_reads); /* (waits for the slot; refuses what slot_place refuses) */
-	if (rc) return rc;
+	RC(bwb_hip_slot_place(c, si, max_mm, places, n_reads)); /* (waits for the slot; refuses what slot_place refuses) */
 	Slot &s = c->slots[si];
 	const uint32_t n = s.n_reads;
 	if (s.placed_alt != max_alt || !n) {
 		uint64_t log_n = 0;
-		if (n) {
-			rc = fetch(c, s.h_ctl.p, s.ctl_count(), 8);
-			if (rc) return rc;
-			log_n = std::min<unsigned long long>(*s.h_ctl.as<unsigned long long>(), s.log_cap);
-		}
-		rc = alt_launch(c, "slot_place_alt", s.d_log.as<uint4>(), log_n, s.d_off.as<uint64_t>(), s.d_n.as<uint32_t>(), n, max_alt, s.alt);
-		if (rc) return rc;
+		if (n) RC(slot_log_n(c, s, &log_n));
+		RC(alt_launch(c, "slot_place_alt", s.d_log.as<uint4>(), log_n, s.d_off.as<uint64_t>(), s.d_n.as<uint32_t>(), n, max_alt, s.alt));
 		s.placed_alt = max_alt;
 	}
 	*alt_off = s.alt.h_off.as<uint64_t>();
@@ -1752,8 +1705,7 @@ extern "C" int bwb_hip_debug_calcd_work(bwb_hip_ctx *c, uint32_t *out) {
 	if (!c || !c->slots[0].uploaded) return fail(BWB_E_STATE, "no batch");
 	Slot &s = c->slots[0];
 	std::vector<uint8_t> h((size_t)s.n_reads * s.dstride);
-	int rc = fetch(c, h.data(), s.d_dbuf.p, h.size());
-	if (rc) return rc;
+	RC(fetch(c, h.data(), s.d_dbuf.p, h.size()));
 	for (uint32_t i = 0; i < s.n_reads; i++) memcpy(&out[i], &h[(size_t)i * s.dstride + s.dstride - 8], 4);
 	return BWB_OK;
 }

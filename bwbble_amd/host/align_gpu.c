@@ -22,11 +22,6 @@
 #include <unistd.h>
 #include "bwb_host.h"
 
-/* reads per GPU batch (BWB_CHUNK).  Batches are streamed as slices that park their unfinished reads for the next slice, so the
- * size no longer decides how much of the GPU idles at the end of a batch; it trades launch overhead against the balance
- * between GPUs and the memory of a slot (about 1 KB per read). */
-#define GPU_CHUNK_DEFAULT (1u << 21)
-
 static double wall(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
 
 void set_default_aln_params(aln_params_t *p) { bwb_default_params(p); } /* align.c:22-38 */
@@ -124,16 +119,21 @@ static void *reader_thread(void *arg) {
 	return NULL;
 }
 
+/* the chunk's output is complete: wakes the writer */
+static void chunk_ready(pipe_t *pp, chunk_t *c) {
+	pthread_mutex_lock(&pp->mu);
+	c->ready = 1;
+	pthread_cond_broadcast(&pp->cv_done);
+	pthread_mutex_unlock(&pp->mu);
+}
+
 /* hands the finished chunk in `slot` to the writer */
 static void retire(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c) {
 	bwb_result r;
 	if (bwb_hip_slot_result(ctx, slot, &r)) bwb_die("align_reads_inexact_gpu: GPU %d: %s", w->gpu, bwb_hip_last_error());
 	c->n = r.n_reads;
 	c->buf = alns2alnf_buf(r.alns, r.aln_off, r.n_reads, &c->buf_len); /* (with all cores; the library's result buffers stay valid until the slot is uploaded again) */
-	pthread_mutex_lock(&w->pp->mu);
-	c->ready = 1;
-	pthread_cond_broadcast(&w->pp->cv_done);
-	pthread_mutex_unlock(&w->pp->mu);
+	chunk_ready(w->pp, c);
 }
 
 /* map: the same hand-over with the chunk's SAM text.  The reads are evaluated where their hits lie (kernel k_place); what comes back is one
@@ -162,10 +162,7 @@ static void retire_map(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c) {
 	}
 	free(c->fq.seq); free(c->fq.len); free(c->fq.name_off); free(c->fq.qual_off); free(c->fq.name_len);
 	c->fq.seq = NULL; c->fq.len = NULL; c->fq.name_off = NULL; c->fq.qual_off = NULL; c->fq.name_len = NULL;
-	pthread_mutex_lock(&w->pp->mu);
-	c->ready = 1;
-	pthread_cond_broadcast(&w->pp->cv_done);
-	pthread_mutex_unlock(&w->pp->mu);
+	chunk_ready(w->pp, c);
 }
 
 /* the CPUs of the GPU's NUMA node, when the machine has several nodes: the worker thread, its pinned staging buffers (first touched
@@ -388,6 +385,27 @@ static int run_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, 
 	return 0;
 }
 
+/* -P (align.c:59-65): the first run on an index leaves <fasta>.pre behind (precalc.c: written, never read).  A file that is there -
+ * load_precalc_sa_intervals (align.c:226-238) would read it - only has its shape checked (precalc.c); without one the index is waited
+ * for, the table built, and *t (the caller's start time, of the index load so far) restarted. */
+static void ensure_precalc(bwt_t *BWT, const char *fastaFname, aln_params_t *params, double *t) {
+	const size_t L = strlen(fastaFname) + 8;
+	char *preFname = (char *)malloc(L);
+	snprintf(preFname, L, "%s.pre", fastaFname);
+	FILE *pf = fopen(preFname, "r");
+	if (pf) {
+		fclose(pf);
+		if (check_precalc_file(preFname)) fprintf(stderr, "warning: %s is not a complete table of 16777216 interval lists (a run of the reference would fail on it): delete it to have it rebuilt\n", preFname);
+	} else {
+		load_bwt_wait(BWT);
+		printf("Total BWT loading time: %.2f sec\n", wall() - *t);
+		*t = wall();
+		precalc_sa_intervals(BWT, params, preFname);
+		printf("Total pre-calculated intervals time: %.2f sec\n", wall() - *t);
+	}
+	free(preFname);
+}
+
 int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_t *params, int n_gpus) { /* align.c:40-87 */
 	printf("**** BWBBLE Read Alignment ****\n");
 	size_t L = strlen(fastaFname) + 8;
@@ -399,22 +417,7 @@ int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_
 	 * file while every GPU worker already uploads its head (bwt_io.c, bwb_hip_ctx_create_streamed), and the reader thread parses the
 	 * FASTQ chunk by chunk while the GPUs align the chunks before. */
 	bwt_t *BWT = load_bwt_start(bwtFname, 0);
-	if (params->use_precalc) { /* align.c:59-65: the first `align -P` on an index leaves <fasta>.pre behind (precalc.c: written, never read) */
-		char *preFname = (char *)malloc(L);
-		snprintf(preFname, L, "%s.pre", fastaFname);
-		FILE *pf = fopen(preFname, "r");
-		if (pf) { /* load_precalc_sa_intervals (align.c:226-238) would read it: here only its shape is checked (precalc.c) */
-			fclose(pf);
-			if (check_precalc_file(preFname)) fprintf(stderr, "warning: %s is not a complete table of 16777216 interval lists (a run of the reference would fail on it): delete it to have it rebuilt\n", preFname);
-		} else {
-			load_bwt_wait(BWT);
-			printf("Total BWT loading time: %.2f sec\n", wall() - t);
-			t = wall();
-			precalc_sa_intervals(BWT, params, preFname);
-			printf("Total pre-calculated intervals time: %.2f sec\n", wall() - t);
-		}
-		free(preFname);
-	}
+	if (params->use_precalc) ensure_precalc(BWT, fastaFname, params, &t);
 	t = wall();
 	align_reads_inexact_gpu_stream(BWT, readsFname, params, alnsFname, n_gpus);   /* the seam: align.c:72-76 */
 	printf("Total read alignment time (index and read loading overlapped): %.2f sec\n", wall() - t);
@@ -435,22 +438,7 @@ int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *
 	double t = wall();
 	bwt_t *BWT = load_bwt_start(bwtFname, 1);
 	fasta_annotations_t *ann = annf2ann(annFname);
-	if (params->use_precalc) { /* as in align_reads (align.c:59-65) */
-		char *preFname = (char *)malloc(L);
-		snprintf(preFname, L, "%s.pre", fastaFname);
-		FILE *pf = fopen(preFname, "r");
-		if (pf) {
-			fclose(pf);
-			if (check_precalc_file(preFname)) fprintf(stderr, "warning: %s is not a complete table of 16777216 interval lists (a run of the reference would fail on it): delete it to have it rebuilt\n", preFname);
-		} else {
-			load_bwt_wait(BWT);
-			printf("Total BWT loading time: %.2f sec\n", wall() - t);
-			t = wall();
-			precalc_sa_intervals(BWT, params, preFname);
-			printf("Total pre-calculated intervals time: %.2f sec\n", wall() - t);
-		}
-		free(preFname);
-	}
+	if (params->use_precalc) ensure_precalc(BWT, fastaFname, params, &t);
 	FILE *sam = fopen(samFname, "w");
 	if (!sam) { perror(samFname); bwb_die("map_reads: Cannot open SAM file: %s!", samFname); }
 	sam_write_header(sam, ann);

@@ -112,6 +112,10 @@ void free_alns_batch(alns_batch_t *b);
 int aln_path_bytes(const bwb_aln *a, unsigned char *path /* >= 272 bytes */); /* edit path from the gap runs; returns aln_length */
 
 /* align_gpu.c */
+/* reads per GPU batch (BWB_CHUNK).  Batches are streamed as slices that park their unfinished reads for the next slice, so the
+ * size no longer decides how much of the GPU idles at the end of a batch; it trades launch overhead against the balance
+ * between GPUs and the memory of a slot (about 1 KB per read). */
+#define GPU_CHUNK_DEFAULT (1u << 21)
 void set_default_aln_params(aln_params_t *params);                     /* align.c:22-38 */
 int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_t *params, int n_gpus); /* align.c:40-87 */
 int align_reads_inexact_gpu_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, char *alnFname, int n_gpus); /* the GPU's align_reads_inexact_parallel (inexact_match.h:40) over a streamed FASTQ */

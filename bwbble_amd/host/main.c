@@ -209,7 +209,7 @@ int main(int argc, char *argv[]) {
 		 * (parallel record scan + base encoding, reads.c) in chunks of BWB_CHUNK reads, and the chunk serialiser (aln_io.c) on an .aln file */
 		if (argc < 3) { printf("Usage: bwbble hostbench <reads_fastq> [<aln>]\n"); exit(1); }
 		struct timespec t0, t1;
-		const uint32_t chunk = getenv("BWB_CHUNK") ? (uint32_t)strtoul(getenv("BWB_CHUNK"), NULL, 10) : (1u << 21);
+		const uint32_t chunk = getenv("BWB_CHUNK") ? (uint32_t)strtoul(getenv("BWB_CHUNK"), NULL, 10) : GPU_CHUNK_DEFAULT;
 		clock_gettime(CLOCK_MONOTONIC, &t0);
 		fq_stream *fs = fq_open(argv[2]);
 		fq_chunk_t ch;

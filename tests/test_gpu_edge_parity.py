@@ -341,6 +341,7 @@ def test_force_64bit_positions(mid, oracle, monkeypatch):
     check(ctx, oracle, idx, ["-n", "3"], seqs, lens)
     check(ctx, oracle, idx, ["-n", "3", "-o", "2"], seqs, lens)
     check(ctx, oracle, idx, ["-S", "-n", "2"], seqs, lens)
+    check(ctx, oracle, idx, ["-S", "-n", "4", "-o", "2", "-e", "4"], seqs, lens)  # 64-bit, 32-byte entries, single genome: the eighth kl_search
     check(ctx, oracle, idx, ["-P", "-n", "2"], seqs, lens)
     ctx.close()
 
