@@ -382,35 +382,6 @@ __device__ __forceinline__ uint32_t wave_children(const uint4 *__restrict__ buck
 	return need ? (ne & 0xFFFEu) : 0u;
 }
 
-/* ---- SA-interval list being built: add_sa_interval (align.c:93-110), tail in registers ------------ */
-template <typename P> struct ListW {
-	int T;        /* intervals so far, including the open tail */
-	P tL, tU;
-	P fL, fU;     /* the list's FIRST interval, once it is final (T >= 2): the step that reads this list next starts with it, and gets it from
-	                 here instead of loading what this step has just stored (kl_search) */
-};
-/* the list being built is the one the current step does not read: buffer base + sel * cap (no pointer kept in registers).
- * One divergent region only - the store of a tail that cannot be merged -, everything else is selects: the loops that call this run
- * several trips per wave iteration with a few lanes each (kl_calc_d: 5.4, kl_search's exact steps: 2.6, tools/bbprof.py), and the nest
- * of four branches this was until round 4 cost more scalar mask bookkeeping per trip (25 instructions) than it did work. */
-template <typename P> __device__ __forceinline__ void list_add(ListW<P> &l, Intv<P> *base, int sel, P L, P U, int cap) {
-	const bool has = l.T != 0;
-	const bool merge = has & (L == (P)(l.tU + 1));
-	const bool flush = has & !merge;
-	/* The tail goes to its slot WHATEVER happens to it (round 5): when it is merged, or when there is none yet (slot 0), the slot is written
-	 * again before anything reads it - a list's readers take the intervals below the tail from memory and the tail from registers - and
-	 * all but one append in two hundred flush anyway: the branch around the store was a divergent region per trip, 2.6 trips per iteration. */
-	{ Intv<P> *buf = base + sel * cap; const int at = l.T > 0 ? l.T - 1 : 0; Intv<P> v; v.L = l.tL; v.U = l.tU; buf[at] = v; }
-	const bool first = flush & (l.T == 1);
-	l.fL = first ? l.tL : l.fL; l.fU = first ? l.tU : l.fU;
-	l.tL = merge ? l.tL : L;
-	l.tU = U;
-	l.T += merge ? 0 : 1;
-}
-/* room for the children of one more interval (at most 15 appends)?  Checked once per interval, ahead of its appends: a list that comes
- * within 15 intervals of its capacity sends the read to the next scratch class a little early, which changes nothing but that. */
-template <typename P> __device__ __forceinline__ bool list_full(const ListW<P> &l, int cap) { return l.T + 15 > cap; }
-
 /* A read is finished: its status, hit count, offset and hit-log records are published BEFORE the slot's counter moves.  The
  * host polls that counter and copies the results on another stream while this kernel may still be running (a slot's parked reads
  * finish inside the NEXT slot's slice): plain stores can sit dirty in this XCD's L2 until the end of the kernel, so a release
@@ -447,12 +418,24 @@ __device__ __forceinline__ void prefetch32(uint32_t &dst, const void *p, unsigne
 	unsigned long long sv;
 	asm volatile("s_and_saveexec_b64 %[sv], %[m]\n\tglobal_load_dword %[d], %[p], off\n\ts_mov_b64 exec, %[sv]" : [d] "+v"(dst), [sv] "=&s"(sv) : [p] "v"(p), [m] "s"(mask) : "memory", "scc");
 }
+/* The same for a store that only the lanes of `mask` make (list_add): one statement in uniform control flow instead of a divergent region.
+ * The data registers are read when the store is issued (and the s_mov that restores the exec mask stands between the store and whatever
+ * writes them next): nothing stays in flight, and tools/check_prefetch_regs.py has nothing to prove about it. */
+__device__ __forceinline__ void store128(void *p, const u32x4 v, unsigned long long mask) {
+	unsigned long long sv;
+	asm volatile("s_and_saveexec_b64 %[sv], %[m]\n\tglobal_store_dwordx4 %[p], %[d], off\n\ts_mov_b64 exec, %[sv]" : [sv] "=&s"(sv) : [p] "v"(p), [d] "v"(v), [m] "s"(mask) : "memory", "scc");
+}
+__device__ __forceinline__ void store64(void *p, const u32x2 v, unsigned long long mask) {
+	unsigned long long sv;
+	asm volatile("s_and_saveexec_b64 %[sv], %[m]\n\tglobal_store_dwordx2 %[p], %[d], off\n\ts_mov_b64 exec, %[sv]" : [sv] "=&s"(sv) : [p] "v"(p), [d] "v"(v), [m] "s"(mask) : "memory", "scc");
+}
 
 /* an SA interval in the registers it is loaded into (16 bytes with 64-bit positions, 8 with 32-bit ones) */
 template <typename P> struct IntvRegs;
 template <> struct IntvRegs<uint64_t> {
 	typedef u32x4 W;
 	static __device__ __forceinline__ void fetch(W &d, const Intv<uint64_t> *p, unsigned long long m) { prefetch128(d, p, m); }
+	static __device__ __forceinline__ void store(Intv<uint64_t> *p, const W v, unsigned long long m) { store128(p, v, m); }
 	static __device__ __forceinline__ uint64_t lo(const W w) { return ((uint64_t)w.y << 32) | w.x; }
 	static __device__ __forceinline__ uint64_t hi(const W w) { return ((uint64_t)w.w << 32) | w.z; }
 	static __device__ __forceinline__ W make(uint64_t L, uint64_t U) { return W{ (uint32_t)L, (uint32_t)(L >> 32), (uint32_t)U, (uint32_t)(U >> 32) }; }
@@ -460,10 +443,54 @@ template <> struct IntvRegs<uint64_t> {
 template <> struct IntvRegs<uint32_t> {
 	typedef u32x2 W;
 	static __device__ __forceinline__ void fetch(W &d, const Intv<uint32_t> *p, unsigned long long m) { prefetch64(d, p, m); }
+	static __device__ __forceinline__ void store(Intv<uint32_t> *p, const W v, unsigned long long m) { store64(p, v, m); }
 	static __device__ __forceinline__ uint32_t lo(const W w) { return w.x; }
 	static __device__ __forceinline__ uint32_t hi(const W w) { return w.y; }
 	static __device__ __forceinline__ W make(uint32_t L, uint32_t U) { return W{ L, U }; }
 };
+/* ---- SA-interval list being built: add_sa_interval (align.c:93-110), tail in registers ------------ */
+template <typename P> struct ListW {
+	int T;        /* intervals so far, including the open tail */
+	P tL, tU;
+	P fL, fU;     /* the list's FIRST interval, once it is final (T >= 2): the step that reads this list next starts with it, and gets it from
+	                 here instead of loading what this step has just stored (kl_search) */
+};
+/* the list being built is the one the current step does not read: buffer base + sel * cap (no pointer kept in registers).
+ * One divergent region only - the store of a tail that cannot be merged -, everything else is selects: the loops that call this run
+ * several trips per wave iteration with a few lanes each (kl_calc_d: 5.4, kl_search's exact steps: 2.6, tools/bbprof.py), and the nest
+ * of four branches this was until round 4 cost more scalar mask bookkeeping per trip (25 instructions) than it did work. */
+/* READ_BACK (kl_search): only the stores that something reads back.  kl_search takes a list's FIRST interval from fL / fU and its tail from
+ * tL / tU (both travel in registers and in the park save area); from memory it reads slots 1 .. T-2 alone.  So the one store that counts is
+ * that of a tail displaced by an append that does not merge, onto a list that already has two intervals - it lands in slot T-1 >= 1 -;
+ * the store of the first append (the zeroed tail to slot 0), of the second (slot 0) and of every merging append (a slot that is written
+ * again before anything could read it) were 8.9 G write requests per 2.5 M-read step at GRCh37 scale, one append in four, for nothing
+ * (`make hist`: list_st_first / _second / _merge against list_st_interior = list_ld).  Slot 0 of such a list is NEVER written.
+ * No branch around the store (the divergent region per trip that round 5 removed): like prefetch128 it is one statement in uniform
+ * control flow whose asm narrows the exec mask itself - and, being a store, it leaves no register in flight behind it.
+ * !READ_BACK (k_dtab_level): every tail goes to its slot, as since round 5 - that kernel copies slots 0 .. T-2 of the finished list from
+ * memory to the level's pool (`dst[t] = lbuf[t]`), slot 0 included. */
+template <typename P, bool READ_BACK = false> __device__ __forceinline__ void list_add(ListW<P> &l, Intv<P> *base, int sel, P L, P U, int cap) {
+	const bool has = l.T != 0;
+	const bool merge = has & (L == (P)(l.tU + 1));
+	const bool flush = has & !merge;
+	if (READ_BACK) {
+		IntvRegs<P>::store(base + sel * cap + (l.T - 1), IntvRegs<P>::make(l.tL, l.tU), wballot(flush & (l.T >= 2))); /* (the address is formed for every lane and used by those of the mask) */
+	} else {
+		/* The tail goes to its slot WHATEVER happens to it (round 5): when it is merged, or when there is none yet (slot 0), the slot is written
+		 * again before anything reads it, and all but one append in two hundred flush anyway: the branch around the store was a divergent
+		 * region per trip. */
+		Intv<P> *buf = base + sel * cap; const int at = l.T > 0 ? l.T - 1 : 0; Intv<P> v; v.L = l.tL; v.U = l.tU; buf[at] = v;
+	}
+	const bool first = flush & (l.T == 1);
+	l.fL = first ? l.tL : l.fL; l.fU = first ? l.tU : l.fU;
+	l.tL = merge ? l.tL : L;
+	l.tU = U;
+	l.T += merge ? 0 : 1;
+}
+/* room for the children of one more interval (at most 15 appends)?  Checked once per interval, ahead of its appends: a list that comes
+ * within 15 intervals of its capacity sends the read to the next scratch class a little early, which changes nothing but that. */
+template <typename P> __device__ __forceinline__ bool list_full(const ListW<P> &l, int cap) { return l.T + 15 > cap; }
+
 /* kl_calc_d's list being built: finished intervals are collected FOUR AT A TIME and stored as one aligned group (round 5: a 16-byte store
  * is a 32-byte write request to the memory fabric, 12 G of them per launch at GRCh37 scale; back-to-back stores into one 64-byte line merge) */
 template <typename P> struct ListBuf { typename IntvRegs<P>::W b0, b1, b2, b3; };
@@ -1143,14 +1170,17 @@ __device__ __forceinline__ uint32_t wave_sum5(uint32_t v) {
 #ifdef BWB_HIST
 #define HIST(k, cond) do { hist[k] += (unsigned long long)__popcll(wballot(cond)); } while (0)
 #define HISTW(k, v) do { hist[k] += (unsigned long long)(v); } while (0)
+#define HISTL(var, cond) do { var += (cond) ? 1ull : 0ull; } while (0) /* a per-lane sum: for code that not every lane of the wave runs */
 #else
 #define HIST(k, cond) do { } while (0)
 #define HISTW(k, v) do { } while (0)
+#define HISTL(var, cond) do { } while (0)
 #endif
 enum { H_ITER = 0, H_POP, H_POP_FROM_MIRROR, H_POP_GAPPED, H_PRUNED, H_HIT, H_EXACT_START, H_EXPAND, H_EXACT_STEP, H_NEED_RANK, H_SAME_BKT, H_TWO_BKT,
        H_W1, H_W2, H_W4, H_W8, H_W32, H_W128, H_WBIG, H_NE0, H_NE1, H_NE2, H_NE3_4, H_NE5_8, H_NE9, H_PUSH_GAP, H_PUSH_MIS, H_PUSH_MATCH,
        H_DEL_OK, H_MM_OK, H_INS_OK, H_TOP_RELOAD, H_WAVE_ITERS, H_WAVE_GAPLOOP, H_WAVE_MISLOOP, H_WAVE_MATCHLOOP, H_WAVE_ANY_TWO_BKT, H_WAVE_ANY_WIDE8,
-       H_WAVE_NREQ_LE16, H_ALPHA, H_EXACT_MULTI, H_FINISH, H_ALLOC, H_WAVE_ANY_EXACT, H_WAVE_ANY_EXPAND, H_WAVE_ALL_EXACT, H_EXP_SAME_W1, H_EXP_SAME_W2_4, H_PH_GAP, H_PH_MIS, H_PH_POP, H_EXPAND_AFTER_HIT, H_N };
+       H_WAVE_NREQ_LE16, H_ALPHA, H_EXACT_MULTI, H_FINISH, H_ALLOC, H_WAVE_ANY_EXACT, H_WAVE_ANY_EXPAND, H_WAVE_ALL_EXACT, H_EXP_SAME_W1, H_EXP_SAME_W2_4, H_PH_GAP, H_PH_MIS, H_PH_POP, H_EXPAND_AFTER_HIT,
+       H_LIST_ST_FIRST, H_LIST_ST_SECOND, H_LIST_ST_MERGE, H_LIST_ST_INTERIOR, H_LIST_LD, H_N };
 
 /* Slices.  One launch of kl_search = one slice of the stream of batches.  Per-read work is heavy-tailed, so a
  * launch that runs until its last read is done ends with ever fewer busy lanes.  Instead, when the cursor of the batch runs
@@ -1298,6 +1328,7 @@ __global__ __launch_bounds__(LANE_BLOCK, LANE_WAVES_PER_SIMD) void kl_search(Dev
 #ifdef BWB_HIST
 	unsigned long long hist[H_N] = { 0 };
 	unsigned long long hl_gap = 0, hl_mis = 0, hl_match = 0, hl_phg = 0, hl_phx = 0; /* per-lane sums */
+	unsigned long long hl_lf = 0, hl_ls = 0, hl_lm = 0, hl_li = 0, hl_ld = 0; /* the exact step's list traffic: appends by class (list_add), interval loads */
 #endif
 	if (wk.resume && (mysave[0].x & 1u)) {
 		/* ---- resume the read this lane parked at the end of the previous slice ---- */
@@ -1504,7 +1535,12 @@ __global__ __launch_bounds__(LANE_BLOCK, LANE_WAVES_PER_SIMD) void kl_search(Dev
 		{
 			const bool mid = ex & (s != curT - 1), take = mid & nxi_valid;
 			iL = take ? nxi.L : iL; iU = take ? nxi.U : iU; /* fetched at the end of the previous step */
-			if (mid & !nxi_valid) { /* (only the iteration after a resume: waited for inside the branch, see LHeap::pop) */
+			/* A fallback that slot 0 - which list_add<P, true> never writes - cannot reach: an exact step leaves nxi_valid == (s != curT - 1) behind
+			 * (or ends the tail), a tail starts with curT == 1, and park / resume carry nxi_valid and nxi along (save words 0 and 5), so `mid`
+			 * implies nxi_valid at every start of an iteration; and s == 0 with curT >= 2 exists only right after a swap, which has put the
+			 * first interval into nxi from registers.  Kept for the slots >= 1, which are in memory. */
+			if (mid & !nxi_valid) { /* (waited for inside the branch, see LHeap::pop) */
+				HISTL(hl_ld, true);
 				const Intv<P> v = (lbase + (cursel ? lcap : 0))[s]; iL = v.L; iU = v.U;
 				asm volatile("" :: "v"(iL), "v"(iU));
 			}
@@ -1512,6 +1548,7 @@ __global__ __launch_bounds__(LANE_BLOCK, LANE_WAVES_PER_SIMD) void kl_search(Dev
 		/* the interval of the step's NEXT iteration, when it is one of the list in memory (not its tail, which is in registers): fetched
 		 * now, under this iteration's gather (round 3 fetched it at the end of the iteration and used it at the start of the next) */
 		if (ex && s + 1 < curT - 1) nxi = (lbase + (cursel ? lcap : 0))[s + 1];
+		HISTL(hl_ld, ex && s + 1 < curT - 1);
 		h.prefetch(pf_top, pf_hdr); /* (the lanes have met again: see prefetch128) */
 
 #ifdef BWB_HIST
@@ -1846,7 +1883,13 @@ __global__ __launch_bounds__(LANE_BLOCK, LANE_WAVES_PER_SIMD) void kl_search(Dev
 					P cl, cu;
 					kid(j, cl, cu);
 					nxw += (uint32_t)(cu - cl + 1);
-					list_add<P>(nx, lbase, cursel ? 0 : 1, cl, cu, lcap);
+#ifdef BWB_HIST
+					{ /* the appends by what becomes of the displaced tail (list_add): only the last class is read back, and only that one is stored */
+						const bool mg_ = nx.T != 0 && cl == (P)(nx.tU + 1);
+						HISTL(hl_lf, nx.T == 0); HISTL(hl_ls, nx.T == 1 && !mg_); HISTL(hl_lm, mg_); HISTL(hl_li, nx.T >= 2 && !mg_);
+					}
+#endif
+					list_add<P, true>(nx, lbase, cursel ? 0 : 1, cl, cu, lcap);
 				}
 				s += isN ? 0 : 1;
 				const bool swap = !isN && !ovf && s >= curT;
@@ -1878,7 +1921,8 @@ __global__ __launch_bounds__(LANE_BLOCK, LANE_WAVES_PER_SIMD) void kl_search(Dev
 					for (int k = 0; k < curT && !ovf; k++) {
 						P iL2, iU2;
 						if (k == curT - 1) { iL2 = cL; iU2 = cU; }
-						else { const Intv<P> v = (lbase + (cursel ? lcap : 0))[k]; iL2 = v.L; iU2 = v.U; }
+						else if (k == 0) { iL2 = nxi.L; iU2 = nxi.U; } /* (the first of several: in registers since the swap above, like the hit path's; slot 0 is not written) */
+						else { HISTL(hl_ld, true); const Intv<P> v = (lbase + (cursel ? lcap : 0))[k]; iL2 = v.L; iU2 = v.U; }
 						const uint32_t st_old = st;
 						st = h.reserve(st_old, 1, ovf, xs);
 						if (!ovf) { if (st != st_old) h.cprev = st_old; st++; h.set_top(iL2, iU2, ent_f, ent_sa, ~0u, ~0u); h.store_packed(st, h.tw, h.tw1); }
@@ -1911,6 +1955,7 @@ __global__ __launch_bounds__(LANE_BLOCK, LANE_WAVES_PER_SIMD) void kl_search(Dev
 						if (curT >= 2) { add_aln(nxi.L, nxi.U, e_score, alen2); k = 1; }
 						if (e_go == 0) { /* no duplicate check (align.c:273-280 applies to gapped entries): four list loads in flight at a time */
 							for (; k + 4 <= curT - 1 && n_alns + 4 <= (int)sc_acap; k += 4) {
+								HISTL(hl_ld, true); HISTL(hl_ld, true); HISTL(hl_ld, true); HISTL(hl_ld, true);
 								const Intv<P> v0 = lst[k], v1 = lst[k + 1], v2 = lst[k + 2], v3 = lst[k + 3];
 								add_aln(v0.L, v0.U, e_score, alen2); add_aln(v1.L, v1.U, e_score, alen2);
 								add_aln(v2.L, v2.U, e_score, alen2); add_aln(v3.L, v3.U, e_score, alen2);
@@ -1918,6 +1963,7 @@ __global__ __launch_bounds__(LANE_BLOCK, LANE_WAVES_PER_SIMD) void kl_search(Dev
 							const int rem = curT - 1 - k; /* 0..3 intervals of the list in memory are left */
 							if (rem > 0 && n_alns + rem <= (int)sc_acap) {
 								Intv<P> v0 = lst[k], v1 = v0, v2 = v0;
+								HISTL(hl_ld, true); HISTL(hl_ld, rem > 1); HISTL(hl_ld, rem > 2);
 								if (rem > 1) v1 = lst[k + 1];
 								if (rem > 2) v2 = lst[k + 2];
 								add_aln(v0.L, v0.U, e_score, alen2);
@@ -1929,7 +1975,7 @@ __global__ __launch_bounds__(LANE_BLOCK, LANE_WAVES_PER_SIMD) void kl_search(Dev
 						for (; k < curT && !ovf; k++) {
 							P L, U;
 							if (k == curT - 1) { L = cL; U = cU; }
-							else { const Intv<P> v = lst[k]; L = v.L; U = v.U; }
+							else { HISTL(hl_ld, true); const Intv<P> v = lst[k]; L = v.L; U = v.U; }
 							add_aln(L, U, e_score, alen2);
 						}
 					}
@@ -2006,6 +2052,11 @@ __global__ __launch_bounds__(LANE_BLOCK, LANE_WAVES_PER_SIMD) void kl_search(Dev
 	if (hl_match) atomicAdd(&R_stats[STAT_HIST + H_PUSH_MATCH], hl_match);
 	if (hl_phg) atomicAdd(&R_stats[STAT_HIST + H_PH_GAP], hl_phg);
 	if (hl_phx) atomicAdd(&R_stats[STAT_HIST + H_PH_MIS], hl_phx);
+	if (hl_lf) atomicAdd(&R_stats[STAT_HIST + H_LIST_ST_FIRST], hl_lf);
+	if (hl_ls) atomicAdd(&R_stats[STAT_HIST + H_LIST_ST_SECOND], hl_ls);
+	if (hl_lm) atomicAdd(&R_stats[STAT_HIST + H_LIST_ST_MERGE], hl_lm);
+	if (hl_li) atomicAdd(&R_stats[STAT_HIST + H_LIST_ST_INTERIOR], hl_li);
+	if (hl_ld) atomicAdd(&R_stats[STAT_HIST + H_LIST_LD], hl_ld);
 #endif
 	if (!parked) mysave[0].x = 0u;
 	/* the last wave of the block to leave hands the block's recycle stack to the next slice */
