@@ -66,6 +66,7 @@ assert ALT_DTYPE.itemsize == 32
 
 _FLAG = {"-M": "mm_score", "-O": "gapo_score", "-E": "gape_score", "-n": "max_diff", "-k": "max_diff_seed",
          "-o": "max_gapo", "-e": "max_gape", "-l": "seed_length", "-m": "max_entries", "-t": "n_threads"}
+NO_FLAG = ("max_best", "no_indel_length")  # fields of aln_params_t without a flag: keyword arguments of params()
 
 _lib = None
 
@@ -150,8 +151,9 @@ def device_count():
     return lib().bwb_hip_device_count()
 
 
-def params(flags=()):
-    """Defaults of set_default_aln_params (align.c:22-38) + `bwbble align` style flags (main.c:100-117)."""
+def params(flags=(), **fields):
+    """Defaults of set_default_aln_params (align.c:22-38) + `bwbble align` style flags (main.c:100-117) + the fields of aln_params_t
+    that the CLI has no flag for and a caller of the C-ABI may still set: max_best=, no_indel_length=."""
     p = Params()
     lib().bwb_default_params(C.byref(p))
     flags = list(flags)
@@ -166,6 +168,10 @@ def params(flags=()):
         else:
             setattr(p, _FLAG[flags[i]], int(flags[i + 1]))
             i += 2
+    for name, v in fields.items():
+        if name not in NO_FLAG:
+            raise TypeError(f"params() takes no field {name!r}")
+        setattr(p, name, int(v))
     return p
 
 

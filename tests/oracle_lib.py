@@ -33,6 +33,7 @@ class Dlb(C.Structure):
 
 _FLAG = {"-M": "mm_score", "-O": "gapo_score", "-E": "gape_score", "-n": "max_diff", "-k": "max_diff_seed",
          "-o": "max_gapo", "-e": "max_gape", "-l": "seed_length", "-m": "max_entries", "-t": "n_threads"}
+NO_FLAG = ("max_best", "no_indel_length")  # fields of aln_params_t that `bwbble align` has no flag for: keyword arguments of params()
 
 
 class Oracle:
@@ -57,7 +58,8 @@ class Oracle:
         L.bwb_or_SA.restype = C.c_uint64
         L.bwb_or_SA.argtypes = [C.POINTER(Index), C.c_uint64]
 
-    def params(self, flags=()):
+    def params(self, flags=(), **fields):
+        """the defaults, `bwbble align` style flags, then aln_params_t fields no flag reaches (max_best=, no_indel_length=)"""
         p = Params()
         self.lib.bwb_or_default_params(C.byref(p))
         flags = list(flags)
@@ -73,6 +75,10 @@ class Oracle:
                 continue
             setattr(p, _FLAG[flags[i]], int(flags[i + 1]))
             i += 2
+        for name, v in fields.items():
+            if name not in NO_FLAG:
+                raise TypeError(f"params() takes no field {name!r}")
+            setattr(p, name, int(v))
         return p
 
     def load_index(self, bwt_path, load_sa=False):
