@@ -24,6 +24,7 @@ EXPORTS = [
     "bwb_hip_ctx_create_async", "bwb_hip_ctx_index_wait", "bwb_hip_setup_times", "bwb_hip_dtab_info",
     "bwb_hip_slot_place", "bwb_hip_batch_place", "bwb_hip_place_stats", "bwb_hip_place_hits",
     "bwb_hip_slot_place_alt", "bwb_hip_batch_place_alt", "bwb_hip_place_alt_stats", "bwb_hip_place_hits_alt",
+    "bwb_hip_set_loci", "bwb_hip_slot_locus", "bwb_hip_batch_locus", "bwb_hip_locus_places", "bwb_hip_locus_stats",
 ]
 ABI_VERSION = 3  # BWB_HIP_ABI_VERSION (include/bwbble_hip.h)
 MAX_SLOTS = 8  # BWB_MAX_SLOTS
@@ -63,6 +64,12 @@ PLACE_MAPPED, PLACE_REVERSE = 1, 2
 ALT_DTYPE = np.dtype([("pos", "<u8"), ("flags", "u1"), ("hit", "u1"), ("num_mm", "u1"), ("num_gapo", "u1"), ("num_gape", "u1"),
                       ("reserved", "u1"), ("aln_length", "<u2"), ("gap_run", "<u2", (8,))])
 assert ALT_DTYPE.itemsize == 32
+# bwb_bubble: one bubble of bubble.data (mg-ref/comb.cpp:245-253); bwb_locus: where a placement lies in reference coordinates (kernel k_locus)
+BUBBLE_DTYPE = np.dtype([("A", "<i8"), ("B_minus_A", "<i8"), ("C", "<i8"), ("D_minus_C", "<i8"), ("ref_len", "<i4"), ("alt_len", "<i4")])
+assert BUBBLE_DTYPE.itemsize == 40
+LOCUS_DTYPE = np.dtype([("seqid", "<i4"), ("pos1", "<i4"), ("bubble", "<i4"), ("kind", "u1"), ("reserved", "u1", (3,)), ("ref_lo", "<i8"), ("ref_hi", "<i8")])
+assert LOCUS_DTYPE.itemsize == 32
+LOCUS_POINT, LOCUS_RANGE = 1, 2
 
 _FLAG = {"-M": "mm_score", "-O": "gapo_score", "-E": "gape_score", "-n": "max_diff", "-k": "max_diff_seed",
          "-o": "max_gapo", "-e": "max_gape", "-l": "seed_length", "-m": "max_entries", "-t": "n_threads"}
@@ -120,6 +127,11 @@ def lib():
         L.bwb_hip_batch_place_alt.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
         L.bwb_hip_place_alt_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         L.bwb_hip_place_hits_alt.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        L.bwb_hip_set_loci.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        L.bwb_hip_slot_locus.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
+        L.bwb_hip_batch_locus.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
+        L.bwb_hip_locus_places.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.bwb_hip_locus_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -388,6 +400,47 @@ class Context:
         """(items, invPsi steps = rank-block visits, kernel ms) of the last place_alt call"""
         return self._count_steps_ms(lib().bwb_hip_place_alt_stats)
 
+    # -- bubble hits in reference coordinates (bC / bP): one LOCUS_DTYPE record per read (needs set_loci; the slot forms need set_sa) -----------
+    def set_loci(self, start, end, bubble_of, bubbles):
+        """the tables of kernel k_locus: the .ann records' first and last text positions (ascending, disjoint), the bubble number of every
+        record (-1: not a bubble record; see bubble_of()) and the bubble table (BUBBLE_DTYPE, see read_bubble_data())"""
+        start = np.ascontiguousarray(start, dtype=np.uint64)
+        end = np.ascontiguousarray(end, dtype=np.uint64)
+        bubble_of = np.ascontiguousarray(bubble_of, dtype=np.int32)
+        bubbles = np.ascontiguousarray(bubbles, dtype=BUBBLE_DTYPE)
+        if not len(start) == len(end) == len(bubble_of):
+            raise ValueError("start, end and bubble_of must have one entry per record")
+        _chk(lib().bwb_hip_set_loci(self._h, start.ctypes.data, end.ctypes.data, bubble_of.ctypes.data, len(start), bubbles.ctypes.data, len(bubbles)))
+
+    @staticmethod
+    def _loci(ptr, n):
+        return np.frombuffer(C.string_at(ptr, n * LOCUS_DTYPE.itemsize), dtype=LOCUS_DTYPE).copy() if n else np.zeros(0, dtype=LOCUS_DTYPE)
+
+    def slot_locus(self, slot, max_mm=6):
+        """(places, loci): slot_place's records and one LOCUS_DTYPE record per read of the slot, in read order"""
+        pp, pl, n = C.c_void_p(), C.c_void_p(), C.c_uint32()
+        _chk(lib().bwb_hip_slot_locus(self._h, slot, max_mm, C.byref(pp), C.byref(pl), C.byref(n)))
+        return self._places(pp, n.value), self._loci(pl, n.value)
+
+    def locus(self, max_mm=6):
+        """the same for the one-batch interface (after run() / align())"""
+        pp, pl, n = C.c_void_p(), C.c_void_p(), C.c_uint32()
+        _chk(lib().bwb_hip_batch_locus(self._h, max_mm, C.byref(pp), C.byref(pl), C.byref(n)))
+        return self._places(pp, n.value), self._loci(pl, n.value)
+
+    def locus_places(self, places):
+        """the same kernel on placement records of the caller's (PLACE_DTYPE)"""
+        places = np.ascontiguousarray(places, dtype=PLACE_DTYPE)
+        out = np.zeros(len(places), dtype=LOCUS_DTYPE)
+        _chk(lib().bwb_hip_locus_places(self._h, places.ctypes.data, len(places), out.ctypes.data))
+        return out
+
+    def locus_stats(self):
+        """(reads, kernel ms) of the last locus call"""
+        n, ms = C.c_uint64(), C.c_double()
+        _chk(lib().bwb_hip_locus_stats(self._h, C.byref(n), C.byref(ms)))
+        return n.value, ms.value
+
     def dtab_info(self):
         """the context's calculate_d table: {K (0: none), build seconds, bytes}"""
         k, sec, nb = C.c_int(), C.c_double(), C.c_uint64()
@@ -400,6 +453,46 @@ class Context:
 
 
 # -- formats ------------------------------------------------------------------------------------
+
+
+def read_ann(path):
+    """.ann of `bwbble index` (io.c:324-349) -> (names, first text positions, last text positions: uint64)"""
+    with open(path) as f:
+        n = int(f.readline().split("\t")[1])
+        rows = [f.readline().rstrip("\n").split("\t") for _ in range(n)]
+    return ([r[0] for r in rows], np.array([int(r[1]) for r in rows], dtype=np.uint64), np.array([int(r[2]) for r in rows], dtype=np.uint64))
+
+
+def read_bubble_data(path):
+    """bubble.data of the reference's `comb` (mg-ref/comb.cpp:245-253) -> (chromosome headers, BUBBLE_DTYPE records): two lines per bubble,
+    the header and `A  B-A  C  D-C  ref_len  alt_len`.  Half a pair or a numbers line without six integers is an error, as in the host tools."""
+    lines = open(path).read().split("\n")
+    if lines and lines[-1] == "":
+        lines.pop()
+    if len(lines) % 2:
+        raise ValueError(f"{path} has an odd number of lines")
+    anns, recs = lines[0::2], np.zeros(len(lines) // 2, dtype=BUBBLE_DTYPE)
+    for k, ln in enumerate(lines[1::2]):
+        v = ln.split()
+        if len(v) < 6:
+            raise ValueError(f"{path} line {2 * k + 2}: expected six integers")
+        recs[k] = tuple(int(x) for x in v[:6])
+    return anns, recs
+
+
+def bubble_of(names, n_bubbles):
+    """the bubble number of every .ann record as the reference's sam_pad reads it from the name (mg-ref/sam_pad.cpp:67-72): -1 unless the name
+    starts with `bubble`, else the leading decimal number (0 without one) of its first word after the word's first six characters"""
+    import re
+    out = np.full(len(names), -1, dtype=np.int32)
+    for i, name in enumerate(names):
+        if name.startswith("bubble"):
+            m = re.match(r"[+-]?[0-9]+", name.split()[0][6:])
+            w = int(m.group()) if m else 0
+            if not 0 <= w < n_bubbles:
+                raise ValueError(f"record {i} ({name!r}) names a bubble outside the table of {n_bubbles}")
+            out[i] = w
+    return out
 
 _BASE_LUT = np.full(256, 4, dtype=np.uint8)  # ASCII -> read->seq code (io.h:112-130): A0 G1 C2 T3 in either case, anything else 4
 _BASE_LUT[np.frombuffer(b"AGCTagct", dtype=np.uint8)] = np.arange(8) % 4

@@ -123,6 +123,9 @@ struct Slot {
 	int placed_mm = -1;           /* h_place holds the records for this max_mm (-1: none) */
 	AltBufs alt;                  /* bwb_hip_slot_place_alt: the items of the slot's reads */
 	int placed_alt = -1;          /* alt holds the items for this max_alt (-1: none) */
+	DevMem d_locus;               /* bwb_hip_slot_locus: one bwb_locus per read */
+	PinMem h_locus;
+	int locus_mm = -1;            /* h_locus holds the records of the placement records for this max_mm (-1: none) */
 	std::vector<uint8_t> h_status;
 	std::vector<uint64_t> h_aln_off;
 	std::vector<bwb_aln> h_alns;
@@ -171,6 +174,9 @@ struct bwb_hip_ctx {
 	DevMem d_altctl;                    /* k_place_alt: its step counter and its count of flagged items */
 	AltBufs hits_alt;                   /* bwb_hip_place_hits_alt: the items of the caller's hit list */
 	double alt_ms = 0; uint64_t alt_steps = 0, alt_items = 0;         /* the last place_alt call */
+	DevMem d_lstart, d_lend, d_lbub, d_bubbles; /* k_locus: the .ann records' first and last positions, their bubble numbers; the bubble table */
+	uint32_t loci_nseq = 0, loci_trips = 0;       /* records (0: bwb_hip_set_loci has not been called); steps of the search, ceil(log2(records)) */
+	double locus_ms = 0; uint64_t locus_reads = 0; /* the last locus call */
 	bool force_slices = false;          /* BWB_FORCE_SLICES: the one-batch API parks and resumes too (tests) */
 	bool dbg = false, dbg_iters = false;
 	const char *launch_log = nullptr;   /* BWB_LAUNCH_LOG=<file>: one JSON line per class-0 kernel launch (synchronises after every launch: a profiling aid) */
@@ -743,7 +749,7 @@ extern "C" int bwb_hip_slot_upload(bwb_hip_ctx *c, int si, const bwb_params *p, 
 	/* (pageable source: the runtime stages it before returning, so h_descs may change again right away) */
 	HIPCHK(hipMemcpyAsync(c->d_descs.as<SlotDesc>() + si, &d, sizeof(SlotDesc), hipMemcpyHostToDevice, c->cstream));
 	HIPCHK(hipEventRecord(s.ev_up.e, c->cstream));
-	s.uploaded = true; s.submitted = false; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1;
+	s.uploaded = true; s.submitted = false; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1;
 	return ensure_class(c, 0);
 }
 
@@ -991,7 +997,7 @@ static int submit(bwb_hip_ctx *c, int si, bool suspend) {
 		HIPCHK(hipStreamWaitEvent(c->stream, s.ev_calcd.e, 0));
 	}
 	HIPCHK(hipMemsetAsync(s.d_ctl.p, 0, 256, c->stream));
-	s.submitted = true; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.launch = 0;
+	s.submitted = true; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.launch = 0;
 	if (s.n_reads == 0) { s.complete = true; s.launch = c->n_launches; return BWB_OK; }
 	HIPCHK(hipMemsetAsync(s.d_n.p, 0, (size_t)s.n_reads * 4, c->stream));
 	if (!ahead) {
@@ -1692,6 +1698,104 @@ extern "C" int bwb_hip_place_alt_stats(bwb_hip_ctx *c, uint64_t *items, uint64_t
 	if (items) *items = c->alt_items;
 	if (steps) *steps = c->alt_steps;
 	if (kernel_ms) *kernel_ms = c->alt_ms;
+	return BWB_OK;
+}
+
+/* ---- bubble hits in reference coordinates: bwb_locus records (k_locus) ---------------------------------------------------------- */
+static_assert(sizeof(bwb_locus) == 32, "bwb_locus is two 16-byte words (k_locus)");
+static_assert(sizeof(bwb_bubble) == 40, "bwb_bubble is five 64-bit words (k_locus)");
+extern "C" int bwb_hip_set_loci(bwb_hip_ctx *c, const uint64_t *start, const uint64_t *end, const int32_t *bubble_of, uint32_t n_seq, const bwb_bubble *bubbles, uint32_t n_bub) {
+	if (!c || !start || !end || !bubble_of || (n_bub && !bubbles)) return fail(BWB_E_ARG, "set_loci: null argument");
+	if (n_seq < 1 || n_seq > 0x7FFFFFFFu || n_bub > 0x7FFFFFFFu) return fail(BWB_E_ARG, "set_loci: the number of records must be 1 .. 2^31 - 1");
+	for (uint32_t i = 0; i < n_seq; i++) {
+		if (start[i] > end[i] || (i && start[i] <= end[i - 1])) return fail(BWB_E_ARG, "set_loci: the records are not ascending and disjoint (record " + std::to_string(i) + ")");
+		if (bubble_of[i] < -1 || (int64_t)bubble_of[i] >= (int64_t)n_bub)
+			return fail(BWB_E_ARG, "set_loci: bubble_of[" + std::to_string(i) + "] = " + std::to_string(bubble_of[i]) + " lies outside the table of " + std::to_string(n_bub) + " bubbles");
+	}
+	HIPCHK(hipSetDevice(c->device));
+	c->loci_nseq = 0; /* (no tables until all four are resident) */
+	for (auto &s : c->slots) s.locus_mm = -1;
+	HIPCHK(c->d_lstart.alloc((size_t)n_seq * 8));
+	HIPCHK(c->d_lend.alloc((size_t)n_seq * 8));
+	HIPCHK(c->d_lbub.alloc((size_t)n_seq * 4));
+	HIPCHK(c->d_bubbles.alloc((size_t)n_bub * sizeof(bwb_bubble)));
+	/* (on the result stream, like set_sa: the caller's thread alone uses it) */
+	HIPCHK(hipMemcpyAsync(c->d_lstart.p, start, (size_t)n_seq * 8, hipMemcpyHostToDevice, c->rstream));
+	HIPCHK(hipMemcpyAsync(c->d_lend.p, end, (size_t)n_seq * 8, hipMemcpyHostToDevice, c->rstream));
+	HIPCHK(hipMemcpyAsync(c->d_lbub.p, bubble_of, (size_t)n_seq * 4, hipMemcpyHostToDevice, c->rstream));
+	if (n_bub) HIPCHK(hipMemcpyAsync(c->d_bubbles.p, bubbles, (size_t)n_bub * sizeof(bwb_bubble), hipMemcpyHostToDevice, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	uint32_t trips = 0;
+	while (((uint64_t)1 << trips) < n_seq) trips++;
+	c->loci_trips = trips;
+	c->loci_nseq = n_seq;
+	return BWB_OK;
+}
+
+/* k_locus over n placement records in device memory -> n records in d_out, copied to h_out; sets the context's locus_ms / locus_reads.  On the
+ * result stream, behind the k_place that wrote the records.  Shared by slot_locus and locus_places. */
+static int locus_launch(bwb_hip_ctx *c, const uint4 *d_places, uint32_t n, uint4 *d_out, bwb_locus *h_out) {
+	c->locus_ms = 0; c->locus_reads = n;
+	if (!n) return BWB_OK;
+	Timed t(c, c->rstream);
+	const unsigned grid = (unsigned)std::min<size_t>(((size_t)n + BWB_BLOCK - 1) / BWB_BLOCK, (size_t)c->num_cu * 8);
+	RC(t.begin());
+	hipLaunchKernelGGL(k_locus, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, d_places, n, c->d_lstart.as<uint64_t>(), c->d_lend.as<uint64_t>(), c->d_lbub.as<int32_t>(),
+	                   c->loci_nseq, c->loci_trips, c->d_bubbles.as<uint64_t>(), d_out);
+	HIPCHK(hipGetLastError());
+	RC(t.end());
+	HIPCHK(hipMemcpyAsync(h_out, d_out, (size_t)n * sizeof(bwb_locus), hipMemcpyDeviceToHost, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	float ms = 0;
+	RC(t.ms(&ms));
+	c->locus_ms = ms;
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_slot_locus(bwb_hip_ctx *c, int si, int max_mm, const bwb_place **places, const bwb_locus **loci, uint32_t *n_reads) {
+	if (!c || !places || !loci || !n_reads || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_locus: bad argument");
+	if (!c->loci_nseq) return fail(BWB_E_STATE, "slot_locus: record and bubble tables not uploaded (bwb_hip_set_loci)");
+	RC(bwb_hip_slot_place(c, si, max_mm, places, n_reads)); /* (waits for the slot; refuses what slot_place refuses; leaves the records in d_place) */
+	Slot &s = c->slots[si];
+	const uint32_t n = s.n_reads;
+	if (s.locus_mm != max_mm || !n) {
+		HIPCHK(s.h_locus.reserve((size_t)n * sizeof(bwb_locus)));
+		if (n) HIPCHK(s.d_locus.reserve((size_t)n * sizeof(bwb_locus)));
+		RC(locus_launch(c, s.d_place.as<uint4>(), n, s.d_locus.as<uint4>(), s.h_locus.as<bwb_locus>()));
+		s.locus_mm = max_mm;
+	}
+	*loci = s.h_locus.as<bwb_locus>();
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_batch_locus(bwb_hip_ctx *c, int max_mm, const bwb_place **places, const bwb_locus **loci, uint32_t *n_reads) {
+	if (!c || !places || !loci || !n_reads) return fail(BWB_E_ARG, "batch_locus: null argument");
+	if (!c->loci_nseq) return fail(BWB_E_STATE, "batch_locus: record and bubble tables not uploaded (bwb_hip_set_loci)");
+	if (!c->d_SA.p) return fail(BWB_E_STATE, "batch_locus: sampled SA not uploaded (bwb_hip_set_sa)");
+	if (!c->slots[0].submitted || !c->slots[0].complete) return fail(BWB_E_STATE, "batch_locus: batch_run has not completed");
+	return bwb_hip_slot_locus(c, 0, max_mm, places, loci, n_reads);
+}
+
+/* k_locus on placement records of the caller's instead of a slot's (for parity tests) */
+extern "C" int bwb_hip_locus_places(bwb_hip_ctx *c, const bwb_place *places, uint32_t n, bwb_locus *out) {
+	if (!c || (n && (!places || !out)) || n > 0x7FFFFFFFu) return fail(BWB_E_ARG, "locus_places: bad argument");
+	if (!c->loci_nseq) return fail(BWB_E_STATE, "locus_places: record and bubble tables not uploaded (bwb_hip_set_loci)");
+	HIPCHK(hipSetDevice(c->device));
+	DevMem d_in, d_out;
+	HIPCHK(d_in.alloc((size_t)n * sizeof(bwb_place)));
+	HIPCHK(d_out.alloc((size_t)n * sizeof(bwb_locus)));
+	if (n) {
+		HIPCHK(hipMemcpyAsync(d_in.p, places, (size_t)n * sizeof(bwb_place), hipMemcpyHostToDevice, c->rstream));
+		HIPCHK(hipStreamSynchronize(c->rstream)); /* (pageable memory of the caller) */
+	}
+	return locus_launch(c, d_in.as<uint4>(), n, d_out.as<uint4>(), out);
+}
+
+/* the last locus call: reads resolved and the kernel's HIP-event time */
+extern "C" int bwb_hip_locus_stats(bwb_hip_ctx *c, uint64_t *reads, double *kernel_ms) {
+	if (!c) return fail(BWB_E_ARG, "locus_stats: null context");
+	if (reads) *reads = c->locus_reads;
+	if (kernel_ms) *kernel_ms = c->locus_ms;
 	return BWB_OK;
 }
 

@@ -7,6 +7,7 @@
  *   k_locate     SA[row] by the invPsi walk (aln2sam)
  *   k_gather     per-read hit lists -> read order
  *   k_place      eval_aln + mapq for every read of a slot (`bwbble map`): one 48-byte placement record per read
+ *   k_locus      the .ann record of every placement record and, on a bubble record, its reference coordinates (`bwbble map -B`)
  * The alignment kernels themselves (kl_calc_d, kl_search: one read per lane) are in bwb_lane.h.
  */
 #pragma once
@@ -431,6 +432,54 @@ __global__ __launch_bounds__(BWB_BLOCK) void k_place(DevIndex ix, const uint64_t
 		if (ol == 0) dst[0] = w0;
 		else if (ol == 1) dst[1] = w1;
 		else if (ol == 2) dst[2] = w2;
+	}
+}
+
+/* ---- bubble hits in reference coordinates (`map -B`: the bC / bP tags) ----------------------------------------------------------
+ * For every placement record: the .ann record that contains its text position, the position SAM prints, and on a `>bubbleN` record what
+ * the reference's sam_pad makes of that position (include/bwbble_hip.h: bwb_locus; mg-ref/sam_pad.cpp:75-87).  One read per LANE - there is
+ * no bucket to gather, so not the octet layout - in a grid-stride loop.  The search is the branch-free lower bound: `trips` =
+ * ceil(log2(n_seq)) steps for every lane (a kernel argument, so the loop is uniform: selects, no divergent while), the candidates
+ * [lo, lo + len) shrinking to one record; every start[] it reads lies inside the table (lo + len <= n_seq throughout, half < len).  The
+ * first positions of 1.3 M records are 10 MB: they stay in the Infinity Cache.  bub[] holds the bwb_bubble records as five 64-bit words
+ * (A, B_minus_A, C, D_minus_C, ref_len | alt_len << 32); bubble_of[] was checked against its size on the host (bwb_hip_set_loci).  The
+ * sums wrap (unsigned arithmetic, compared as signed) like the host's bubble_locus. */
+__global__ __launch_bounds__(BWB_BLOCK) void k_locus(const uint4 *places, uint32_t n_reads, const uint64_t *start, const uint64_t *end, const int32_t *bubble_of,
+                                                      uint32_t n_seq, uint32_t trips, const uint64_t *bub, uint4 *out) {
+	const uint32_t stride = gridDim.x * BWB_BLOCK;
+	for (uint32_t r = blockIdx.x * BWB_BLOCK + threadIdx.x; r < n_reads; r += stride) {
+		const uint4 p0 = places[(size_t)r * 3], p1 = places[(size_t)r * 3 + 1];
+		const uint64_t pos = (uint64_t)p0.x | ((uint64_t)p0.y << 32);
+		const bool mapped = ((p1.x >> 24) & PLACE_F_MAPPED) != 0;
+		uint32_t lo = 0, len = n_seq;
+		for (uint32_t t = 0; t < trips; t++) {
+			const uint32_t half = len >> 1, mid = lo + half;
+			lo = start[mid] <= pos ? mid : lo;
+			len -= half;
+		}
+		const uint64_t s = start[lo];
+		const bool in = mapped && pos >= s && pos <= end[lo];
+		const int32_t b = in ? bubble_of[lo] : -1;
+		const uint32_t pos1 = in ? (uint32_t)(pos - s + 1) : 0u;
+		uint32_t kind = 0;
+		uint64_t rlo = 0, rhi = 0;
+		if (b >= 0) {
+			const uint64_t *q = bub + (size_t)b * 5;
+			const uint64_t A = q[0], B = q[1], C = q[2], D = q[3], la = q[4];
+			const uint64_t ref_len = (uint64_t)(int64_t)(int32_t)(uint32_t)la, alt_len = (uint64_t)(int64_t)(int32_t)(uint32_t)(la >> 32);
+			const int64_t locus = (int64_t)(int32_t)pos1;
+			const uint64_t right = B + alt_len + 1u;
+			const bool left_flank = locus >= 1 && locus <= (int64_t)B;
+			const bool right_flank = locus >= (int64_t)right && locus <= (int64_t)(right + D);
+			const uint64_t point = left_flank ? A + (uint64_t)locus - 1u : (uint64_t)locus + C - right;
+			const bool is_point = left_flank || right_flank;
+			kind = is_point ? 1u : 2u;
+			rlo = is_point ? point : A + B;
+			rhi = is_point ? point : A + B + ref_len - 1u;
+		}
+		uint4 *dst = out + (size_t)r * 2;
+		dst[0] = make_uint4(in ? lo : 0xFFFFFFFFu, pos1, (uint32_t)b, kind);
+		dst[1] = make_uint4((uint32_t)rlo, (uint32_t)(rlo >> 32), (uint32_t)rhi, (uint32_t)(rhi >> 32));
 	}
 }
 

@@ -41,7 +41,12 @@ typedef struct chunk {
 } chunk_t;
 
 /* what `map` adds to the pipeline (NULL: align) */
-typedef struct { int max_mm; int max_alt /* -X (0: no tags) */; const fasta_annotations_t *ann; int ann_sorted; } map_t;
+typedef struct {
+	int max_mm; int max_alt /* -X (0: no tags) */; const fasta_annotations_t *ann; int ann_sorted;
+	/* -B (bub NULL: no tags): the bubble table, every .ann record's bubble number, and - when the records are ascending and disjoint, so that
+	 * kernel k_locus can search them (gpu_loci) - their first and last positions as the arrays bwb_hip_set_loci takes */
+	const bubble_table_t *bub; const int32_t *bubble_of; int gpu_loci; const uint64_t *rec_start, *rec_end;
+} map_t;
 
 typedef struct {
 	pthread_mutex_t mu;
@@ -71,6 +76,7 @@ typedef struct {
 	unsigned long long n_reads; /* reads of the chunks this worker took */
 	double place_ms; unsigned long long place_steps; /* map: k_place, summed over the chunks */
 	double alt_ms; unsigned long long alt_steps, alt_items; /* map -X: k_alt_count + scan + k_place_alt, summed over the chunks */
+	double locus_ms; unsigned long long locus_reads; /* map -B: k_locus, summed over the chunks */
 } worker_t;
 
 /* The reader: chunk k+1 is parsed (record boundaries by one sequential scan, bases encoded by all cores: reads.c) while chunk k is on
@@ -148,9 +154,23 @@ static void retire_map(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c) {
 		bwb_die("map_reads: GPU %d: %s", w->gpu, bwb_hip_last_error());
 	{ uint64_t st = 0; double ms = 0; bwb_hip_place_stats(ctx, NULL, &st, &ms); w->place_ms += ms; w->place_steps += st; }
 	if (m->max_alt) { uint64_t it = 0, st = 0; double ms = 0; bwb_hip_place_alt_stats(ctx, &it, &st, &ms); w->alt_ms += ms; w->alt_steps += st; w->alt_items += it; }
+	/* -B: the loci of the same records, resolved where they lie (kernel k_locus behind k_place on the result stream; the slot's placement
+	 * records are cached, so nothing is evaluated twice); on an .ann that is not ascending and disjoint, by the host's resolver */
+	const bwb_locus *loci = NULL;
+	bwb_locus *host_loci = NULL;
+	if (m->bub && m->gpu_loci) {
+		if (bwb_hip_slot_locus(ctx, slot, m->max_mm, &pl, &loci, &n)) bwb_die("map_reads: GPU %d: %s", w->gpu, bwb_hip_last_error());
+		uint64_t nr = 0; double ms = 0;
+		bwb_hip_locus_stats(ctx, &nr, &ms);
+		w->locus_ms += ms; w->locus_reads += nr;
+	} else if (m->bub) {
+		loci = host_loci = (bwb_locus *)malloc((n ? n : 1) * sizeof(bwb_locus));
+#pragma omp parallel for schedule(static) num_threads(bwb_host_team())
+		for (long r = 0; r < (long)n; r++) locus_resolve(&pl[r], m->ann, m->ann_sorted, m->bubble_of, m->bub, &host_loci[r]);
+	}
 	const sam_reads_t rd = { .pl = pl, .seq = c->fq.seq, .stride = c->fq.stride, .len = c->fq.len, .text = c->fq.text,
 	                         .name_off = c->fq.name_off, .qual_off = c->fq.qual_off, .name_len = c->fq.name_len, .first = c->first_read,
-	                         .alt_off = alt_off, .alts = alts };
+	                         .alt_off = alt_off, .alts = alts, .loci = loci, .bubbles = m->bub };
 	c->n = n;
 	c->n_sam = ((size_t)n + SAM_BLOCK_READS - 1) / SAM_BLOCK_READS;
 	c->sam = (char **)calloc(c->n_sam ? c->n_sam : 1, sizeof(char *));
@@ -160,6 +180,7 @@ static void retire_map(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c) {
 		const size_t r0 = (size_t)bi * SAM_BLOCK_READS, r1 = r0 + SAM_BLOCK_READS < n ? r0 + SAM_BLOCK_READS : n;
 		c->sam[bi] = sam_format_reads(&rd, r0, r1, m->ann, m->ann_sorted, &c->sam_len[bi]);
 	}
+	free(host_loci);
 	free(c->fq.seq); free(c->fq.len); free(c->fq.name_off); free(c->fq.qual_off); free(c->fq.name_len);
 	c->fq.seq = NULL; c->fq.len = NULL; c->fq.name_off = NULL; c->fq.qual_off = NULL; c->fq.name_len = NULL;
 	chunk_ready(w->pp, c);
@@ -215,6 +236,10 @@ static void *gpu_worker(void *arg) {
 		while (!__atomic_load_n(&w->BWT->sa_ready, __ATOMIC_ACQUIRE)) { struct timespec ts = { 0, 200000 }; nanosleep(&ts, NULL); }
 		if (bwb_hip_set_sa(ctx, w->BWT->SA, w->BWT->num_sa)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
 		if (dbg) fprintf(stderr, "[bwb host] worker %d: sampled SA resident at +%.3f s\n", w->gpu, wall() - tq);
+		/* -B: the record and bubble tables of k_locus (every worker's context gets them; 30 MB at GRCh37 scale) */
+		if (pp->map->bub && pp->map->gpu_loci &&
+		    bwb_hip_set_loci(ctx, pp->map->rec_start, pp->map->rec_end, pp->map->bubble_of, (uint32_t)pp->map->ann->num_seq, pp->map->bub->b, (uint32_t)pp->map->bub->n))
+			bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
 	}
 	void (*const hand_over)(worker_t *, bwb_hip_ctx *, int, chunk_t *) = pp->map ? retire_map : retire;
 	enum { NS = BWB_MAX_SLOTS }; /* chunks in flight: the heaviest reads of a chunk take several slices' time (they are parked and resumed), and
@@ -368,7 +393,13 @@ static int run_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, 
 	if (map) {
 		double pms = 0; unsigned long long pst = 0;
 		for (int g = 0; g < n_gpus; g++) { pst += ws[g].place_steps; if (ws[g].place_ms > pms) pms = ws[g].place_ms; }
-		printf("placements on the GPU: reads %llu  rank-block visits %llu  kernel %.3f ms\n", (unsigned long long)pp.n_reads, pst, pms);
+		printf("placements on the GPU: reads %llu  rank-block visits %llu  kernel %.3f ms", (unsigned long long)pp.n_reads, pst, pms);
+		if (map->bub && map->gpu_loci) { /* -B: the loci of the same reads */
+			double lms = 0; unsigned long long lrd = 0;
+			for (int g = 0; g < n_gpus; g++) { lrd += ws[g].locus_reads; if (ws[g].locus_ms > lms) lms = ws[g].locus_ms; }
+			printf("  loci resolved %llu  k_locus %.3f ms", lrd, lms);
+		} else if (map->bub) printf("  loci resolved %llu on the host (the .ann records are not ascending and disjoint)", (unsigned long long)pp.n_reads);
+		printf("\n");
 		if (map->max_alt) {
 			double ams = 0; unsigned long long ast = 0, ait = 0;
 			for (int g = 0; g < n_gpus; g++) { ast += ws[g].alt_steps; ait += ws[g].alt_items; if (ws[g].alt_ms > ams) ams = ws[g].alt_ms; }
@@ -427,8 +458,10 @@ int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_
 }
 
 /* `bwbble map`: align_reads + alns2sam in one pass.  The .bwt is loaded once, with its SA; the SAM header is written before the first chunk. */
-int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, int n_gpus) {
+int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int n_gpus) {
 	printf("**** BWBBLE Read Mapping (align + aln2sam in one pass) ****\n");
+	/* -B: the table first (a refused table stops the run before anything is created) */
+	bubble_table_t *bub = bubbleFname ? load_bubbles(bubbleFname) : NULL;
 	/* before anything is created: without a GPU no SAM file is left behind */
 	if (bwb_hip_device_count() < 1) bwb_die("align_reads_inexact_gpu: no HIP device found (this build has no CPU alignment path)");
 	size_t L = strlen(fastaFname) + 8;
@@ -438,16 +471,31 @@ int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *
 	double t = wall();
 	bwt_t *BWT = load_bwt_start(bwtFname, 1);
 	fasta_annotations_t *ann = annf2ann(annFname);
+	/* -B: every record's bubble number, before the SAM file exists (a record that names a bubble outside the table leaves none behind) */
+	int32_t *bubble_of = bub ? ann_bubble_of(ann, bub) : NULL;
+	uint64_t *rec_start = NULL, *rec_end = NULL;
+	int gpu_loci = bub && ann->num_seq > 0 && sam_ann_sorted(ann) && bub->n <= INT32_MAX;
+	if (bub) {
+		const size_t n_rec = ann->num_seq > 0 ? (size_t)ann->num_seq : 1;
+		rec_start = (uint64_t *)malloc(n_rec * 8);
+		rec_end = (uint64_t *)malloc(n_rec * 8);
+		for (int i = 0; i < ann->num_seq; i++) {
+			rec_start[i] = ann->seq_anns[i].start_index; rec_end[i] = ann->seq_anns[i].end_index;
+			if (rec_start[i] > rec_end[i]) gpu_loci = 0; /* (an empty record: sam_ann_sorted does not look for it, bwb_hip_set_loci refuses it) */
+		}
+	}
 	if (params->use_precalc) ensure_precalc(BWT, fastaFname, params, &t);
 	FILE *sam = fopen(samFname, "w");
 	if (!sam) { perror(samFname); bwb_die("map_reads: Cannot open SAM file: %s!", samFname); }
 	sam_write_header(sam, ann);
-	const map_t m = { .max_mm = max_mm, .max_alt = max_alt, .ann = ann, .ann_sorted = sam_ann_sorted(ann) };
+	const map_t m = { .max_mm = max_mm, .max_alt = max_alt, .ann = ann, .ann_sorted = sam_ann_sorted(ann),
+	                  .bub = bub, .bubble_of = bubble_of, .gpu_loci = gpu_loci, .rec_start = rec_start, .rec_end = rec_end };
 	t = wall();
 	printf("BWBBLE Inexact Alignment (MI355X)...\n");
 	run_stream(BWT, readsFname, params, sam, samFname, n_gpus, &m);
 	printf("Total read mapping time (index and read loading overlapped): %.2f sec\n", wall() - t);
 	free_bwt(BWT); free_ann(ann);
 	free(bwtFname); free(annFname);
+	free(bubble_of); free(rec_start); free(rec_end); free_bubbles(bub);
 	return 0;
 }

@@ -1,5 +1,6 @@
 /* main.c - `bwbble` command line, same commands and flags as the reference (mg-aligner/main.c:38-160),
- * plus -g <n_gpus> on align / aln2sam, and `map` = align + aln2sam in one pass. */
+ * plus -g <n_gpus> on align / aln2sam, `map` = align + aln2sam in one pass, and `sampad` = mg-ref/sam_pad (-B on map / aln2sam: the same
+ * tags without a second pass). */
 #define _GNU_SOURCE
 #include <getopt.h>
 #include <time.h>
@@ -13,7 +14,8 @@ static int usage(void) {
 	printf("         align    exact or inexact read alignment (MI355X)\n");
 	printf("         map      align + aln2sam in one pass: FASTQ to SAM (MI355X)\n");
 	printf("         fasta2ref    constructs a single linear reference from the input file \n");
-	printf("         aln2sam  convert alignment results to SAM file format for single-end mapping\n\n");
+	printf("         aln2sam  convert alignment results to SAM file format for single-end mapping\n");
+	printf("         sampad   add the reference coordinates of bubble hits to a SAM file (tags bC:Z: / bP:Z:, the reference's sam_pad)\n\n");
 	return 1;
 }
 static int align_usage(void) {
@@ -29,17 +31,19 @@ static int align_usage(void) {
 }
 
 static int map_usage(void) {
-	printf("Usage: bwbble map [align options] [-Q <int>] [-X <int>] [-g <gpus>] <seq_fasta> <reads_fastq> <out_sam> \n");
+	printf("Usage: bwbble map [align options] [-Q <int>] [-X <int>] [-B <bubble.data>] [-g <gpus>] <seq_fasta> <reads_fastq> <out_sam> \n");
 	printf("         writes the SAM file that `bwbble align [align options]` followed by `bwbble aln2sam [-n <Q>] [-X <N>]` writes, without the .aln file\n");
 	printf("Options: the options of align, and\n");
 	printf("         Q    the mismatch count at which a unique hit gets MAPQ 25 (aln2sam's -n; default: 6)\n");
-	printf("         X    1..255: mapped reads get the tags X0:i / X1:i, and a read with 2..X+1 placements lists the others as XA:Z:name,<+|->pos,CIGAR,NM; (default: no tags)\n\n");
+	printf("         X    1..255: mapped reads get the tags X0:i / X1:i, and a read with 2..X+1 placements lists the others as XA:Z:name,<+|->pos,CIGAR,NM; (default: no tags)\n");
+	printf("         B    the bubble table of the multi-genome (bubble.data): reads on a bubble record get the tags bC:Z:<chromosome> bP:Z:<position | lo-hi>, what `bwbble sampad` adds to the SAM file; resolved on the GPU (default: no tags)\n\n");
 	return 1;
 }
 static int aln2sam_usage(void) {
-	printf("Usage: bwbble aln2sam [-S, -n, -g, -X] <seq_fasta> <reads_fastq> <alns_aln> <out_sam> \n");
+	printf("Usage: bwbble aln2sam [-S, -n, -g, -X, -B] <seq_fasta> <reads_fastq> <alns_aln> <out_sam> \n");
 	printf("Options: n    the mismatch count at which a unique hit gets MAPQ 25 (default: 6)\n         g    number of GPUs for the SA lookups (default: 1)\n");
-	printf("         X    1..255: the tags X0:i / X1:i / XA:Z: of `bwbble map -X` (default: no tags)\n\n");
+	printf("         X    1..255: the tags X0:i / X1:i / XA:Z: of `bwbble map -X` (default: no tags)\n");
+	printf("         B    the bubble table (bubble.data): the tags bC:Z: / bP:Z: of `bwbble map -B` (default: no tags)\n\n");
 	return 1;
 }
 /* -X's argument: 1..255, anything else is refused */
@@ -97,20 +101,30 @@ int main(int argc, char *argv[]) {
 		aln_params_t params;
 		set_default_aln_params(&params);
 		int c, n_gpus = 1, max_mm = 6, max_alt = 0; /* (aln2sam's default, mg-aligner/main.c:142) */
-		while ((c = getopt(argc - 1, argv + 1, "M:O:E:n:k:o:e:l:m:t:g:SPQ:X:")) >= 0) {
+		const char *bubbleFname = NULL;
+		while ((c = getopt(argc - 1, argv + 1, "M:O:E:n:k:o:e:l:m:t:g:SPQ:X:B:")) >= 0) {
 			if (align_option(c, &params, &n_gpus)) continue;
 			if (c == 'Q') { max_mm = atoi(optarg); continue; }
 			if (c == 'X') { max_alt = alt_option(optarg); continue; }
+			if (c == 'B') { bubbleFname = optarg; continue; }
 			if (c == '?') { map_usage(); return 1; }
 			return 1;
 		}
 		if (argc - 1 - optind < 3) { map_usage(); exit(1); }
-		map_reads(argv[optind + 1], argv[optind + 2], argv[optind + 3], &params, max_mm, max_alt, n_gpus);
+		map_reads(argv[optind + 1], argv[optind + 2], argv[optind + 3], &params, max_mm, max_alt, bubbleFname, n_gpus);
 	} else if (strcmp(argv[1], "places2sam") == 0) {
 		/* developer command (CPU only, used by the tests): placement records (bwb_place, include/bwbble_hip.h) from a file -> SAM text */
 		/* (a sixth argument: u64 alt_off[n + 1] followed by the bwb_alt records - the X tags of `map -X`) */
-		if (argc < 6) { printf("Usage: bwbble places2sam <seq_fasta> <reads_fastq> <places_bin> <out_sam> [<alts_bin>] \n"); exit(1); }
-		places2sam(argv[2], argv[3], argv[4], argv[5], argc >= 7 ? argv[6] : NULL);
+		/* (a leading `-B <bubble.data>`: the tags of `map -B`, the loci from the host resolver) */
+		char **a = argv + 2;
+		int na = argc - 2;
+		const char *bubbleFname = NULL;
+		if (na >= 2 && strcmp(a[0], "-B") == 0) { bubbleFname = a[1]; a += 2; na -= 2; }
+		if (na < 4) { printf("Usage: bwbble places2sam [-B <bubble.data>] <seq_fasta> <reads_fastq> <places_bin> <out_sam> [<alts_bin>] \n"); exit(1); }
+		places2sam(a[0], a[1], a[2], a[3], na >= 5 ? a[4] : NULL, bubbleFname);
+	} else if (strcmp(argv[1], "sampad") == 0) {
+		if (argc < 5) { printf("Usage: bwbble sampad <bubble.data> <in_sam> <out_sam> \n"); exit(1); }
+		sam_pad(argv[2], argv[3], argv[4]);
 	} else if (strcmp(argv[1], "fasta2ref") == 0) {
 		if (argc < 3) { printf("Usage: bwbble fasta2ref <seq_fasta> \n"); exit(1); }
 		size_t L = strlen(argv[2]) + 8;
@@ -124,9 +138,11 @@ int main(int argc, char *argv[]) {
 	} else if (strcmp(argv[1], "aln2sam") == 0) {
 		if (argc < 6) { aln2sam_usage(); exit(1); }
 		int is_multiref = 1, max_diff = 6, n_gpus = 1, max_alt = 0, c;
-		while ((c = getopt(argc - 1, argv + 1, "n:g:SX:")) >= 0) {
+		const char *bubbleFname = NULL;
+		while ((c = getopt(argc - 1, argv + 1, "n:g:SX:B:")) >= 0) {
 			switch (c) {
 			case 'X': max_alt = alt_option(optarg); break;
+			case 'B': bubbleFname = optarg; break;
 			case 'S': is_multiref = 0; break;
 			case 'n': max_diff = atoi(optarg); break;
 			case 'g': n_gpus = atoi(optarg); break;
@@ -135,7 +151,7 @@ int main(int argc, char *argv[]) {
 			}
 		}
 		if (argc - 1 - optind < 4) { aln2sam_usage(); exit(1); }
-		alns2sam(argv[optind + 1], argv[optind + 2], argv[optind + 3], argv[optind + 4], is_multiref, max_diff, n_gpus, max_alt);
+		alns2sam(argv[optind + 1], argv[optind + 2], argv[optind + 3], argv[optind + 4], is_multiref, max_diff, n_gpus, max_alt, bubbleFname);
 	} else if (strcmp(argv[1], "dumpreads") == 0) {
 		/* developer command (CPU only, used by the tests): what fastq2reads made of a FASTQ - per read "name<TAB>codes<TAB>quality" */
 		if (argc < 4) { printf("Usage: bwbble dumpreads <reads_fastq> <out_tsv> [chunk_reads [text]] \n"); exit(1); }

@@ -93,20 +93,6 @@ int sam_ann_sorted(const fasta_annotations_t *ann) { /* records as fasta2ref wri
 	return 1;
 }
 
-/* the record that contains aln_pos, -1: none (align.c:796-801 scans linearly; a multi-genome has a record per bubble - 1.3 M at
- * GRCh37 scale - and the records are disjoint and in text order, so a binary search finds the same one) */
-static int sam_find_record(const fasta_annotations_t *ann, int ann_sorted, uint64_t aln_pos) {
-	if (ann_sorted) {
-		int lo = 0, hi = ann->num_seq - 1;
-		while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (ann->seq_anns[mid].start_index <= aln_pos) lo = mid; else hi = mid - 1; }
-		if (ann->num_seq > 0 && aln_pos >= ann->seq_anns[lo].start_index && aln_pos <= ann->seq_anns[lo].end_index) return lo;
-		return -1;
-	}
-	for (int i = 0; i < ann->num_seq; i++)
-		if (aln_pos >= ann->seq_anns[i].start_index && aln_pos <= ann->seq_anns[i].end_index) return i;
-	return -1;
-}
-
 /* CIGAR of a path given by its length and gap runs (as bwb_place.gap_run), reversed for the reverse strand: runs of the path walked from
  * its end to its start (align.c:588-609); returns the end of the text */
 static char *sam_put_cigar(char *o, uint16_t aln_length, const uint16_t *gap_run, int strand) {
@@ -136,6 +122,8 @@ char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_
 		cap += (r1 - r0) * 48;
 		for (uint64_t k = rd->alt_off[r0]; k < rd->alt_off[r1]; k++) cap += MAX_SEQ_NAME_LEN + 64 + 8 * (size_t)rd->alts[k].num_gapo;
 	}
+	if (rd->loci) /* -B: on a bubble record the chromosome's header and one or two 64-bit numbers */
+		for (size_t r = r0; r < r1; r++) if (rd->loci[r].bubble >= 0) cap += strlen(rd->bubbles->ann[rd->loci[r].bubble]) + 64;
 	char *o = (char *)malloc(cap ? cap : 1), *o0 = o;
 	for (size_t r = r0; r < r1; r++) {
 		const bwb_place *pl = &rd->pl[r];
@@ -153,9 +141,10 @@ char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_
 		}
 		const int strand = (pl->flags & BWB_PLACE_REVERSE) != 0;
 		const uint64_t aln_pos = pl->pos;
-		const int seqid = sam_find_record(ann, ann_sorted, aln_pos);
-		if (seqid < 0) bwb_die("alns2sam: read %zu maps outside every annotated sequence", rd->first + r); /* the reference indexes seq_anns[-1] here */
-		o += sprintf(o, "\t%d\t%s\t%d\t%d\t", strand ? SAM_FSR : 0, ann->seq_anns[seqid].name, (int)(aln_pos - ann->seq_anns[seqid].start_index + 1), (int)pl->mapq);
+		/* -B: the read's record and POS were resolved with its locus (kernel k_locus for `map`, locus_resolve otherwise) */
+		const int seqid = rd->loci ? rd->loci[r].seqid : ann_find_record(ann, ann_sorted, aln_pos);
+		if (seqid < 0 || seqid >= ann->num_seq) bwb_die("alns2sam: read %zu maps outside every annotated sequence", rd->first + r); /* the reference indexes seq_anns[-1] here */
+		o += sprintf(o, "\t%d\t%s\t%d\t%d\t", strand ? SAM_FSR : 0, ann->seq_anns[seqid].name, rd->loci ? (int)rd->loci[r].pos1 : (int)(aln_pos - ann->seq_anns[seqid].start_index + 1), (int)pl->mapq);
 		o = sam_put_cigar(o, pl->aln_length, pl->gap_run, strand);
 		memcpy(o, "\t*\t0\t0\t", 7); o += 7;
 		if (strand) for (int k = 0; k < len; k++) { const int c = seq[len - 1 - k]; o[k] = "AGCTN"[c > 3 ? 4 : 3 - c]; } /* read->rc */
@@ -169,13 +158,14 @@ char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_
 			if (rd->alt_off[r + 1] > rd->alt_off[r]) { memcpy(o, "\tXA:Z:", 6); o += 6; }
 			for (uint64_t k = rd->alt_off[r]; k < rd->alt_off[r + 1]; k++) {
 				const bwb_alt *a = &rd->alts[k];
-				const int sid = sam_find_record(ann, ann_sorted, a->pos);
+				const int sid = ann_find_record(ann, ann_sorted, a->pos);
 				if (sid < 0) continue;
 				o += sprintf(o, "%s,%c%d,", ann->seq_anns[sid].name, (a->flags & BWB_PLACE_REVERSE) ? '-' : '+', (int)(a->pos - ann->seq_anns[sid].start_index + 1));
 				o = sam_put_cigar(o, a->aln_length, a->gap_run, (a->flags & BWB_PLACE_REVERSE) != 0);
 				o += sprintf(o, ",%d;", (int)a->num_mm + (int)a->num_gapo + (int)a->num_gape);
 			}
 		}
+		if (rd->loci && rd->loci[r].bubble >= 0) o = locus_put_tags(o, &rd->loci[r], rd->bubbles); /* last on the line, like sam_pad's */
 		*o++ = '\n';
 	}
 	*out_len = (size_t)(o - o0);
@@ -196,7 +186,15 @@ static void *locate_worker(void *arg) {
 	return NULL;
 }
 
-void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt) {
+/* -B on the host (aln2sam, places2sam): the locus record of every placement record, with all cores */
+static bwb_locus *host_loci(const bwb_place *pl, size_t n, const fasta_annotations_t *ann, int ann_sorted, const int32_t *bubble_of, const bubble_table_t *bub) {
+	bwb_locus *loci = (bwb_locus *)malloc((n ? n : 1) * sizeof(bwb_locus));
+#pragma omp parallel for schedule(static) num_threads(bwb_host_team())
+	for (long r = 0; r < (long)n; r++) locus_resolve(&pl[r], ann, ann_sorted, bubble_of, bub, &loci[r]);
+	return loci;
+}
+
+void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname) {
 	(void)is_multiref;
 	printf("**** BWBBLE Alignment Evaluation/SAM File Generation ****\n");
 	size_t Ln = strlen(fastaFname) + 8;
@@ -205,6 +203,8 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 	snprintf(annFname, Ln, "%s.ann", fastaFname);
 	bwt_t *BWT = load_bwt(bwtFname, 1);
 	fasta_annotations_t *ann = annf2ann(annFname);
+	bubble_table_t *bub = bubbleFname ? load_bubbles(bubbleFname) : NULL; /* (refused tables stop the run before the SAM file exists) */
+	int32_t *bubble_of = bub ? ann_bubble_of(ann, bub) : NULL;
 	alns_batch_t *alns = alnsf2alns_bin(alnsFname);
 	reads_t *reads = fastq2reads(readsFname);
 	FILE *sam = fopen(samFname, "w");
@@ -271,10 +271,11 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 #pragma omp parallel for schedule(static) num_threads(bwb_host_team())
 	for (long r = 0; r < (long)n; r++)
 		place_from_alns(alns->alns + alns->aln_off[r], alns->aln_off[r + 1] - alns->aln_off[r], ref_pos[r], BWT->length, max_diff, &pl[r]);
+	const int ann_sorted = sam_ann_sorted(ann);
+	bwb_locus *loci = bub ? host_loci(pl, n, ann, ann_sorted, bubble_of, bub) : NULL;
 	const sam_reads_t rd = { .pl = pl, .seq = reads->seq, .stride = reads->stride, .len = reads->len, .text = reads->raw,
 	                         .name_off = reads->name_off, .qual_off = reads->qual_off, .name_len = reads->name_len, .first = 0,
-	                         .alt_off = alt_off, .alts = alts };
-	const int ann_sorted = sam_ann_sorted(ann);
+	                         .alt_off = alt_off, .alts = alts, .loci = loci, .bubbles = bub };
 	/* The text: blocks of reads are formatted into memory by all cores and written in order (round 5: one thread's fprintf calls were
 	 * the wall time of aln2sam on a 10 M-read file, not the SA lookups). */
 	const size_t BLK = SAM_BLOCK_READS;
@@ -294,7 +295,7 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 			free(bufs[bi]); bufs[bi] = NULL;
 		}
 	}
-	free(pl); free(alt_off); free(alts);
+	free(pl); free(alt_off); free(alts); free(loci); free(bubble_of); free_bubbles(bub);
 	free(bufs); free(lens);
 	printf("Processed %zu reads.\n", n);
 	free(rows); free(pos); free(which); free(ref_pos);
@@ -304,12 +305,14 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 }
 
 /* developer command (CPU only, for the tests): raw bwb_place records from a file through sam_format_reads - the formatter `map` uses, on a
- * machine without a GPU */
-void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname) {
+ * machine without a GPU (bubbleFname: -B, the loci from the host resolver) */
+void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname) {
 	size_t Ln = strlen(fastaFname) + 8;
 	char *annFname = (char *)malloc(Ln);
 	snprintf(annFname, Ln, "%s.ann", fastaFname);
 	fasta_annotations_t *ann = annf2ann(annFname);
+	bubble_table_t *bub = bubbleFname ? load_bubbles(bubbleFname) : NULL;
+	int32_t *bubble_of = bub ? ann_bubble_of(ann, bub) : NULL;
 	reads_t *reads = fastq2reads(readsFname);
 	FILE *pf = fopen(placesFname, "rb");
 	if (!pf) { perror(placesFname); bwb_die("places2sam: Cannot open the placements file: %s!", placesFname); }
@@ -333,10 +336,11 @@ void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *sam
 	FILE *sam = fopen(samFname, "w");
 	if (!sam) { perror(samFname); bwb_die("places2sam: Cannot open SAM file: %s!", samFname); }
 	sam_write_header(sam, ann);
+	const int ann_sorted = sam_ann_sorted(ann);
+	bwb_locus *loci = bub ? host_loci(pl, n, ann, ann_sorted, bubble_of, bub) : NULL;
 	const sam_reads_t rd = { .pl = pl, .seq = reads->seq, .stride = reads->stride, .len = reads->len, .text = reads->raw,
 	                         .name_off = reads->name_off, .qual_off = reads->qual_off, .name_len = reads->name_len, .first = 0,
-	                         .alt_off = alt_off, .alts = alts };
-	const int ann_sorted = sam_ann_sorted(ann);
+	                         .alt_off = alt_off, .alts = alts, .loci = loci, .bubbles = bub };
 	for (size_t r0 = 0; r0 < n; r0 += SAM_BLOCK_READS) {
 		size_t len = 0;
 		char *buf = sam_format_reads(&rd, r0, r0 + SAM_BLOCK_READS < n ? r0 + SAM_BLOCK_READS : n, ann, ann_sorted, &len);
@@ -344,7 +348,7 @@ void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *sam
 		free(buf);
 	}
 	printf("Processed %zu reads.\n", n);
-	free(pl); free(annFname); free(alt_off); free(alts);
+	free(pl); free(annFname); free(alt_off); free(alts); free(loci); free(bubble_of); free_bubbles(bub);
 	free_reads(reads); free_ann(ann);
 	fclose(sam);
 }

@@ -264,6 +264,43 @@ int bwb_hip_place_alt_stats(bwb_hip_ctx *ctx, uint64_t *items, uint64_t *steps, 
 int bwb_hip_place_hits_alt(bwb_hip_ctx *ctx, const bwb_aln *alns, const uint64_t *aln_off, uint32_t n_reads, int max_mm, int max_alt,
                            bwb_place *out, const uint64_t **alt_off, const bwb_alt **alts);
 
+/* Bubble hits in reference coordinates (`bwbble map -B`: the tags bC:Z: / bP:Z: that the reference's sam_pad appends, mg-ref/sam_pad.cpp:47-94).
+ * A multi-genome holds one `>bubbleN chr pos` record per indel; bubble.data (mg-ref/comb.cpp:245-253) says where its two flanks lie on the
+ * chromosome.  Kernel k_locus resolves every read of a slot next to k_place: the .ann record that contains the read's text position (a binary
+ * search of a uniform number of steps over the records' first positions), the position SAM prints, and on a bubble record with B = B_minus_A
+ * and the printed position as `locus`, in 64-bit signed arithmetic:
+ *     1 <= locus <= B                                         -> the point A + locus - 1
+ *     B + alt_len + 1 <= locus <= B + alt_len + D_minus_C + 1 -> the point locus + C - (B + alt_len + 1)
+ *     anything else                                           -> the range A + B .. A + B + ref_len - 1 (its upper end one below its lower end
+ *                                                                when ref_len == 0)
+ * (Added without a version change: no structure or existing entry point changed.) */
+typedef struct { int64_t A, B_minus_A, C, D_minus_C; int32_t ref_len, alt_len; } bwb_bubble;
+#define BWB_LOCUS_POINT 1
+#define BWB_LOCUS_RANGE 2
+typedef struct {                 /* 32 bytes, two 16-byte words */
+	int32_t seqid;               /* .ann record that contains bwb_place.pos; -1: none / unmapped */
+	int32_t pos1;                /* what SAM POS prints: (int)(pos - start + 1); 0 unmapped */
+	int32_t bubble;              /* index into the bubble table; -1: not a bubble record */
+	uint8_t kind, reserved[3];   /* 0 none, BWB_LOCUS_POINT, BWB_LOCUS_RANGE */
+	int64_t ref_lo, ref_hi;      /* bP: lo == hi for a point */
+} bwb_locus;
+/* Uploads the tables once per context: record i of the .ann file spans the text positions start[i] .. end[i] and is bubble bubble_of[i] (-1: not a
+ * bubble record).  BWB_E_ARG when the records are not ascending and disjoint (start[i] <= end[i] < start[i + 1]), when there is none, or when a
+ * bubble_of lies outside -1 .. n_bub - 1; n_bub == 0 with every bubble_of -1 is allowed.  A second call replaces the tables. */
+int bwb_hip_set_loci(bwb_hip_ctx *ctx, const uint64_t *start, const uint64_t *end, const int32_t *bubble_of, uint32_t n_seq,
+                     const bwb_bubble *bubbles, uint32_t n_bub);
+/* slot_place (or its cached records), then k_locus over the slot's device-resident placement records on the result stream and D2H of n_reads
+ * locus records in read order into pinned memory of the slot, valid until the slot is uploaded again.  The same records whether it is called
+ * before or after slot_place / slot_place_alt / slot_result.  BWB_E_STATE without set_loci, without set_sa, or on a slot that has not been
+ * submitted; the context stays usable after each.  batch_locus is the one-batch form (slot 0 after batch_run). */
+int bwb_hip_slot_locus(bwb_hip_ctx *ctx, int slot, int max_mm, const bwb_place **places, const bwb_locus **loci, uint32_t *n_reads);
+int bwb_hip_batch_locus(bwb_hip_ctx *ctx, int max_mm, const bwb_place **places, const bwb_locus **loci, uint32_t *n_reads);
+/* The same kernel on n placement records of the caller's (like place_hits): n locus records go to out.  Needs set_loci; touches no slot.
+ * For parity tests. */
+int bwb_hip_locus_places(bwb_hip_ctx *ctx, const bwb_place *places, uint32_t n, bwb_locus *out);
+/* the last locus call on the context: reads resolved and the kernel's HIP-event time (any pointer may be NULL) */
+int bwb_hip_locus_stats(bwb_hip_ctx *ctx, uint64_t *reads, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
