@@ -25,6 +25,7 @@ EXPORTS = [
     "bwb_hip_slot_place", "bwb_hip_batch_place", "bwb_hip_place_stats", "bwb_hip_place_hits",
     "bwb_hip_slot_place_alt", "bwb_hip_batch_place_alt", "bwb_hip_place_alt_stats", "bwb_hip_place_hits_alt",
     "bwb_hip_set_loci", "bwb_hip_slot_locus", "bwb_hip_batch_locus", "bwb_hip_locus_places", "bwb_hip_locus_stats",
+    "bwb_hip_set_bubble_chrom", "bwb_hip_slot_join", "bwb_hip_batch_join", "bwb_hip_join_records", "bwb_hip_join_stats",
 ]
 ABI_VERSION = 3  # BWB_HIP_ABI_VERSION (include/bwbble_hip.h)
 MAX_SLOTS = 8  # BWB_MAX_SLOTS
@@ -70,6 +71,9 @@ assert BUBBLE_DTYPE.itemsize == 40
 LOCUS_DTYPE = np.dtype([("seqid", "<i4"), ("pos1", "<i4"), ("bubble", "<i4"), ("kind", "u1"), ("reserved", "u1", (3,)), ("ref_lo", "<i8"), ("ref_hi", "<i8")])
 assert LOCUS_DTYPE.itemsize == 32
 LOCUS_POINT, LOCUS_RANGE = 1, 2
+# bwb_join: a read's counts and MAPQ once the placements that lie where its primary lies are counted as one (kernels k_join_items / k_join_reads)
+JOIN_DTYPE = np.dtype([("top1", "<i4"), ("top2", "<i4"), ("mapq", "u1"), ("joined", "u1"), ("reserved", "<u2"), ("reserved2", "<u4")])
+assert JOIN_DTYPE.itemsize == 16
 
 _FLAG = {"-M": "mm_score", "-O": "gapo_score", "-E": "gape_score", "-n": "max_diff", "-k": "max_diff_seed",
          "-o": "max_gapo", "-e": "max_gape", "-l": "seed_length", "-m": "max_entries", "-t": "n_threads"}
@@ -132,6 +136,11 @@ def lib():
         L.bwb_hip_batch_locus.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
         L.bwb_hip_locus_places.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.bwb_hip_locus_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.bwb_hip_set_bubble_chrom.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.bwb_hip_slot_join.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_void_p)] * 5 + [C.POINTER(C.c_uint32)]
+        L.bwb_hip_batch_join.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_void_p)] * 5 + [C.POINTER(C.c_uint32)]
+        L.bwb_hip_join_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.bwb_hip_join_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -441,6 +450,44 @@ class Context:
         _chk(lib().bwb_hip_locus_stats(self._h, C.byref(n), C.byref(ms)))
         return n.value, ms.value
 
+    # -- a read's placements counted by locus (-J): one JOIN_DTYPE record per read (needs set_loci and set_bubble_chrom; the slot forms set_sa) --
+    def set_bubble_chrom(self, chrom_of):
+        """after set_loci: the .ann record of the chromosome every bubble lies on (see bubble_chrom_of())"""
+        chrom_of = np.ascontiguousarray(chrom_of, dtype=np.int32)
+        _chk(lib().bwb_hip_set_bubble_chrom(self._h, chrom_of.ctypes.data, len(chrom_of)))
+
+    def _joined(self, call, *args):
+        p = [C.c_void_p() for _ in range(5)]
+        n = C.c_uint32()
+        _chk(call(self._h, *args, *[C.byref(x) for x in p], C.byref(n)))
+        n = n.value
+        joins = np.frombuffer(C.string_at(p[4], n * JOIN_DTYPE.itemsize), dtype=JOIN_DTYPE).copy() if n else np.zeros(0, dtype=JOIN_DTYPE)
+        return (self._places(p[0], n),) + self._alts(n, p[1], p[2]) + (self._loci(p[3], n), joins)
+
+    def slot_join(self, slot, max_mm=6, max_alt=5):
+        """(places, alt_off, alts, loci, joins): slot_place_alt's and slot_locus's records and one JOIN_DTYPE record per read of the slot"""
+        return self._joined(lib().bwb_hip_slot_join, slot, max_mm, max_alt)
+
+    def join(self, max_mm=6, max_alt=5):
+        """the same for the one-batch interface (after run() / align())"""
+        return self._joined(lib().bwb_hip_batch_join, max_mm, max_alt)
+
+    def join_records(self, places, alt_off, alts, alt_sub, max_mm=6):
+        """the same kernels on records of the caller's: read r owns alts[alt_off[r]:alt_off[r + 1]], alt_sub[q] != 0: item q is suboptimal"""
+        places = np.ascontiguousarray(places, dtype=PLACE_DTYPE)
+        alt_off = np.ascontiguousarray(alt_off, dtype=np.uint64)
+        alts = np.ascontiguousarray(alts, dtype=ALT_DTYPE)
+        alt_sub = np.ascontiguousarray(alt_sub, dtype=np.uint8)
+        if len(alt_off) != len(places) + 1 or not len(alts) == len(alt_sub) == int(alt_off[-1]):
+            raise ValueError("alt_off must have one entry per read and one more, alts and alt_sub one per item")
+        out = np.zeros(len(places), dtype=JOIN_DTYPE)
+        _chk(lib().bwb_hip_join_records(self._h, places.ctypes.data, len(places), alt_off.ctypes.data, alts.ctypes.data, alt_sub.ctypes.data, max_mm, out.ctypes.data))
+        return out
+
+    def join_stats(self):
+        """(items, joined items, kernel ms) of the last join call"""
+        return self._count_steps_ms(lib().bwb_hip_join_stats)
+
     def dtab_info(self):
         """the context's calculate_d table: {K (0: none), build seconds, bytes}"""
         k, sec, nb = C.c_int(), C.c_double(), C.c_uint64()
@@ -493,6 +540,24 @@ def bubble_of(names, n_bubbles):
                 raise ValueError(f"record {i} ({name!r}) names a bubble outside the table of {n_bubbles}")
             out[i] = w
     return out
+
+
+def bubble_chrom_of(names, anns):
+    """the .ann record of the chromosome every bubble lies on (-J): the one record whose name's first word is the first word of the bubble's
+    header line in bubble.data (anns, see read_bubble_data()); none, several, or a bubble record is an error, as in the host tools"""
+    word = lambda t: t.split()[0] if t.split() else ""
+    by_word = {}
+    for i, n in enumerate(names):
+        by_word.setdefault(word(n), []).append(i)
+    out = np.zeros(len(anns), dtype=np.int32)
+    for b, a in enumerate(anns):
+        w = word(a)
+        hits = by_word.get(w, [])
+        if len(hits) != 1 or names[hits[0]].startswith("bubble"):
+            raise ValueError(f"bubble {b} ({a!r}): {len(hits)} records are named {w!r}" if len(hits) != 1 else f"bubble {b} ({a!r}): record {hits[0]} is itself a bubble record")
+        out[b] = hits[0]
+    return out
+
 
 _BASE_LUT = np.full(256, 4, dtype=np.uint8)  # ASCII -> read->seq code (io.h:112-130): A0 G1 C2 T3 in either case, anything else 4
 _BASE_LUT[np.frombuffer(b"AGCTagct", dtype=np.uint8)] = np.arange(8) % 4

@@ -126,6 +126,9 @@ struct Slot {
 	DevMem d_locus;               /* bwb_hip_slot_locus: one bwb_locus per read */
 	PinMem h_locus;
 	int locus_mm = -1;            /* h_locus holds the records of the placement records for this max_mm (-1: none) */
+	DevMem d_cls, d_join;         /* bwb_hip_slot_join: one class byte per item, one bwb_join per read */
+	PinMem h_join;
+	int join_mm = -1, join_alt = -1; /* h_join holds the records for this max_mm and max_alt (-1: none) */
 	std::vector<uint8_t> h_status;
 	std::vector<uint64_t> h_aln_off;
 	std::vector<bwb_aln> h_alns;
@@ -177,6 +180,10 @@ struct bwb_hip_ctx {
 	DevMem d_lstart, d_lend, d_lbub, d_bubbles; /* k_locus: the .ann records' first and last positions, their bubble numbers; the bubble table */
 	uint32_t loci_nseq = 0, loci_trips = 0;       /* records (0: bwb_hip_set_loci has not been called); steps of the search, ceil(log2(records)) */
 	double locus_ms = 0; uint64_t locus_reads = 0; /* the last locus call */
+	std::vector<int32_t> loci_bub_of;             /* set_loci's bubble_of (set_bubble_chrom checks its table against it) */
+	uint32_t loci_nbub = 0;
+	DevMem d_chrom; bool chrom_set = false;       /* k_join_items: the chromosome record of every bubble (bwb_hip_set_bubble_chrom) */
+	double join_ms = 0; uint64_t join_items = 0, join_joined = 0; /* the last join call */
 	bool force_slices = false;          /* BWB_FORCE_SLICES: the one-batch API parks and resumes too (tests) */
 	bool dbg = false, dbg_iters = false;
 	const char *launch_log = nullptr;   /* BWB_LAUNCH_LOG=<file>: one JSON line per class-0 kernel launch (synchronises after every launch: a profiling aid) */
@@ -749,7 +756,7 @@ extern "C" int bwb_hip_slot_upload(bwb_hip_ctx *c, int si, const bwb_params *p, 
 	/* (pageable source: the runtime stages it before returning, so h_descs may change again right away) */
 	HIPCHK(hipMemcpyAsync(c->d_descs.as<SlotDesc>() + si, &d, sizeof(SlotDesc), hipMemcpyHostToDevice, c->cstream));
 	HIPCHK(hipEventRecord(s.ev_up.e, c->cstream));
-	s.uploaded = true; s.submitted = false; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1;
+	s.uploaded = true; s.submitted = false; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.join_mm = -1;
 	return ensure_class(c, 0);
 }
 
@@ -997,7 +1004,7 @@ static int submit(bwb_hip_ctx *c, int si, bool suspend) {
 		HIPCHK(hipStreamWaitEvent(c->stream, s.ev_calcd.e, 0));
 	}
 	HIPCHK(hipMemsetAsync(s.d_ctl.p, 0, 256, c->stream));
-	s.submitted = true; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.launch = 0;
+	s.submitted = true; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.join_mm = -1; s.launch = 0;
 	if (s.n_reads == 0) { s.complete = true; s.launch = c->n_launches; return BWB_OK; }
 	HIPCHK(hipMemsetAsync(s.d_n.p, 0, (size_t)s.n_reads * 4, c->stream));
 	if (!ahead) {
@@ -1486,18 +1493,21 @@ extern "C" int bwb_hip_locate_stats(bwb_hip_ctx *c, uint64_t *rows, uint64_t *st
 
 /* ---- placement records: eval_aln + mapq on the GPU (k_place) ------------------------------------------------------ */
 static_assert(sizeof(bwb_place) == 48, "bwb_place is three 16-byte words (k_place)");
+static int ensure_qtab(bwb_hip_ctx *c) { /* mapq's table (k_place, k_join_reads), followed by k_place's step counter */
+	if (c->d_qtab.p) return BWB_OK;
+	uint8_t tab[256 + 8] = { 0 }; /* the only floating point of mapq (align.c:744), with the host's own expression */
+	for (int k = 1; k < 256; k++) tab[k] = (uint8_t)(int)(4.343 * log((double)k) + 0.5);
+	HIPCHK(c->d_qtab.alloc(sizeof(tab)));
+	HIPCHK(hipMemcpyAsync(c->d_qtab.p, tab, sizeof(tab), hipMemcpyHostToDevice, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	return BWB_OK;
+}
 /* k_place over n reads whose hits are log[off[r] .. off[r] + cnt[r]) (all device memory, log_n hits in the log) -> n records in d_out, copied to
  * h_out; sets the context's place_ms / place_steps.  On the result stream.  Shared by slot_place (the slot's hit log) and place_hits (a hit
  * list of the caller's): the same kernel, the same launch. */
 static int place_launch(bwb_hip_ctx *c, const char *who, const uint4 *d_log, uint64_t log_n, const uint64_t *d_off, const uint32_t *d_cnt, uint32_t n, int max_mm,
                         uint4 *d_out, bwb_place *h_out) {
-	if (!c->d_qtab.p) { /* the only floating point of mapq (align.c:744), with the host's own expression */
-		uint8_t tab[256 + 8] = { 0 };
-		for (int k = 1; k < 256; k++) tab[k] = (uint8_t)(int)(4.343 * log((double)k) + 0.5);
-		HIPCHK(c->d_qtab.alloc(sizeof(tab)));
-		HIPCHK(hipMemcpyAsync(c->d_qtab.p, tab, sizeof(tab), hipMemcpyHostToDevice, c->rstream));
-		HIPCHK(hipStreamSynchronize(c->rstream));
-	}
+	RC(ensure_qtab(c));
 	c->place_ms = 0; c->place_steps = 0; c->place_reads = n;
 	if (!n) return BWB_OK;
 	Timed t(c, c->rstream);
@@ -1714,7 +1724,8 @@ extern "C" int bwb_hip_set_loci(bwb_hip_ctx *c, const uint64_t *start, const uin
 	}
 	HIPCHK(hipSetDevice(c->device));
 	c->loci_nseq = 0; /* (no tables until all four are resident) */
-	for (auto &s : c->slots) s.locus_mm = -1;
+	c->chrom_set = false;
+	for (auto &s : c->slots) { s.locus_mm = -1; s.join_mm = -1; }
 	HIPCHK(c->d_lstart.alloc((size_t)n_seq * 8));
 	HIPCHK(c->d_lend.alloc((size_t)n_seq * 8));
 	HIPCHK(c->d_lbub.alloc((size_t)n_seq * 4));
@@ -1728,6 +1739,8 @@ extern "C" int bwb_hip_set_loci(bwb_hip_ctx *c, const uint64_t *start, const uin
 	uint32_t trips = 0;
 	while (((uint64_t)1 << trips) < n_seq) trips++;
 	c->loci_trips = trips;
+	c->loci_bub_of.assign(bubble_of, bubble_of + n_seq);
+	c->loci_nbub = n_bub;
 	c->loci_nseq = n_seq;
 	return BWB_OK;
 }
@@ -1796,6 +1809,144 @@ extern "C" int bwb_hip_locus_stats(bwb_hip_ctx *c, uint64_t *reads, double *kern
 	if (!c) return fail(BWB_E_ARG, "locus_stats: null context");
 	if (reads) *reads = c->locus_reads;
 	if (kernel_ms) *kernel_ms = c->locus_ms;
+	return BWB_OK;
+}
+
+/* ---- a read's placements counted by locus: bwb_join records (k_join_items, k_join_reads) ---------------------------------------- */
+static_assert(sizeof(bwb_join) == 16, "bwb_join is one 16-byte word (k_join_reads)");
+extern "C" int bwb_hip_set_bubble_chrom(bwb_hip_ctx *c, const int32_t *chrom_of, uint32_t n_bub) {
+	if (!c || (n_bub && !chrom_of)) return fail(BWB_E_ARG, "set_bubble_chrom: null argument");
+	if (!c->loci_nseq) return fail(BWB_E_STATE, "set_bubble_chrom: record and bubble tables not uploaded (bwb_hip_set_loci)");
+	if (n_bub != c->loci_nbub) return fail(BWB_E_ARG, "set_bubble_chrom: " + std::to_string(n_bub) + " bubbles, the table of set_loci has " + std::to_string(c->loci_nbub));
+	for (uint32_t b = 0; b < n_bub; b++)
+		if (chrom_of[b] < 0 || (uint32_t)chrom_of[b] >= c->loci_nseq || c->loci_bub_of[chrom_of[b]] != -1)
+			return fail(BWB_E_ARG, "set_bubble_chrom: chrom_of[" + std::to_string(b) + "] = " + std::to_string(chrom_of[b]) + " is not a non-bubble record of the table of " +
+			                           std::to_string(c->loci_nseq) + " records");
+	HIPCHK(hipSetDevice(c->device));
+	c->chrom_set = false;
+	for (auto &s : c->slots) s.join_mm = -1;
+	HIPCHK(c->d_chrom.alloc((size_t)n_bub * 4));
+	if (n_bub) {
+		HIPCHK(hipMemcpyAsync(c->d_chrom.p, chrom_of, (size_t)n_bub * 4, hipMemcpyHostToDevice, c->rstream));
+		HIPCHK(hipStreamSynchronize(c->rstream));
+	}
+	c->chrom_set = true;
+	return BWB_OK;
+}
+
+/* what the two kernels read, all device memory: n placement records, their locus records, alt_off[n + 1], n_items items, and for the suboptimal
+ * bit either the hit log the items came from (log, log_n, off, cnt) or one byte per item (sub) */
+struct JoinIn {
+	const uint4 *places; uint32_t n; const uint4 *loci; const uint64_t *alt_off; const uint4 *alts; uint64_t n_items;
+	const uint4 *log; uint64_t log_n; const uint64_t *off; const uint32_t *cnt; const uint8_t *sub;
+};
+/* k_join_items + k_join_reads -> n records in d_out, copied to h_out; sets the context's join_ms / join_items / join_joined.  On the result
+ * stream, behind the kernels that wrote the records.  Shared by slot_join and join_records. */
+static int join_launch(bwb_hip_ctx *c, const JoinIn &in, int max_mm, DevMem &d_cls, uint4 *d_out, bwb_join *h_out) {
+	c->join_ms = 0; c->join_items = in.n_items; c->join_joined = 0;
+	if (!in.n) return BWB_OK;
+	RC(ensure_qtab(c));
+	HIPCHK(d_cls.reserve((size_t)in.n_items));
+	uint32_t owner_trips = 0;
+	while (((uint64_t)1 << owner_trips) < in.n) owner_trips++;
+	const size_t cap = (size_t)c->num_cu * 8;
+	Timed t(c, c->rstream);
+	RC(t.begin());
+	if (in.n_items)
+		hipLaunchKernelGGL(k_join_items, dim3((unsigned)std::min<size_t>((size_t)((in.n_items + BWB_BLOCK - 1) / BWB_BLOCK), cap)), dim3(BWB_BLOCK), 0, c->rstream,
+		                   in.places, in.n, owner_trips, in.alt_off, in.alts, in.n_items, in.loci, c->d_lstart.as<uint64_t>(), c->d_lend.as<uint64_t>(), c->d_lbub.as<int32_t>(),
+		                   c->loci_nseq, c->loci_trips, c->d_bubbles.as<uint64_t>(), c->d_chrom.as<int32_t>(), in.log, in.log_n, in.off, in.cnt, in.sub, d_cls.as<uint8_t>());
+	hipLaunchKernelGGL(k_join_reads, dim3((unsigned)std::min<size_t>(((size_t)in.n + BWB_BLOCK - 1) / BWB_BLOCK, cap)), dim3(BWB_BLOCK), 0, c->rstream,
+	                   in.places, in.n, in.alt_off, d_cls.as<uint8_t>(), max_mm, c->d_qtab.as<uint8_t>(), d_out);
+	HIPCHK(hipGetLastError());
+	RC(t.end());
+	HIPCHK(hipMemcpyAsync(h_out, d_out, (size_t)in.n * sizeof(bwb_join), hipMemcpyDeviceToHost, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	float ms = 0;
+	RC(t.ms(&ms));
+	c->join_ms = ms;
+	for (uint32_t r = 0; r < in.n; r++) c->join_joined += h_out[r].joined;
+	return BWB_OK;
+}
+
+static int join_ready(bwb_hip_ctx *c, const char *who, int max_alt) {
+	if (max_alt < 1 || max_alt > 255) return fail(BWB_E_ARG, std::string(who) + ": max_alt must be 1..255");
+	if (!c->loci_nseq) return fail(BWB_E_STATE, std::string(who) + ": record and bubble tables not uploaded (bwb_hip_set_loci)");
+	if (!c->chrom_set) return fail(BWB_E_STATE, std::string(who) + ": the bubbles' chromosome records not uploaded (bwb_hip_set_bubble_chrom)");
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_slot_join(bwb_hip_ctx *c, int si, int max_mm, int max_alt, const bwb_place **places, const uint64_t **alt_off, const bwb_alt **alts,
+                                 const bwb_locus **loci, const bwb_join **joins, uint32_t *n_reads) {
+	if (!c || !places || !alt_off || !alts || !loci || !joins || !n_reads || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_join: bad argument");
+	RC(join_ready(c, "slot_join", max_alt));
+	/* (both wait for the slot, refuse what slot_place refuses, and leave their records in the slot's device memory) */
+	RC(bwb_hip_slot_place_alt(c, si, max_mm, max_alt, places, alt_off, alts, n_reads));
+	RC(bwb_hip_slot_locus(c, si, max_mm, places, loci, n_reads));
+	Slot &s = c->slots[si];
+	const uint32_t n = s.n_reads;
+	if (s.join_mm != max_mm || s.join_alt != max_alt || !n) {
+		HIPCHK(s.h_join.reserve((size_t)n * sizeof(bwb_join)));
+		uint64_t log_n = 0;
+		if (n) {
+			HIPCHK(s.d_join.reserve((size_t)n * sizeof(bwb_join)));
+			RC(slot_log_n(c, s, &log_n));
+		}
+		const JoinIn in = { s.d_place.as<uint4>(), n, s.d_locus.as<uint4>(), s.alt.d_off.as<uint64_t>(), s.alt.d_alts.as<uint4>(), n ? (*alt_off)[n] : 0,
+		                    s.d_log.as<uint4>(), log_n, s.d_off.as<uint64_t>(), s.d_n.as<uint32_t>(), nullptr };
+		RC(join_launch(c, in, max_mm, s.d_cls, s.d_join.as<uint4>(), s.h_join.as<bwb_join>()));
+		s.join_mm = max_mm; s.join_alt = max_alt;
+	}
+	*joins = s.h_join.as<bwb_join>();
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_batch_join(bwb_hip_ctx *c, int max_mm, int max_alt, const bwb_place **places, const uint64_t **alt_off, const bwb_alt **alts,
+                                  const bwb_locus **loci, const bwb_join **joins, uint32_t *n_reads) {
+	if (!c || !places || !alt_off || !alts || !loci || !joins || !n_reads) return fail(BWB_E_ARG, "batch_join: null argument");
+	RC(join_ready(c, "batch_join", max_alt));
+	if (!c->d_SA.p) return fail(BWB_E_STATE, "batch_join: sampled SA not uploaded (bwb_hip_set_sa)");
+	if (!c->slots[0].submitted || !c->slots[0].complete) return fail(BWB_E_STATE, "batch_join: batch_run has not completed");
+	return bwb_hip_slot_join(c, 0, max_mm, max_alt, places, alt_off, alts, loci, joins, n_reads);
+}
+
+/* the kernels on records of the caller's instead of a slot's (for parity tests): k_locus for the primaries' loci, then the two join kernels */
+extern "C" int bwb_hip_join_records(bwb_hip_ctx *c, const bwb_place *places, uint32_t n, const uint64_t *alt_off, const bwb_alt *alts, const uint8_t *alt_sub, int max_mm,
+                                    bwb_join *out) {
+	if (!c || !alt_off || (n && (!places || !out)) || n > 0x7FFFFFFFu) return fail(BWB_E_ARG, "join_records: bad argument");
+	RC(join_ready(c, "join_records", 1));
+	if (alt_off[0] != 0) return fail(BWB_E_ARG, "join_records: alt_off[0] must be 0");
+	for (uint32_t r = 0; r < n; r++)
+		if (alt_off[r + 1] < alt_off[r] || alt_off[r + 1] - alt_off[r] > 255) return fail(BWB_E_ARG, "join_records: read " + std::to_string(r) + " does not own 0..255 items");
+	const uint64_t n_items = alt_off[n];
+	if (n_items && (!alts || !alt_sub)) return fail(BWB_E_ARG, "join_records: null argument");
+	HIPCHK(hipSetDevice(c->device));
+	DevMem d_places, d_loci, d_off, d_alts, d_sub, d_cls, d_out;
+	HIPCHK(d_places.alloc((size_t)n * sizeof(bwb_place)));
+	HIPCHK(d_loci.alloc((size_t)n * sizeof(bwb_locus)));
+	HIPCHK(d_off.alloc(((size_t)n + 1) * 8));
+	HIPCHK(d_alts.alloc((size_t)n_items * sizeof(bwb_alt)));
+	HIPCHK(d_sub.alloc((size_t)n_items));
+	HIPCHK(d_out.alloc((size_t)n * sizeof(bwb_join)));
+	if (n) HIPCHK(hipMemcpyAsync(d_places.p, places, (size_t)n * sizeof(bwb_place), hipMemcpyHostToDevice, c->rstream));
+	HIPCHK(hipMemcpyAsync(d_off.p, alt_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->rstream));
+	if (n_items) {
+		HIPCHK(hipMemcpyAsync(d_alts.p, alts, (size_t)n_items * sizeof(bwb_alt), hipMemcpyHostToDevice, c->rstream));
+		HIPCHK(hipMemcpyAsync(d_sub.p, alt_sub, (size_t)n_items, hipMemcpyHostToDevice, c->rstream));
+	}
+	HIPCHK(hipStreamSynchronize(c->rstream)); /* (pageable memory of the caller) */
+	std::vector<bwb_locus> h_loci(n ? n : 1);
+	RC(locus_launch(c, d_places.as<uint4>(), n, d_loci.as<uint4>(), h_loci.data()));
+	const JoinIn in = { d_places.as<uint4>(), n, d_loci.as<uint4>(), d_off.as<uint64_t>(), d_alts.as<uint4>(), n_items, nullptr, 0, nullptr, nullptr, d_sub.as<uint8_t>() };
+	return join_launch(c, in, max_mm, d_cls, d_out.as<uint4>(), out);
+}
+
+/* the last join call: items compared, items joined and the two kernels' HIP-event time */
+extern "C" int bwb_hip_join_stats(bwb_hip_ctx *c, uint64_t *items, uint64_t *joined, double *kernel_ms) {
+	if (!c) return fail(BWB_E_ARG, "join_stats: null context");
+	if (items) *items = c->join_items;
+	if (joined) *joined = c->join_joined;
+	if (kernel_ms) *kernel_ms = c->join_ms;
 	return BWB_OK;
 }
 

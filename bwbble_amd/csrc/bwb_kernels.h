@@ -8,6 +8,7 @@
  *   k_gather     per-read hit lists -> read order
  *   k_place      eval_aln + mapq for every read of a slot (`bwbble map`): one 48-byte placement record per read
  *   k_locus      the .ann record of every placement record and, on a bubble record, its reference coordinates (`bwbble map -B`)
+ *   k_join_items, k_join_reads   a read's other placements that lie where its primary lies, and its MAPQ without them (`bwbble map -J`)
  * The alignment kernels themselves (kl_calc_d, kl_search: one read per lane) are in bwb_lane.h.
  */
 #pragma once
@@ -368,6 +369,16 @@ __device__ __forceinline__ void place_runs(uint32_t alen, const uint32_t rw[4], 
 	}
 }
 
+/* mapq, align.c:738-746: all integer, qtab[n] = (int)(4.343 * log(n) + 0.5) tabulated by the host (k_place, k_join_reads) */
+__device__ __forceinline__ uint32_t place_mapq(int top1, int top2, int num_mm, int max_mm, const uint8_t *qtab) {
+	if (top1 == 0) return 23u;
+	if (top1 > 1) return 0u;
+	if (num_mm == max_mm) return 25u;
+	if (top2 == 0) return 37u;
+	const uint32_t q = qtab[top2 >= 255 ? 255 : (top2 < 0 ? 0 : top2)];
+	return 23 < q ? 0u : 23 - q;
+}
+
 /* eval_aln + mapq (align.c:738-812) for every read of a slot, where its hits lie: one octet per read -> one 48-byte bwb_place record
  * (include/bwbble_hip.h) in read order.  log/off/n are the slot's hit log (bwb_aln: three uint4 per hit, a read's hits contiguous and in
  * discovery order).  All integer: qtab[n] = (int)(4.343 * log(n) + 0.5), tabulated by the host (the only floating point of mapq). */
@@ -415,14 +426,7 @@ __global__ __launch_bounds__(BWB_BLOCK) void k_place(DevIndex ix, const uint64_t
 				uint64_t pos;
 				if (rp > (ix.length - 1) / 2) pos = ((ix.length - 1) - rp - 1) - (uint64_t)ref_len + 1;
 				else { flags |= PLACE_F_REVERSE; pos = rp; }
-				/* mapq, align.c:738-746 */
-				uint32_t mq;
-				const int top1 = (int)t1, top2 = (int)t2;
-				if (top1 == 0) mq = 23;
-				else if (top1 > 1) mq = 0;
-				else if ((int)num_mm == max_mm) mq = 25;
-				else if (top2 == 0) mq = 37;
-				else { const uint32_t q = qtab[top2 >= 255 ? 255 : (top2 < 0 ? 0 : top2)]; mq = 23 < q ? 0 : 23 - q; }
+				const uint32_t mq = place_mapq((int)t1, (int)t2, (int)num_mm, max_mm, qtab);
 				w0 = make_uint4((uint32_t)pos, (uint32_t)(pos >> 32), t1, t2);
 				w1 = make_uint4(best | (mq << 16) | (flags << 24), (e1.x >> 16) | ((e1.y & 0xFFu) << 16), alen | (ref_len << 16), 0u);
 				w2 = make_uint4(rr[0] | (rr[1] << 16), rr[2] | (rr[3] << 16), rr[4] | (rr[5] << 16), rr[6] | (rr[7] << 16));
@@ -444,42 +448,46 @@ __global__ __launch_bounds__(BWB_BLOCK) void k_place(DevIndex ix, const uint64_t
  * first positions of 1.3 M records are 10 MB: they stay in the Infinity Cache.  bub[] holds the bwb_bubble records as five 64-bit words
  * (A, B_minus_A, C, D_minus_C, ref_len | alt_len << 32); bubble_of[] was checked against its size on the host (bwb_hip_set_loci).  The
  * sums wrap (unsigned arithmetic, compared as signed) like the host's bubble_locus. */
+struct Locus { uint32_t seqid /* 0xFFFFFFFF: none */, pos1; int32_t b; uint32_t kind; uint64_t lo, hi; };
+__device__ __forceinline__ Locus locus_at(uint64_t pos, bool mapped, const uint64_t *start, const uint64_t *end, const int32_t *bubble_of, uint32_t n_seq, uint32_t trips,
+                                          const uint64_t *bub) {
+	uint32_t lo = 0, len = n_seq;
+	for (uint32_t t = 0; t < trips; t++) {
+		const uint32_t half = len >> 1, mid = lo + half;
+		lo = start[mid] <= pos ? mid : lo;
+		len -= half;
+	}
+	const uint64_t s = start[lo];
+	const bool in = mapped && pos >= s && pos <= end[lo];
+	const int32_t b = in ? bubble_of[lo] : -1;
+	const uint32_t pos1 = in ? (uint32_t)(pos - s + 1) : 0u;
+	uint32_t kind = 0;
+	uint64_t rlo = 0, rhi = 0;
+	if (b >= 0) {
+		const uint64_t *q = bub + (size_t)b * 5;
+		const uint64_t A = q[0], B = q[1], C = q[2], D = q[3], la = q[4];
+		const uint64_t ref_len = (uint64_t)(int64_t)(int32_t)(uint32_t)la, alt_len = (uint64_t)(int64_t)(int32_t)(uint32_t)(la >> 32);
+		const int64_t locus = (int64_t)(int32_t)pos1;
+		const uint64_t right = B + alt_len + 1u;
+		const bool left_flank = locus >= 1 && locus <= (int64_t)B;
+		const bool right_flank = locus >= (int64_t)right && locus <= (int64_t)(right + D);
+		const uint64_t point = left_flank ? A + (uint64_t)locus - 1u : (uint64_t)locus + C - right;
+		const bool is_point = left_flank || right_flank;
+		kind = is_point ? 1u : 2u;
+		rlo = is_point ? point : A + B;
+		rhi = is_point ? point : A + B + ref_len - 1u;
+	}
+	return Locus{ in ? lo : 0xFFFFFFFFu, pos1, b, kind, rlo, rhi };
+}
 __global__ __launch_bounds__(BWB_BLOCK) void k_locus(const uint4 *places, uint32_t n_reads, const uint64_t *start, const uint64_t *end, const int32_t *bubble_of,
                                                       uint32_t n_seq, uint32_t trips, const uint64_t *bub, uint4 *out) {
 	const uint32_t stride = gridDim.x * BWB_BLOCK;
 	for (uint32_t r = blockIdx.x * BWB_BLOCK + threadIdx.x; r < n_reads; r += stride) {
 		const uint4 p0 = places[(size_t)r * 3], p1 = places[(size_t)r * 3 + 1];
-		const uint64_t pos = (uint64_t)p0.x | ((uint64_t)p0.y << 32);
-		const bool mapped = ((p1.x >> 24) & PLACE_F_MAPPED) != 0;
-		uint32_t lo = 0, len = n_seq;
-		for (uint32_t t = 0; t < trips; t++) {
-			const uint32_t half = len >> 1, mid = lo + half;
-			lo = start[mid] <= pos ? mid : lo;
-			len -= half;
-		}
-		const uint64_t s = start[lo];
-		const bool in = mapped && pos >= s && pos <= end[lo];
-		const int32_t b = in ? bubble_of[lo] : -1;
-		const uint32_t pos1 = in ? (uint32_t)(pos - s + 1) : 0u;
-		uint32_t kind = 0;
-		uint64_t rlo = 0, rhi = 0;
-		if (b >= 0) {
-			const uint64_t *q = bub + (size_t)b * 5;
-			const uint64_t A = q[0], B = q[1], C = q[2], D = q[3], la = q[4];
-			const uint64_t ref_len = (uint64_t)(int64_t)(int32_t)(uint32_t)la, alt_len = (uint64_t)(int64_t)(int32_t)(uint32_t)(la >> 32);
-			const int64_t locus = (int64_t)(int32_t)pos1;
-			const uint64_t right = B + alt_len + 1u;
-			const bool left_flank = locus >= 1 && locus <= (int64_t)B;
-			const bool right_flank = locus >= (int64_t)right && locus <= (int64_t)(right + D);
-			const uint64_t point = left_flank ? A + (uint64_t)locus - 1u : (uint64_t)locus + C - right;
-			const bool is_point = left_flank || right_flank;
-			kind = is_point ? 1u : 2u;
-			rlo = is_point ? point : A + B;
-			rhi = is_point ? point : A + B + ref_len - 1u;
-		}
+		const Locus lc = locus_at((uint64_t)p0.x | ((uint64_t)p0.y << 32), ((p1.x >> 24) & PLACE_F_MAPPED) != 0, start, end, bubble_of, n_seq, trips, bub);
 		uint4 *dst = out + (size_t)r * 2;
-		dst[0] = make_uint4(in ? lo : 0xFFFFFFFFu, pos1, (uint32_t)b, kind);
-		dst[1] = make_uint4((uint32_t)rlo, (uint32_t)(rlo >> 32), (uint32_t)rhi, (uint32_t)(rhi >> 32));
+		dst[0] = make_uint4(lc.seqid, lc.pos1, (uint32_t)lc.b, lc.kind);
+		dst[1] = make_uint4((uint32_t)lc.lo, (uint32_t)(lc.lo >> 32), (uint32_t)lc.hi, (uint32_t)(lc.hi >> 32));
 	}
 }
 
@@ -619,5 +627,76 @@ __global__ __launch_bounds__(BWB_BLOCK) void k_place_alt(DevIndex ix, const uint
 	if (lane == 0) {
 		if (my_steps) atomicAdd(&ctl[0], my_steps);
 		if (my_bad) atomicAdd(&ctl[1], my_bad);
+	}
+}
+
+/* ---- a read's placements counted by locus (`map -X N -B table -J`) -------------------------------------------------------------
+ * The rule is in include/bwbble_hip.h (bwb_join).  Per ITEM like k_place_alt, and for the same reason; nothing is gathered, so one item per
+ * LANE like k_locus.  k_join_items: the item's owner by the branch-free lower bound over alt_off[0 .. n_reads) - the last read whose offset
+ * is <= q: reads without items share their successor's offset -, `owner_trips` = ceil(log2(n_reads)) steps for every lane; the item's own
+ * locus by k_locus's search and rule (locus_at); the primary's from the bwb_locus record k_locus left for the read; one class byte.  The
+ * suboptimal bit: the score of hit `hit` in the hit log against the primary's (bwb_place.score is the first hit's), or with alt_sub != NULL
+ * the caller's byte (bwb_hip_join_records).  chrom_of[] was checked against the record table on the host (bwb_hip_set_bubble_chrom). */
+#define JOIN_C_JOINED 1u
+#define JOIN_C_SUB 2u
+/* (c, lo, hi') of a placement from its locus record; false: it has none */
+__device__ __forceinline__ bool join_locus(uint32_t seqid, uint32_t pos1, int32_t b, uint64_t rlo, uint64_t rhi, const int32_t *chrom_of, int32_t &c, int64_t &lo, int64_t &hi) {
+	const bool has = seqid != 0xFFFFFFFFu, bubble = has && b >= 0;
+	c = bubble ? chrom_of[b] : (int32_t)seqid;
+	lo = bubble ? (int64_t)rlo : (int64_t)(int32_t)pos1;
+	hi = bubble ? (int64_t)rhi : lo;
+	hi = hi < lo ? lo : hi; /* a pure insertion's empty range counts as its left edge */
+	return has;
+}
+__global__ __launch_bounds__(BWB_BLOCK) void k_join_items(const uint4 *places, uint32_t n_reads, uint32_t owner_trips, const uint64_t *alt_off, const uint4 *alts, uint64_t n_items,
+                                                           const uint4 *loci, const uint64_t *start, const uint64_t *end, const int32_t *bubble_of, uint32_t n_seq, uint32_t trips,
+                                                           const uint64_t *bub, const int32_t *chrom_of, const uint4 *log, uint64_t log_n, const uint64_t *off, const uint32_t *n,
+                                                           const uint8_t *alt_sub, uint8_t *cls) {
+	const uint64_t stride = (uint64_t)gridDim.x * BWB_BLOCK;
+	for (uint64_t q = (uint64_t)blockIdx.x * BWB_BLOCK + threadIdx.x; q < n_items; q += stride) {
+		uint32_t r = 0, len = n_reads;
+		for (uint32_t t = 0; t < owner_trips; t++) {
+			const uint32_t half = len >> 1, mid = r + half;
+			r = alt_off[mid] <= q ? mid : r;
+			len -= half;
+		}
+		const uint4 a0 = alts[q * 2]; /* pos | flags hit mm go | ge - alen16 */
+		const uint32_t hit = (a0.z >> 8) & 0xFFu;
+		const Locus il = locus_at((uint64_t)a0.x | ((uint64_t)a0.y << 32), (a0.z & PLACE_F_MAPPED) != 0, start, end, bubble_of, n_seq, trips, bub);
+		const uint4 p1 = places[(size_t)r * 3 + 1], l0 = loci[(size_t)r * 2], l1 = loci[(size_t)r * 2 + 1];
+		int32_t ci, cp;
+		int64_t loi, hii, lop, hip;
+		const bool has_i = join_locus(il.seqid, il.pos1, il.b, il.lo, il.hi, chrom_of, ci, loi, hii);
+		const bool has_p = join_locus(l0.x, l0.y, (int32_t)l0.z, (uint64_t)l1.x | ((uint64_t)l1.y << 32), (uint64_t)l1.z | ((uint64_t)l1.w << 32), chrom_of, cp, lop, hip);
+		const bool joined = has_i && has_p && ci == cp && (((p1.x >> 24) ^ a0.z) & PLACE_F_REVERSE) == 0 && loi <= hip && lop <= hii;
+		bool sub;
+		if (alt_sub) sub = alt_sub[q] != 0;
+		else {
+			const uint32_t ne = n[r];
+			const uint64_t o = ne ? off[r] : 0;
+			sub = hit < ne && o < log_n && hit < log_n - o && (log[(o + hit) * 3 + 1].x & 0xFFFFu) > (p1.x & 0xFFFFu);
+		}
+		cls[q] = (uint8_t)((joined ? JOIN_C_JOINED : 0u) | (sub ? JOIN_C_SUB : 0u));
+	}
+}
+
+/* One lane per read, grid-strided: the sums of the read's class bytes (contiguous, at most 255; most reads have none) -> one 16-byte bwb_join.
+ * A read without items keeps its record's counts and MAPQ; with items the MAPQ is the reference's formula on the new counts (place_mapq and
+ * the table of k_place). */
+__global__ __launch_bounds__(BWB_BLOCK) void k_join_reads(const uint4 *places, uint32_t n_reads, const uint64_t *alt_off, const uint8_t *cls, int max_mm, const uint8_t *qtab, uint4 *out) {
+	const uint32_t stride = gridDim.x * BWB_BLOCK;
+	for (uint32_t r = blockIdx.x * BWB_BLOCK + threadIdx.x; r < n_reads; r += stride) {
+		const uint4 p0 = places[(size_t)r * 3], p1 = places[(size_t)r * 3 + 1];
+		const uint64_t q0 = alt_off[r], q1 = alt_off[r + 1];
+		uint32_t best = 0, subopt = 0;
+		for (uint64_t q = q0; q < q1; q++) {
+			const uint32_t c = cls[q];
+			best += c == JOIN_C_JOINED;
+			subopt += c == (JOIN_C_JOINED | JOIN_C_SUB);
+		}
+		const uint32_t top1 = p0.z - best, top2 = p0.w - subopt;
+		const uint32_t mq = q1 > q0 ? place_mapq((int)top1, (int)top2, (int)(p1.y & 0xFFu), max_mm, qtab) : (p1.x >> 16) & 0xFFu;
+		const bool mapped = ((p1.x >> 24) & PLACE_F_MAPPED) != 0;
+		out[r] = mapped ? make_uint4(top1, top2, mq | ((best + subopt) << 8), 0u) : make_uint4(0u, 0u, 0u, 0u);
 	}
 }

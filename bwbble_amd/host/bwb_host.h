@@ -119,14 +119,14 @@ int aln_path_bytes(const bwb_aln *a, unsigned char *path /* >= 272 bytes */); /*
 void set_default_aln_params(aln_params_t *params);                     /* align.c:22-38 */
 int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_t *params, int n_gpus); /* align.c:40-87 */
 int align_reads_inexact_gpu_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, char *alnFname, int n_gpus); /* the GPU's align_reads_inexact_parallel (inexact_match.h:40) over a streamed FASTQ */
-int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int n_gpus); /* `bwbble map`: align + aln2sam in one pass, the hits evaluated on the GPU */
+int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int n_gpus); /* `bwbble map`: align + aln2sam in one pass, the hits evaluated on the GPU */
 
 /* precalc.c */
 void precalc_sa_intervals(bwt_t *BWT, const aln_params_t *params, const char *preFname); /* align.c:200-224: writes <fasta>.pre */
 int check_precalc_file(const char *preFname); /* the walk of load_precalc_sa_intervals (align.c:226-238) over an existing table: 0 = complete */
 
 /* sam.c */
-void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname); /* align.c:494-556; max_alt: -X (0: no tags); bubbleFname: -B (NULL: no tags) */
+void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join); /* align.c:494-556; max_alt: -X (0: no tags); bubbleFname: -B (NULL: no tags); join: -J */
 /* the two halves of alns2sam: eval_aln of one read on the host, and the text of a block of reads from placement records (which `map` gets
  * from the GPU instead, bwb_hip_slot_place) */
 #define SAM_BLOCK_READS ((size_t)1 << 14)                              /* reads formatted by one thread at a time */
@@ -137,14 +137,16 @@ typedef struct {
 	size_t first;                                                      /* number of read 0 in the file (error messages) */
 	const uint64_t *alt_off; const bwb_alt *alts;                      /* -X (NULL: no tags): read r's other placements are alts[alt_off[r] .. alt_off[r + 1]) */
 	const bwb_locus *loci; const struct bubble_table *bubbles;         /* -B (NULL: no tags): read r's record and POS come from loci[r], and on a bubble record the tags bC / bP */
+	const bwb_join *joins;                                             /* -J (NULL: pl's MAPQ, no tag): read r's MAPQ comes from joins[r], and with joined items the tag bJ */
 } sam_reads_t;
+int sam_mapq(int top1, int top2, int num_mm, int max_mm);               /* align.c:738-746 */
 void place_from_alns(const bwb_aln *e, uint64_t ne, uint64_t ref_pos, uint64_t bwt_length, int max_mm, bwb_place *out);
 void alt_from_aln(const bwb_aln *e, unsigned hit, uint64_t ref_pos, uint64_t bwt_length, bwb_alt *out); /* one of the other placements, from its hit and SA(its row) */
 uint64_t alt_placements(const bwb_aln *e, uint64_t ne);               /* the rows of all hits: 64-bit, saturating */
 void sam_write_header(FILE *sam, const fasta_annotations_t *ann);
 int sam_ann_sorted(const fasta_annotations_t *ann);
 char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_annotations_t *ann, int ann_sorted, size_t *out_len);
-void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname); /* developer command: records from a file (altsFname: NULL or the items; bubbleFname: NULL or -B's table) */
+void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join); /* developer command: records from a file (altsFname: NULL or the items; bubbleFname: NULL or -B's table; join: -J, the items file then ends with one suboptimal byte per item) */
 
 /* pad.c: bubble hits in reference coordinates (the reference's mg-ref/sam_pad.cpp) */
 typedef struct bubble_table {                                          /* bubble.data (mg-ref/comb.cpp:245-253): the k-th pair of lines is bubble k */
@@ -160,6 +162,9 @@ void bubble_locus(const bwb_bubble *b, int64_t locus, bwb_locus *out); /* sam_pa
 int ann_find_record(const fasta_annotations_t *ann, int ann_sorted, uint64_t aln_pos); /* the record that contains aln_pos, -1: none */
 void locus_resolve(const bwb_place *pl, const fasta_annotations_t *ann, int ann_sorted, const int32_t *bubble_of, const bubble_table_t *t, bwb_locus *out); /* kernel k_locus on the host */
 char *locus_put_tags(char *o, const bwb_locus *lc, const bubble_table_t *t);
+int32_t *bubble_chrom_of(const fasta_annotations_t *ann, const int32_t *bubble_of, const bubble_table_t *t); /* -J: [t->n] the chromosome's record of every bubble (malloc'ed); none, several or a bubble record is refused */
+void join_resolve(const bwb_place *pl, const bwb_locus *lc, const bwb_alt *items, const uint8_t *sub, uint64_t n_items, const fasta_annotations_t *ann, int ann_sorted,
+                  const int32_t *bubble_of, const int32_t *chrom_of, const bubble_table_t *t, int max_mm, bwb_join *out); /* kernels k_join_items + k_join_reads on the host, one read */
 void sam_pad(const char *dataFname, const char *inFname, const char *outFname); /* `bwbble sampad`: sam_pad.cpp:47-94 over SAM text */
 
 /* The OpenMP teams of the host stages of `align` / `aln2sam` (base encoding, .aln serialisation, SAM text) have at most 32 threads unless

@@ -8,6 +8,9 @@
  * (map -B: the same arithmetic on the GPU, next to k_place).  Where the reference's behaviour is undefined - a table with half a pair, a
  * numbers line without six integers, a bubble number outside the table, a SAM line without a POS field - this build stops with a message
  * that names the place.
+ *
+ * -J (no counterpart in the reference): bubble_chrom_of and join_resolve - which of a read's other placements lie where its primary lies,
+ * once both are in chromosome coordinates, and the read's counts and MAPQ without them (include/bwbble_hip.h: bwb_join).
  */
 #define _GNU_SOURCE
 #include <ctype.h>
@@ -140,6 +143,78 @@ char *locus_put_tags(char *o, const bwb_locus *lc, const bubble_table_t *t) {
 	o += sprintf(o, "\tbC:Z:%s\tbP:Z:", t->ann[lc->bubble]);
 	if (lc->kind == BWB_LOCUS_POINT) return o + sprintf(o, "%lld", (long long)lc->ref_lo);
 	return o + sprintf(o, "%lld-%lld", (long long)lc->ref_lo, (long long)lc->ref_hi);
+}
+
+/* ---- -J: a read's placements counted by locus (include/bwbble_hip.h: bwb_join; kernels k_join_items / k_join_reads) -------------------- */
+
+/* the first white-space delimited word of a name */
+typedef struct { const char *w; size_t len; int rec; } name_word_t;
+static name_word_t first_word(const char *s, int rec) {
+	while (*s && isspace((unsigned char)*s)) s++;
+	size_t n = 0;
+	while (s[n] && !isspace((unsigned char)s[n])) n++;
+	return (name_word_t){ .w = s, .len = n, .rec = rec };
+}
+static int word_cmp(const void *a, const void *b) {
+	const name_word_t *x = (const name_word_t *)a, *y = (const name_word_t *)b;
+	const int c = memcmp(x->w, y->w, x->len < y->len ? x->len : y->len);
+	return c ? c : (x->len > y->len) - (x->len < y->len);
+}
+
+/* chrom_of[k]: the .ann record of the chromosome bubble k lies on - the one record whose name's first word is the first word of the bubble's
+ * header line in bubble.data.  None, several, or a record that is itself a bubble record: refused, naming the bubble. */
+int32_t *bubble_chrom_of(const fasta_annotations_t *ann, const int32_t *bubble_of, const bubble_table_t *t) {
+	const size_t n_rec = ann->num_seq > 0 ? (size_t)ann->num_seq : 0;
+	name_word_t *words = (name_word_t *)malloc((n_rec ? n_rec : 1) * sizeof(name_word_t));
+	for (size_t i = 0; i < n_rec; i++) words[i] = first_word(ann->seq_anns[i].name, (int)i);
+	qsort(words, n_rec, sizeof(name_word_t), word_cmp);
+	int32_t *chrom_of = (int32_t *)malloc((t->n ? (size_t)t->n : 1) * sizeof(int32_t));
+	for (int64_t k = 0; k < t->n; k++) {
+		const name_word_t key = first_word(t->ann[k], -1);
+		size_t lo = 0, hi = n_rec; /* the first record whose word is not below the key */
+		while (lo < hi) { const size_t mid = lo + (hi - lo) / 2; if (word_cmp(&words[mid], &key) < 0) lo = mid + 1; else hi = mid; }
+		size_t same = 0;
+		while (lo + same < n_rec && word_cmp(&words[lo + same], &key) == 0) same++;
+		if (same != 1)
+			bwb_die("bubble table: bubble %lld (\"%s\"): %zu .ann records are named \"%.*s\", one chromosome record is needed (-J)", (long long)k, t->ann[k], same, (int)key.len, key.w);
+		if (bubble_of[words[lo].rec] != -1)
+			bwb_die("bubble table: bubble %lld (\"%s\"): .ann record %d (\"%s\") is itself a bubble record (-J)", (long long)k, t->ann[k], words[lo].rec, ann->seq_anns[words[lo].rec].name);
+		chrom_of[k] = words[lo].rec;
+	}
+	free(words);
+	return chrom_of;
+}
+
+/* (c, lo, hi') of a placement from its locus record; 0: it has none */
+static int join_locus(const bwb_locus *lc, const int32_t *chrom_of, int32_t *c, int64_t *lo, int64_t *hi) {
+	if (lc->seqid < 0) return 0;
+	if (lc->bubble >= 0) { *c = chrom_of[lc->bubble]; *lo = lc->ref_lo; *hi = lc->ref_hi; }
+	else { *c = lc->seqid; *lo = *hi = (int64_t)lc->pos1; }
+	if (*hi < *lo) *hi = *lo; /* a pure insertion's empty range counts as its left edge */
+	return 1;
+}
+
+/* one read: its placement record, that record's locus, its items and their suboptimal bytes -> its join record: what the two kernels compute
+ * for `map -J` */
+void join_resolve(const bwb_place *pl, const bwb_locus *lc, const bwb_alt *items, const uint8_t *sub, uint64_t n_items, const fasta_annotations_t *ann, int ann_sorted,
+                  const int32_t *bubble_of, const int32_t *chrom_of, const bubble_table_t *t, int max_mm, bwb_join *out) {
+	memset(out, 0, sizeof(*out));
+	if (!(pl->flags & BWB_PLACE_MAPPED)) return;
+	int32_t cp = 0, ci = 0;
+	int64_t lop = 0, hip = 0, loi = 0, hii = 0;
+	const int has_p = join_locus(lc, chrom_of, &cp, &lop, &hip);
+	uint32_t best = 0, subopt = 0;
+	for (uint64_t k = 0; k < n_items && has_p; k++) {
+		const bwb_place as_place = { .pos = items[k].pos, .flags = items[k].flags };
+		bwb_locus il;
+		locus_resolve(&as_place, ann, ann_sorted, bubble_of, t, &il);
+		if (!join_locus(&il, chrom_of, &ci, &loi, &hii) || ci != cp || ((items[k].flags ^ pl->flags) & BWB_PLACE_REVERSE) || loi > hip || lop > hii) continue;
+		if (sub[k]) subopt++; else best++;
+	}
+	out->top1 = (int32_t)((uint32_t)pl->top1 - best);
+	out->top2 = (int32_t)((uint32_t)pl->top2 - subopt);
+	out->mapq = n_items ? (uint8_t)sam_mapq(out->top1, out->top2, pl->num_mm, max_mm) : pl->mapq;
+	out->joined = (uint8_t)(best + subopt);
 }
 
 /* `bwbble sampad <bubble.data> <in.sam> <out.sam>`: process_sam (sam_pad.cpp:47-94), one line in memory at a time.  A refused line leaves

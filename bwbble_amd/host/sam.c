@@ -19,7 +19,7 @@
 #define SAM_FSU 4
 #define SAM_FSR 16
 
-static int mapq(int top1, int top2, int num_mm, int max_mm) { /* align.c:738-746 */
+int sam_mapq(int top1, int top2, int num_mm, int max_mm) { /* align.c:738-746 */
 	if (top1 == 0) return 23;
 	if (top1 > 1) return 0;
 	if (num_mm == max_mm) return 25;
@@ -49,7 +49,7 @@ void place_from_alns(const bwb_aln *e, uint64_t ne, uint64_t ref_pos, uint64_t b
 	else { out->flags |= BWB_PLACE_REVERSE; out->pos = ref_pos; }
 	out->top1 = top1; out->top2 = top2;
 	out->score = e[0].score;
-	out->mapq = (uint8_t)mapq(top1, top2, e[0].num_mm, max_mm);
+	out->mapq = (uint8_t)sam_mapq(top1, top2, e[0].num_mm, max_mm);
 	out->num_mm = e[0].num_mm; out->num_gapo = e[0].num_gapo; out->num_gape = e[0].num_gape;
 	out->aln_length = (uint16_t)alen; out->ref_len = (uint16_t)ref_len;
 	memcpy(out->gap_run, e[0].gap_run, sizeof(out->gap_run));
@@ -122,6 +122,7 @@ char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_
 		cap += (r1 - r0) * 48;
 		for (uint64_t k = rd->alt_off[r0]; k < rd->alt_off[r1]; k++) cap += MAX_SEQ_NAME_LEN + 64 + 8 * (size_t)rd->alts[k].num_gapo;
 	}
+	if (rd->joins) cap += (r1 - r0) * 12; /* -J: "\tbJ:i:255" */
 	if (rd->loci) /* -B: on a bubble record the chromosome's header and one or two 64-bit numbers */
 		for (size_t r = r0; r < r1; r++) if (rd->loci[r].bubble >= 0) cap += strlen(rd->bubbles->ann[rd->loci[r].bubble]) + 64;
 	char *o = (char *)malloc(cap ? cap : 1), *o0 = o;
@@ -144,7 +145,7 @@ char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_
 		/* -B: the read's record and POS were resolved with its locus (kernel k_locus for `map`, locus_resolve otherwise) */
 		const int seqid = rd->loci ? rd->loci[r].seqid : ann_find_record(ann, ann_sorted, aln_pos);
 		if (seqid < 0 || seqid >= ann->num_seq) bwb_die("alns2sam: read %zu maps outside every annotated sequence", rd->first + r); /* the reference indexes seq_anns[-1] here */
-		o += sprintf(o, "\t%d\t%s\t%d\t%d\t", strand ? SAM_FSR : 0, ann->seq_anns[seqid].name, rd->loci ? (int)rd->loci[r].pos1 : (int)(aln_pos - ann->seq_anns[seqid].start_index + 1), (int)pl->mapq);
+		o += sprintf(o, "\t%d\t%s\t%d\t%d\t", strand ? SAM_FSR : 0, ann->seq_anns[seqid].name, rd->loci ? (int)rd->loci[r].pos1 : (int)(aln_pos - ann->seq_anns[seqid].start_index + 1), rd->joins ? (int)rd->joins[r].mapq : (int)pl->mapq);
 		o = sam_put_cigar(o, pl->aln_length, pl->gap_run, strand);
 		memcpy(o, "\t*\t0\t0\t", 7); o += 7;
 		if (strand) for (int k = 0; k < len; k++) { const int c = seq[len - 1 - k]; o[k] = "AGCTN"[c > 3 ? 4 : 3 - c]; } /* read->rc */
@@ -166,6 +167,7 @@ char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_
 			}
 		}
 		if (rd->loci && rd->loci[r].bubble >= 0) o = locus_put_tags(o, &rd->loci[r], rd->bubbles); /* last on the line, like sam_pad's */
+		if (rd->joins && rd->joins[r].joined) o += sprintf(o, "\tbJ:i:%d", (int)rd->joins[r].joined); /* -J: behind them */
 		*o++ = '\n';
 	}
 	*out_len = (size_t)(o - o0);
@@ -194,7 +196,17 @@ static bwb_locus *host_loci(const bwb_place *pl, size_t n, const fasta_annotatio
 	return loci;
 }
 
-void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname) {
+/* -J on the host (aln2sam, places2sam): the join record of every read, with all cores */
+static bwb_join *host_joins(const bwb_place *pl, const bwb_locus *loci, const uint64_t *alt_off, const bwb_alt *alts, const uint8_t *alt_sub, size_t n, const fasta_annotations_t *ann,
+                            int ann_sorted, const int32_t *bubble_of, const int32_t *chrom_of, const bubble_table_t *bub, int max_mm) {
+	bwb_join *joins = (bwb_join *)malloc((n ? n : 1) * sizeof(bwb_join));
+#pragma omp parallel for schedule(static) num_threads(bwb_host_team())
+	for (long r = 0; r < (long)n; r++)
+		join_resolve(&pl[r], &loci[r], alts + alt_off[r], alt_sub + alt_off[r], alt_off[r + 1] - alt_off[r], ann, ann_sorted, bubble_of, chrom_of, bub, max_mm, &joins[r]);
+	return joins;
+}
+
+void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join) {
 	(void)is_multiref;
 	printf("**** BWBBLE Alignment Evaluation/SAM File Generation ****\n");
 	size_t Ln = strlen(fastaFname) + 8;
@@ -205,6 +217,7 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 	fasta_annotations_t *ann = annf2ann(annFname);
 	bubble_table_t *bub = bubbleFname ? load_bubbles(bubbleFname) : NULL; /* (refused tables stop the run before the SAM file exists) */
 	int32_t *bubble_of = bub ? ann_bubble_of(ann, bub) : NULL;
+	int32_t *chrom_of = join ? bubble_chrom_of(ann, bubble_of, bub) : NULL; /* -J (main.c: only with -X and -B) */
 	alns_batch_t *alns = alnsf2alns_bin(alnsFname);
 	reads_t *reads = fastq2reads(readsFname);
 	FILE *sam = fopen(samFname, "w");
@@ -273,9 +286,16 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 		place_from_alns(alns->alns + alns->aln_off[r], alns->aln_off[r + 1] - alns->aln_off[r], ref_pos[r], BWT->length, max_diff, &pl[r]);
 	const int ann_sorted = sam_ann_sorted(ann);
 	bwb_locus *loci = bub ? host_loci(pl, n, ann, ann_sorted, bubble_of, bub) : NULL;
+	uint8_t *alt_sub = NULL; /* -J: an item is suboptimal when its hit's score is greater than the first hit's (align.c:771-779) */
+	if (join) {
+		alt_sub = (uint8_t *)malloc(n_alt ? n_alt : 1);
+		for (size_t r = 0; r < n; r++)
+			for (uint64_t q = alt_off[r]; q < alt_off[r + 1]; q++) alt_sub[q] = alns->alns[alns->aln_off[r] + alts[q].hit].score > alns->alns[alns->aln_off[r]].score;
+	}
+	bwb_join *joins = join ? host_joins(pl, loci, alt_off, alts, alt_sub, n, ann, ann_sorted, bubble_of, chrom_of, bub, max_diff) : NULL;
 	const sam_reads_t rd = { .pl = pl, .seq = reads->seq, .stride = reads->stride, .len = reads->len, .text = reads->raw,
 	                         .name_off = reads->name_off, .qual_off = reads->qual_off, .name_len = reads->name_len, .first = 0,
-	                         .alt_off = alt_off, .alts = alts, .loci = loci, .bubbles = bub };
+	                         .alt_off = alt_off, .alts = alts, .loci = loci, .bubbles = bub, .joins = joins };
 	/* The text: blocks of reads are formatted into memory by all cores and written in order (round 5: one thread's fprintf calls were
 	 * the wall time of aln2sam on a 10 M-read file, not the SA lookups). */
 	const size_t BLK = SAM_BLOCK_READS;
@@ -296,6 +316,7 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 		}
 	}
 	free(pl); free(alt_off); free(alts); free(loci); free(bubble_of); free_bubbles(bub);
+	free(alt_sub); free(joins); free(chrom_of);
 	free(bufs); free(lens);
 	printf("Processed %zu reads.\n", n);
 	free(rows); free(pos); free(which); free(ref_pos);
@@ -305,14 +326,15 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 }
 
 /* developer command (CPU only, for the tests): raw bwb_place records from a file through sam_format_reads - the formatter `map` uses, on a
- * machine without a GPU (bubbleFname: -B, the loci from the host resolver) */
-void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname) {
+ * machine without a GPU (bubbleFname: -B, the loci from the host resolver; join: -J, the join records from the host's rule) */
+void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join) {
 	size_t Ln = strlen(fastaFname) + 8;
 	char *annFname = (char *)malloc(Ln);
 	snprintf(annFname, Ln, "%s.ann", fastaFname);
 	fasta_annotations_t *ann = annf2ann(annFname);
 	bubble_table_t *bub = bubbleFname ? load_bubbles(bubbleFname) : NULL;
 	int32_t *bubble_of = bub ? ann_bubble_of(ann, bub) : NULL;
+	int32_t *chrom_of = join ? bubble_chrom_of(ann, bubble_of, bub) : NULL; /* -J (main.c: only with -B and an items file) */
 	reads_t *reads = fastq2reads(readsFname);
 	FILE *pf = fopen(placesFname, "rb");
 	if (!pf) { perror(placesFname); bwb_die("places2sam: Cannot open the placements file: %s!", placesFname); }
@@ -323,6 +345,7 @@ void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *sam
 	/* optional: u64 alt_off[n + 1], then alt_off[n] bwb_alt records (what slot_place_alt returns) - the X tags */
 	uint64_t *alt_off = NULL;
 	bwb_alt *alts = NULL;
+	uint8_t *alt_sub = NULL; /* -J: behind the records, one byte per item - not zero: the item is suboptimal */
 	if (altsFname) {
 		FILE *af = fopen(altsFname, "rb");
 		if (!af) { perror(altsFname); bwb_die("places2sam: Cannot open the alternatives file: %s!", altsFname); }
@@ -331,6 +354,10 @@ void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *sam
 		for (size_t r = 0; r < n; r++) if (alt_off[r + 1] < alt_off[r]) bwb_die("places2sam: %s: the offsets do not ascend", altsFname);
 		alts = (bwb_alt *)malloc((alt_off[n] ? alt_off[n] : 1) * sizeof(bwb_alt));
 		if (alt_off[0] != 0 || fread(alts, sizeof(bwb_alt), alt_off[n], af) != alt_off[n]) bwb_die("places2sam: %s does not hold the records its offsets name", altsFname);
+		if (join) {
+			alt_sub = (uint8_t *)malloc(alt_off[n] ? alt_off[n] : 1);
+			if (fread(alt_sub, 1, alt_off[n], af) != alt_off[n]) bwb_die("places2sam: %s does not hold one suboptimal byte per item behind its records (-J)", altsFname);
+		}
 		fclose(af);
 	}
 	FILE *sam = fopen(samFname, "w");
@@ -338,9 +365,10 @@ void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *sam
 	sam_write_header(sam, ann);
 	const int ann_sorted = sam_ann_sorted(ann);
 	bwb_locus *loci = bub ? host_loci(pl, n, ann, ann_sorted, bubble_of, bub) : NULL;
+	bwb_join *joins = join ? host_joins(pl, loci, alt_off, alts, alt_sub, n, ann, ann_sorted, bubble_of, chrom_of, bub, 6) : NULL; /* (aln2sam's default -n: the records carry no max_mm) */
 	const sam_reads_t rd = { .pl = pl, .seq = reads->seq, .stride = reads->stride, .len = reads->len, .text = reads->raw,
 	                         .name_off = reads->name_off, .qual_off = reads->qual_off, .name_len = reads->name_len, .first = 0,
-	                         .alt_off = alt_off, .alts = alts, .loci = loci, .bubbles = bub };
+	                         .alt_off = alt_off, .alts = alts, .loci = loci, .bubbles = bub, .joins = joins };
 	for (size_t r0 = 0; r0 < n; r0 += SAM_BLOCK_READS) {
 		size_t len = 0;
 		char *buf = sam_format_reads(&rd, r0, r0 + SAM_BLOCK_READS < n ? r0 + SAM_BLOCK_READS : n, ann, ann_sorted, &len);
@@ -349,6 +377,7 @@ void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *sam
 	}
 	printf("Processed %zu reads.\n", n);
 	free(pl); free(annFname); free(alt_off); free(alts); free(loci); free(bubble_of); free_bubbles(bub);
+	free(alt_sub); free(joins); free(chrom_of);
 	free_reads(reads); free_ann(ann);
 	fclose(sam);
 }

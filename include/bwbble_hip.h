@@ -301,6 +301,42 @@ int bwb_hip_locus_places(bwb_hip_ctx *ctx, const bwb_place *places, uint32_t n, 
 /* the last locus call on the context: reads resolved and the kernel's HIP-event time (any pointer may be NULL) */
 int bwb_hip_locus_stats(bwb_hip_ctx *ctx, uint64_t *reads, double *kernel_ms);
 
+/* A read's placements counted by LOCUS (`bwbble map -X N -B table -J`).  A read beside an indel site lies twice in a multi-genome's text - in
+ * the chromosome and in a flank of the `>bubbleN` record that copies it - and eval_aln counts two placements (MAPQ 0).  A PLACEMENT is the
+ * primary (bwb_place) or one of the read's items (bwb_alt).  Its locus is (c, s, lo, hi): s the BWB_PLACE_REVERSE bit; on a non-bubble
+ * record i, c = i and lo = hi = the position SAM prints (bwb_locus.pos1, widened to 64 bits); on a record of bubble b, c = chrom_of[b] and
+ * lo .. hi = ref_lo .. ref_hi of bwb_locus; an unmapped placement or one in no record has no locus.  With hi' = max(hi, lo) - the empty range of
+ * a pure insertion counts as its left edge - an item is JOINED to the primary when both have a locus, c and s are equal, and
+ * lo_item <= hi'_primary && lo_primary <= hi'_item (signed 64-bit).  Items are compared with the primary only.  An item is SUBOPTIMAL when
+ * its hit's score is greater than the first hit's (the comparison of eval_aln, align.c:771-779).  Per read:
+ *     joined = the number of joined items
+ *     top1   = bwb_place.top1 - (joined items that are not suboptimal),  top2 = bwb_place.top2 - (joined suboptimal items)  (32-bit, wrapping)
+ *     mapq   = the reference's formula (align.c:738-746) on these counts
+ * A read without items keeps top1, top2 and mapq of its bwb_place verbatim; an unmapped read is all zero.  Two kernels behind k_place_alt and
+ * k_locus on the result stream: k_join_items (one lane per item: its locus, compared with the primary's; one class byte) and k_join_reads
+ * (one lane per read: the sums of its class bytes, one 16-byte record).  (Added without a version change: no structure or existing entry
+ * point changed.) */
+typedef struct { int32_t top1, top2; uint8_t mapq, joined; uint16_t reserved; uint32_t reserved2; } bwb_join; /* 16 bytes */
+/* After set_loci: the .ann record of the chromosome every bubble lies on.  BWB_E_STATE without set_loci; BWB_E_ARG when n_bub is not set_loci's,
+ * or a value lies outside 0 .. n_seq - 1 or names a bubble record.  set_loci forgets it. */
+int bwb_hip_set_bubble_chrom(bwb_hip_ctx *ctx, const int32_t *chrom_of, uint32_t n_bub);
+/* slot_place_alt and slot_locus (or their cached records), then the two kernels over what they left in device memory, and D2H of n_reads join
+ * records in read order into pinned memory of the slot, valid until the slot is uploaded again.  The same records whether it is called before
+ * or after slot_place_alt / slot_locus / slot_result.  BWB_E_ARG for max_alt outside 1..255; BWB_E_STATE without set_sa, set_loci or
+ * set_bubble_chrom, or on a slot that has not been submitted; the context stays usable after each.  batch_join is the one-batch form. */
+int bwb_hip_slot_join(bwb_hip_ctx *ctx, int slot, int max_mm, int max_alt, const bwb_place **places, const uint64_t **alt_off,
+                      const bwb_alt **alts, const bwb_locus **loci, const bwb_join **joins, uint32_t *n_reads);
+int bwb_hip_batch_join(bwb_hip_ctx *ctx, int max_mm, int max_alt, const bwb_place **places, const uint64_t **alt_off,
+                       const bwb_alt **alts, const bwb_locus **loci, const bwb_join **joins, uint32_t *n_reads);
+/* The same kernels (and k_locus) on records of the caller's: read r owns alts[alt_off[r] .. alt_off[r + 1]), at most 255 of them, alt_off[0] == 0;
+ * alt_sub[q] != 0 says that item q is suboptimal.  n join records go to out.  Needs set_loci and set_bubble_chrom; touches no slot; locus_stats
+ * then reports its k_locus launch.  BWB_E_ARG when alt_off does not fit that description.  For parity tests. */
+int bwb_hip_join_records(bwb_hip_ctx *ctx, const bwb_place *places, uint32_t n, const uint64_t *alt_off, const bwb_alt *alts,
+                         const uint8_t *alt_sub, int max_mm, bwb_join *out);
+/* the last join call on the context that launched the kernels: items compared, items joined and the two kernels' HIP-event time (any pointer
+ * may be NULL).  A slot_join that returns the slot's cached records launches nothing and leaves these figures as they were. */
+int bwb_hip_join_stats(bwb_hip_ctx *ctx, uint64_t *items, uint64_t *joined, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
