@@ -26,6 +26,7 @@ EXPORTS = [
     "bwb_hip_slot_place_alt", "bwb_hip_batch_place_alt", "bwb_hip_place_alt_stats", "bwb_hip_place_hits_alt",
     "bwb_hip_set_loci", "bwb_hip_slot_locus", "bwb_hip_batch_locus", "bwb_hip_locus_places", "bwb_hip_locus_stats",
     "bwb_hip_set_bubble_chrom", "bwb_hip_slot_join", "bwb_hip_batch_join", "bwb_hip_join_records", "bwb_hip_join_stats",
+    "bwb_hip_slot_lift", "bwb_hip_batch_lift", "bwb_hip_lift_records", "bwb_hip_lift_stats",
 ]
 ABI_VERSION = 3  # BWB_HIP_ABI_VERSION (include/bwbble_hip.h)
 MAX_SLOTS = 8  # BWB_MAX_SLOTS
@@ -74,6 +75,11 @@ LOCUS_POINT, LOCUS_RANGE = 1, 2
 # bwb_join: a read's counts and MAPQ once the placements that lie where its primary lies are counted as one (kernels k_join_items / k_join_reads)
 JOIN_DTYPE = np.dtype([("top1", "<i4"), ("top2", "<i4"), ("mapq", "u1"), ("joined", "u1"), ("reserved", "<u2"), ("reserved2", "<u4")])
 assert JOIN_DTYPE.itemsize == 16
+# bwb_lift: the header of a lifted placement's record (kernels k_lift_count / k_lift); n_ops ops follow as uint32 = len << 4 | op, zero-padded to four
+LIFT_DTYPE = np.dtype([("pos", "<i8"), ("seqid", "<i4"), ("n_ops", "u1"), ("reserved", "u1", (3,))])
+assert LIFT_DTYPE.itemsize == 16
+LIFT_M, LIFT_I, LIFT_D, LIFT_S, LIFT_MAX_OPS = 0, 1, 2, 4, 20
+LIFT_NONE, LIFT_LIFTED, LIFT_UNLIFTABLE = 0, 1, 2
 
 _FLAG = {"-M": "mm_score", "-O": "gapo_score", "-E": "gape_score", "-n": "max_diff", "-k": "max_diff_seed",
          "-o": "max_gapo", "-e": "max_gape", "-l": "seed_length", "-m": "max_entries", "-t": "n_threads"}
@@ -141,6 +147,10 @@ def lib():
         L.bwb_hip_batch_join.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_void_p)] * 5 + [C.POINTER(C.c_uint32)]
         L.bwb_hip_join_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.bwb_hip_join_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.bwb_hip_slot_lift.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(C.c_uint64)]
+        L.bwb_hip_batch_lift.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(C.c_uint64)]
+        L.bwb_hip_lift_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p] + [C.POINTER(C.c_void_p)] * 3
+        L.bwb_hip_lift_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -452,7 +462,7 @@ class Context:
 
     # -- a read's placements counted by locus (-J): one JOIN_DTYPE record per read (needs set_loci and set_bubble_chrom; the slot forms set_sa) --
     def set_bubble_chrom(self, chrom_of):
-        """after set_loci: the .ann record of the chromosome every bubble lies on (see bubble_chrom_of())"""
+        """after set_loci: the .ann record of the chromosome every bubble lies on (see bubble_chrom_of()); for join() and lift()"""
         chrom_of = np.ascontiguousarray(chrom_of, dtype=np.int32)
         _chk(lib().bwb_hip_set_bubble_chrom(self._h, chrom_of.ctypes.data, len(chrom_of)))
 
@@ -487,6 +497,46 @@ class Context:
     def join_stats(self):
         """(items, joined items, kernel ms) of the last join call"""
         return self._count_steps_ms(lib().bwb_hip_join_stats)
+
+    # -- placements on bubble records in chromosome coordinates (-R): per placement a kind byte, and for a lifted one a record (needs set_loci and
+    #    set_bubble_chrom; the slot forms set_sa).  Placement q < n_reads is read q's primary, n_reads + j is item j --
+    @staticmethod
+    def _lifted(p, nq):
+        kinds = np.frombuffer(C.string_at(p[0], nq), dtype=np.uint8).copy() if nq else np.zeros(0, dtype=np.uint8)
+        off = np.frombuffer(C.string_at(p[1], (nq + 1) * 8), dtype=np.uint64).copy()
+        words = int(off[-1])
+        recs = np.frombuffer(C.string_at(p[2], words * 16), dtype=np.uint32).copy() if words else np.zeros(0, dtype=np.uint32)
+        return kinds, off, recs.reshape(-1, 4)
+
+    def slot_lift(self, slot, max_mm=6, max_alt=5):
+        """(kinds, lift_off, words): the kind byte of every placement of the slot, and the 16-byte words of the lifted ones' records as rows of
+        four uint32 - see lift_record().  max_alt 0: the primaries alone"""
+        p = [C.c_void_p() for _ in range(3)]
+        nq = C.c_uint64()
+        _chk(lib().bwb_hip_slot_lift(self._h, slot, max_mm, max_alt, *[C.byref(x) for x in p], C.byref(nq)))
+        return self._lifted(p, nq.value)
+
+    def lift(self, max_mm=6, max_alt=5):
+        """the same for the one-batch interface (after run() / align())"""
+        p = [C.c_void_p() for _ in range(3)]
+        nq = C.c_uint64()
+        _chk(lib().bwb_hip_batch_lift(self._h, max_mm, max_alt, *[C.byref(x) for x in p], C.byref(nq)))
+        return self._lifted(p, nq.value)
+
+    def lift_records(self, places, alt_off, alts):
+        """the same kernels on records of the caller's: read r owns alts[alt_off[r]:alt_off[r + 1]]"""
+        places = np.ascontiguousarray(places, dtype=PLACE_DTYPE)
+        alt_off = np.ascontiguousarray(alt_off, dtype=np.uint64)
+        alts = np.ascontiguousarray(alts, dtype=ALT_DTYPE)
+        if len(alt_off) != len(places) + 1 or len(alts) != int(alt_off[-1]):
+            raise ValueError("alt_off must have one entry per read and one more, alts one per item")
+        p = [C.c_void_p() for _ in range(3)]
+        _chk(lib().bwb_hip_lift_records(self._h, places.ctypes.data, len(places), alt_off.ctypes.data, alts.ctypes.data, *[C.byref(x) for x in p]))
+        return self._lifted(p, len(places) + len(alts))
+
+    def lift_stats(self):
+        """(placements lifted, placements not liftable, kernel ms) of the last lift call"""
+        return self._count_steps_ms(lib().bwb_hip_lift_stats)
 
     def dtab_info(self):
         """the context's calculate_d table: {K (0: none), build seconds, bytes}"""
@@ -543,7 +593,7 @@ def bubble_of(names, n_bubbles):
 
 
 def bubble_chrom_of(names, anns):
-    """the .ann record of the chromosome every bubble lies on (-J): the one record whose name's first word is the first word of the bubble's
+    """the .ann record of the chromosome every bubble lies on (-J, -R): the one record whose name's first word is the first word of the bubble's
     header line in bubble.data (anns, see read_bubble_data()); none, several, or a bubble record is an error, as in the host tools"""
     word = lambda t: t.split()[0] if t.split() else ""
     by_word = {}
@@ -557,6 +607,13 @@ def bubble_chrom_of(names, anns):
             raise ValueError(f"bubble {b} ({a!r}): {len(hits)} records are named {w!r}" if len(hits) != 1 else f"bubble {b} ({a!r}): record {hits[0]} is itself a bubble record")
         out[b] = hits[0]
     return out
+
+
+def lift_record(words, off):
+    """(pos, seqid, [(len, op), ...]) of the record that starts at 16-byte word `off` of slot_lift's words"""
+    hdr = words[int(off)].view(LIFT_DTYPE)[0]
+    ops = words[int(off) + 1:int(off) + 1 + (int(hdr["n_ops"]) + 3) // 4].reshape(-1)[:int(hdr["n_ops"])]
+    return int(hdr["pos"]), int(hdr["seqid"]), [(int(v) >> 4, int(v) & 15) for v in ops]
 
 
 _BASE_LUT = np.full(256, 4, dtype=np.uint8)  # ASCII -> read->seq code (io.h:112-130): A0 G1 C2 T3 in either case, anything else 4

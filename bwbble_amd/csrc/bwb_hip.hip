@@ -100,6 +100,13 @@ struct AltBufs {
 	PinMem h_off, h_alts;
 };
 
+/* the buffers of one lift call: the kind byte and record size of every placement, the sizes' exclusive scan and its block sums, the records; and
+ * what the host gets */
+struct LiftBufs {
+	DevMem d_kind, d_cnt, d_off, d_bsum, d_recs;
+	PinMem h_kind, h_off, h_recs;
+};
+
 /* per-lane scratch of one class (class 0 = every resident lane, classes 1/2 = fewer lanes with larger lists) */
 struct ScratchClass {
 	DevMem mem;
@@ -129,6 +136,8 @@ struct Slot {
 	DevMem d_cls, d_join;         /* bwb_hip_slot_join: one class byte per item, one bwb_join per read */
 	PinMem h_join;
 	int join_mm = -1, join_alt = -1; /* h_join holds the records for this max_mm and max_alt (-1: none) */
+	LiftBufs lift;                /* bwb_hip_slot_lift */
+	int lift_mm = -1, lift_alt = -1; /* lift holds the records for this max_mm and max_alt (-1: none) */
 	std::vector<uint8_t> h_status;
 	std::vector<uint64_t> h_aln_off;
 	std::vector<bwb_aln> h_alns;
@@ -184,6 +193,9 @@ struct bwb_hip_ctx {
 	uint32_t loci_nbub = 0;
 	DevMem d_chrom; bool chrom_set = false;       /* k_join_items: the chromosome record of every bubble (bwb_hip_set_bubble_chrom) */
 	double join_ms = 0; uint64_t join_items = 0, join_joined = 0; /* the last join call */
+	std::string lift_refusal;                     /* set_loci: why the rule of bwb_lift refuses the bubble table (empty: it does not) */
+	LiftBufs lift_rec;                            /* bwb_hip_lift_records */
+	double lift_ms = 0; uint64_t lift_lifted = 0, lift_unliftable = 0; /* the last lift call */
 	bool force_slices = false;          /* BWB_FORCE_SLICES: the one-batch API parks and resumes too (tests) */
 	bool dbg = false, dbg_iters = false;
 	const char *launch_log = nullptr;   /* BWB_LAUNCH_LOG=<file>: one JSON line per class-0 kernel launch (synchronises after every launch: a profiling aid) */
@@ -756,7 +768,7 @@ extern "C" int bwb_hip_slot_upload(bwb_hip_ctx *c, int si, const bwb_params *p, 
 	/* (pageable source: the runtime stages it before returning, so h_descs may change again right away) */
 	HIPCHK(hipMemcpyAsync(c->d_descs.as<SlotDesc>() + si, &d, sizeof(SlotDesc), hipMemcpyHostToDevice, c->cstream));
 	HIPCHK(hipEventRecord(s.ev_up.e, c->cstream));
-	s.uploaded = true; s.submitted = false; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.join_mm = -1;
+	s.uploaded = true; s.submitted = false; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.join_mm = -1; s.lift_mm = -1;
 	return ensure_class(c, 0);
 }
 
@@ -1004,7 +1016,7 @@ static int submit(bwb_hip_ctx *c, int si, bool suspend) {
 		HIPCHK(hipStreamWaitEvent(c->stream, s.ev_calcd.e, 0));
 	}
 	HIPCHK(hipMemsetAsync(s.d_ctl.p, 0, 256, c->stream));
-	s.submitted = true; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.join_mm = -1; s.launch = 0;
+	s.submitted = true; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.join_mm = -1; s.lift_mm = -1; s.launch = 0;
 	if (s.n_reads == 0) { s.complete = true; s.launch = c->n_launches; return BWB_OK; }
 	HIPCHK(hipMemsetAsync(s.d_n.p, 0, (size_t)s.n_reads * 4, c->stream));
 	if (!ahead) {
@@ -1714,6 +1726,17 @@ extern "C" int bwb_hip_place_alt_stats(bwb_hip_ctx *c, uint64_t *items, uint64_t
 /* ---- bubble hits in reference coordinates: bwb_locus records (k_locus) ---------------------------------------------------------- */
 static_assert(sizeof(bwb_locus) == 32, "bwb_locus is two 16-byte words (k_locus)");
 static_assert(sizeof(bwb_bubble) == 40, "bwb_bubble is five 64-bit words (k_locus)");
+/* empty, or the first bubble the rule of bwb_lift refuses and why (bwb_hip_slot_lift answers BWB_E_ARG with it; -B and -J take any table) */
+static std::string lift_table_refusal(const bwb_bubble *bubbles, uint32_t n_bub) {
+	for (uint32_t k = 0; k < n_bub; k++) {
+		const bwb_bubble &b = bubbles[k];
+		const __int128 gap = (__int128)b.C - (__int128)b.A - (__int128)b.B_minus_A;
+		const char *why = b.B_minus_A < 0 ? "B_minus_A is negative" : b.D_minus_C < -1 ? "D_minus_C is below -1" : b.alt_len < 0 ? "alt_len is negative" :
+		                  gap < 0 ? "its flanks overlap on the chromosome (C - A - B_minus_A is negative)" : gap >= ((__int128)1 << 28) ? "its flanks lie 2^28 positions or more apart" : nullptr;
+		if (why) return "bubble " + std::to_string(k) + ": " + why;
+	}
+	return std::string();
+}
 extern "C" int bwb_hip_set_loci(bwb_hip_ctx *c, const uint64_t *start, const uint64_t *end, const int32_t *bubble_of, uint32_t n_seq, const bwb_bubble *bubbles, uint32_t n_bub) {
 	if (!c || !start || !end || !bubble_of || (n_bub && !bubbles)) return fail(BWB_E_ARG, "set_loci: null argument");
 	if (n_seq < 1 || n_seq > 0x7FFFFFFFu || n_bub > 0x7FFFFFFFu) return fail(BWB_E_ARG, "set_loci: the number of records must be 1 .. 2^31 - 1");
@@ -1725,7 +1748,8 @@ extern "C" int bwb_hip_set_loci(bwb_hip_ctx *c, const uint64_t *start, const uin
 	HIPCHK(hipSetDevice(c->device));
 	c->loci_nseq = 0; /* (no tables until all four are resident) */
 	c->chrom_set = false;
-	for (auto &s : c->slots) { s.locus_mm = -1; s.join_mm = -1; }
+	for (auto &s : c->slots) { s.locus_mm = -1; s.join_mm = -1; s.lift_mm = -1; }
+	c->lift_refusal = lift_table_refusal(bubbles, n_bub);
 	HIPCHK(c->d_lstart.alloc((size_t)n_seq * 8));
 	HIPCHK(c->d_lend.alloc((size_t)n_seq * 8));
 	HIPCHK(c->d_lbub.alloc((size_t)n_seq * 4));
@@ -1824,7 +1848,7 @@ extern "C" int bwb_hip_set_bubble_chrom(bwb_hip_ctx *c, const int32_t *chrom_of,
 			                           std::to_string(c->loci_nseq) + " records");
 	HIPCHK(hipSetDevice(c->device));
 	c->chrom_set = false;
-	for (auto &s : c->slots) s.join_mm = -1;
+	for (auto &s : c->slots) { s.join_mm = -1; s.lift_mm = -1; }
 	HIPCHK(c->d_chrom.alloc((size_t)n_bub * 4));
 	if (n_bub) {
 		HIPCHK(hipMemcpyAsync(c->d_chrom.p, chrom_of, (size_t)n_bub * 4, hipMemcpyHostToDevice, c->rstream));
@@ -1947,6 +1971,139 @@ extern "C" int bwb_hip_join_stats(bwb_hip_ctx *c, uint64_t *items, uint64_t *joi
 	if (items) *items = c->join_items;
 	if (joined) *joined = c->join_joined;
 	if (kernel_ms) *kernel_ms = c->join_ms;
+	return BWB_OK;
+}
+
+/* ---- placements on bubble records in chromosome coordinates: bwb_lift records (k_lift_count, k_lift) ---------------------------------- */
+static_assert(sizeof(bwb_lift) == 16, "bwb_lift is one 16-byte word (k_lift)");
+static int lift_ready(bwb_hip_ctx *c, const char *who, int max_alt) {
+	if (max_alt < 0 || max_alt > 255) return fail(BWB_E_ARG, std::string(who) + ": max_alt must be 0..255");
+	if (!c->loci_nseq) return fail(BWB_E_STATE, std::string(who) + ": record and bubble tables not uploaded (bwb_hip_set_loci)");
+	if (!c->chrom_set) return fail(BWB_E_STATE, std::string(who) + ": the bubbles' chromosome records not uploaded (bwb_hip_set_bubble_chrom)");
+	if (!c->lift_refusal.empty()) return fail(BWB_E_ARG, std::string(who) + ": " + c->lift_refusal);
+	return BWB_OK;
+}
+/* k_lift_count, the scan and k_lift over n placement records, their locus records and n_items items (all device memory) -> lb.h_kind[n + n_items],
+ * lb.h_off[n + n_items + 1] and lb.h_recs[h_off[last]]; sets the context's lift_ms / lift_lifted / lift_unliftable.  On the result stream, behind
+ * the kernels that wrote the records.  The only host round trip is the read of the total, which sizes the record buffers: they hold the records
+ * there are.  Shared by slot_lift and lift_records. */
+static int lift_launch(bwb_hip_ctx *c, const char *who, const uint4 *d_places, uint32_t n, const uint4 *d_loci, const uint4 *d_alts, uint64_t n_items, LiftBufs &lb) {
+	c->lift_ms = 0; c->lift_lifted = 0; c->lift_unliftable = 0;
+	const uint64_t n_q = (uint64_t)n + n_items;
+	if (n_q > 0x7FFFFFFFu) return fail(BWB_E_ARG, std::string(who) + ": more than 2^31 - 1 placements");
+	HIPCHK(lb.h_off.reserve(((size_t)n_q + 1) * 8));
+	HIPCHK(lb.h_kind.reserve((size_t)n_q));
+	HIPCHK(lb.h_recs.reserve(sizeof(bwb_lift)));
+	lb.h_off.as<uint64_t>()[0] = 0;
+	if (!n_q) return BWB_OK;
+	const unsigned nblk = (unsigned)((n_q + BWB_BLOCK - 1) / BWB_BLOCK);
+	const unsigned grid = (unsigned)std::min<size_t>(nblk, (size_t)c->num_cu * 8);
+	HIPCHK(lb.d_kind.reserve((size_t)n_q));
+	HIPCHK(lb.d_cnt.reserve((size_t)n_q * 4));
+	HIPCHK(lb.d_off.reserve(((size_t)n_q + 1) * 8));
+	HIPCHK(lb.d_bsum.reserve((size_t)nblk * 8));
+	uint64_t *d_off = lb.d_off.as<uint64_t>();
+	Timed t_count(c, c->rstream), t_lift(c, c->rstream); /* k_lift_count and the scan; k_lift */
+	RC(t_count.begin());
+	hipLaunchKernelGGL(k_lift_count, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, d_places, n, d_loci, d_alts, n_q, c->d_lstart.as<uint64_t>(), c->d_lend.as<uint64_t>(),
+	                   c->d_lbub.as<int32_t>(), c->loci_nseq, c->loci_trips, c->d_bubbles.as<uint64_t>(), lb.d_kind.as<uint8_t>(), lb.d_cnt.as<uint32_t>());
+	hipLaunchKernelGGL(k_scan_blocks, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, lb.d_cnt.as<uint32_t>(), (uint32_t)n_q, d_off, lb.d_bsum.as<uint64_t>());
+	hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(BWB_BLOCK), 0, c->rstream, lb.d_bsum.as<uint64_t>(), (uint32_t)nblk, d_off + n_q);
+	hipLaunchKernelGGL(k_scan_add, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, d_off, (uint32_t)n_q, lb.d_bsum.as<uint64_t>());
+	HIPCHK(hipGetLastError());
+	RC(t_count.end());
+	HIPCHK(hipMemcpyAsync(lb.h_off.p, d_off, ((size_t)n_q + 1) * 8, hipMemcpyDeviceToHost, c->rstream));
+	HIPCHK(hipMemcpyAsync(lb.h_kind.p, lb.d_kind.p, (size_t)n_q, hipMemcpyDeviceToHost, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	const uint64_t total = lb.h_off.as<uint64_t>()[n_q];
+	float ms = 0, ms2 = 0;
+	RC(t_count.ms(&ms));
+	if (total) {
+		HIPCHK(lb.d_recs.reserve((size_t)total * sizeof(bwb_lift)));
+		HIPCHK(lb.h_recs.reserve((size_t)total * sizeof(bwb_lift)));
+		RC(t_lift.begin());
+		hipLaunchKernelGGL(k_lift, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, d_places, n, d_loci, d_alts, n_q, c->d_lstart.as<uint64_t>(), c->d_lend.as<uint64_t>(),
+		                   c->d_lbub.as<int32_t>(), c->loci_nseq, c->loci_trips, c->d_bubbles.as<uint64_t>(), c->d_chrom.as<int32_t>(), lb.d_kind.as<uint8_t>(), (const uint64_t *)d_off,
+		                   lb.d_recs.as<uint4>());
+		HIPCHK(hipGetLastError());
+		RC(t_lift.end());
+		HIPCHK(hipMemcpyAsync(lb.h_recs.p, lb.d_recs.p, (size_t)total * sizeof(bwb_lift), hipMemcpyDeviceToHost, c->rstream));
+		HIPCHK(hipStreamSynchronize(c->rstream));
+		RC(t_lift.ms(&ms2));
+	}
+	c->lift_ms = (double)ms + ms2;
+	const uint8_t *kind = lb.h_kind.as<uint8_t>();
+	for (uint64_t q = 0; q < n_q; q++) { c->lift_lifted += kind[q] == BWB_LIFT_LIFTED; c->lift_unliftable += kind[q] == BWB_LIFT_UNLIFTABLE; }
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_slot_lift(bwb_hip_ctx *c, int si, int max_mm, int max_alt, const uint8_t **kinds, const uint64_t **lift_off, const bwb_lift **recs, uint64_t *n_placements) {
+	if (!c || !kinds || !lift_off || !recs || !n_placements || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_lift: bad argument");
+	RC(lift_ready(c, "slot_lift", max_alt));
+	/* (both wait for the slot, refuse what slot_place refuses, and leave their records in the slot's device memory) */
+	const bwb_place *places = nullptr;
+	const uint64_t *alt_off = nullptr;
+	const bwb_alt *alts = nullptr;
+	const bwb_locus *loci = nullptr;
+	uint32_t n = 0;
+	if (max_alt) RC(bwb_hip_slot_place_alt(c, si, max_mm, max_alt, &places, &alt_off, &alts, &n));
+	RC(bwb_hip_slot_locus(c, si, max_mm, &places, &loci, &n));
+	Slot &s = c->slots[si];
+	n = s.n_reads;
+	const uint64_t n_items = max_alt && n ? alt_off[n] : 0;
+	if (s.lift_mm != max_mm || s.lift_alt != max_alt || !n) {
+		RC(lift_launch(c, "slot_lift", s.d_place.as<uint4>(), n, s.d_locus.as<uint4>(), s.alt.d_alts.as<uint4>(), n_items, s.lift));
+		s.lift_mm = max_mm; s.lift_alt = max_alt;
+	}
+	*kinds = s.lift.h_kind.as<uint8_t>();
+	*lift_off = s.lift.h_off.as<uint64_t>();
+	*recs = s.lift.h_recs.as<bwb_lift>();
+	*n_placements = (uint64_t)n + n_items;
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_batch_lift(bwb_hip_ctx *c, int max_mm, int max_alt, const uint8_t **kinds, const uint64_t **lift_off, const bwb_lift **recs, uint64_t *n_placements) {
+	if (!c || !kinds || !lift_off || !recs || !n_placements) return fail(BWB_E_ARG, "batch_lift: null argument");
+	RC(lift_ready(c, "batch_lift", max_alt));
+	if (!c->d_SA.p) return fail(BWB_E_STATE, "batch_lift: sampled SA not uploaded (bwb_hip_set_sa)");
+	if (!c->slots[0].submitted || !c->slots[0].complete) return fail(BWB_E_STATE, "batch_lift: batch_run has not completed");
+	return bwb_hip_slot_lift(c, 0, max_mm, max_alt, kinds, lift_off, recs, n_placements);
+}
+
+/* the kernels on records of the caller's instead of a slot's (for parity tests): k_locus for the primaries' loci, then the lift kernels */
+extern "C" int bwb_hip_lift_records(bwb_hip_ctx *c, const bwb_place *places, uint32_t n, const uint64_t *alt_off, const bwb_alt *alts, const uint8_t **kinds,
+                                    const uint64_t **lift_off, const bwb_lift **recs) {
+	if (!c || !alt_off || !kinds || !lift_off || !recs || (n && !places) || n > 0x7FFFFFFFu) return fail(BWB_E_ARG, "lift_records: bad argument");
+	RC(lift_ready(c, "lift_records", 1));
+	if (alt_off[0] != 0) return fail(BWB_E_ARG, "lift_records: alt_off[0] must be 0");
+	for (uint32_t r = 0; r < n; r++)
+		if (alt_off[r + 1] < alt_off[r]) return fail(BWB_E_ARG, "lift_records: alt_off does not ascend at read " + std::to_string(r));
+	const uint64_t n_items = alt_off[n];
+	if (n_items && !alts) return fail(BWB_E_ARG, "lift_records: null argument");
+	if ((uint64_t)n + n_items > 0x7FFFFFFFu) return fail(BWB_E_ARG, "lift_records: more than 2^31 - 1 placements");
+	HIPCHK(hipSetDevice(c->device));
+	DevMem d_places, d_loci, d_alts;
+	HIPCHK(d_places.alloc((size_t)n * sizeof(bwb_place)));
+	HIPCHK(d_loci.alloc((size_t)n * sizeof(bwb_locus)));
+	HIPCHK(d_alts.alloc((size_t)n_items * sizeof(bwb_alt)));
+	if (n) HIPCHK(hipMemcpyAsync(d_places.p, places, (size_t)n * sizeof(bwb_place), hipMemcpyHostToDevice, c->rstream));
+	if (n_items) HIPCHK(hipMemcpyAsync(d_alts.p, alts, (size_t)n_items * sizeof(bwb_alt), hipMemcpyHostToDevice, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream)); /* (pageable memory of the caller) */
+	std::vector<bwb_locus> h_loci(n ? n : 1);
+	RC(locus_launch(c, d_places.as<uint4>(), n, d_loci.as<uint4>(), h_loci.data()));
+	RC(lift_launch(c, "lift_records", d_places.as<uint4>(), n, d_loci.as<uint4>(), d_alts.as<uint4>(), n_items, c->lift_rec));
+	*kinds = c->lift_rec.h_kind.as<uint8_t>();
+	*lift_off = c->lift_rec.h_off.as<uint64_t>();
+	*recs = c->lift_rec.h_recs.as<bwb_lift>();
+	return BWB_OK;
+}
+
+/* the last lift call: placements lifted, placements on a bubble record that are not liftable, and the kernels' HIP-event time */
+extern "C" int bwb_hip_lift_stats(bwb_hip_ctx *c, uint64_t *lifted, uint64_t *unliftable, double *kernel_ms) {
+	if (!c) return fail(BWB_E_ARG, "lift_stats: null context");
+	if (lifted) *lifted = c->lift_lifted;
+	if (unliftable) *unliftable = c->lift_unliftable;
+	if (kernel_ms) *kernel_ms = c->lift_ms;
 	return BWB_OK;
 }
 

@@ -9,6 +9,7 @@
  *   k_place      eval_aln + mapq for every read of a slot (`bwbble map`): one 48-byte placement record per read
  *   k_locus      the .ann record of every placement record and, on a bubble record, its reference coordinates (`bwbble map -B`)
  *   k_join_items, k_join_reads   a read's other placements that lie where its primary lies, and its MAPQ without them (`bwbble map -J`)
+ *   k_lift_count, k_lift         a placement on a bubble record in the chromosome's coordinates: POS and CIGAR (`bwbble map -R`)
  * The alignment kernels themselves (kl_calc_d, kl_search: one read per lane) are in bwb_lane.h.
  */
 #pragma once
@@ -698,5 +699,154 @@ __global__ __launch_bounds__(BWB_BLOCK) void k_join_reads(const uint4 *places, u
 		const uint32_t mq = q1 > q0 ? place_mapq((int)top1, (int)top2, (int)(p1.y & 0xFFu), max_mm, qtab) : (p1.x >> 16) & 0xFFu;
 		const bool mapped = ((p1.x >> 24) & PLACE_F_MAPPED) != 0;
 		out[r] = mapped ? make_uint4(top1, top2, mq | ((best + subopt) << 8), 0u) : make_uint4(0u, 0u, 0u, 0u);
+	}
+}
+
+/* ---- a placement on a bubble record in chromosome coordinates (`map -B table -R`) ----------------------------------------------------
+ * The rule is in include/bwbble_hip.h (bwb_lift).  One lane per PLACEMENT, grid-strided: q < n_reads is read q's primary - its record, strand
+ * and gap runs from bwb_place, its bubble and printed position from the bwb_locus record k_locus left -, n_reads + j is item j - its locus by
+ * k_locus's search and rule (locus_at, as in k_join_items).  Most placements lie on no bubble record and leave after one load.  The walk
+ * (lift_walk) takes the CIGAR one text position at a time - at most 8 gap runs are compared per position - twice: once for the span and the first
+ * and last M that stays an M, once to emit.  k_lift_count keeps the kind byte and the record's size in 16-byte words; the scan of k_place_alt
+ * turns the sizes into lift_off[]; k_lift walks the lifted placements again and writes header and ops, four ops per store. */
+struct LiftBub { int64_t A, Bm, C, Dm, alt, gap; };
+__device__ __forceinline__ LiftBub lift_bubble(const uint64_t *bub, int32_t b) {
+	const uint64_t *q = bub + (size_t)b * 5;
+	const uint64_t la = q[4];
+	LiftBub v;
+	v.A = (int64_t)q[0]; v.Bm = (int64_t)q[1]; v.C = (int64_t)q[2]; v.Dm = (int64_t)q[3];
+	v.alt = (int64_t)(int32_t)(uint32_t)(la >> 32);
+	v.gap = (int64_t)(q[2] - q[0] - q[1]);
+	return v;
+}
+/* the op of text position t: the path byte the host's aln_path_bytes gives (a later run wins), walked as sam_put_cigar walks it */
+__device__ __forceinline__ uint32_t lift_op_at(const uint4 runs, uint32_t alen, bool reverse, uint32_t t) {
+	const uint32_t p = reverse ? t : alen - 1u - t;
+	const uint32_t rw[4] = { runs.x, runs.y, runs.z, runs.w };
+	uint32_t op = 0;
+#pragma unroll
+	for (int k = 0; k < 8; k++) {
+		const uint32_t run = (rw[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu;
+		if (run != 0xFFFFu && p - (run & 0xFFu) < ((run >> 8) & 0x7Fu)) op = (run >> 15) ? 2u : 1u;
+	}
+	return op;
+}
+__device__ __forceinline__ int lift_zone(const LiftBub &b, int64_t x) { return x <= b.Bm ? 0 : (x - b.Bm <= b.alt ? 1 : 2); }
+/* the ops as they are emitted: merged with their neighbour, four to a 16-byte word (dst NULL: counted only) */
+struct LiftOut {
+	uint4 *dst; uint32_t cap /* 16-byte words at dst */; uint4 w; uint32_t n, kind; uint64_t len;
+	__device__ __forceinline__ void put() {
+		if (kind == 0xFFu) return;
+		if (dst && n < 20u) {
+			const uint32_t v = (uint32_t)(len << 4) | kind, c = n & 3u;
+			w.x = c == 0 ? v : w.x; w.y = c == 1 ? v : w.y; w.z = c == 2 ? v : w.z; w.w = c == 3 ? v : w.w;
+			if (c == 3) { if (1u + (n >> 2) < cap) dst[1 + (n >> 2)] = w; w = make_uint4(0u, 0u, 0u, 0u); }
+		}
+		n++;
+	}
+	__device__ __forceinline__ void emit(uint32_t k, uint64_t l) {
+		if (k == kind && len + l < (1ull << 28)) { len += l; return; }
+		put();
+		kind = k; len = l;
+	}
+};
+/* -> the number of ops, 0: not liftable; with dst the record is written there (header seqid = chrom) */
+__device__ __forceinline__ uint32_t lift_walk(const LiftBub &b, int64_t pos1, bool reverse, uint32_t alen, const uint4 runs, int32_t chrom, uint4 *dst, uint32_t cap) {
+	int64_t x = pos1, first = -1, last = -1, x_first = 0;
+	for (uint32_t t = 0; t < alen; t++) {
+		const uint32_t op = lift_op_at(runs, alen, reverse, t);
+		if (op == 1u) continue;
+		if (op == 0u && x >= 1 && lift_zone(b, x) != 1) { if (first < 0) { first = (int64_t)t; x_first = x; } last = (int64_t)t; }
+		x++;
+	}
+	const int64_t end = x - 1;
+	/* (pos1 < 1: the rule's own condition, as in the host's lift_resolve - locus_at gives a placement on a bubble record pos1 >= 1) */
+	if (pos1 < 1 || first < 0) return 0u;
+	if (end > b.Bm && end - b.Bm > b.alt && end - b.Bm - b.alt - 1 > b.Dm) return 0u;
+	LiftOut o;
+	o.dst = dst; o.cap = cap; o.w = make_uint4(0u, 0u, 0u, 0u); o.n = 0; o.kind = 0xFFu; o.len = 0;
+	uint64_t lead = 0, trail = 0;
+	x = pos1;
+	for (uint32_t t = 0; t < alen; t++) {
+		const uint32_t op = lift_op_at(runs, alen, reverse, t);
+		uint32_t kind = 1u;
+		if (op != 1u) {
+			const int z = lift_zone(b, x);
+			if (z == 2 && x - b.Bm == b.alt + 1 && x > pos1 && b.gap > 0 && (int64_t)t > first && (int64_t)t <= last) o.emit(2u, (uint64_t)b.gap);
+			kind = op == 0u ? (z == 1 ? 1u : 0u) : (z == 1 ? 0xFFu : 2u);
+			x++;
+		}
+		if (kind == 0xFFu) continue;
+		if ((int64_t)t < first) lead += kind == 1u;
+		else if ((int64_t)t > last) trail += kind == 1u;
+		else {
+			if ((int64_t)t == first && lead) o.emit(4u, lead);
+			o.emit(kind, 1);
+		}
+	}
+	o.put();
+	if (trail) { o.kind = 4u; o.len = trail; o.put(); }
+	if (o.n > 20u) return 0u; /* (17 runs and the three the allele adds: not reached) */
+	if (dst) {
+		if ((o.n & 3u) && 1u + (o.n >> 2) < cap) dst[1 + (o.n >> 2)] = o.w;
+		const uint64_t pos = x_first <= b.Bm ? (uint64_t)b.A + (uint64_t)x_first - 1u : (uint64_t)b.C + (uint64_t)(x_first - (b.Bm + b.alt + 1));
+		dst[0] = make_uint4((uint32_t)pos, (uint32_t)(pos >> 32), (uint32_t)chrom, o.n);
+	}
+	return o.n;
+}
+/* placement q: its bubble (-1: none), printed position, strand, path length and gap runs */
+struct LiftPlacement { int32_t b; int64_t pos1; bool reverse; uint32_t alen; uint4 runs; };
+__device__ __forceinline__ LiftPlacement lift_placement(uint64_t q, const uint4 *places, uint32_t n_reads, const uint4 *loci, const uint4 *alts, const uint64_t *start, const uint64_t *end,
+                                                        const int32_t *bubble_of, uint32_t n_seq, uint32_t trips, const uint64_t *bub) {
+	LiftPlacement v;
+	if (q < n_reads) {
+		const uint4 l0 = loci[q * 2];
+		v.b = l0.x != 0xFFFFFFFFu ? (int32_t)l0.z : -1;
+		v.pos1 = (int64_t)(int32_t)l0.y;
+		if (v.b >= 0) {
+			const uint4 p1 = places[q * 3 + 1];
+			v.reverse = ((p1.x >> 24) & PLACE_F_REVERSE) != 0;
+			v.alen = p1.z & 0xFFFFu;
+			v.runs = places[q * 3 + 2];
+		}
+	} else {
+		const uint64_t j = q - n_reads;
+		const uint4 a0 = alts[j * 2];
+		const Locus il = locus_at((uint64_t)a0.x | ((uint64_t)a0.y << 32), (a0.z & PLACE_F_MAPPED) != 0, start, end, bubble_of, n_seq, trips, bub);
+		v.b = il.seqid != 0xFFFFFFFFu ? il.b : -1;
+		v.pos1 = (int64_t)(int32_t)il.pos1;
+		v.reverse = (a0.z & PLACE_F_REVERSE) != 0;
+		v.alen = a0.w >> 16;
+		if (v.b >= 0) v.runs = alts[j * 2 + 1];
+	}
+	return v;
+}
+__global__ __launch_bounds__(BWB_BLOCK) void k_lift_count(const uint4 *places, uint32_t n_reads, const uint4 *loci, const uint4 *alts, uint64_t n_q, const uint64_t *start, const uint64_t *end,
+                                                           const int32_t *bubble_of, uint32_t n_seq, uint32_t trips, const uint64_t *bub, uint8_t *kind, uint32_t *words) {
+	const uint64_t stride = (uint64_t)gridDim.x * BWB_BLOCK;
+	for (uint64_t q = (uint64_t)blockIdx.x * BWB_BLOCK + threadIdx.x; q < n_q; q += stride) {
+		const LiftPlacement v = lift_placement(q, places, n_reads, loci, alts, start, end, bubble_of, n_seq, trips, bub);
+		uint32_t k = 0, wn = 0;
+		if (v.b >= 0) {
+			const uint32_t n_ops = lift_walk(lift_bubble(bub, v.b), v.pos1, v.reverse, v.alen, v.runs, 0, nullptr, 0u);
+			k = n_ops ? 1u : 2u;
+			wn = n_ops ? 1u + ((n_ops + 3u) >> 2) : 0u;
+		}
+		kind[q] = (uint8_t)k;
+		words[q] = wn;
+	}
+}
+__global__ __launch_bounds__(BWB_BLOCK) void k_lift(const uint4 *places, uint32_t n_reads, const uint4 *loci, const uint4 *alts, uint64_t n_q, const uint64_t *start, const uint64_t *end,
+                                                     const int32_t *bubble_of, uint32_t n_seq, uint32_t trips, const uint64_t *bub, const int32_t *chrom_of, const uint8_t *kind,
+                                                     const uint64_t *lift_off, uint4 *out) {
+	const uint64_t stride = (uint64_t)gridDim.x * BWB_BLOCK;
+	for (uint64_t q = (uint64_t)blockIdx.x * BWB_BLOCK + threadIdx.x; q < n_q; q += stride) {
+		if (kind[q] != 1u) continue;
+		const LiftPlacement v = lift_placement(q, places, n_reads, loci, alts, start, end, bubble_of, n_seq, trips, bub);
+		if (v.b < 0) continue;
+		const uint64_t o = lift_off[q];
+		const uint64_t cap = lift_off[q + 1] - o; /* (k_lift_count sized it from the same walk; nothing is stored beyond it) */
+		if (cap < 2u || cap > 6u) continue;
+		lift_walk(lift_bubble(bub, v.b), v.pos1, v.reverse, v.alen, v.runs, chrom_of[v.b], out + o, (uint32_t)cap);
 	}
 }

@@ -46,7 +46,9 @@ typedef struct {
 	/* -B (bub NULL: no tags): the bubble table, every .ann record's bubble number, and - when the records are ascending and disjoint, so that
 	 * kernel k_locus can search them (gpu_loci) - their first and last positions as the arrays bwb_hip_set_loci takes */
 	const bubble_table_t *bub; const int32_t *bubble_of; int gpu_loci; const uint64_t *rec_start, *rec_end;
-	const int32_t *chrom_of;  /* -J (NULL: every placement counts): the chromosome's record of every bubble; needs max_alt and bub */
+	const int32_t *chrom_of;  /* -J, -R (NULL: neither): the chromosome's record of every bubble; needs bub */
+	int join;                 /* -J: a read's placements counted by locus; needs max_alt and bub */
+	int lift;                 /* -R: placements on a bubble record written in chromosome coordinates; needs bub */
 } map_t;
 
 typedef struct {
@@ -79,6 +81,7 @@ typedef struct {
 	double alt_ms; unsigned long long alt_steps, alt_items; /* map -X: k_alt_count + scan + k_place_alt, summed over the chunks */
 	double locus_ms; unsigned long long locus_reads; /* map -B: k_locus, summed over the chunks */
 	double join_ms; unsigned long long join_items, join_joined, join_mapq; /* map -J: k_join_items + k_join_reads, summed over the chunks; reads whose MAPQ changed */
+	double lift_ms; unsigned long long lift_lifted, lift_unliftable, lift_bytes; /* map -R: k_lift_count + scan + k_lift, summed over the chunks; what came back for them */
 } worker_t;
 
 /* The reader: chunk k+1 is parsed (record boundaries by one sequential scan, bases encoded by all cores: reads.c) while chunk k is on
@@ -174,12 +177,12 @@ static void retire_map(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c) {
 	 * k_locus on the result stream); with the host's loci, the host's rule - the suboptimal bit then needs the hits' scores (slot_result) */
 	const bwb_join *joins = NULL;
 	bwb_join *host_joins = NULL;
-	if (m->chrom_of && m->gpu_loci) {
+	if (m->join && m->gpu_loci) {
 		if (bwb_hip_slot_join(ctx, slot, m->max_mm, m->max_alt, &pl, &alt_off, &alts, &loci, &joins, &n)) bwb_die("map_reads: GPU %d: %s", w->gpu, bwb_hip_last_error());
 		uint64_t it = 0, jn = 0; double ms = 0;
 		bwb_hip_join_stats(ctx, &it, &jn, &ms);
 		w->join_ms += ms; w->join_items += it; w->join_joined += jn;
-	} else if (m->chrom_of) {
+	} else if (m->join) {
 		bwb_result res;
 		if (bwb_hip_slot_result(ctx, slot, &res)) bwb_die("map_reads: GPU %d: %s", w->gpu, bwb_hip_last_error());
 		uint8_t *sub = (uint8_t *)malloc(alt_off[n] ? alt_off[n] : 1);
@@ -198,9 +201,27 @@ static void retire_map(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c) {
 		w->join_mapq += changed;
 		if (!m->gpu_loci) w->join_joined += joined; /* (on the GPU path join_stats has counted them) */
 	}
+	/* -R: RNAME, POS and CIGAR of the placements on bubble records, from the records and loci the slot already holds (kernels k_lift_count / k_lift
+	 * behind them on the result stream); with the host's loci, the host's rule */
+	const uint8_t *lift_kind = NULL;
+	const uint64_t *lift_off = NULL;
+	const bwb_lift *lift_recs = NULL;
+	lift_set_t *host_lift = NULL;
+	if (m->lift && m->gpu_loci) {
+		uint64_t nq = 0, nl = 0, nu = 0; double ms = 0;
+		if (bwb_hip_slot_lift(ctx, slot, m->max_mm, m->max_alt, &lift_kind, &lift_off, &lift_recs, &nq)) bwb_die("map_reads: GPU %d: %s", w->gpu, bwb_hip_last_error());
+		bwb_hip_lift_stats(ctx, &nl, &nu, &ms);
+		w->lift_ms += ms; w->lift_lifted += nl; w->lift_unliftable += nu;
+		w->lift_bytes += nq + (nq + 1) * 8 + lift_off[nq] * sizeof(bwb_lift);
+	} else if (m->lift) {
+		host_lift = lift_host(pl, loci, n, alt_off, alts, m->ann, m->ann_sorted, m->bubble_of, m->chrom_of, m->bub);
+		lift_kind = host_lift->kind; lift_off = host_lift->off; lift_recs = host_lift->recs;
+		w->lift_lifted += host_lift->n_lifted; w->lift_unliftable += host_lift->n_unliftable;
+	}
 	const sam_reads_t rd = { .pl = pl, .seq = c->fq.seq, .stride = c->fq.stride, .len = c->fq.len, .text = c->fq.text,
 	                         .name_off = c->fq.name_off, .qual_off = c->fq.qual_off, .name_len = c->fq.name_len, .first = c->first_read,
-	                         .alt_off = alt_off, .alts = alts, .loci = loci, .bubbles = m->bub, .joins = joins };
+	                         .alt_off = alt_off, .alts = alts, .loci = loci, .bubbles = m->bub, .joins = joins,
+	                         .lift_kind = lift_kind, .lift_off = lift_off, .lift_recs = lift_recs, .lift_n = n };
 	c->n = n;
 	c->n_sam = ((size_t)n + SAM_BLOCK_READS - 1) / SAM_BLOCK_READS;
 	c->sam = (char **)calloc(c->n_sam ? c->n_sam : 1, sizeof(char *));
@@ -210,7 +231,7 @@ static void retire_map(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c) {
 		const size_t r0 = (size_t)bi * SAM_BLOCK_READS, r1 = r0 + SAM_BLOCK_READS < n ? r0 + SAM_BLOCK_READS : n;
 		c->sam[bi] = sam_format_reads(&rd, r0, r1, m->ann, m->ann_sorted, &c->sam_len[bi]);
 	}
-	free(host_loci); free(host_joins);
+	free(host_loci); free(host_joins); lift_free(host_lift);
 	free(c->fq.seq); free(c->fq.len); free(c->fq.name_off); free(c->fq.qual_off); free(c->fq.name_len);
 	c->fq.seq = NULL; c->fq.len = NULL; c->fq.name_off = NULL; c->fq.qual_off = NULL; c->fq.name_len = NULL;
 	chunk_ready(w->pp, c);
@@ -270,7 +291,7 @@ static void *gpu_worker(void *arg) {
 		if (pp->map->bub && pp->map->gpu_loci &&
 		    bwb_hip_set_loci(ctx, pp->map->rec_start, pp->map->rec_end, pp->map->bubble_of, (uint32_t)pp->map->ann->num_seq, pp->map->bub->b, (uint32_t)pp->map->bub->n))
 			bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
-		/* -J: the chromosome's record of every bubble, beside them */
+		/* -J, -R: the chromosome's record of every bubble, beside them */
 		if (pp->map->chrom_of && pp->map->gpu_loci && bwb_hip_set_bubble_chrom(ctx, pp->map->chrom_of, (uint32_t)pp->map->bub->n))
 			bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
 	}
@@ -431,13 +452,19 @@ static int run_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, 
 			double lms = 0; unsigned long long lrd = 0;
 			for (int g = 0; g < n_gpus; g++) { lrd += ws[g].locus_reads; if (ws[g].locus_ms > lms) lms = ws[g].locus_ms; }
 			printf("  loci resolved %llu  k_locus %.3f ms", lrd, lms);
-		} else if (map->bub) printf("  loci resolved %llu on the host%s (the .ann records are not ascending and disjoint)", (unsigned long long)pp.n_reads, map->chrom_of ? " and joined there" : "");
+		} else if (map->bub) printf("  loci resolved %llu on the host%s (the .ann records are not ascending and disjoint)", (unsigned long long)pp.n_reads, map->join ? " and joined there" : "");
 		printf("\n");
-		if (map->chrom_of) { /* -J */
+		if (map->join) { /* -J */
 			double jms = 0; unsigned long long jit = 0, jjn = 0, jmq = 0;
 			for (int g = 0; g < n_gpus; g++) { jit += ws[g].join_items; jjn += ws[g].join_joined; jmq += ws[g].join_mapq; if (ws[g].join_ms > jms) jms = ws[g].join_ms; }
 			if (map->gpu_loci) printf("placements joined by locus on the GPU: items %llu  joined %llu  reads with another MAPQ %llu  kernels %.3f ms\n", jit, jjn, jmq, jms);
 			else printf("placements joined by locus on the host: joined %llu  reads with another MAPQ %llu\n", jjn, jmq);
+		}
+		if (map->lift) { /* -R */
+			double lms = 0; unsigned long long ll = 0, lu = 0, lb = 0;
+			for (int g = 0; g < n_gpus; g++) { ll += ws[g].lift_lifted; lu += ws[g].lift_unliftable; lb += ws[g].lift_bytes; if (ws[g].lift_ms > lms) lms = ws[g].lift_ms; }
+			if (map->gpu_loci) printf("placements lifted to chromosome coordinates on the GPU: lifted %llu  not liftable %llu  kernels %.3f ms  bytes to the host %llu\n", ll, lu, lms, lb);
+			else printf("placements lifted to chromosome coordinates on the host (the .ann records are not ascending and disjoint): lifted %llu  not liftable %llu\n", ll, lu);
 		}
 		if (map->max_alt) {
 			double ams = 0; unsigned long long ast = 0, ait = 0;
@@ -497,10 +524,11 @@ int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_
 }
 
 /* `bwbble map`: align_reads + alns2sam in one pass.  The .bwt is loaded once, with its SA; the SAM header is written before the first chunk. */
-int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int n_gpus) {
+int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int lift, int n_gpus) {
 	printf("**** BWBBLE Read Mapping (align + aln2sam in one pass) ****\n");
 	/* -B: the table first (a refused table stops the run before anything is created) */
 	bubble_table_t *bub = bubbleFname ? load_bubbles(bubbleFname) : NULL;
+	if (lift && bub) lift_check_table(bub); /* -R (main.c: only with -B): a bubble the rule refuses is named here */
 	/* before anything is created: without a GPU no SAM file is left behind */
 	if (bwb_hip_device_count() < 1) bwb_die("align_reads_inexact_gpu: no HIP device found (this build has no CPU alignment path)");
 	size_t L = strlen(fastaFname) + 8;
@@ -513,7 +541,8 @@ int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *
 	/* -B: every record's bubble number, before the SAM file exists (a record that names a bubble outside the table leaves none behind) */
 	int32_t *bubble_of = bub ? ann_bubble_of(ann, bub) : NULL;
 	/* -J (main.c: only with -X and -B): the chromosome's record of every bubble; one without a chromosome leaves no SAM file behind either */
-	int32_t *chrom_of = join && bub && max_alt ? bubble_chrom_of(ann, bubble_of, bub) : NULL;
+	join = join && bub && max_alt; lift = lift && bub;
+	int32_t *chrom_of = join || lift ? bubble_chrom_of(ann, bubble_of, bub, join ? "-J" : "-R") : NULL;
 	uint64_t *rec_start = NULL, *rec_end = NULL;
 	int gpu_loci = bub && ann->num_seq > 0 && sam_ann_sorted(ann) && bub->n <= INT32_MAX;
 	if (bub) {
@@ -530,7 +559,7 @@ int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *
 	if (!sam) { perror(samFname); bwb_die("map_reads: Cannot open SAM file: %s!", samFname); }
 	sam_write_header(sam, ann);
 	const map_t m = { .max_mm = max_mm, .max_alt = max_alt, .ann = ann, .ann_sorted = sam_ann_sorted(ann),
-	                  .bub = bub, .bubble_of = bubble_of, .gpu_loci = gpu_loci, .rec_start = rec_start, .rec_end = rec_end, .chrom_of = chrom_of };
+	                  .bub = bub, .bubble_of = bubble_of, .gpu_loci = gpu_loci, .rec_start = rec_start, .rec_end = rec_end, .chrom_of = chrom_of, .join = join, .lift = lift };
 	t = wall();
 	printf("BWBBLE Inexact Alignment (MI355X)...\n");
 	run_stream(BWT, readsFname, params, sam, samFname, n_gpus, &m);

@@ -119,14 +119,14 @@ int aln_path_bytes(const bwb_aln *a, unsigned char *path /* >= 272 bytes */); /*
 void set_default_aln_params(aln_params_t *params);                     /* align.c:22-38 */
 int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_t *params, int n_gpus); /* align.c:40-87 */
 int align_reads_inexact_gpu_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, char *alnFname, int n_gpus); /* the GPU's align_reads_inexact_parallel (inexact_match.h:40) over a streamed FASTQ */
-int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int n_gpus); /* `bwbble map`: align + aln2sam in one pass, the hits evaluated on the GPU */
+int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int lift, int n_gpus); /* `bwbble map`: align + aln2sam in one pass, the hits evaluated on the GPU */
 
 /* precalc.c */
 void precalc_sa_intervals(bwt_t *BWT, const aln_params_t *params, const char *preFname); /* align.c:200-224: writes <fasta>.pre */
 int check_precalc_file(const char *preFname); /* the walk of load_precalc_sa_intervals (align.c:226-238) over an existing table: 0 = complete */
 
 /* sam.c */
-void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join); /* align.c:494-556; max_alt: -X (0: no tags); bubbleFname: -B (NULL: no tags); join: -J */
+void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join, int lift); /* align.c:494-556; max_alt: -X (0: no tags); bubbleFname: -B (NULL: no tags); join: -J; lift: -R */
 /* the two halves of alns2sam: eval_aln of one read on the host, and the text of a block of reads from placement records (which `map` gets
  * from the GPU instead, bwb_hip_slot_place) */
 #define SAM_BLOCK_READS ((size_t)1 << 14)                              /* reads formatted by one thread at a time */
@@ -138,6 +138,9 @@ typedef struct {
 	const uint64_t *alt_off; const bwb_alt *alts;                      /* -X (NULL: no tags): read r's other placements are alts[alt_off[r] .. alt_off[r + 1]) */
 	const bwb_locus *loci; const struct bubble_table *bubbles;         /* -B (NULL: no tags): read r's record and POS come from loci[r], and on a bubble record the tags bC / bP */
 	const bwb_join *joins;                                             /* -J (NULL: pl's MAPQ, no tag): read r's MAPQ comes from joins[r], and with joined items the tag bJ */
+	/* -R (lift_kind NULL: as placed): placement q - read q's primary, or lift_n + k for item alts[k] - with lift_kind[q] == BWB_LIFT_LIFTED prints
+	 * RNAME, POS and CIGAR of the record at lift_recs + lift_off[q], and a lifted primary the tag bO */
+	const uint8_t *lift_kind; const uint64_t *lift_off; const bwb_lift *lift_recs; size_t lift_n;
 } sam_reads_t;
 int sam_mapq(int top1, int top2, int num_mm, int max_mm);               /* align.c:738-746 */
 void place_from_alns(const bwb_aln *e, uint64_t ne, uint64_t ref_pos, uint64_t bwt_length, int max_mm, bwb_place *out);
@@ -146,7 +149,7 @@ uint64_t alt_placements(const bwb_aln *e, uint64_t ne);               /* the row
 void sam_write_header(FILE *sam, const fasta_annotations_t *ann);
 int sam_ann_sorted(const fasta_annotations_t *ann);
 char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_annotations_t *ann, int ann_sorted, size_t *out_len);
-void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join); /* developer command: records from a file (altsFname: NULL or the items; bubbleFname: NULL or -B's table; join: -J, the items file then ends with one suboptimal byte per item) */
+void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join, int lift); /* developer command: records from a file (altsFname: NULL or the items; bubbleFname: NULL or -B's table; join: -J, the items file then ends with one suboptimal byte per item; lift: -R) */
 
 /* pad.c: bubble hits in reference coordinates (the reference's mg-ref/sam_pad.cpp) */
 typedef struct bubble_table {                                          /* bubble.data (mg-ref/comb.cpp:245-253): the k-th pair of lines is bubble k */
@@ -162,9 +165,17 @@ void bubble_locus(const bwb_bubble *b, int64_t locus, bwb_locus *out); /* sam_pa
 int ann_find_record(const fasta_annotations_t *ann, int ann_sorted, uint64_t aln_pos); /* the record that contains aln_pos, -1: none */
 void locus_resolve(const bwb_place *pl, const fasta_annotations_t *ann, int ann_sorted, const int32_t *bubble_of, const bubble_table_t *t, bwb_locus *out); /* kernel k_locus on the host */
 char *locus_put_tags(char *o, const bwb_locus *lc, const bubble_table_t *t);
-int32_t *bubble_chrom_of(const fasta_annotations_t *ann, const int32_t *bubble_of, const bubble_table_t *t); /* -J: [t->n] the chromosome's record of every bubble (malloc'ed); none, several or a bubble record is refused */
+int32_t *bubble_chrom_of(const fasta_annotations_t *ann, const int32_t *bubble_of, const bubble_table_t *t, const char *flag); /* -J, -R (flag: the one the message names): [t->n] the chromosome's record of every bubble (malloc'ed); none, several or a bubble record is refused */
 void join_resolve(const bwb_place *pl, const bwb_locus *lc, const bwb_alt *items, const uint8_t *sub, uint64_t n_items, const fasta_annotations_t *ann, int ann_sorted,
                   const int32_t *bubble_of, const int32_t *chrom_of, const bubble_table_t *t, int max_mm, bwb_join *out); /* kernels k_join_items + k_join_reads on the host, one read */
+/* -R: placements on a bubble record in chromosome coordinates (include/bwbble_hip.h: bwb_lift) */
+const char *lift_bubble_refusal(const bwb_bubble *b);                  /* NULL, or why the rule refuses the bubble */
+void lift_check_table(const bubble_table_t *t);                        /* a refused bubble stops the run and is named */
+int lift_resolve(const bwb_bubble *b, int32_t chrom, int64_t pos1, int reverse, unsigned alen, const uint16_t *gap_run, bwb_lift *hdr, uint32_t *ops /* BWB_LIFT_MAX_OPS */); /* kernels k_lift_count + k_lift on the host, one placement; returns the ops, 0: not liftable */
+typedef struct { uint8_t *kind; uint64_t *off; bwb_lift *recs; uint64_t n_lifted, n_unliftable; } lift_set_t; /* what bwb_hip_slot_lift returns, malloc'ed */
+lift_set_t *lift_host(const bwb_place *pl, const bwb_locus *loci, size_t n, const uint64_t *alt_off, const bwb_alt *alts, const fasta_annotations_t *ann, int ann_sorted,
+                      const int32_t *bubble_of, const int32_t *chrom_of, const bubble_table_t *t);
+void lift_free(lift_set_t *ls);
 void sam_pad(const char *dataFname, const char *inFname, const char *outFname); /* `bwbble sampad`: sam_pad.cpp:47-94 over SAM text */
 
 /* The OpenMP teams of the host stages of `align` / `aln2sam` (base encoding, .aln serialisation, SAM text) have at most 32 threads unless

@@ -11,6 +11,9 @@
  *
  * -J (no counterpart in the reference): bubble_chrom_of and join_resolve - which of a read's other placements lie where its primary lies,
  * once both are in chromosome coordinates, and the read's counts and MAPQ without them (include/bwbble_hip.h: bwb_join).
+ *
+ * -R (no counterpart either): lift_check_table, lift_resolve and lift_host - RNAME, POS and CIGAR of a placement on a bubble record rewritten
+ * to the chromosome's, the alternate allele as an insertion and the positions the record skips as a deletion (include/bwbble_hip.h: bwb_lift).
  */
 #define _GNU_SOURCE
 #include <ctype.h>
@@ -163,7 +166,7 @@ static int word_cmp(const void *a, const void *b) {
 
 /* chrom_of[k]: the .ann record of the chromosome bubble k lies on - the one record whose name's first word is the first word of the bubble's
  * header line in bubble.data.  None, several, or a record that is itself a bubble record: refused, naming the bubble. */
-int32_t *bubble_chrom_of(const fasta_annotations_t *ann, const int32_t *bubble_of, const bubble_table_t *t) {
+int32_t *bubble_chrom_of(const fasta_annotations_t *ann, const int32_t *bubble_of, const bubble_table_t *t, const char *flag) {
 	const size_t n_rec = ann->num_seq > 0 ? (size_t)ann->num_seq : 0;
 	name_word_t *words = (name_word_t *)malloc((n_rec ? n_rec : 1) * sizeof(name_word_t));
 	for (size_t i = 0; i < n_rec; i++) words[i] = first_word(ann->seq_anns[i].name, (int)i);
@@ -176,9 +179,9 @@ int32_t *bubble_chrom_of(const fasta_annotations_t *ann, const int32_t *bubble_o
 		size_t same = 0;
 		while (lo + same < n_rec && word_cmp(&words[lo + same], &key) == 0) same++;
 		if (same != 1)
-			bwb_die("bubble table: bubble %lld (\"%s\"): %zu .ann records are named \"%.*s\", one chromosome record is needed (-J)", (long long)k, t->ann[k], same, (int)key.len, key.w);
+			bwb_die("bubble table: bubble %lld (\"%s\"): %zu .ann records are named \"%.*s\", one chromosome record is needed (%s)", (long long)k, t->ann[k], same, (int)key.len, key.w, flag);
 		if (bubble_of[words[lo].rec] != -1)
-			bwb_die("bubble table: bubble %lld (\"%s\"): .ann record %d (\"%s\") is itself a bubble record (-J)", (long long)k, t->ann[k], words[lo].rec, ann->seq_anns[words[lo].rec].name);
+			bwb_die("bubble table: bubble %lld (\"%s\"): .ann record %d (\"%s\") is itself a bubble record (%s)", (long long)k, t->ann[k], words[lo].rec, ann->seq_anns[words[lo].rec].name, flag);
 		chrom_of[k] = words[lo].rec;
 	}
 	free(words);
@@ -215,6 +218,155 @@ void join_resolve(const bwb_place *pl, const bwb_locus *lc, const bwb_alt *items
 	out->top2 = (int32_t)((uint32_t)pl->top2 - subopt);
 	out->mapq = n_items ? (uint8_t)sam_mapq(out->top1, out->top2, pl->num_mm, max_mm) : pl->mapq;
 	out->joined = (uint8_t)(best + subopt);
+}
+
+/* ---- -R: a placement on a bubble record in chromosome coordinates (include/bwbble_hip.h: bwb_lift; kernels k_lift_count / k_lift) ---------- */
+
+/* 0: the rule can use bubble b; else why not (the five refusals of -R) */
+const char *lift_bubble_refusal(const bwb_bubble *b) {
+	const __int128 gap = (__int128)b->C - (__int128)b->A - (__int128)b->B_minus_A;
+	if (b->B_minus_A < 0) return "B_minus_A is negative";
+	if (b->D_minus_C < -1) return "D_minus_C is below -1";
+	if (b->alt_len < 0) return "alt_len is negative";
+	if (gap < 0) return "its flanks overlap on the chromosome (C - A - B_minus_A is negative)";
+	if (gap >= ((__int128)1 << 28)) return "its flanks lie 2^28 positions or more apart";
+	return NULL;
+}
+
+void lift_check_table(const bubble_table_t *t) {
+	for (int64_t k = 0; k < t->n; k++) {
+		const char *why = lift_bubble_refusal(&t->b[k]);
+		if (why) bwb_die("bubble table: bubble %lld (\"%s\"): %s (-R)", (long long)k, t->ann[k], why);
+	}
+}
+
+/* the op of text position t of a placement's CIGAR: the path byte aln_path_bytes gives (a later run wins), walked as sam_put_cigar walks it */
+static inline unsigned lift_op_at(const uint16_t *gap_run, unsigned alen, int reverse, unsigned t) {
+	const unsigned p = reverse ? t : alen - 1 - t;
+	unsigned op = 0;
+	for (int k = 0; k < BWB_MAX_GAP_RUNS; k++) {
+		const unsigned run = gap_run[k];
+		if (run != 0xFFFFu && p - (run & 0xFFu) < ((run >> 8) & 0x7Fu)) op = (run >> 15) ? BWB_LIFT_D : BWB_LIFT_I;
+	}
+	return op;
+}
+
+/* 0 left flank, 1 alternate allele, 2 right flank, of a record position x >= 1 that the span check has kept inside the record */
+static inline int lift_zone(const bwb_bubble *b, int64_t x) { return x <= b->B_minus_A ? 0 : (x - b->B_minus_A <= (int64_t)b->alt_len ? 1 : 2); }
+
+typedef struct { uint32_t *ops; unsigned n, kind; uint64_t len; } lift_out_t;
+static inline void lift_put(lift_out_t *o) {
+	if (o->kind == 0xFFu) return;
+	if (o->n < BWB_LIFT_MAX_OPS) o->ops[o->n] = (uint32_t)(o->len << 4) | o->kind;
+	o->n++;
+}
+static inline void lift_emit(lift_out_t *o, unsigned kind, uint64_t len) {
+	if (kind == o->kind && o->len + len < ((uint64_t)1 << 28)) { o->len += len; return; }
+	lift_put(o);
+	o->kind = kind; o->len = len;
+}
+
+/* The rule on one placement of bubble b (a table lift_check_table has passed): printed position pos1, strand, path length and gap runs as
+ * bwb_place / bwb_alt hold them -> the record's header and ops.  Returns the number of ops, 0: not liftable (the span leaves the record, or
+ * no M remains).  What kernels k_lift_count / k_lift compute. */
+int lift_resolve(const bwb_bubble *b, int32_t chrom, int64_t pos1, int reverse, unsigned alen, const uint16_t *gap_run, bwb_lift *hdr, uint32_t *ops) {
+	const int64_t gap = (int64_t)((uint64_t)b->C - (uint64_t)b->A - (uint64_t)b->B_minus_A);
+	/* first pass: the span on the record, and the first and last M that stays an M */
+	int64_t x = pos1, first = -1, last = -1, x_first = 0;
+	for (unsigned t = 0; t < alen; t++) {
+		const unsigned op = lift_op_at(gap_run, alen, reverse, t);
+		if (op == BWB_LIFT_I) continue;
+		if (op == BWB_LIFT_M && x >= 1 && lift_zone(b, x) != 1) { if (first < 0) { first = t; x_first = x; } last = t; }
+		x++;
+	}
+	const int64_t end = x - 1; /* the last record position consumed */
+	/* (pos1 < 1: the rule's own condition, kept for a caller of this function - a locus on a bubble record always has pos1 >= 1) */
+	if (pos1 < 1 || first < 0) return 0;
+	if (end > b->B_minus_A && end - b->B_minus_A > (int64_t)b->alt_len && end - b->B_minus_A - (int64_t)b->alt_len - 1 > b->D_minus_C) return 0;
+	lift_out_t o = { .ops = ops, .n = 0, .kind = 0xFFu, .len = 0 };
+	uint64_t lead = 0, trail = 0;
+	x = pos1;
+	for (unsigned t = 0; t < alen; t++) {
+		const unsigned op = lift_op_at(gap_run, alen, reverse, t);
+		unsigned kind = BWB_LIFT_I;
+		if (op != BWB_LIFT_I) {
+			const int z = lift_zone(b, x);
+			/* the walk enters the right flank: the positions the record skips, behind the allele's I */
+			if (z == 2 && x - b->B_minus_A == (int64_t)b->alt_len + 1 && x > pos1 && gap > 0 && (int64_t)t > first && (int64_t)t <= last) lift_emit(&o, BWB_LIFT_D, (uint64_t)gap);
+			kind = op == BWB_LIFT_M ? (z == 1 ? BWB_LIFT_I : BWB_LIFT_M) : (z == 1 ? 0xFFu : BWB_LIFT_D);
+			x++;
+		}
+		if (kind == 0xFFu) continue;
+		if ((int64_t)t < first) lead += kind == BWB_LIFT_I;
+		else if ((int64_t)t > last) trail += kind == BWB_LIFT_I;
+		else {
+			if ((int64_t)t == first && lead) lift_emit(&o, BWB_LIFT_S, lead);
+			lift_emit(&o, kind, 1);
+		}
+	}
+	lift_put(&o);
+	if (trail) { o.kind = BWB_LIFT_S; o.len = trail; lift_put(&o); }
+	if (o.n > BWB_LIFT_MAX_OPS) return 0; /* (17 runs and the three the allele adds: not reached) */
+	memset(hdr, 0, sizeof(*hdr));
+	const int64_t right = b->B_minus_A + (int64_t)b->alt_len + 1;
+	hdr->pos = x_first <= b->B_minus_A ? (int64_t)((uint64_t)b->A + (uint64_t)x_first - 1u) : (int64_t)((uint64_t)b->C + (uint64_t)(x_first - right));
+	hdr->seqid = chrom;
+	hdr->n_ops = (uint8_t)o.n;
+	return (int)o.n;
+}
+
+/* -R on the host (aln2sam, places2sam, and map on an .ann that is not ascending and disjoint): the lift records of n reads and their items
+ * (alt_off NULL: none), laid out as bwb_hip_slot_lift returns them; with all cores */
+lift_set_t *lift_host(const bwb_place *pl, const bwb_locus *loci, size_t n, const uint64_t *alt_off, const bwb_alt *alts, const fasta_annotations_t *ann, int ann_sorted,
+                      const int32_t *bubble_of, const int32_t *chrom_of, const bubble_table_t *t) {
+	const size_t n_items = alt_off ? (size_t)alt_off[n] : 0, nq = n + n_items;
+	lift_set_t *ls = (lift_set_t *)calloc(1, sizeof(*ls));
+	ls->kind = (uint8_t *)calloc(nq ? nq : 1, 1);
+	ls->off = (uint64_t *)calloc(nq + 1, 8);
+	for (int pass = 0; pass < 2; pass++) {
+		uint64_t lifted = 0, unliftable = 0;
+#pragma omp parallel for schedule(static) reduction(+ : lifted, unliftable) num_threads(bwb_host_team())
+		for (long q = 0; q < (long)nq; q++) {
+			if (pass && ls->kind[q] != BWB_LIFT_LIFTED) continue;
+			bwb_locus il;
+			const bwb_locus *lc = &il;
+			const uint16_t *runs;
+			unsigned alen;
+			int reverse;
+			if ((size_t)q < n) { lc = &loci[q]; runs = pl[q].gap_run; alen = pl[q].aln_length; reverse = (pl[q].flags & BWB_PLACE_REVERSE) != 0; }
+			else {
+				const bwb_alt *a = &alts[(size_t)q - n];
+				const bwb_place as_place = { .pos = a->pos, .flags = a->flags };
+				locus_resolve(&as_place, ann, ann_sorted, bubble_of, t, &il);
+				runs = a->gap_run; alen = a->aln_length; reverse = (a->flags & BWB_PLACE_REVERSE) != 0;
+			}
+			if (lc->bubble < 0) continue;
+			bwb_lift hdr;
+			uint32_t ops[BWB_LIFT_MAX_OPS];
+			const int n_ops = lift_resolve(&t->b[lc->bubble], chrom_of[lc->bubble], (int64_t)lc->pos1, reverse, alen, runs, &hdr, ops);
+			if (!pass) {
+				ls->kind[q] = n_ops ? BWB_LIFT_LIFTED : BWB_LIFT_UNLIFTABLE;
+				ls->off[q + 1] = n_ops ? 1 + ((uint64_t)n_ops + 3) / 4 : 0;
+				lifted += n_ops != 0; unliftable += n_ops == 0;
+			} else {
+				bwb_lift *dst = ls->recs + ls->off[q];
+				memset(dst, 0, (size_t)(ls->off[q + 1] - ls->off[q]) * sizeof(bwb_lift));
+				dst[0] = hdr;
+				memcpy(dst + 1, ops, (size_t)n_ops * 4);
+			}
+		}
+		if (!pass) {
+			ls->n_lifted = lifted; ls->n_unliftable = unliftable;
+			for (size_t q = 0; q < nq; q++) ls->off[q + 1] += ls->off[q];
+			ls->recs = (bwb_lift *)malloc((ls->off[nq] ? (size_t)ls->off[nq] : 1) * sizeof(bwb_lift));
+		}
+	}
+	return ls;
+}
+
+void lift_free(lift_set_t *ls) {
+	if (!ls) return;
+	free(ls->kind); free(ls->off); free(ls->recs); free(ls);
 }
 
 /* `bwbble sampad <bubble.data> <in.sam> <out.sam>`: process_sam (sam_pad.cpp:47-94), one line in memory at a time.  A refused line leaves

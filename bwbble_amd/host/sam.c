@@ -113,6 +113,13 @@ static char *sam_put_cigar(char *o, uint16_t aln_length, const uint16_t *gap_run
 	return o;
 }
 
+/* CIGAR of a lift record (-R): its ops as they lie; returns the end of the text */
+static char *sam_put_lifted_cigar(char *o, const bwb_lift *rec) {
+	const uint32_t *ops = (const uint32_t *)(rec + 1);
+	for (unsigned i = 0; i < rec->n_ops; i++) o += sprintf(o, "%u%c", ops[i] >> 4, "MID?S???????????"[ops[i] & 15u]);
+	return o;
+}
+
 /* print_aln2sam (align.c:562-652) for reads [r0, r1) of rd: placement records + names / bases / qualities + annotations -> SAM text in a
  * malloc'ed buffer.  Shared by aln2sam (records from place_from_alns), map (records from the GPU) and places2sam (records from a file). */
 char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_annotations_t *ann, int ann_sorted, size_t *out_len) {
@@ -123,6 +130,10 @@ char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_
 		for (uint64_t k = rd->alt_off[r0]; k < rd->alt_off[r1]; k++) cap += MAX_SEQ_NAME_LEN + 64 + 8 * (size_t)rd->alts[k].num_gapo;
 	}
 	if (rd->joins) cap += (r1 - r0) * 12; /* -J: "\tbJ:i:255" */
+	if (rd->lift_kind) { /* -R: a lifted placement prints another name, a 64-bit position and up to 20 ops; a primary also the tag bO with its own CIGAR */
+		for (size_t r = r0; r < r1; r++) if (rd->lift_kind[r] == BWB_LIFT_LIFTED) cap += 2 * MAX_SEQ_NAME_LEN + 480 + 8 * (size_t)rd->pl[r].num_gapo;
+		if (rd->alt_off) for (uint64_t k = rd->alt_off[r0]; k < rd->alt_off[r1]; k++) if (rd->lift_kind[rd->lift_n + k] == BWB_LIFT_LIFTED) cap += MAX_SEQ_NAME_LEN + 320;
+	}
 	if (rd->loci) /* -B: on a bubble record the chromosome's header and one or two 64-bit numbers */
 		for (size_t r = r0; r < r1; r++) if (rd->loci[r].bubble >= 0) cap += strlen(rd->bubbles->ann[rd->loci[r].bubble]) + 64;
 	char *o = (char *)malloc(cap ? cap : 1), *o0 = o;
@@ -145,8 +156,16 @@ char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_
 		/* -B: the read's record and POS were resolved with its locus (kernel k_locus for `map`, locus_resolve otherwise) */
 		const int seqid = rd->loci ? rd->loci[r].seqid : ann_find_record(ann, ann_sorted, aln_pos);
 		if (seqid < 0 || seqid >= ann->num_seq) bwb_die("alns2sam: read %zu maps outside every annotated sequence", rd->first + r); /* the reference indexes seq_anns[-1] here */
-		o += sprintf(o, "\t%d\t%s\t%d\t%d\t", strand ? SAM_FSR : 0, ann->seq_anns[seqid].name, rd->loci ? (int)rd->loci[r].pos1 : (int)(aln_pos - ann->seq_anns[seqid].start_index + 1), rd->joins ? (int)rd->joins[r].mapq : (int)pl->mapq);
-		o = sam_put_cigar(o, pl->aln_length, pl->gap_run, strand);
+		/* -R: a lifted placement lies on the chromosome of its bubble */
+		const bwb_lift *lifted = rd->lift_kind && rd->lift_kind[r] == BWB_LIFT_LIFTED ? rd->lift_recs + rd->lift_off[r] : NULL;
+		if (lifted) {
+			if (lifted->seqid < 0 || lifted->seqid >= ann->num_seq) bwb_die("alns2sam: read %zu is lifted to a record outside the annotations", rd->first + r);
+			o += sprintf(o, "\t%d\t%s\t%lld\t%d\t", strand ? SAM_FSR : 0, ann->seq_anns[lifted->seqid].name, (long long)lifted->pos, rd->joins ? (int)rd->joins[r].mapq : (int)pl->mapq);
+			o = sam_put_lifted_cigar(o, lifted);
+		} else {
+			o += sprintf(o, "\t%d\t%s\t%d\t%d\t", strand ? SAM_FSR : 0, ann->seq_anns[seqid].name, rd->loci ? (int)rd->loci[r].pos1 : (int)(aln_pos - ann->seq_anns[seqid].start_index + 1), rd->joins ? (int)rd->joins[r].mapq : (int)pl->mapq);
+			o = sam_put_cigar(o, pl->aln_length, pl->gap_run, strand);
+		}
 		memcpy(o, "\t*\t0\t0\t", 7); o += 7;
 		if (strand) for (int k = 0; k < len; k++) { const int c = seq[len - 1 - k]; o[k] = "AGCTN"[c > 3 ? 4 : 3 - c]; } /* read->rc */
 		else for (int k = 0; k < len; k++) o[k] = "AGCTN"[seq[k]];
@@ -161,6 +180,13 @@ char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_
 				const bwb_alt *a = &rd->alts[k];
 				const int sid = ann_find_record(ann, ann_sorted, a->pos);
 				if (sid < 0) continue;
+				const bwb_lift *li = rd->lift_kind && rd->lift_kind[rd->lift_n + k] == BWB_LIFT_LIFTED ? rd->lift_recs + rd->lift_off[rd->lift_n + k] : NULL;
+				if (li && li->seqid >= 0 && li->seqid < ann->num_seq) {
+					o += sprintf(o, "%s,%c%lld,", ann->seq_anns[li->seqid].name, (a->flags & BWB_PLACE_REVERSE) ? '-' : '+', (long long)li->pos);
+					o = sam_put_lifted_cigar(o, li);
+					o += sprintf(o, ",%d;", (int)a->num_mm + (int)a->num_gapo + (int)a->num_gape);
+					continue;
+				}
 				o += sprintf(o, "%s,%c%d,", ann->seq_anns[sid].name, (a->flags & BWB_PLACE_REVERSE) ? '-' : '+', (int)(a->pos - ann->seq_anns[sid].start_index + 1));
 				o = sam_put_cigar(o, a->aln_length, a->gap_run, (a->flags & BWB_PLACE_REVERSE) != 0);
 				o += sprintf(o, ",%d;", (int)a->num_mm + (int)a->num_gapo + (int)a->num_gape);
@@ -168,6 +194,13 @@ char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_
 		}
 		if (rd->loci && rd->loci[r].bubble >= 0) o = locus_put_tags(o, &rd->loci[r], rd->bubbles); /* last on the line, like sam_pad's */
 		if (rd->joins && rd->joins[r].joined) o += sprintf(o, "\tbJ:i:%d", (int)rd->joins[r].joined); /* -J: behind them */
+		if (lifted) { /* -R: where the read was placed - the bubble record's first word, POS and CIGAR there; last */
+			const char *bn = ann->seq_anns[seqid].name;
+			size_t wl = 0;
+			while (bn[wl] && bn[wl] != ' ' && bn[wl] != '\t') wl++;
+			o += sprintf(o, "\tbO:Z:%.*s,%d,", (int)wl, bn, rd->loci ? (int)rd->loci[r].pos1 : (int)(aln_pos - ann->seq_anns[seqid].start_index + 1));
+			o = sam_put_cigar(o, pl->aln_length, pl->gap_run, strand);
+		}
 		*o++ = '\n';
 	}
 	*out_len = (size_t)(o - o0);
@@ -206,7 +239,7 @@ static bwb_join *host_joins(const bwb_place *pl, const bwb_locus *loci, const ui
 	return joins;
 }
 
-void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join) {
+void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join, int lift) {
 	(void)is_multiref;
 	printf("**** BWBBLE Alignment Evaluation/SAM File Generation ****\n");
 	size_t Ln = strlen(fastaFname) + 8;
@@ -217,7 +250,8 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 	fasta_annotations_t *ann = annf2ann(annFname);
 	bubble_table_t *bub = bubbleFname ? load_bubbles(bubbleFname) : NULL; /* (refused tables stop the run before the SAM file exists) */
 	int32_t *bubble_of = bub ? ann_bubble_of(ann, bub) : NULL;
-	int32_t *chrom_of = join ? bubble_chrom_of(ann, bubble_of, bub) : NULL; /* -J (main.c: only with -X and -B) */
+	if (lift) lift_check_table(bub); /* -R (main.c: only with -B) */
+	int32_t *chrom_of = join || lift ? bubble_chrom_of(ann, bubble_of, bub, join ? "-J" : "-R") : NULL; /* -J (main.c: only with -X and -B), -R */
 	alns_batch_t *alns = alnsf2alns_bin(alnsFname);
 	reads_t *reads = fastq2reads(readsFname);
 	FILE *sam = fopen(samFname, "w");
@@ -293,9 +327,12 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 			for (uint64_t q = alt_off[r]; q < alt_off[r + 1]; q++) alt_sub[q] = alns->alns[alns->aln_off[r] + alts[q].hit].score > alns->alns[alns->aln_off[r]].score;
 	}
 	bwb_join *joins = join ? host_joins(pl, loci, alt_off, alts, alt_sub, n, ann, ann_sorted, bubble_of, chrom_of, bub, max_diff) : NULL;
+	lift_set_t *ls = lift ? lift_host(pl, loci, n, alt_off, alts, ann, ann_sorted, bubble_of, chrom_of, bub) : NULL;
+	if (ls) printf("placements lifted to chromosome coordinates on the host: %llu  not liftable %llu\n", (unsigned long long)ls->n_lifted, (unsigned long long)ls->n_unliftable);
 	const sam_reads_t rd = { .pl = pl, .seq = reads->seq, .stride = reads->stride, .len = reads->len, .text = reads->raw,
 	                         .name_off = reads->name_off, .qual_off = reads->qual_off, .name_len = reads->name_len, .first = 0,
-	                         .alt_off = alt_off, .alts = alts, .loci = loci, .bubbles = bub, .joins = joins };
+	                         .alt_off = alt_off, .alts = alts, .loci = loci, .bubbles = bub, .joins = joins,
+	                         .lift_kind = ls ? ls->kind : NULL, .lift_off = ls ? ls->off : NULL, .lift_recs = ls ? ls->recs : NULL, .lift_n = n };
 	/* The text: blocks of reads are formatted into memory by all cores and written in order (round 5: one thread's fprintf calls were
 	 * the wall time of aln2sam on a 10 M-read file, not the SA lookups). */
 	const size_t BLK = SAM_BLOCK_READS;
@@ -316,7 +353,7 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 		}
 	}
 	free(pl); free(alt_off); free(alts); free(loci); free(bubble_of); free_bubbles(bub);
-	free(alt_sub); free(joins); free(chrom_of);
+	free(alt_sub); free(joins); free(chrom_of); lift_free(ls);
 	free(bufs); free(lens);
 	printf("Processed %zu reads.\n", n);
 	free(rows); free(pos); free(which); free(ref_pos);
@@ -326,15 +363,17 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 }
 
 /* developer command (CPU only, for the tests): raw bwb_place records from a file through sam_format_reads - the formatter `map` uses, on a
- * machine without a GPU (bubbleFname: -B, the loci from the host resolver; join: -J, the join records from the host's rule) */
-void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join) {
+ * machine without a GPU (bubbleFname: -B, the loci from the host resolver; join: -J, the join records from the host's rule; lift: -R, the
+ * lift records from the host's rule) */
+void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join, int lift) {
 	size_t Ln = strlen(fastaFname) + 8;
 	char *annFname = (char *)malloc(Ln);
 	snprintf(annFname, Ln, "%s.ann", fastaFname);
 	fasta_annotations_t *ann = annf2ann(annFname);
 	bubble_table_t *bub = bubbleFname ? load_bubbles(bubbleFname) : NULL;
 	int32_t *bubble_of = bub ? ann_bubble_of(ann, bub) : NULL;
-	int32_t *chrom_of = join ? bubble_chrom_of(ann, bubble_of, bub) : NULL; /* -J (main.c: only with -B and an items file) */
+	if (lift) lift_check_table(bub); /* -R (main.c: only with -B) */
+	int32_t *chrom_of = join || lift ? bubble_chrom_of(ann, bubble_of, bub, join ? "-J" : "-R") : NULL; /* -J (main.c: only with -B and an items file), -R */
 	reads_t *reads = fastq2reads(readsFname);
 	FILE *pf = fopen(placesFname, "rb");
 	if (!pf) { perror(placesFname); bwb_die("places2sam: Cannot open the placements file: %s!", placesFname); }
@@ -366,9 +405,11 @@ void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *sam
 	const int ann_sorted = sam_ann_sorted(ann);
 	bwb_locus *loci = bub ? host_loci(pl, n, ann, ann_sorted, bubble_of, bub) : NULL;
 	bwb_join *joins = join ? host_joins(pl, loci, alt_off, alts, alt_sub, n, ann, ann_sorted, bubble_of, chrom_of, bub, 6) : NULL; /* (aln2sam's default -n: the records carry no max_mm) */
+	lift_set_t *ls = lift ? lift_host(pl, loci, n, alt_off, alts, ann, ann_sorted, bubble_of, chrom_of, bub) : NULL;
 	const sam_reads_t rd = { .pl = pl, .seq = reads->seq, .stride = reads->stride, .len = reads->len, .text = reads->raw,
 	                         .name_off = reads->name_off, .qual_off = reads->qual_off, .name_len = reads->name_len, .first = 0,
-	                         .alt_off = alt_off, .alts = alts, .loci = loci, .bubbles = bub, .joins = joins };
+	                         .alt_off = alt_off, .alts = alts, .loci = loci, .bubbles = bub, .joins = joins,
+	                         .lift_kind = ls ? ls->kind : NULL, .lift_off = ls ? ls->off : NULL, .lift_recs = ls ? ls->recs : NULL, .lift_n = n };
 	for (size_t r0 = 0; r0 < n; r0 += SAM_BLOCK_READS) {
 		size_t len = 0;
 		char *buf = sam_format_reads(&rd, r0, r0 + SAM_BLOCK_READS < n ? r0 + SAM_BLOCK_READS : n, ann, ann_sorted, &len);
@@ -377,7 +418,7 @@ void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *sam
 	}
 	printf("Processed %zu reads.\n", n);
 	free(pl); free(annFname); free(alt_off); free(alts); free(loci); free(bubble_of); free_bubbles(bub);
-	free(alt_sub); free(joins); free(chrom_of);
+	free(alt_sub); free(joins); free(chrom_of); lift_free(ls);
 	free_reads(reads); free_ann(ann);
 	fclose(sam);
 }

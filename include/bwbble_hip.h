@@ -317,7 +317,7 @@ int bwb_hip_locus_stats(bwb_hip_ctx *ctx, uint64_t *reads, double *kernel_ms);
  * (one lane per read: the sums of its class bytes, one 16-byte record).  (Added without a version change: no structure or existing entry
  * point changed.) */
 typedef struct { int32_t top1, top2; uint8_t mapq, joined; uint16_t reserved; uint32_t reserved2; } bwb_join; /* 16 bytes */
-/* After set_loci: the .ann record of the chromosome every bubble lies on.  BWB_E_STATE without set_loci; BWB_E_ARG when n_bub is not set_loci's,
+/* After set_loci: the .ann record of the chromosome every bubble lies on (what -J and -R both need).  BWB_E_STATE without set_loci; BWB_E_ARG when n_bub is not set_loci's,
  * or a value lies outside 0 .. n_seq - 1 or names a bubble record.  set_loci forgets it. */
 int bwb_hip_set_bubble_chrom(bwb_hip_ctx *ctx, const int32_t *chrom_of, uint32_t n_bub);
 /* slot_place_alt and slot_locus (or their cached records), then the two kernels over what they left in device memory, and D2H of n_reads join
@@ -336,6 +336,54 @@ int bwb_hip_join_records(bwb_hip_ctx *ctx, const bwb_place *places, uint32_t n, 
 /* the last join call on the context that launched the kernels: items compared, items joined and the two kernels' HIP-event time (any pointer
  * may be NULL).  A slot_join that returns the slot's cached records launches nothing and leaves these figures as they were. */
 int bwb_hip_join_stats(bwb_hip_ctx *ctx, uint64_t *items, uint64_t *joined, double *kernel_ms);
+
+/* A placement on a bubble record in CHROMOSOME coordinates (`bwbble map -B table -R`): RNAME, POS and CIGAR rewritten, the alternate allele as
+ * an insertion and the positions the record skips as a deletion.  Bubble b = (A, Bm = B_minus_A, C, Dm = D_minus_C, ref_len, alt_len) has a
+ * record of reclen = Bm + alt_len + Dm + 1 characters whose 1-based coordinate x lies in one of three zones:
+ *     L  1 .. Bm                          the chromosome's A + x - 1
+ *     V  Bm + 1 .. Bm + alt_len           no chromosome position (the alternate allele)
+ *     R  Bm + alt_len + 1 .. reclen       the chromosome's C + x - (Bm + alt_len + 1)
+ * gap = C - A - Bm is the number of chromosome positions between the flanks.  It is NOT ref_len: comb gives an allele written `.` a length of 1
+ * in C and of 0 in ref_len, and the flanks' coordinates are what place the M bases.
+ * A placement with printed position pos1 (bwb_locus.pos1) and the CIGAR SAM prints (the M / I / D ops of its gap runs in text order, on either
+ * strand) is LIFTABLE when pos1 >= 1 and pos1 + (the M and D lengths) - 1 <= reclen and an M remains below.  The ops are walked with x running
+ * from pos1:  I stays I;  M on an x in L or R stays M, on an x in V it becomes I;  D on an x in L or R stays D, on an x in V it disappears;  when
+ * the walk consumes x = Bm + alt_len + 1 after a smaller x and gap > 0, D x gap comes first (so: the allele's I, then the D);  before the first
+ * and behind the last M, I becomes S (a soft clip) and D is dropped;  POS is the chromosome position of the first M;  neighbouring ops of one
+ * kind are merged (while the sum stays below 2^28).  At most BWB_LIFT_MAX_OPS ops remain: 17 runs and the three the allele adds.
+ * The index space is the PLACEMENTS of n_reads reads: q < n_reads is read q's primary (bwb_place), n_reads + j is item j (bwb_alt).  Per
+ * placement one kind byte - BWB_LIFT_NONE: not on a bubble record, or unmapped; BWB_LIFT_LIFTED; BWB_LIFT_UNLIFTABLE: on a bubble record, printed
+ * as it is - and for a lifted one a record of 16-byte words at recs + lift_off[q]: the header below, then n_ops ops as uint32 = len << 4 | op,
+ * padded with zeros to a multiple of four.  lift_off has one entry per placement and one more; the buffers hold the records there are.
+ * Kernels k_lift_count (one lane per placement: the kind byte and the record's size), the exclusive scan of k_place_alt, and k_lift, behind
+ * k_place_alt / k_locus on the result stream.  (Added without a version change: no structure or existing entry point changed.) */
+#define BWB_LIFT_M 0
+#define BWB_LIFT_I 1
+#define BWB_LIFT_D 2
+#define BWB_LIFT_S 4
+#define BWB_LIFT_MAX_OPS 20
+#define BWB_LIFT_NONE 0
+#define BWB_LIFT_LIFTED 1
+#define BWB_LIFT_UNLIFTABLE 2
+typedef struct { int64_t pos; int32_t seqid; uint8_t n_ops, reserved[3]; } bwb_lift; /* 16 bytes: POS, the chromosome's .ann record, the ops that follow */
+/* slot_locus and, with max_alt 1..255, slot_place_alt (or their cached records; max_alt 0: the primaries alone), then the kernels over what they
+ * left in device memory, and D2H into pinned memory of the slot, valid until the next slot_lift on that slot or its next upload.  *n_placements = n_reads + the items.
+ * The same records whether it is called before or after slot_place_alt / slot_locus / slot_join / slot_result.  BWB_E_ARG for max_alt outside
+ * 0..255 and for a bubble table the rule refuses - gap < 0, gap >= 2^28, alt_len < 0, Bm < 0 or Dm < -1; the message names the bubble -;
+ * BWB_E_STATE without set_sa, set_loci or set_bubble_chrom, or on a slot that has not been submitted; the context stays usable after each.
+ * batch_lift is the one-batch form. */
+int bwb_hip_slot_lift(bwb_hip_ctx *ctx, int slot, int max_mm, int max_alt, const uint8_t **kinds, const uint64_t **lift_off, const bwb_lift **recs,
+                      uint64_t *n_placements);
+int bwb_hip_batch_lift(bwb_hip_ctx *ctx, int max_mm, int max_alt, const uint8_t **kinds, const uint64_t **lift_off, const bwb_lift **recs,
+                       uint64_t *n_placements);
+/* The same kernels (and k_locus for the primaries) on records of the caller's: read r owns alts[alt_off[r] .. alt_off[r + 1]), alt_off[0] == 0.
+ * kinds, lift_off and recs point into memory of the context, valid until the next lift_records call on it.  Needs set_loci and set_bubble_chrom;
+ * touches no slot.  BWB_E_ARG when alt_off does not ascend or n + the items exceed 2^31 - 1.  For parity tests. */
+int bwb_hip_lift_records(bwb_hip_ctx *ctx, const bwb_place *places, uint32_t n, const uint64_t *alt_off, const bwb_alt *alts,
+                         const uint8_t **kinds, const uint64_t **lift_off, const bwb_lift **recs);
+/* the last lift call on the context that launched the kernels: placements lifted, placements on a bubble record that are not liftable, and the
+ * kernels' HIP-event time (any pointer may be NULL) */
+int bwb_hip_lift_stats(bwb_hip_ctx *ctx, uint64_t *lifted, uint64_t *unliftable, double *kernel_ms);
 
 #ifdef __cplusplus
 }
