@@ -27,6 +27,7 @@ EXPORTS = [
     "bwb_hip_set_loci", "bwb_hip_slot_locus", "bwb_hip_batch_locus", "bwb_hip_locus_places", "bwb_hip_locus_stats",
     "bwb_hip_set_bubble_chrom", "bwb_hip_slot_join", "bwb_hip_batch_join", "bwb_hip_join_records", "bwb_hip_join_stats",
     "bwb_hip_slot_lift", "bwb_hip_batch_lift", "bwb_hip_lift_records", "bwb_hip_lift_stats",
+    "bwb_hip_set_text", "bwb_hip_slot_md", "bwb_hip_batch_md", "bwb_hip_md_records", "bwb_hip_md_stats",
 ]
 ABI_VERSION = 3  # BWB_HIP_ABI_VERSION (include/bwbble_hip.h)
 MAX_SLOTS = 8  # BWB_MAX_SLOTS
@@ -80,6 +81,10 @@ LIFT_DTYPE = np.dtype([("pos", "<i8"), ("seqid", "<i4"), ("n_ops", "u1"), ("rese
 assert LIFT_DTYPE.itemsize == 16
 LIFT_M, LIFT_I, LIFT_D, LIFT_S, LIFT_MAX_OPS = 0, 1, 2, 4, 20
 LIFT_NONE, LIFT_LIFTED, LIFT_UNLIFTABLE = 0, 1, 2
+# bwb_md: a read's NM and the length of its MD text against the index's text (kernels k_md_count / k_md)
+MD_DTYPE = np.dtype([("nm", "<u4"), ("md_len", "<u2"), ("kind", "u1"), ("reserved", "u1")])
+assert MD_DTYPE.itemsize == 8
+MD_NONE, MD_OK, MD_TOO_LONG, MD_MAX_SPAN = 0, 1, 2, 4096
 
 _FLAG = {"-M": "mm_score", "-O": "gapo_score", "-E": "gape_score", "-n": "max_diff", "-k": "max_diff_seed",
          "-o": "max_gapo", "-e": "max_gape", "-l": "seed_length", "-m": "max_entries", "-t": "n_threads"}
@@ -151,6 +156,11 @@ def lib():
         L.bwb_hip_batch_lift.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(C.c_uint64)]
         L.bwb_hip_lift_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p] + [C.POINTER(C.c_void_p)] * 3
         L.bwb_hip_lift_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.bwb_hip_set_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.bwb_hip_slot_md.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(C.c_uint32)]
+        L.bwb_hip_batch_md.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(C.c_uint32)]
+        L.bwb_hip_md_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p] + [C.POINTER(C.c_void_p)] * 3
+        L.bwb_hip_md_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -538,6 +548,57 @@ class Context:
         """(placements lifted, placements not liftable, kernel ms) of the last lift call"""
         return self._count_steps_ms(lib().bwb_hip_lift_stats)
 
+    # -- NM:i and MD:Z against the index's text (-D): per read an MD_DTYPE record and, for kind MD_OK, its MD bytes (needs set_text; the slot forms
+    #    set_sa, and with lifted set_loci and set_bubble_chrom) --
+    def set_text(self, codes):
+        """the forward text, one code 0..15 per character (see read_ref()): packed to 4 bits per character on the device.  Before the first upload"""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        _chk(lib().bwb_hip_set_text(self._h, codes.ctypes.data, len(codes)))
+
+    @staticmethod
+    def _md(p, n):
+        recs = np.frombuffer(C.string_at(p[0], n * MD_DTYPE.itemsize), dtype=MD_DTYPE).copy() if n else np.zeros(0, dtype=MD_DTYPE)
+        off = np.frombuffer(C.string_at(p[1], (n + 1) * 8), dtype=np.uint64).copy()
+        return recs, off, C.string_at(p[2], int(off[-1])) if int(off[-1]) else b""
+
+    def slot_md(self, slot, max_mm=6, max_alt=5, lifted=False):
+        """(recs, md_off, text): read r's MD text is text[md_off[r]:md_off[r + 1]].  lifted: the primaries slot_lift(max_mm, max_alt) lifts are
+        walked by their lift records"""
+        p = [C.c_void_p() for _ in range(3)]
+        n = C.c_uint32()
+        _chk(lib().bwb_hip_slot_md(self._h, slot, max_mm, max_alt, int(bool(lifted)), *[C.byref(x) for x in p], C.byref(n)))
+        return self._md(p, n.value)
+
+    def batch_md(self, max_mm=6, max_alt=5, lifted=False):
+        """the same for the one-batch interface (after run() / align())"""
+        p = [C.c_void_p() for _ in range(3)]
+        n = C.c_uint32()
+        _chk(lib().bwb_hip_batch_md(self._h, max_mm, max_alt, int(bool(lifted)), *[C.byref(x) for x in p], C.byref(n)))
+        return self._md(p, n.value)
+
+    def md_records(self, seqs, lens, places, kinds=None, lift_off=None, words=None):
+        """the same kernels on reads and placement records of the caller's; kinds / lift_off / words: every read's lift kind and the 16-byte words
+        of the lifted ones' records, laid out as slot_lift() returns them for its primaries"""
+        seqs, lens = _read_arrays(seqs, lens)
+        places = np.ascontiguousarray(places, dtype=PLACE_DTYPE)
+        if len(places) != len(lens):
+            raise ValueError("one placement record per read")
+        lift = [None, None, None]
+        if kinds is not None:
+            kinds = np.ascontiguousarray(kinds, dtype=np.uint8)
+            lift_off = np.ascontiguousarray(lift_off, dtype=np.uint64)
+            words = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, 4)
+            if len(kinds) != len(lens) or len(lift_off) != len(lens) + 1 or len(words) != int(lift_off[-1]):
+                raise ValueError("kinds must have one entry per read, lift_off one more, words one row per 16-byte word")
+            lift = [kinds.ctypes.data, lift_off.ctypes.data, words.ctypes.data]
+        p = [C.c_void_p() for _ in range(3)]
+        _chk(lib().bwb_hip_md_records(self._h, seqs.ctypes.data, lens.ctypes.data, seqs.shape[1], places.ctypes.data, len(lens), *lift, *[C.byref(x) for x in p]))
+        return self._md(p, len(lens))
+
+    def md_stats(self):
+        """(reads of kind MD_OK, MD bytes, kernel ms) of the last md call"""
+        return self._count_steps_ms(lib().bwb_hip_md_stats)
+
     def dtab_info(self):
         """the context's calculate_d table: {K (0: none), build seconds, bytes}"""
         k, sec, nb = C.c_int(), C.c_double(), C.c_uint64()
@@ -558,6 +619,15 @@ def read_ann(path):
         n = int(f.readline().split("\t")[1])
         rows = [f.readline().rstrip("\n").split("\t") for _ in range(n)]
     return ([r[0] for r in rows], np.array([int(r[1]) for r in rows], dtype=np.uint64), np.array([int(r[2]) for r in rows], dtype=np.uint64))
+
+
+def read_ref(path_fa):
+    """the forward text of <fasta>.ref (`bwbble index` / `fasta2ref`): one code per byte, n_fwd = the first number of <fasta>.ann"""
+    with open(str(path_fa) + ".ann") as f:
+        n_fwd = int(f.readline().split("\t")[0])
+    if os.path.getsize(str(path_fa) + ".ref") != 2 * n_fwd:
+        raise ValueError(f"{path_fa}.ref: not 2 x {n_fwd} bytes (bwbble fasta2ref writes it)")
+    return np.fromfile(str(path_fa) + ".ref", dtype=np.uint8, count=n_fwd)
 
 
 def read_bubble_data(path):

@@ -107,6 +107,12 @@ struct LiftBufs {
 	PinMem h_kind, h_off, h_recs;
 };
 
+/* the buffers of one md call: one bwb_md per read, the MD lengths, their exclusive scan and its block sums, the MD bytes; and what the host gets */
+struct MdBufs {
+	DevMem d_recs, d_cnt, d_off, d_bsum, d_text;
+	PinMem h_recs, h_off, h_text;
+};
+
 /* per-lane scratch of one class (class 0 = every resident lane, classes 1/2 = fewer lanes with larger lists) */
 struct ScratchClass {
 	DevMem mem;
@@ -138,6 +144,8 @@ struct Slot {
 	int join_mm = -1, join_alt = -1; /* h_join holds the records for this max_mm and max_alt (-1: none) */
 	LiftBufs lift;                /* bwb_hip_slot_lift */
 	int lift_mm = -1, lift_alt = -1; /* lift holds the records for this max_mm and max_alt (-1: none) */
+	MdBufs md;                    /* bwb_hip_slot_md */
+	int md_mm = -1, md_alt = -1, md_lifted = -1; /* md holds the records for this max_mm, and with lifted for this max_alt (-1: none) */
 	std::vector<uint8_t> h_status;
 	std::vector<uint64_t> h_aln_off;
 	std::vector<bwb_aln> h_alns;
@@ -196,6 +204,9 @@ struct bwb_hip_ctx {
 	std::string lift_refusal;                     /* set_loci: why the rule of bwb_lift refuses the bubble table (empty: it does not) */
 	LiftBufs lift_rec;                            /* bwb_hip_lift_records */
 	double lift_ms = 0; uint64_t lift_lifted = 0, lift_unliftable = 0; /* the last lift call */
+	DevMem d_text; uint64_t text_n = 0;           /* k_md_count / k_md: the forward text at 4 bits per character (bwb_hip_set_text; 0: none) */
+	MdBufs md_rec;                                /* bwb_hip_md_records */
+	double md_ms = 0; uint64_t md_reads = 0, md_bytes = 0; /* the last md call */
 	bool force_slices = false;          /* BWB_FORCE_SLICES: the one-batch API parks and resumes too (tests) */
 	bool dbg = false, dbg_iters = false;
 	const char *launch_log = nullptr;   /* BWB_LAUNCH_LOG=<file>: one JSON line per class-0 kernel launch (synchronises after every launch: a profiling aid) */
@@ -768,7 +779,7 @@ extern "C" int bwb_hip_slot_upload(bwb_hip_ctx *c, int si, const bwb_params *p, 
 	/* (pageable source: the runtime stages it before returning, so h_descs may change again right away) */
 	HIPCHK(hipMemcpyAsync(c->d_descs.as<SlotDesc>() + si, &d, sizeof(SlotDesc), hipMemcpyHostToDevice, c->cstream));
 	HIPCHK(hipEventRecord(s.ev_up.e, c->cstream));
-	s.uploaded = true; s.submitted = false; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.join_mm = -1; s.lift_mm = -1;
+	s.uploaded = true; s.submitted = false; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.join_mm = -1; s.lift_mm = -1; s.md_mm = -1;
 	return ensure_class(c, 0);
 }
 
@@ -1016,7 +1027,7 @@ static int submit(bwb_hip_ctx *c, int si, bool suspend) {
 		HIPCHK(hipStreamWaitEvent(c->stream, s.ev_calcd.e, 0));
 	}
 	HIPCHK(hipMemsetAsync(s.d_ctl.p, 0, 256, c->stream));
-	s.submitted = true; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.join_mm = -1; s.lift_mm = -1; s.launch = 0;
+	s.submitted = true; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.join_mm = -1; s.lift_mm = -1; s.md_mm = -1; s.launch = 0;
 	if (s.n_reads == 0) { s.complete = true; s.launch = c->n_launches; return BWB_OK; }
 	HIPCHK(hipMemsetAsync(s.d_n.p, 0, (size_t)s.n_reads * 4, c->stream));
 	if (!ahead) {
@@ -1748,7 +1759,7 @@ extern "C" int bwb_hip_set_loci(bwb_hip_ctx *c, const uint64_t *start, const uin
 	HIPCHK(hipSetDevice(c->device));
 	c->loci_nseq = 0; /* (no tables until all four are resident) */
 	c->chrom_set = false;
-	for (auto &s : c->slots) { s.locus_mm = -1; s.join_mm = -1; s.lift_mm = -1; }
+	for (auto &s : c->slots) { s.locus_mm = -1; s.join_mm = -1; s.lift_mm = -1; s.md_mm = -1; }
 	c->lift_refusal = lift_table_refusal(bubbles, n_bub);
 	HIPCHK(c->d_lstart.alloc((size_t)n_seq * 8));
 	HIPCHK(c->d_lend.alloc((size_t)n_seq * 8));
@@ -1848,7 +1859,7 @@ extern "C" int bwb_hip_set_bubble_chrom(bwb_hip_ctx *c, const int32_t *chrom_of,
 			                           std::to_string(c->loci_nseq) + " records");
 	HIPCHK(hipSetDevice(c->device));
 	c->chrom_set = false;
-	for (auto &s : c->slots) { s.join_mm = -1; s.lift_mm = -1; }
+	for (auto &s : c->slots) { s.join_mm = -1; s.lift_mm = -1; s.md_mm = -1; }
 	HIPCHK(c->d_chrom.alloc((size_t)n_bub * 4));
 	if (n_bub) {
 		HIPCHK(hipMemcpyAsync(c->d_chrom.p, chrom_of, (size_t)n_bub * 4, hipMemcpyHostToDevice, c->rstream));
@@ -2104,6 +2115,184 @@ extern "C" int bwb_hip_lift_stats(bwb_hip_ctx *c, uint64_t *lifted, uint64_t *un
 	if (lifted) *lifted = c->lift_lifted;
 	if (unliftable) *unliftable = c->lift_unliftable;
 	if (kernel_ms) *kernel_ms = c->lift_ms;
+	return BWB_OK;
+}
+
+/* ---- NM:i and MD:Z against the text: bwb_md records and the MD bytes (k_text_pack, k_md_count, k_md) ------------------------------------ */
+static_assert(sizeof(bwb_md) == 8, "bwb_md is one 8-byte word (k_md_count)");
+static_assert(BWB_MD_NONE == MD_NONE && BWB_MD_OK == MD_OK && BWB_MD_TOO_LONG == MD_TOO_LONG && BWB_MD_MAX_SPAN == MD_MAX_SPAN, "the kernels' kinds are the header's");
+#ifndef BWB_TEXT_CHUNK_SHIFT
+#define BWB_TEXT_CHUNK_SHIFT (BWB_IDX_CHUNK_SHIFT + 5) /* text characters per staged chunk of set_text = 2^25 (the test build: 2^15, so that a text of 40 000 characters takes two) */
+#endif
+extern "C" int bwb_hip_set_text(bwb_hip_ctx *c, const uint8_t *codes, uint64_t n_fwd) {
+	if (!c || !codes || !n_fwd) return fail(BWB_E_ARG, "set_text: null argument or an empty text");
+	HIPCHK(hipSetDevice(c->device));
+	HIPCHK(hipStreamSynchronize(c->rstream)); /* (a kernel of an earlier md call may still read the text that is replaced) */
+	c->text_n = 0;
+	for (auto &s : c->slots) s.md_mm = -1;
+	const uint64_t CH = 1ull << BWB_TEXT_CHUNK_SHIFT, n_words = (n_fwd + 31) / 32;
+	HIPCHK(c->d_text.alloc((size_t)n_words * 16));
+	DevMem d_stage, d_bad;
+	HIPCHK(d_stage.alloc((size_t)std::min<uint64_t>(CH, n_words * 32)));
+	HIPCHK(d_bad.alloc(4));
+	HIPCHK(hipMemsetAsync(d_bad.p, 0, 4, c->rstream));
+	for (uint64_t c0 = 0; c0 < n_fwd; c0 += CH) { /* (CH is a multiple of 32: every chunk begins a 16-byte word of the packed text) */
+		const uint64_t nc = std::min<uint64_t>(CH, n_fwd - c0), nw = (nc + 31) / 32;
+		HIPCHK(hipMemcpyAsync(d_stage.p, codes + c0, (size_t)nc, hipMemcpyHostToDevice, c->rstream));
+		const unsigned grid = (unsigned)std::min<uint64_t>((nw + BWB_BLOCK - 1) / BWB_BLOCK, (uint64_t)c->num_cu * 8);
+		hipLaunchKernelGGL(k_text_pack, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, d_stage.as<uint8_t>(), nc, c->d_text.as<uint4>() + c0 / 32, d_bad.as<uint32_t>());
+		HIPCHK(hipGetLastError());
+	}
+	uint32_t bad = 0;
+	HIPCHK(hipMemcpyAsync(&bad, d_bad.p, 4, hipMemcpyDeviceToHost, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	if (bad) { c->d_text.release(); return fail(BWB_E_ARG, "set_text: the text holds a code above 15"); }
+	c->text_n = n_fwd;
+	return BWB_OK;
+}
+
+/* k_md_count, the scan and k_md over n reads (reads, lengths, placement records and - d_kind NULL: none - lift records, all device memory) ->
+ * mb.h_recs[n], mb.h_off[n + 1] and mb.h_text[h_off[n]]; sets the context's md_ms / md_reads / md_bytes.  On the result stream, behind the kernels
+ * that wrote the records.  The only host round trip is the read of the total, which sizes the text buffers: they hold the bytes there are.  Eight
+ * blocks per CU, the grid of k_locus and the lift kernels: a lane's walk is a chain of dependent loads, and the waves beside it are what hides
+ * their latency.  Shared by slot_md and md_records. */
+static int md_launch(bwb_hip_ctx *c, const uint8_t *d_reads, const uint16_t *d_lens, uint32_t stride, const uint4 *d_places, uint32_t n, const uint8_t *d_kind, const uint64_t *d_loff,
+                     const uint4 *d_lrecs, MdBufs &mb) {
+	c->md_ms = 0; c->md_reads = 0; c->md_bytes = 0;
+	HIPCHK(mb.h_off.reserve(((size_t)n + 1) * 8));
+	HIPCHK(mb.h_recs.reserve((size_t)n * sizeof(bwb_md)));
+	HIPCHK(mb.h_text.reserve(1));
+	mb.h_off.as<uint64_t>()[0] = 0;
+	if (!n) return BWB_OK;
+	const unsigned nblk = (unsigned)(((size_t)n + BWB_BLOCK - 1) / BWB_BLOCK);
+	const unsigned grid = (unsigned)std::min<size_t>(nblk, (size_t)c->num_cu * 8);
+	HIPCHK(mb.d_recs.reserve((size_t)n * sizeof(bwb_md)));
+	HIPCHK(mb.d_cnt.reserve((size_t)n * 4));
+	HIPCHK(mb.d_off.reserve(((size_t)n + 1) * 8));
+	HIPCHK(mb.d_bsum.reserve((size_t)nblk * 8));
+	uint64_t *d_off = mb.d_off.as<uint64_t>();
+	const uint32_t n_seq = d_kind ? c->loci_nseq : 0u;
+	Timed t_count(c, c->rstream), t_md(c, c->rstream); /* k_md_count and the scan; k_md */
+	RC(t_count.begin());
+	hipLaunchKernelGGL(k_md_count, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, d_reads, d_lens, stride, d_places, n, d_kind, d_loff, d_lrecs, c->d_lstart.as<uint64_t>(), n_seq,
+	                   c->d_text.as<uint4>(), c->text_n, mb.d_recs.as<uint2>(), mb.d_cnt.as<uint32_t>());
+	hipLaunchKernelGGL(k_scan_blocks, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, mb.d_cnt.as<uint32_t>(), n, d_off, mb.d_bsum.as<uint64_t>());
+	hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(BWB_BLOCK), 0, c->rstream, mb.d_bsum.as<uint64_t>(), (uint32_t)nblk, d_off + n);
+	hipLaunchKernelGGL(k_scan_add, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, d_off, n, mb.d_bsum.as<uint64_t>());
+	HIPCHK(hipGetLastError());
+	RC(t_count.end());
+	HIPCHK(hipMemcpyAsync(mb.h_off.p, d_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, c->rstream));
+	HIPCHK(hipMemcpyAsync(mb.h_recs.p, mb.d_recs.p, (size_t)n * sizeof(bwb_md), hipMemcpyDeviceToHost, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	const uint64_t total = mb.h_off.as<uint64_t>()[n];
+	float ms = 0, ms2 = 0;
+	RC(t_count.ms(&ms));
+	if (total) {
+		HIPCHK(mb.d_text.reserve((size_t)total));
+		HIPCHK(mb.h_text.reserve((size_t)total));
+		RC(t_md.begin());
+		hipLaunchKernelGGL(k_md, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, d_reads, d_lens, stride, d_places, n, d_kind, d_loff, d_lrecs, c->d_lstart.as<uint64_t>(), n_seq,
+		                   c->d_text.as<uint4>(), mb.d_recs.as<uint2>(), (const uint64_t *)d_off, mb.d_text.as<char>());
+		HIPCHK(hipGetLastError());
+		RC(t_md.end());
+		HIPCHK(hipMemcpyAsync(mb.h_text.p, mb.d_text.p, (size_t)total, hipMemcpyDeviceToHost, c->rstream));
+		HIPCHK(hipStreamSynchronize(c->rstream));
+		RC(t_md.ms(&ms2));
+	}
+	c->md_ms = (double)ms + ms2;
+	c->md_bytes = total;
+	const bwb_md *recs = mb.h_recs.as<bwb_md>();
+	for (uint32_t q = 0; q < n; q++) c->md_reads += recs[q].kind == BWB_MD_OK;
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_slot_md(bwb_hip_ctx *c, int si, int max_mm, int max_alt, int lifted, const bwb_md **recs, const uint64_t **md_off, const char **md_text, uint32_t *n_reads) {
+	if (!c || !recs || !md_off || !md_text || !n_reads || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_md: bad argument");
+	if (!c->text_n) return fail(BWB_E_STATE, "slot_md: the text has not been uploaded (bwb_hip_set_text)");
+	if (!c->d_SA.p) return fail(BWB_E_STATE, "slot_md: sampled SA not uploaded (bwb_hip_set_sa)");
+	/* (both wait for the slot, refuse what slot_place refuses, and leave their records in the slot's device memory) */
+	const bwb_place *places = nullptr;
+	uint32_t n = 0;
+	if (lifted) {
+		const uint8_t *kinds = nullptr;
+		const uint64_t *lift_off = nullptr;
+		const bwb_lift *lrecs = nullptr;
+		uint64_t nq = 0;
+		RC(bwb_hip_slot_lift(c, si, max_mm, max_alt, &kinds, &lift_off, &lrecs, &nq));
+	} else RC(bwb_hip_slot_place(c, si, max_mm, &places, &n));
+	Slot &s = c->slots[si];
+	n = s.n_reads; /* (not n_tot: a carried read that rides along behind the batch's reads has no record) */
+	/* (cached records launch nothing and leave md_stats at the last launch's figures, whichever slot's: a caller that sums them - retire_map -
+	 * asks every slot once) */
+	if (s.md_mm != max_mm || s.md_lifted != (lifted ? 1 : 0) || (lifted && s.md_alt != max_alt) || !n) {
+		HIPCHK(hipStreamWaitEvent(c->rstream, s.ev_up.e, 0)); /* (the slot's reads, uploaded on the copy stream) */
+		/* (a slot whose every placement lies on no bubble record has no lift records at all: d_recs may be NULL, and no lane reads it) */
+		RC(md_launch(c, s.d_reads.as<uint8_t>(), s.d_lens.as<uint16_t>(), s.stride, s.d_place.as<uint4>(), n, lifted ? s.lift.d_kind.as<uint8_t>() : nullptr,
+		             s.lift.d_off.as<uint64_t>(), s.lift.d_recs.as<uint4>(), s.md));
+		s.md_mm = max_mm; s.md_alt = max_alt; s.md_lifted = lifted ? 1 : 0;
+	}
+	*recs = s.md.h_recs.as<bwb_md>();
+	*md_off = s.md.h_off.as<uint64_t>();
+	*md_text = s.md.h_text.as<char>();
+	*n_reads = n;
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_batch_md(bwb_hip_ctx *c, int max_mm, int max_alt, int lifted, const bwb_md **recs, const uint64_t **md_off, const char **md_text, uint32_t *n_reads) {
+	if (!c || !recs || !md_off || !md_text || !n_reads) return fail(BWB_E_ARG, "batch_md: null argument");
+	if (!c->text_n) return fail(BWB_E_STATE, "batch_md: the text has not been uploaded (bwb_hip_set_text)");
+	if (!c->d_SA.p) return fail(BWB_E_STATE, "batch_md: sampled SA not uploaded (bwb_hip_set_sa)");
+	if (!c->slots[0].submitted || !c->slots[0].complete) return fail(BWB_E_STATE, "batch_md: batch_run has not completed");
+	return bwb_hip_slot_md(c, 0, max_mm, max_alt, lifted, recs, md_off, md_text, n_reads);
+}
+
+/* the kernels on reads and records of the caller's instead of a slot's (for parity tests) */
+extern "C" int bwb_hip_md_records(bwb_hip_ctx *c, const uint8_t *reads_fwd, const uint16_t *lens, uint32_t stride, const bwb_place *places, uint32_t n, const uint8_t *kinds,
+                                  const uint64_t *lift_off, const bwb_lift *lift_recs, const bwb_md **recs, const uint64_t **md_off, const char **md_text) {
+	if (!c || !recs || !md_off || !md_text || (n && (!reads_fwd || !lens || !places)) || n > 0x7FFFFFFFu || stride < 1 || stride > 255) return fail(BWB_E_ARG, "md_records: bad argument");
+	if ((kinds != nullptr) != (lift_off != nullptr)) return fail(BWB_E_ARG, "md_records: the lift kinds and offsets come together");
+	if (!c->text_n) return fail(BWB_E_STATE, "md_records: the text has not been uploaded (bwb_hip_set_text)");
+	if (kinds && !c->loci_nseq) return fail(BWB_E_STATE, "md_records: lift records need the record table (bwb_hip_set_loci)");
+	uint64_t words = 0;
+	if (kinds) {
+		if (lift_off[0] != 0) return fail(BWB_E_ARG, "md_records: lift_off[0] must be 0");
+		for (uint32_t r = 0; r < n; r++)
+			if (lift_off[r + 1] < lift_off[r]) return fail(BWB_E_ARG, "md_records: lift_off does not ascend at read " + std::to_string(r));
+		words = lift_off[n];
+		if (words && !lift_recs) return fail(BWB_E_ARG, "md_records: null argument");
+	}
+	HIPCHK(hipSetDevice(c->device));
+	DevMem d_reads, d_lens, d_places, d_kind, d_loff, d_lrecs;
+	HIPCHK(d_reads.alloc((size_t)n * stride));
+	HIPCHK(d_lens.alloc((size_t)n * 2));
+	HIPCHK(d_places.alloc((size_t)n * sizeof(bwb_place)));
+	if (n) {
+		HIPCHK(hipMemcpyAsync(d_reads.p, reads_fwd, (size_t)n * stride, hipMemcpyHostToDevice, c->rstream));
+		HIPCHK(hipMemcpyAsync(d_lens.p, lens, (size_t)n * 2, hipMemcpyHostToDevice, c->rstream));
+		HIPCHK(hipMemcpyAsync(d_places.p, places, (size_t)n * sizeof(bwb_place), hipMemcpyHostToDevice, c->rstream));
+	}
+	if (kinds) {
+		HIPCHK(d_kind.alloc((size_t)n));
+		HIPCHK(d_loff.alloc(((size_t)n + 1) * 8));
+		HIPCHK(d_lrecs.alloc((size_t)words * sizeof(bwb_lift)));
+		if (n) HIPCHK(hipMemcpyAsync(d_kind.p, kinds, (size_t)n, hipMemcpyHostToDevice, c->rstream));
+		HIPCHK(hipMemcpyAsync(d_loff.p, lift_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->rstream));
+		if (words) HIPCHK(hipMemcpyAsync(d_lrecs.p, lift_recs, (size_t)words * sizeof(bwb_lift), hipMemcpyHostToDevice, c->rstream));
+	}
+	HIPCHK(hipStreamSynchronize(c->rstream)); /* (pageable memory of the caller) */
+	RC(md_launch(c, d_reads.as<uint8_t>(), d_lens.as<uint16_t>(), stride, d_places.as<uint4>(), n, kinds ? d_kind.as<uint8_t>() : nullptr, d_loff.as<uint64_t>(), d_lrecs.as<uint4>(), c->md_rec));
+	*recs = c->md_rec.h_recs.as<bwb_md>();
+	*md_off = c->md_rec.h_off.as<uint64_t>();
+	*md_text = c->md_rec.h_text.as<char>();
+	return BWB_OK;
+}
+
+/* the last md call: reads that got their tags, MD bytes written, and the kernels' HIP-event time */
+extern "C" int bwb_hip_md_stats(bwb_hip_ctx *c, uint64_t *reads, uint64_t *md_bytes, double *kernel_ms) {
+	if (!c) return fail(BWB_E_ARG, "md_stats: null context");
+	if (reads) *reads = c->md_reads;
+	if (md_bytes) *md_bytes = c->md_bytes;
+	if (kernel_ms) *kernel_ms = c->md_ms;
 	return BWB_OK;
 }
 

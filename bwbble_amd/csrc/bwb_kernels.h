@@ -10,6 +10,7 @@
  *   k_locus      the .ann record of every placement record and, on a bubble record, its reference coordinates (`bwbble map -B`)
  *   k_join_items, k_join_reads   a read's other placements that lie where its primary lies, and its MAPQ without them (`bwbble map -J`)
  *   k_lift_count, k_lift         a placement on a bubble record in the chromosome's coordinates: POS and CIGAR (`bwbble map -R`)
+ *   k_text_pack, k_md_count, k_md   the forward text at 4 bits per character, and a read's NM and MD text against it (`bwbble map -D`)
  * The alignment kernels themselves (kl_calc_d, kl_search: one read per lane) are in bwb_lane.h.
  */
 #pragma once
@@ -848,5 +849,172 @@ __global__ __launch_bounds__(BWB_BLOCK) void k_lift(const uint4 *places, uint32_
 		const uint64_t cap = lift_off[q + 1] - o; /* (k_lift_count sized it from the same walk; nothing is stored beyond it) */
 		if (cap < 2u || cap > 6u) continue;
 		lift_walk(lift_bubble(bub, v.b), v.pos1, v.reverse, v.alen, v.runs, chrom_of[v.b], out + o, (uint32_t)cap);
+	}
+}
+
+/* ---- NM:i and MD:Z of a read's line against the text (`map -D`) ---------------------------------------------------------------------
+ * The rule is in include/bwbble_hip.h (bwb_md).  The text lies in device memory at 4 bits per character: character i is nibble i & 7 of the
+ * 32-bit word i >> 3, so that an aligned 16-byte word holds 32 characters.  k_text_pack makes that of a staged chunk of one-byte codes: one
+ * lane per 16-byte word, the 32 codes by two 16-byte loads (the last word of the text, which may hold fewer, byte by byte; what lies beyond
+ * the text is 0); a code above 15 sets *bad. */
+__device__ __forceinline__ uint32_t text_pack4(uint32_t v) { return (v & 0xFu) | ((v >> 4) & 0xF0u) | ((v >> 8) & 0xF00u) | ((v >> 12) & 0xF000u); }
+__global__ __launch_bounds__(BWB_BLOCK) void k_text_pack(const uint8_t *codes /* 16-byte aligned */, uint64_t n_chunk, uint4 *packed, uint32_t *bad) {
+	const uint64_t stride = (uint64_t)gridDim.x * BWB_BLOCK, n_words = (n_chunk + 31u) >> 5;
+	for (uint64_t w = (uint64_t)blockIdx.x * BWB_BLOCK + threadIdx.x; w < n_words; w += stride) {
+		uint32_t src[8] = { 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u };
+		if (w * 32u + 32u <= n_chunk) {
+			const uint4 a = ((const uint4 *)codes)[w * 2u], b = ((const uint4 *)codes)[w * 2u + 1u];
+			src[0] = a.x; src[1] = a.y; src[2] = a.z; src[3] = a.w; src[4] = b.x; src[5] = b.y; src[6] = b.z; src[7] = b.w;
+		} else
+			for (uint64_t i = w * 32u; i < n_chunk; i++) src[(i & 31u) >> 2] |= (uint32_t)codes[i] << ((i & 3u) * 8u);
+		uint32_t over = 0;
+#pragma unroll
+		for (int k = 0; k < 8; k++) over |= src[k] & 0xF0F0F0F0u;
+		if (over) atomicOr(bad, 1u);
+		packed[w] = make_uint4(text_pack4(src[0]) | (text_pack4(src[1]) << 16), text_pack4(src[2]) | (text_pack4(src[3]) << 16),
+		                       text_pack4(src[4]) | (text_pack4(src[5]) << 16), text_pack4(src[6]) | (text_pack4(src[7]) << 16));
+	}
+}
+
+/* One lane per READ, grid-strided.  A lane walks its read's ops - the printed CIGAR of its placement one path position at a time (lift_op_at, as
+ * k_lift walks it), or the ops of its lift record - with the read base from the slot's resident reads and the text's code from the 16-byte word
+ * the lane holds in registers: a read of 100 bases loads four or five of them.  k_md_count walks for the kind, NM and the exact length of the MD
+ * text; the scan of k_place_alt turns the lengths into md_off[]; k_md walks the reads of kind BWB_MD_OK again and stores the bytes.  Every text
+ * position fetched lies in [0, n_fwd) - k_md_count has checked the span before either kernel walks -, every read base in [0, len), and k_md
+ * stores nothing beyond the length k_md_count left. */
+#define MD_NONE 0u
+#define MD_OK 1u
+#define MD_TOO_LONG 2u
+#define MD_MAX_SPAN 4096u
+/* eight letters as the bytes of one 64-bit constant, the first lowest: a register, not a table in memory */
+__host__ __device__ constexpr uint64_t md_letters8(const char (&s)[9]) {
+	return (uint64_t)(uint8_t)s[0] | (uint64_t)(uint8_t)s[1] << 8 | (uint64_t)(uint8_t)s[2] << 16 | (uint64_t)(uint8_t)s[3] << 24 | (uint64_t)(uint8_t)s[4] << 32 |
+	       (uint64_t)(uint8_t)s[5] << 40 | (uint64_t)(uint8_t)s[6] << 48 | (uint64_t)(uint8_t)s[7] << 56;
+}
+static_assert((md_letters8("NTKGSBYC") & 0xFF) == 'N' && (md_letters8("MHNVRDWA") >> 16 & 0xFF) == 'N' && (md_letters8("MHNVRDWA") >> 56) == 'A', "code 0 prints N, code 10 N, code 15 A");
+struct MdWalk {
+	const uint4 *text; uint64_t cur; uint4 w;             /* the packed text and the word held */
+	const uint8_t *seq; uint32_t len; bool reverse;       /* the read as uploaded */
+	char *dst; uint32_t cap, n;                           /* the MD text (dst NULL: counted only) */
+	uint32_t ri, run, mm, gaps; uint64_t tp; bool in_del;
+	__device__ __forceinline__ uint32_t code() {
+		const uint64_t wi = tp >> 5;
+		if (wi != cur) { w = text[wi]; cur = wi; }
+		const uint32_t k = (uint32_t)tp & 31u;
+		const uint64_t lo = (uint64_t)w.x | ((uint64_t)w.y << 32), hi = (uint64_t)w.z | ((uint64_t)w.w << 32); /* (two shifts and a select: a component chosen by index goes through scratch) */
+		tp++;
+		return (uint32_t)((k < 16u ? lo : hi) >> ((k & 15u) * 4u)) & 15u;
+	}
+	__device__ __forceinline__ uint32_t base() { /* SEQ as SAM prints it: read->rc on the reverse strand */
+		const uint32_t c = reverse ? seq[len - 1u - ri] : seq[ri];
+		ri++;
+		return reverse ? (c > 3u ? 4u : 3u - c) : c;
+	}
+	__device__ __forceinline__ void put(uint32_t ch) { if (dst && n < cap) dst[n] = (char)ch; n++; }
+	__device__ __forceinline__ void letter(uint32_t c) { /* "NTKGSBYCMHNVRDWA"[c] */
+		put((uint32_t)((c < 8u ? md_letters8("NTKGSBYC") : md_letters8("MHNVRDWA")) >> ((c & 7u) * 8u)) & 0xFFu);
+	}
+	__device__ __forceinline__ void number(uint32_t v) {
+		if (v >= 10000u) put('0' + v / 10000u % 10u);
+		if (v >= 1000u) put('0' + v / 1000u % 10u);
+		if (v >= 100u) put('0' + v / 100u % 10u);
+		if (v >= 10u) put('0' + v / 10u % 10u);
+		put('0' + v % 10u);
+	}
+	__device__ __forceinline__ void step(uint32_t op, uint32_t count) { /* op: 0 M, 1 I, 2 D, 4 S */
+		if (op == 0u) {
+			for (uint32_t k = 0; k < count; k++) {
+				const uint32_t b = base(), c = code();
+				if (b < 4u && ((member_mask((int)b) >> c) & 1u)) run++;
+				else { number(run); letter(c); run = 0; mm++; }
+			}
+		} else if (op == 2u) {
+			if (!in_del) { number(run); put('^'); run = 0; }
+			for (uint32_t k = 0; k < count; k++) letter(code());
+			gaps += count;
+		} else {
+			ri += count;
+			if (op == 1u) gaps += count;
+		}
+		in_del = op == 2u;
+	}
+};
+/* read q's ops: kind 1 with a record (hdr: pos, seqid, n_ops; its ops in the words behind) or the placement's own */
+struct MdRead { bool mapped, reverse, lifted; uint32_t alen, n_ops; uint4 runs; const uint4 *rec; int64_t start; };
+__device__ __forceinline__ MdRead md_read(uint32_t q, const uint4 *places, const uint8_t *lift_kind, const uint64_t *lift_off, const uint4 *lift_recs, const uint64_t *lstart, uint32_t n_seq) {
+	MdRead v;
+	const uint4 p0 = places[(size_t)q * 3], p1 = places[(size_t)q * 3 + 1];
+	v.mapped = ((p1.x >> 24) & PLACE_F_MAPPED) != 0;
+	v.reverse = ((p1.x >> 24) & PLACE_F_REVERSE) != 0;
+	v.alen = p1.z & 0xFFFFu;
+	v.runs = places[(size_t)q * 3 + 2];
+	v.start = (int64_t)((uint64_t)p0.x | ((uint64_t)p0.y << 32));
+	v.lifted = lift_kind && lift_kind[q] == 1u;
+	v.n_ops = 0; v.rec = nullptr;
+	if (v.lifted) {
+		const uint64_t o = lift_off[q], words = lift_off[q + 1] - o;
+		const uint4 hdr = words ? lift_recs[o] : make_uint4(0u, 0u, 0xFFFFFFFFu, 0xFFu);
+		const uint32_t n_ops = hdr.w & 0xFFu;
+		/* (a record that does not fit its own words, or names no record of the table: walked by nobody) */
+		if (n_ops < 1u || n_ops > 20u || 1u + ((n_ops + 3u) >> 2) > words || hdr.z >= n_seq) v.mapped = false;
+		else {
+			v.n_ops = n_ops; v.rec = lift_recs + o;
+			v.start = (int64_t)(lstart[hdr.z] + ((uint64_t)hdr.x | ((uint64_t)hdr.y << 32)) - 1u);
+		}
+	}
+	return v;
+}
+__device__ __forceinline__ uint32_t md_rec_op(const uint4 *rec, uint32_t i) {
+	return ((const uint32_t *)(rec + 1))[i];
+}
+__device__ __forceinline__ void md_walk(MdWalk &m, const MdRead &v) {
+	if (v.lifted) for (uint32_t i = 0; i < v.n_ops; i++) { const uint32_t op = md_rec_op(v.rec, i); m.step(op & 15u, op >> 4); }
+	else for (uint32_t t = 0; t < v.alen; t++) m.step(lift_op_at(v.runs, v.alen, v.reverse, t), 1u);
+}
+__device__ __forceinline__ MdWalk md_begin(const uint4 *text, const uint8_t *seq, uint32_t len, const MdRead &v, char *dst, uint32_t cap) {
+	MdWalk m;
+	m.text = text; m.cur = ~0ull; m.w = make_uint4(0u, 0u, 0u, 0u);
+	m.seq = seq; m.len = len; m.reverse = v.reverse;
+	m.dst = dst; m.cap = cap; m.n = 0;
+	m.ri = 0; m.run = 0; m.mm = 0; m.gaps = 0; m.tp = (uint64_t)v.start; m.in_del = false;
+	return m;
+}
+__global__ __launch_bounds__(BWB_BLOCK) void k_md_count(const uint8_t *reads, const uint16_t *lens, uint32_t stride, const uint4 *places, uint32_t n_reads, const uint8_t *lift_kind,
+                                                         const uint64_t *lift_off, const uint4 *lift_recs, const uint64_t *lstart, uint32_t n_seq, const uint4 *text, uint64_t n_fwd,
+                                                         uint2 *recs, uint32_t *md_len) {
+	const uint32_t gstride = gridDim.x * BWB_BLOCK;
+	for (uint32_t q = blockIdx.x * BWB_BLOCK + threadIdx.x; q < n_reads; q += gstride) {
+		const MdRead v = md_read(q, places, lift_kind, lift_off, lift_recs, lstart, n_seq);
+		const uint32_t len = lens[q];
+		uint32_t kind = MD_NONE, nm = 0, bytes = 0;
+		if (v.mapped && len <= 255u && len <= stride) {
+			/* the span on the text and the read bases the ops consume */
+			uint64_t span = 0, on_read = 0;
+			if (v.lifted) for (uint32_t i = 0; i < v.n_ops; i++) { const uint32_t op = md_rec_op(v.rec, i); if ((op & 15u) == 0u || (op & 15u) == 2u) span += op >> 4; if ((op & 15u) != 2u) on_read += op >> 4; }
+			else for (uint32_t t = 0; t < v.alen; t++) { const uint32_t op = lift_op_at(v.runs, v.alen, v.reverse, t); span += op != 1u; on_read += op != 2u; }
+			if (span > MD_MAX_SPAN) kind = MD_TOO_LONG;
+			else if (v.start >= 0 && (uint64_t)v.start <= n_fwd && span <= n_fwd - (uint64_t)v.start && on_read == len) {
+				MdWalk m = md_begin(text, reads + (size_t)q * stride, len, v, nullptr, 0u);
+				md_walk(m, v);
+				m.number(m.run);
+				kind = MD_OK; nm = m.mm + m.gaps; bytes = m.n;
+			}
+		}
+		recs[q] = make_uint2(nm, bytes | (kind << 16));
+		md_len[q] = bytes;
+	}
+}
+__global__ __launch_bounds__(BWB_BLOCK) void k_md(const uint8_t *reads, const uint16_t *lens, uint32_t stride, const uint4 *places, uint32_t n_reads, const uint8_t *lift_kind,
+                                                   const uint64_t *lift_off, const uint4 *lift_recs, const uint64_t *lstart, uint32_t n_seq, const uint4 *text, const uint2 *recs,
+                                                   const uint64_t *md_off, char *out) {
+	const uint32_t gstride = gridDim.x * BWB_BLOCK;
+	for (uint32_t q = blockIdx.x * BWB_BLOCK + threadIdx.x; q < n_reads; q += gstride) {
+		if (((recs[q].y >> 16) & 0xFFu) != MD_OK) continue;
+		const MdRead v = md_read(q, places, lift_kind, lift_off, lift_recs, lstart, n_seq);
+		const uint64_t o = md_off[q], cap = md_off[q + 1] - o; /* (k_md_count sized it from the same walk; nothing is stored beyond it) */
+		if (!v.mapped || cap > 0xFFFFu) continue;
+		MdWalk m = md_begin(text, reads + (size_t)q * stride, lens[q], v, out + o, (uint32_t)cap);
+		md_walk(m, v);
+		m.number(m.run);
 	}
 }

@@ -49,6 +49,7 @@ typedef struct {
 	const int32_t *chrom_of;  /* -J, -R (NULL: neither): the chromosome's record of every bubble; needs bub */
 	int join;                 /* -J: a read's placements counted by locus; needs max_alt and bub */
 	int lift;                 /* -R: placements on a bubble record written in chromosome coordinates; needs bub */
+	md_text_t *text;          /* -D (NULL: no tags): the forward text of <seq_fasta>.ref, for the tags NM:i / MD:Z */
 } map_t;
 
 typedef struct {
@@ -82,6 +83,7 @@ typedef struct {
 	double locus_ms; unsigned long long locus_reads; /* map -B: k_locus, summed over the chunks */
 	double join_ms; unsigned long long join_items, join_joined, join_mapq; /* map -J: k_join_items + k_join_reads, summed over the chunks; reads whose MAPQ changed */
 	double lift_ms; unsigned long long lift_lifted, lift_unliftable, lift_bytes; /* map -R: k_lift_count + scan + k_lift, summed over the chunks; what came back for them */
+	double md_ms, text_s; unsigned long long md_reads, md_bytes, md_back; /* map -D: k_md_count + scan + k_md, summed over the chunks; set_text's seconds; reads tagged, MD bytes, what came back */
 } worker_t;
 
 /* The reader: chunk k+1 is parsed (record boundaries by one sequential scan, bases encoded by all cores: reads.c) while chunk k is on
@@ -218,10 +220,28 @@ static void retire_map(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c) {
 		lift_kind = host_lift->kind; lift_off = host_lift->off; lift_recs = host_lift->recs;
 		w->lift_lifted += host_lift->n_lifted; w->lift_unliftable += host_lift->n_unliftable;
 	}
+	/* -D: NM and the MD text of every mapped read against the text in HBM (kernels k_md_count / k_md behind them on the result stream, on the
+	 * slot's resident reads); with the host's lift records, the host's rule */
+	const bwb_md *md_recs = NULL;
+	const uint64_t *md_off = NULL;
+	const char *md_text = NULL;
+	md_set_t *host_md = NULL;
+	if (m->text && !host_lift) {
+		uint64_t nr = 0, nb = 0; double ms = 0;
+		if (bwb_hip_slot_md(ctx, slot, m->max_mm, m->max_alt, m->lift, &md_recs, &md_off, &md_text, &n)) bwb_die("map_reads: GPU %d: %s", w->gpu, bwb_hip_last_error());
+		bwb_hip_md_stats(ctx, &nr, &nb, &ms); /* (the figures of the last call that LAUNCHED: this one, since a chunk's slot is asked once - a second slot_md on it would return its cached records and leave them) */
+		w->md_ms += ms; w->md_reads += nr; w->md_bytes += nb;
+		w->md_back += (unsigned long long)n * sizeof(bwb_md) + ((unsigned long long)n + 1) * 8 + md_off[n];
+	} else if (m->text) {
+		host_md = md_host(pl, n, c->fq.seq, c->fq.stride, c->fq.len, lift_kind, lift_off, lift_recs, m->ann, m->text);
+		md_recs = host_md->recs; md_off = host_md->off; md_text = host_md->text;
+		w->md_reads += host_md->n_ok; w->md_bytes += host_md->off[n];
+	}
 	const sam_reads_t rd = { .pl = pl, .seq = c->fq.seq, .stride = c->fq.stride, .len = c->fq.len, .text = c->fq.text,
 	                         .name_off = c->fq.name_off, .qual_off = c->fq.qual_off, .name_len = c->fq.name_len, .first = c->first_read,
 	                         .alt_off = alt_off, .alts = alts, .loci = loci, .bubbles = m->bub, .joins = joins,
-	                         .lift_kind = lift_kind, .lift_off = lift_off, .lift_recs = lift_recs, .lift_n = n };
+	                         .lift_kind = lift_kind, .lift_off = lift_off, .lift_recs = lift_recs, .lift_n = n,
+	                         .md = md_recs, .md_off = md_off, .md_text = md_text };
 	c->n = n;
 	c->n_sam = ((size_t)n + SAM_BLOCK_READS - 1) / SAM_BLOCK_READS;
 	c->sam = (char **)calloc(c->n_sam ? c->n_sam : 1, sizeof(char *));
@@ -231,7 +251,7 @@ static void retire_map(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c) {
 		const size_t r0 = (size_t)bi * SAM_BLOCK_READS, r1 = r0 + SAM_BLOCK_READS < n ? r0 + SAM_BLOCK_READS : n;
 		c->sam[bi] = sam_format_reads(&rd, r0, r1, m->ann, m->ann_sorted, &c->sam_len[bi]);
 	}
-	free(host_loci); free(host_joins); lift_free(host_lift);
+	free(host_loci); free(host_joins); lift_free(host_lift); md_free(host_md);
 	free(c->fq.seq); free(c->fq.len); free(c->fq.name_off); free(c->fq.qual_off); free(c->fq.name_len);
 	c->fq.seq = NULL; c->fq.len = NULL; c->fq.name_off = NULL; c->fq.qual_off = NULL; c->fq.name_len = NULL;
 	chunk_ready(w->pp, c);
@@ -294,6 +314,15 @@ static void *gpu_worker(void *arg) {
 		/* -J, -R: the chromosome's record of every bubble, beside them */
 		if (pp->map->chrom_of && pp->map->gpu_loci && bwb_hip_set_bubble_chrom(ctx, pp->map->chrom_of, (uint32_t)pp->map->bub->n))
 			bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
+		/* -D: the forward text (n_fwd / 2 bytes in HBM: 1.7 GB at GRCh37 scale), before the first slot_upload sizes the chunk pool as well; its
+		 * bytes are read by the .bwt loader behind the SA (bwt_io.c: load_bwt_start_job, md.c: md_text_read).  Not with the host's lift records: the host's rule then */
+		md_text_wait(pp->map->text);
+		if (pp->map->text && !(pp->map->lift && !pp->map->gpu_loci)) {
+			const double t0 = wall();
+			if (bwb_hip_set_text(ctx, pp->map->text->codes, pp->map->text->n_fwd)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
+			w->text_s = wall() - t0;
+			if (dbg) fprintf(stderr, "[bwb host] worker %d: text resident at +%.3f s\n", w->gpu, wall() - tq);
+		}
 	}
 	void (*const hand_over)(worker_t *, bwb_hip_ctx *, int, chunk_t *) = pp->map ? retire_map : retire;
 	enum { NS = BWB_MAX_SLOTS }; /* chunks in flight: the heaviest reads of a chunk take several slices' time (they are parked and resumed), and
@@ -466,6 +495,14 @@ static int run_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, 
 			if (map->gpu_loci) printf("placements lifted to chromosome coordinates on the GPU: lifted %llu  not liftable %llu  kernels %.3f ms  bytes to the host %llu\n", ll, lu, lms, lb);
 			else printf("placements lifted to chromosome coordinates on the host (the .ann records are not ascending and disjoint): lifted %llu  not liftable %llu\n", ll, lu);
 		}
+		if (map->text) { /* -D */
+			double mms = 0, ts = 0; unsigned long long mr = 0, mb = 0, bk = 0;
+			for (int g = 0; g < n_gpus; g++) { mr += ws[g].md_reads; mb += ws[g].md_bytes; bk += ws[g].md_back; if (ws[g].md_ms > mms) mms = ws[g].md_ms; if (ws[g].text_s > ts) ts = ws[g].text_s; }
+			if (!(map->lift && !map->gpu_loci))
+				printf("NM and MD against the text on the GPU: reads %llu  MD bytes %llu  kernels %.3f ms  bytes to the host %llu  text %llu characters read in %.3f s, set in %.3f s\n", mr, mb, mms, bk,
+				       (unsigned long long)map->text->n_fwd, map->text->seconds, ts);
+			else printf("NM and MD against the text on the host (the .ann records are not ascending and disjoint): reads %llu  MD bytes %llu\n", mr, mb);
+		}
 		if (map->max_alt) {
 			double ams = 0; unsigned long long ast = 0, ait = 0;
 			for (int g = 0; g < n_gpus; g++) { ast += ws[g].alt_steps; ait += ws[g].alt_items; if (ws[g].alt_ms > ams) ams = ws[g].alt_ms; }
@@ -524,11 +561,13 @@ int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_
 }
 
 /* `bwbble map`: align_reads + alns2sam in one pass.  The .bwt is loaded once, with its SA; the SAM header is written before the first chunk. */
-int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int lift, int n_gpus) {
+int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int lift, int md, int n_gpus) {
 	printf("**** BWBBLE Read Mapping (align + aln2sam in one pass) ****\n");
 	/* -B: the table first (a refused table stops the run before anything is created) */
 	bubble_table_t *bub = bubbleFname ? load_bubbles(bubbleFname) : NULL;
 	if (lift && bub) lift_check_table(bub); /* -R (main.c: only with -B): a bubble the rule refuses is named here */
+	/* -D: a missing <seq_fasta>.ref, or one of another size than the .ann says, stops the run here; the .bwt loader reads its forward half, behind the sampled SA */
+	md_text_t *text = md ? md_text_open(fastaFname, 1) : NULL;
 	/* before anything is created: without a GPU no SAM file is left behind */
 	if (bwb_hip_device_count() < 1) bwb_die("align_reads_inexact_gpu: no HIP device found (this build has no CPU alignment path)");
 	size_t L = strlen(fastaFname) + 8;
@@ -536,7 +575,7 @@ int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *
 	snprintf(bwtFname, L, "%s.bwt", fastaFname);
 	snprintf(annFname, L, "%s.ann", fastaFname);
 	double t = wall();
-	bwt_t *BWT = load_bwt_start(bwtFname, 1);
+	bwt_t *BWT = load_bwt_start_job(bwtFname, 1, text ? md_text_read : NULL, text);
 	fasta_annotations_t *ann = annf2ann(annFname);
 	/* -B: every record's bubble number, before the SAM file exists (a record that names a bubble outside the table leaves none behind) */
 	int32_t *bubble_of = bub ? ann_bubble_of(ann, bub) : NULL;
@@ -559,13 +598,13 @@ int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *
 	if (!sam) { perror(samFname); bwb_die("map_reads: Cannot open SAM file: %s!", samFname); }
 	sam_write_header(sam, ann);
 	const map_t m = { .max_mm = max_mm, .max_alt = max_alt, .ann = ann, .ann_sorted = sam_ann_sorted(ann),
-	                  .bub = bub, .bubble_of = bubble_of, .gpu_loci = gpu_loci, .rec_start = rec_start, .rec_end = rec_end, .chrom_of = chrom_of, .join = join, .lift = lift };
+	                  .bub = bub, .bubble_of = bubble_of, .gpu_loci = gpu_loci, .rec_start = rec_start, .rec_end = rec_end, .chrom_of = chrom_of, .join = join, .lift = lift, .text = text };
 	t = wall();
 	printf("BWBBLE Inexact Alignment (MI355X)...\n");
 	run_stream(BWT, readsFname, params, sam, samFname, n_gpus, &m);
 	printf("Total read mapping time (index and read loading overlapped): %.2f sec\n", wall() - t);
 	free_bwt(BWT); free_ann(ann);
 	free(bwtFname); free(annFname);
-	free(bubble_of); free(chrom_of); free(rec_start); free(rec_end); free_bubbles(bub);
+	free(bubble_of); free(chrom_of); free(rec_start); free(rec_end); free_bubbles(bub); md_text_free(text);
 	return 0;
 }

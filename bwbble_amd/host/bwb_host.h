@@ -74,6 +74,7 @@ void store_bwt(const bwt_t *BWT, const char *bwtFname);                /* bwt.c:
 bwt_t *load_bwt(const char *bwtFname, int loadSA);                     /* bwt.c:90-125 */
 double bwt_load_seconds(const bwt_t *B);
 bwt_t *load_bwt_start(const char *bwtFname, int loadSA);               /* returns after the header: the arrays fill in the background (blocks_ready) */
+bwt_t *load_bwt_start_job(const char *bwtFname, int loadSA, void (*job)(void *), void *job_arg); /* the same; one loader thread also runs job(job_arg) behind the sampled SA (`map -D`: md_text_read) */
 void load_bwt_wait(bwt_t *BWT);                                        /* until the whole file is in memory */
 void free_bwt(bwt_t *BWT);
 
@@ -119,14 +120,14 @@ int aln_path_bytes(const bwb_aln *a, unsigned char *path /* >= 272 bytes */); /*
 void set_default_aln_params(aln_params_t *params);                     /* align.c:22-38 */
 int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_t *params, int n_gpus); /* align.c:40-87 */
 int align_reads_inexact_gpu_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, char *alnFname, int n_gpus); /* the GPU's align_reads_inexact_parallel (inexact_match.h:40) over a streamed FASTQ */
-int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int lift, int n_gpus); /* `bwbble map`: align + aln2sam in one pass, the hits evaluated on the GPU */
+int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int lift, int md, int n_gpus); /* `bwbble map`: align + aln2sam in one pass, the hits evaluated on the GPU */
 
 /* precalc.c */
 void precalc_sa_intervals(bwt_t *BWT, const aln_params_t *params, const char *preFname); /* align.c:200-224: writes <fasta>.pre */
 int check_precalc_file(const char *preFname); /* the walk of load_precalc_sa_intervals (align.c:226-238) over an existing table: 0 = complete */
 
 /* sam.c */
-void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join, int lift); /* align.c:494-556; max_alt: -X (0: no tags); bubbleFname: -B (NULL: no tags); join: -J; lift: -R */
+void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join, int lift, int md); /* align.c:494-556; max_alt: -X (0: no tags); bubbleFname: -B (NULL: no tags); join: -J; lift: -R; md: -D */
 /* the two halves of alns2sam: eval_aln of one read on the host, and the text of a block of reads from placement records (which `map` gets
  * from the GPU instead, bwb_hip_slot_place) */
 #define SAM_BLOCK_READS ((size_t)1 << 14)                              /* reads formatted by one thread at a time */
@@ -141,6 +142,8 @@ typedef struct {
 	/* -R (lift_kind NULL: as placed): placement q - read q's primary, or lift_n + k for item alts[k] - with lift_kind[q] == BWB_LIFT_LIFTED prints
 	 * RNAME, POS and CIGAR of the record at lift_recs + lift_off[q], and a lifted primary the tag bO */
 	const uint8_t *lift_kind; const uint64_t *lift_off; const bwb_lift *lift_recs; size_t lift_n;
+	/* -D (md NULL: no tags): read r with md[r].kind == BWB_MD_OK gains NM:i:md[r].nm and MD:Z: with the bytes md_text[md_off[r] .. md_off[r + 1]), behind QUAL */
+	const bwb_md *md; const uint64_t *md_off; const char *md_text;
 } sam_reads_t;
 int sam_mapq(int top1, int top2, int num_mm, int max_mm);               /* align.c:738-746 */
 void place_from_alns(const bwb_aln *e, uint64_t ne, uint64_t ref_pos, uint64_t bwt_length, int max_mm, bwb_place *out);
@@ -149,7 +152,7 @@ uint64_t alt_placements(const bwb_aln *e, uint64_t ne);               /* the row
 void sam_write_header(FILE *sam, const fasta_annotations_t *ann);
 int sam_ann_sorted(const fasta_annotations_t *ann);
 char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_annotations_t *ann, int ann_sorted, size_t *out_len);
-void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join, int lift); /* developer command: records from a file (altsFname: NULL or the items; bubbleFname: NULL or -B's table; join: -J, the items file then ends with one suboptimal byte per item; lift: -R) */
+void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join, int lift, int md); /* developer command: records from a file (altsFname: NULL or the items; bubbleFname: NULL or -B's table; join: -J, the items file then ends with one suboptimal byte per item; lift: -R; md: -D) */
 
 /* pad.c: bubble hits in reference coordinates (the reference's mg-ref/sam_pad.cpp) */
 typedef struct bubble_table {                                          /* bubble.data (mg-ref/comb.cpp:245-253): the k-th pair of lines is bubble k */
@@ -176,6 +179,31 @@ typedef struct { uint8_t *kind; uint64_t *off; bwb_lift *recs; uint64_t n_lifted
 lift_set_t *lift_host(const bwb_place *pl, const bwb_locus *loci, size_t n, const uint64_t *alt_off, const bwb_alt *alts, const fasta_annotations_t *ann, int ann_sorted,
                       const int32_t *bubble_of, const int32_t *chrom_of, const bubble_table_t *t);
 void lift_free(lift_set_t *ls);
+/* the op of text position t of a placement's CIGAR: the path byte aln_path_bytes gives (a later run wins), walked as sam_put_cigar walks it
+ * (lift_resolve and md_place_ops) */
+static inline unsigned lift_op_at(const uint16_t *gap_run, unsigned alen, int reverse, unsigned t) {
+	const unsigned p = reverse ? t : alen - 1 - t;
+	unsigned op = 0;
+	for (int k = 0; k < BWB_MAX_GAP_RUNS; k++) {
+		const unsigned run = gap_run[k];
+		if (run != 0xFFFFu && p - (run & 0xFFu) < ((run >> 8) & 0x7Fu)) op = (run >> 15) ? BWB_LIFT_D : BWB_LIFT_I;
+	}
+	return op;
+}
+
+/* md.c: -D, NM:i and MD:Z against the text of <seq_fasta>.ref (include/bwbble_hip.h: bwb_md) */
+typedef struct md_text { uint8_t *codes; uint64_t n_fwd; double seconds; char *refFname; volatile int ready; } md_text_t; /* the forward text, one code per byte; ready: the bytes are in memory (release/acquire) */
+md_text_t *md_text_open(const char *fastaFname, int deferred);        /* a missing .ref or one that is not 2 x n_fwd bytes stops the run and names `bwbble fasta2ref`; deferred: the bytes are not read here but by md_text_read */
+void md_text_read(void *text);                                         /* reads the n_fwd bytes of a deferred text (a job of the .bwt loader: load_bwt_start_job) */
+void md_text_wait(md_text_t *t);                                       /* until the n_fwd bytes are in memory */
+void md_text_free(md_text_t *t);
+unsigned md_place_ops(unsigned alen, const uint16_t *gap_run, int reverse, uint32_t *ops /* 2 * BWB_MAX_GAP_RUNS + 1 */); /* the printed CIGAR as ops of a lift record: len << 4 | op */
+int md_resolve(const uint8_t *text, uint64_t n_fwd, const uint8_t *seq, unsigned len, int reverse, int64_t start, const uint32_t *ops, unsigned n_ops,
+               bwb_md *rec, char *md, size_t cap); /* kernels k_md_count + k_md on the host, one read: seq as uploaded, the ops from text position start; md NULL: counted only; returns the kind */
+typedef struct { bwb_md *recs; uint64_t *off; char *text; uint64_t n_ok, n_too_long; } md_set_t; /* what bwb_hip_slot_md returns, malloc'ed */
+md_set_t *md_host(const bwb_place *pl, size_t n, const uint8_t *seq, uint32_t stride, const uint16_t *len, const uint8_t *lift_kind, const uint64_t *lift_off,
+                  const bwb_lift *lift_recs, const fasta_annotations_t *ann, const md_text_t *t);
+void md_free(md_set_t *ms);
 void sam_pad(const char *dataFname, const char *inFname, const char *outFname); /* `bwbble sampad`: sam_pad.cpp:47-94 over SAM text */
 
 /* The OpenMP teams of the host stages of `align` / `aln2sam` (base encoding, .aln serialisation, SAM text) have at most 32 threads unless

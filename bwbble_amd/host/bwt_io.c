@@ -46,6 +46,7 @@ typedef struct {
 	char *fname;
 	uint64_t n_units, next_unit, off_bwt, off_O, off_SA, unit;
 	int load_sa, sa_done;
+	void (*job)(void *); void *job_arg; int job_done; /* load_bwt_start_job: one more read a loader thread takes behind the sampled SA (NULL: none) */
 	unsigned char *done;
 	pthread_mutex_t mu;
 	pthread_t th[16];
@@ -70,8 +71,12 @@ static void *bwt_loader_thread(void *arg) {
 		/* the sampled SA first, by one thread: `map` uploads it before its first batch sizes the chunk pool from what is free */
 		const int do_sa = L->load_sa && !L->sa_done;
 		if (do_sa) L->sa_done = 1;
-		const uint64_t u = do_sa ? 0 : L->next_unit++;
+		/* then the caller's job, by one thread (`map -D`: the forward text of <fasta>.ref, which goes to HBM before the pool is sized as well) */
+		const int do_job = !do_sa && L->job && !L->job_done;
+		if (do_job) L->job_done = 1;
+		const uint64_t u = do_sa || do_job ? 0 : L->next_unit++;
 		pthread_mutex_unlock(&L->mu);
+		if (do_job) { L->job(L->job_arg); continue; }
 		if (do_sa) {
 			pread_all(L->fd, B->SA, B->num_sa * sizeof(bwtint_t), L->off_SA, L->fname);
 			__atomic_store_n(&B->sa_ready, 1, __ATOMIC_RELEASE);
@@ -102,7 +107,9 @@ static void *bwt_loader_thread(void *arg) {
 	}
 }
 
-bwt_t *load_bwt_start(const char *bwtFname, int loadSA) {
+bwt_t *load_bwt_start(const char *bwtFname, int loadSA) { return load_bwt_start_job(bwtFname, loadSA, NULL, NULL); }
+
+bwt_t *load_bwt_start_job(const char *bwtFname, int loadSA, void (*job)(void *), void *job_arg) {
 	const int fd = open(bwtFname, O_RDONLY);
 	if (fd < 0) bwb_die("load_bwt: Cannot open the BWT file: %s!", bwtFname);
 	bwt_t *B = (bwt_t *)calloc(1, sizeof(bwt_t));
@@ -131,6 +138,7 @@ bwt_t *load_bwt_start(const char *bwtFname, int loadSA) {
 	}
 	bwt_loader_t *L = (bwt_loader_t *)calloc(1, sizeof(bwt_loader_t));
 	L->B = B; L->fd = fd; L->fname = strdup(bwtFname); L->load_sa = loadSA;
+	L->job = job; L->job_arg = job_arg;
 	L->off_bwt = sizeof(hdr); L->off_O = L->off_bwt + B->num_words * sizeof(uint32_t); L->off_SA = L->off_O + B->num_occ * ALPHABET_SIZE * sizeof(bwtint_t);
 	L->unit = load_unit();
 	L->n_units = (B->num_occ + L->unit - 1) / L->unit;

@@ -240,17 +240,6 @@ void lift_check_table(const bubble_table_t *t) {
 	}
 }
 
-/* the op of text position t of a placement's CIGAR: the path byte aln_path_bytes gives (a later run wins), walked as sam_put_cigar walks it */
-static inline unsigned lift_op_at(const uint16_t *gap_run, unsigned alen, int reverse, unsigned t) {
-	const unsigned p = reverse ? t : alen - 1 - t;
-	unsigned op = 0;
-	for (int k = 0; k < BWB_MAX_GAP_RUNS; k++) {
-		const unsigned run = gap_run[k];
-		if (run != 0xFFFFu && p - (run & 0xFFu) < ((run >> 8) & 0x7Fu)) op = (run >> 15) ? BWB_LIFT_D : BWB_LIFT_I;
-	}
-	return op;
-}
-
 /* 0 left flank, 1 alternate allele, 2 right flank, of a record position x >= 1 that the span check has kept inside the record */
 static inline int lift_zone(const bwb_bubble *b, int64_t x) { return x <= b->B_minus_A ? 0 : (x - b->B_minus_A <= (int64_t)b->alt_len ? 1 : 2); }
 

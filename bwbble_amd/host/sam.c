@@ -134,6 +134,7 @@ char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_
 		for (size_t r = r0; r < r1; r++) if (rd->lift_kind[r] == BWB_LIFT_LIFTED) cap += 2 * MAX_SEQ_NAME_LEN + 480 + 8 * (size_t)rd->pl[r].num_gapo;
 		if (rd->alt_off) for (uint64_t k = rd->alt_off[r0]; k < rd->alt_off[r1]; k++) if (rd->lift_kind[rd->lift_n + k] == BWB_LIFT_LIFTED) cap += MAX_SEQ_NAME_LEN + 320;
 	}
+	if (rd->md) cap += (r1 - r0) * 32 + (size_t)(rd->md_off[r1] - rd->md_off[r0]); /* -D: "\tNM:i:<32-bit>\tMD:Z:" and the MD bytes */
 	if (rd->loci) /* -B: on a bubble record the chromosome's header and one or two 64-bit numbers */
 		for (size_t r = r0; r < r1; r++) if (rd->loci[r].bubble >= 0) cap += strlen(rd->bubbles->ann[rd->loci[r].bubble]) + 64;
 	char *o = (char *)malloc(cap ? cap : 1), *o0 = o;
@@ -173,6 +174,10 @@ char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_
 		if (strand) for (int k = 0; k < len; k++) o[k] = qual[len - 1 - k];
 		else memcpy(o, qual, (size_t)len);
 		o += len;
+		if (rd->md && rd->md[r].kind == BWB_MD_OK) { /* -D: directly behind QUAL, the bytes the kernel (or md_resolve) wrote */
+			o += sprintf(o, "\tNM:i:%u\tMD:Z:", rd->md[r].nm);
+			memcpy(o, rd->md_text + rd->md_off[r], rd->md[r].md_len); o += rd->md[r].md_len;
+		}
 		if (rd->alt_off) { /* -X: the two counters as they are, and the read's other placements (an item outside every record is left out) */
 			o += sprintf(o, "\tX0:i:%d\tX1:i:%d", (int)pl->top1, (int)pl->top2);
 			if (rd->alt_off[r + 1] > rd->alt_off[r]) { memcpy(o, "\tXA:Z:", 6); o += 6; }
@@ -239,9 +244,10 @@ static bwb_join *host_joins(const bwb_place *pl, const bwb_locus *loci, const ui
 	return joins;
 }
 
-void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join, int lift) {
+void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join, int lift, int md) {
 	(void)is_multiref;
 	printf("**** BWBBLE Alignment Evaluation/SAM File Generation ****\n");
+	md_text_t *text = md ? md_text_open(fastaFname, 0) : NULL; /* -D (a missing .ref, or one of another size than the .ann says, stops the run before anything is loaded or created) */
 	size_t Ln = strlen(fastaFname) + 8;
 	char *bwtFname = (char *)malloc(Ln), *annFname = (char *)malloc(Ln);
 	snprintf(bwtFname, Ln, "%s.bwt", fastaFname);
@@ -329,10 +335,13 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 	bwb_join *joins = join ? host_joins(pl, loci, alt_off, alts, alt_sub, n, ann, ann_sorted, bubble_of, chrom_of, bub, max_diff) : NULL;
 	lift_set_t *ls = lift ? lift_host(pl, loci, n, alt_off, alts, ann, ann_sorted, bubble_of, chrom_of, bub) : NULL;
 	if (ls) printf("placements lifted to chromosome coordinates on the host: %llu  not liftable %llu\n", (unsigned long long)ls->n_lifted, (unsigned long long)ls->n_unliftable);
+	md_set_t *ms = text ? md_host(pl, n, reads->seq, reads->stride, reads->len, ls ? ls->kind : NULL, ls ? ls->off : NULL, ls ? ls->recs : NULL, ann, text) : NULL;
+	if (ms) printf("NM and MD against the text on the host: reads %llu  too long %llu  MD bytes %llu\n", (unsigned long long)ms->n_ok, (unsigned long long)ms->n_too_long, (unsigned long long)ms->off[n]);
 	const sam_reads_t rd = { .pl = pl, .seq = reads->seq, .stride = reads->stride, .len = reads->len, .text = reads->raw,
 	                         .name_off = reads->name_off, .qual_off = reads->qual_off, .name_len = reads->name_len, .first = 0,
 	                         .alt_off = alt_off, .alts = alts, .loci = loci, .bubbles = bub, .joins = joins,
-	                         .lift_kind = ls ? ls->kind : NULL, .lift_off = ls ? ls->off : NULL, .lift_recs = ls ? ls->recs : NULL, .lift_n = n };
+	                         .lift_kind = ls ? ls->kind : NULL, .lift_off = ls ? ls->off : NULL, .lift_recs = ls ? ls->recs : NULL, .lift_n = n,
+	                         .md = ms ? ms->recs : NULL, .md_off = ms ? ms->off : NULL, .md_text = ms ? ms->text : NULL };
 	/* The text: blocks of reads are formatted into memory by all cores and written in order (round 5: one thread's fprintf calls were
 	 * the wall time of aln2sam on a 10 M-read file, not the SA lookups). */
 	const size_t BLK = SAM_BLOCK_READS;
@@ -353,7 +362,7 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 		}
 	}
 	free(pl); free(alt_off); free(alts); free(loci); free(bubble_of); free_bubbles(bub);
-	free(alt_sub); free(joins); free(chrom_of); lift_free(ls);
+	free(alt_sub); free(joins); free(chrom_of); lift_free(ls); md_free(ms); md_text_free(text);
 	free(bufs); free(lens);
 	printf("Processed %zu reads.\n", n);
 	free(rows); free(pos); free(which); free(ref_pos);
@@ -364,8 +373,8 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 
 /* developer command (CPU only, for the tests): raw bwb_place records from a file through sam_format_reads - the formatter `map` uses, on a
  * machine without a GPU (bubbleFname: -B, the loci from the host resolver; join: -J, the join records from the host's rule; lift: -R, the
- * lift records from the host's rule) */
-void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join, int lift) {
+ * lift records from the host's rule; md: -D, NM and MD from the host's rule) */
+void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join, int lift, int md) {
 	size_t Ln = strlen(fastaFname) + 8;
 	char *annFname = (char *)malloc(Ln);
 	snprintf(annFname, Ln, "%s.ann", fastaFname);
@@ -374,6 +383,7 @@ void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *sam
 	int32_t *bubble_of = bub ? ann_bubble_of(ann, bub) : NULL;
 	if (lift) lift_check_table(bub); /* -R (main.c: only with -B) */
 	int32_t *chrom_of = join || lift ? bubble_chrom_of(ann, bubble_of, bub, join ? "-J" : "-R") : NULL; /* -J (main.c: only with -B and an items file), -R */
+	md_text_t *text = md ? md_text_open(fastaFname, 0) : NULL; /* -D */
 	reads_t *reads = fastq2reads(readsFname);
 	FILE *pf = fopen(placesFname, "rb");
 	if (!pf) { perror(placesFname); bwb_die("places2sam: Cannot open the placements file: %s!", placesFname); }
@@ -406,10 +416,12 @@ void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *sam
 	bwb_locus *loci = bub ? host_loci(pl, n, ann, ann_sorted, bubble_of, bub) : NULL;
 	bwb_join *joins = join ? host_joins(pl, loci, alt_off, alts, alt_sub, n, ann, ann_sorted, bubble_of, chrom_of, bub, 6) : NULL; /* (aln2sam's default -n: the records carry no max_mm) */
 	lift_set_t *ls = lift ? lift_host(pl, loci, n, alt_off, alts, ann, ann_sorted, bubble_of, chrom_of, bub) : NULL;
+	md_set_t *ms = text ? md_host(pl, n, reads->seq, reads->stride, reads->len, ls ? ls->kind : NULL, ls ? ls->off : NULL, ls ? ls->recs : NULL, ann, text) : NULL;
 	const sam_reads_t rd = { .pl = pl, .seq = reads->seq, .stride = reads->stride, .len = reads->len, .text = reads->raw,
 	                         .name_off = reads->name_off, .qual_off = reads->qual_off, .name_len = reads->name_len, .first = 0,
 	                         .alt_off = alt_off, .alts = alts, .loci = loci, .bubbles = bub, .joins = joins,
-	                         .lift_kind = ls ? ls->kind : NULL, .lift_off = ls ? ls->off : NULL, .lift_recs = ls ? ls->recs : NULL, .lift_n = n };
+	                         .lift_kind = ls ? ls->kind : NULL, .lift_off = ls ? ls->off : NULL, .lift_recs = ls ? ls->recs : NULL, .lift_n = n,
+	                         .md = ms ? ms->recs : NULL, .md_off = ms ? ms->off : NULL, .md_text = ms ? ms->text : NULL };
 	for (size_t r0 = 0; r0 < n; r0 += SAM_BLOCK_READS) {
 		size_t len = 0;
 		char *buf = sam_format_reads(&rd, r0, r0 + SAM_BLOCK_READS < n ? r0 + SAM_BLOCK_READS : n, ann, ann_sorted, &len);
@@ -418,7 +430,7 @@ void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *sam
 	}
 	printf("Processed %zu reads.\n", n);
 	free(pl); free(annFname); free(alt_off); free(alts); free(loci); free(bubble_of); free_bubbles(bub);
-	free(alt_sub); free(joins); free(chrom_of); lift_free(ls);
+	free(alt_sub); free(joins); free(chrom_of); lift_free(ls); md_free(ms); md_text_free(text);
 	free_reads(reads); free_ann(ann);
 	fclose(sam);
 }

@@ -385,6 +385,61 @@ int bwb_hip_lift_records(bwb_hip_ctx *ctx, const bwb_place *places, uint32_t n, 
  * kernels' HIP-event time (any pointer may be NULL) */
 int bwb_hip_lift_stats(bwb_hip_ctx *ctx, uint64_t *lifted, uint64_t *unliftable, double *kernel_ms);
 
+/* NM:i and MD:Z of a read's line (`bwbble map -D`), computed against the TEXT the index was built from - which holds IUPAC codes, so that no
+ * stock tool can add the two tags afterwards.  The text is <seq_fasta>.ref as `bwbble index` / `fasta2ref` write it: one code per byte
+ * (0 `$`, 1 T, 2 K, 3 G, 4 S, 5 B, 6 Y, 7 C, 8 M, 9 H, 10 N, 11 V, 12 R, 13 D, 14 W, 15 A), the forward text of n_fwd characters - the first
+ * number of the .ann file - and then its reverse complement; only the forward half is used.
+ * The rule, for one read:
+ *   SEQ     the read as SAM prints it: reversed and complemented when BWB_PLACE_REVERSE.
+ *   ops     the placement's printed CIGAR (the M / I / D ops of its gap runs in text order), from text position bwb_place.pos; or, for a primary
+ *           whose lift kind is BWB_LIFT_LIFTED, the ops of its lift record (M / I / D / S), from text position start[rec.seqid] + rec.pos - 1.
+ *   kind    BWB_MD_NONE for an unmapped read;  else BWB_MD_TOO_LONG when span = the M and D lengths exceeds BWB_MD_MAX_SPAN (only a lifted
+ *           record with a long gap gets there: the rule of bwb_lift admits a D of 2^28 - 1);  else BWB_MD_NONE when the span leaves
+ *           [0, n_fwd), when the M, I and S lengths are not the read's length, or when a lift record names no record of the table;  else
+ *           BWB_MD_OK.  Only BWB_MD_OK has nm and md_len; the line of any other kind is printed as without -D.
+ *   walk    with a match run `run` = 0:
+ *           M  per base: a match when the read base is A / G / C / T and the text's code is one of the codes that base is a member of (the
+ *              search's own rule; the codes 0 `$` and 10 `N` match nothing, and a read N matches nothing): run + 1.  Otherwise `run` in
+ *              decimal and the text's letter - "NTKGSBYCMHNVRDWA"[code] - are written, run = 0, mm + 1.
+ *           D  `run` in decimal, `^` and the text's letters over the deletion; run = 0.  (A D directly behind a D continues its letters.)
+ *           I  consumes read bases only.     S  consumes read bases only and counts for nothing.
+ *           at the end: `run` in decimal.
+ *   NM      mm + the I lengths + the D lengths.
+ * This is the SAM specification's MD, so `10^AC0T5` and a leading `0` fall out by themselves.  MD and NM for XA items are not computed.
+ * Per read one bwb_md record, and for kind BWB_MD_OK the md_len ASCII bytes md_text[md_off[r] .. md_off[r + 1]) (no terminator); md_off has one
+ * entry per read and one more; the buffers hold the bytes there are.  Kernels k_md_count (one lane per read, grid-strided: kind, NM and the
+ * exact length), the exclusive scan of k_place_alt, and k_md (writes the bytes), behind k_place / k_lift on the result stream; they fetch the text,
+ * packed to 4 bits per character by k_text_pack, in aligned 16-byte words of 32 characters.  (Added without a version change: no structure or
+ * existing entry point changed.) */
+#define BWB_MD_NONE 0
+#define BWB_MD_OK 1
+#define BWB_MD_TOO_LONG 2
+#define BWB_MD_MAX_SPAN 4096
+typedef struct { uint32_t nm; uint16_t md_len; uint8_t kind, reserved; } bwb_md; /* 8 bytes */
+/* Uploads the forward text (codes[0 .. n_fwd), one code per byte) and packs it on the device, staged in chunks: n_fwd / 2 bytes stay resident.
+ * Call it before the first slot_upload sizes the context's pool.  BWB_E_ARG for a code above 15 (no text is set then) or n_fwd == 0.  A second
+ * call replaces the text. */
+int bwb_hip_set_text(bwb_hip_ctx *ctx, const uint8_t *codes, uint64_t n_fwd);
+/* slot_place (or its cached records) and, with lifted != 0, slot_lift (max_alt as given to it, so that cached records are used), then the kernels
+ * over the slot's reads - still resident from its upload - and D2H into pinned memory of the slot, valid until the next slot_md on that slot or
+ * its next upload.  BWB_E_STATE without set_text, without set_sa, on a slot that has not been submitted, or with lifted != 0 without set_loci /
+ * set_bubble_chrom; the context stays usable after each.  batch_md is the one-batch form (slot 0 after batch_run). */
+int bwb_hip_slot_md(bwb_hip_ctx *ctx, int slot, int max_mm, int max_alt, int lifted, const bwb_md **recs, const uint64_t **md_off,
+                    const char **md_text, uint32_t *n_reads);
+int bwb_hip_batch_md(bwb_hip_ctx *ctx, int max_mm, int max_alt, int lifted, const bwb_md **recs, const uint64_t **md_off, const char **md_text,
+                     uint32_t *n_reads);
+/* The same kernels on records of the caller's: read r is reads_fwd[r * stride .. + lens[r]) (read->seq codes, lens[r] <= stride, at most 255)
+ * with the placement places[r].  kinds / lift_off / lift_recs (all three or none): read r's lift kind, and the 16-byte words of its record at
+ * lift_recs + lift_off[r] as slot_lift lays them out; lift_off has n + 1 ascending entries.  recs, md_off and md_text point into memory of the
+ * context, valid until the next md_records call on it.  Needs set_text, and set_loci with the lift arguments (BWB_E_STATE); touches no slot.
+ * For parity tests. */
+int bwb_hip_md_records(bwb_hip_ctx *ctx, const uint8_t *reads_fwd, const uint16_t *lens, uint32_t stride, const bwb_place *places, uint32_t n,
+                       const uint8_t *kinds, const uint64_t *lift_off, const bwb_lift *lift_recs, const bwb_md **recs, const uint64_t **md_off,
+                       const char **md_text);
+/* the last md call on the context that launched the kernels: reads of kind BWB_MD_OK, the MD bytes written, and the kernels' HIP-event time
+ * (any pointer may be NULL) */
+int bwb_hip_md_stats(bwb_hip_ctx *ctx, uint64_t *reads, uint64_t *md_bytes, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
