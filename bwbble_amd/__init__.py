@@ -28,6 +28,7 @@ EXPORTS = [
     "bwb_hip_set_bubble_chrom", "bwb_hip_slot_join", "bwb_hip_batch_join", "bwb_hip_join_records", "bwb_hip_join_stats",
     "bwb_hip_slot_lift", "bwb_hip_batch_lift", "bwb_hip_lift_records", "bwb_hip_lift_stats",
     "bwb_hip_set_text", "bwb_hip_slot_md", "bwb_hip_batch_md", "bwb_hip_md_records", "bwb_hip_md_stats",
+    "bwb_hip_pile_begin", "bwb_hip_slot_pile", "bwb_hip_batch_pile", "bwb_hip_pile_records", "bwb_hip_pile_counts", "bwb_hip_pile_reset", "bwb_hip_pile_site_of", "bwb_hip_pile_stats",
 ]
 ABI_VERSION = 3  # BWB_HIP_ABI_VERSION (include/bwbble_hip.h)
 MAX_SLOTS = 8  # BWB_MAX_SLOTS
@@ -161,6 +162,14 @@ def lib():
         L.bwb_hip_batch_md.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(C.c_uint32)]
         L.bwb_hip_md_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p] + [C.POINTER(C.c_void_p)] * 3
         L.bwb_hip_md_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.bwb_hip_pile_begin.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.bwb_hip_slot_pile.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+        L.bwb_hip_batch_pile.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+        L.bwb_hip_pile_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.bwb_hip_pile_counts.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        L.bwb_hip_pile_reset.argtypes = [C.c_void_p]
+        L.bwb_hip_pile_site_of.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.bwb_hip_pile_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -598,6 +607,69 @@ class Context:
     def md_stats(self):
         """(reads of kind MD_OK, MD bytes, kernel ms) of the last md call"""
         return self._count_steps_ms(lib().bwb_hip_md_stats)
+
+    # -- allele counts at the text's IUPAC sites (-A): device-resident counters, n_sites x (A, C, G, T), summed over every pile call (needs set_text
+    #    and pile_begin; the slot forms set_sa, with lifted / joined set_loci and set_bubble_chrom) --
+    def pile_begin(self):
+        """builds the site index over the text and zeroed counters -> the number of sites.  After set_text, before the first upload"""
+        n = C.c_uint64()
+        _chk(lib().bwb_hip_pile_begin(self._h, C.byref(n)))
+        return n.value
+
+    def slot_pile(self, slot, max_mm=6, max_alt=5, lifted=False, joined=False, min_mapq=0):
+        """counts the slot's reads -> the reads counted; a second call on the same submission counts nothing and returns 0"""
+        n = C.c_uint64()
+        _chk(lib().bwb_hip_slot_pile(self._h, slot, max_mm, max_alt, int(bool(lifted)), int(bool(joined)), min_mapq, C.byref(n)))
+        return n.value
+
+    def batch_pile(self, max_mm=6, max_alt=5, lifted=False, joined=False, min_mapq=0):
+        """the same for the one-batch interface (after run() / align())"""
+        n = C.c_uint64()
+        _chk(lib().bwb_hip_batch_pile(self._h, max_mm, max_alt, int(bool(lifted)), int(bool(joined)), min_mapq, C.byref(n)))
+        return n.value
+
+    def pile_records(self, seqs, lens, places, kinds=None, lift_off=None, words=None, mapq=None, min_mapq=0):
+        """the same kernel on reads and records of the caller's, laid out as for md_records; mapq: one value per read in place of the records' own"""
+        seqs, lens = _read_arrays(seqs, lens)
+        places = np.ascontiguousarray(places, dtype=PLACE_DTYPE)
+        if len(places) != len(lens):
+            raise ValueError("one placement record per read")
+        lift = [None, None, None]
+        if kinds is not None:
+            kinds = np.ascontiguousarray(kinds, dtype=np.uint8)
+            lift_off = np.ascontiguousarray(lift_off, dtype=np.uint64)
+            words = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, 4)
+            if len(kinds) != len(lens) or len(lift_off) != len(lens) + 1 or len(words) != int(lift_off[-1]):
+                raise ValueError("kinds must have one entry per read, lift_off one more, words one row per 16-byte word")
+            lift = [kinds.ctypes.data, lift_off.ctypes.data, words.ctypes.data]
+        if mapq is not None:
+            mapq = np.ascontiguousarray(mapq, dtype=np.uint8)
+            if len(mapq) != len(lens):
+                raise ValueError("one MAPQ per read")
+        _chk(lib().bwb_hip_pile_records(self._h, seqs.ctypes.data, lens.ctypes.data, seqs.shape[1], places.ctypes.data, len(lens), *lift,
+                                        mapq.ctypes.data if mapq is not None else None, min_mapq))
+
+    def pile_counts(self, first=0, n=None, n_sites=None):
+        """the counters of the sites first .. first + n - 1 as an (n, 4) uint32 array: A, C, G, T (n None: up to n_sites, which pile_begin returned)"""
+        if n is None:
+            n = n_sites - first
+        out = np.zeros((n, 4), dtype=np.uint32)
+        _chk(lib().bwb_hip_pile_counts(self._h, first, n, out.ctypes.data))
+        return out
+
+    def pile_reset(self):
+        _chk(lib().bwb_hip_pile_reset(self._h))
+
+    def pile_site_of(self, pos):
+        """the site number of every text position, -1 where it is no site"""
+        pos = np.ascontiguousarray(pos, dtype=np.uint64)
+        out = np.zeros(len(pos), dtype=np.int64)
+        _chk(lib().bwb_hip_pile_site_of(self._h, pos.ctypes.data, len(pos), out.ctypes.data))
+        return out
+
+    def pile_stats(self):
+        """(reads counted, adds, kernel ms) of the last pile call that launched"""
+        return self._count_steps_ms(lib().bwb_hip_pile_stats)
 
     def dtab_info(self):
         """the context's calculate_d table: {K (0: none), build seconds, bytes}"""

@@ -146,6 +146,7 @@ struct Slot {
 	int lift_mm = -1, lift_alt = -1; /* lift holds the records for this max_mm and max_alt (-1: none) */
 	MdBufs md;                    /* bwb_hip_slot_md */
 	int md_mm = -1, md_alt = -1, md_lifted = -1; /* md holds the records for this max_mm, and with lifted for this max_alt (-1: none) */
+	bool piled = false;           /* bwb_hip_slot_pile has counted this submission (cleared at the next upload) */
 	std::vector<uint8_t> h_status;
 	std::vector<uint64_t> h_aln_off;
 	std::vector<bwb_aln> h_alns;
@@ -207,6 +208,10 @@ struct bwb_hip_ctx {
 	DevMem d_text; uint64_t text_n = 0;           /* k_md_count / k_md: the forward text at 4 bits per character (bwb_hip_set_text; 0: none) */
 	MdBufs md_rec;                                /* bwb_hip_md_records */
 	double md_ms = 0; uint64_t md_reads = 0, md_bytes = 0; /* the last md call */
+	DevMem d_site_base, d_counts, d_pile_stats;   /* k_pile: the sites below every 16-byte word of the text, the n_sites x 4 counters, reads and adds of one launch (bwb_hip_pile_begin) */
+	PinMem h_pile_stats;
+	bool pile_on = false; uint64_t pile_sites = 0; /* pile_begin has run on this text; its sites */
+	double pile_ms = 0; uint64_t pile_reads = 0, pile_adds = 0; /* the last pile call that launched */
 	bool force_slices = false;          /* BWB_FORCE_SLICES: the one-batch API parks and resumes too (tests) */
 	bool dbg = false, dbg_iters = false;
 	const char *launch_log = nullptr;   /* BWB_LAUNCH_LOG=<file>: one JSON line per class-0 kernel launch (synchronises after every launch: a profiling aid) */
@@ -779,7 +784,7 @@ extern "C" int bwb_hip_slot_upload(bwb_hip_ctx *c, int si, const bwb_params *p, 
 	/* (pageable source: the runtime stages it before returning, so h_descs may change again right away) */
 	HIPCHK(hipMemcpyAsync(c->d_descs.as<SlotDesc>() + si, &d, sizeof(SlotDesc), hipMemcpyHostToDevice, c->cstream));
 	HIPCHK(hipEventRecord(s.ev_up.e, c->cstream));
-	s.uploaded = true; s.submitted = false; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.join_mm = -1; s.lift_mm = -1; s.md_mm = -1;
+	s.uploaded = true; s.submitted = false; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.join_mm = -1; s.lift_mm = -1; s.md_mm = -1; s.piled = false;
 	return ensure_class(c, 0);
 }
 
@@ -1027,7 +1032,7 @@ static int submit(bwb_hip_ctx *c, int si, bool suspend) {
 		HIPCHK(hipStreamWaitEvent(c->stream, s.ev_calcd.e, 0));
 	}
 	HIPCHK(hipMemsetAsync(s.d_ctl.p, 0, 256, c->stream));
-	s.submitted = true; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.join_mm = -1; s.lift_mm = -1; s.md_mm = -1; s.launch = 0;
+	s.submitted = true; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.join_mm = -1; s.lift_mm = -1; s.md_mm = -1; s.piled = false; s.launch = 0;
 	if (s.n_reads == 0) { s.complete = true; s.launch = c->n_launches; return BWB_OK; }
 	HIPCHK(hipMemsetAsync(s.d_n.p, 0, (size_t)s.n_reads * 4, c->stream));
 	if (!ahead) {
@@ -2130,6 +2135,8 @@ extern "C" int bwb_hip_set_text(bwb_hip_ctx *c, const uint8_t *codes, uint64_t n
 	HIPCHK(hipStreamSynchronize(c->rstream)); /* (a kernel of an earlier md call may still read the text that is replaced) */
 	c->text_n = 0;
 	for (auto &s : c->slots) s.md_mm = -1;
+	c->pile_on = false; c->pile_sites = 0; /* (the site index and the counters were this text's) */
+	c->d_site_base.release(); c->d_counts.release();
 	const uint64_t CH = 1ull << BWB_TEXT_CHUNK_SHIFT, n_words = (n_fwd + 31) / 32;
 	HIPCHK(c->d_text.alloc((size_t)n_words * 16));
 	DevMem d_stage, d_bad;
@@ -2293,6 +2300,211 @@ extern "C" int bwb_hip_md_stats(bwb_hip_ctx *c, uint64_t *reads, uint64_t *md_by
 	if (reads) *reads = c->md_reads;
 	if (md_bytes) *md_bytes = c->md_bytes;
 	if (kernel_ms) *kernel_ms = c->md_ms;
+	return BWB_OK;
+}
+
+/* ---- allele counts at the text's IUPAC sites (k_site_count, k_site_add, k_pile, k_site_of) ---------------------------------------------- */
+extern "C" int bwb_hip_pile_begin(bwb_hip_ctx *c, uint64_t *n_sites) {
+	if (!c || !n_sites) return fail(BWB_E_ARG, "pile_begin: null argument");
+	if (!c->text_n) return fail(BWB_E_STATE, "pile_begin: the text has not been uploaded (bwb_hip_set_text)");
+	const uint64_t n_words = (c->text_n + 31) / 32;
+	if (n_words > 0xFFFFFFFFull) return fail(BWB_E_ARG, "pile_begin: the text has more than 2^32 - 1 words of 32 characters");
+	HIPCHK(hipSetDevice(c->device));
+	HIPCHK(hipStreamSynchronize(c->rstream)); /* (a pile kernel of an earlier call may still add to the counters that are replaced) */
+	c->pile_on = false; c->pile_sites = 0;
+	const unsigned nblk = (unsigned)((n_words + BWB_BLOCK - 1) / BWB_BLOCK);
+	DevMem d_bsum, d_total;
+	HIPCHK(c->d_site_base.alloc((size_t)n_words * 4));
+	HIPCHK(d_bsum.alloc((size_t)nblk * 8));
+	HIPCHK(d_total.alloc(8));
+	hipLaunchKernelGGL(k_site_count, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, c->d_text.as<uint4>(), (uint32_t)n_words, c->d_site_base.as<uint32_t>(), d_bsum.as<uint64_t>());
+	hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(BWB_BLOCK), 0, c->rstream, d_bsum.as<uint64_t>(), (uint32_t)nblk, d_total.as<uint64_t>());
+	hipLaunchKernelGGL(k_site_add, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, c->d_site_base.as<uint32_t>(), (uint32_t)n_words, d_bsum.as<uint64_t>());
+	HIPCHK(hipGetLastError());
+	uint64_t total = 0;
+	HIPCHK(hipMemcpyAsync(&total, d_total.p, 8, hipMemcpyDeviceToHost, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	if (total > 0xFFFFFFFFull) { c->d_site_base.release(); return fail(BWB_E_ARG, "pile_begin: the text has more than 2^32 - 1 sites"); }
+	HIPCHK(c->d_counts.alloc((size_t)total * 16));
+	if (total) HIPCHK(hipMemsetAsync(c->d_counts.p, 0, (size_t)total * 16, c->rstream));
+	HIPCHK(c->d_pile_stats.alloc(16));
+	HIPCHK(c->h_pile_stats.reserve(16));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	c->pile_on = true; c->pile_sites = total;
+	c->pile_ms = 0; c->pile_reads = 0; c->pile_adds = 0;
+	*n_sites = total;
+	return BWB_OK;
+}
+
+/* k_pile over n reads (reads, lengths, placement records, - d_kind NULL: none - lift records and - d_mapq NULL: the placement's own - one MAPQ
+ * byte every mapq_stride bytes, all device memory) into the context's counters; sets pile_ms / pile_reads / pile_adds.  On the result stream,
+ * behind the kernels that wrote the records; the grid of the md kernels, for their reason (a lane's walk is a chain of dependent loads).  What
+ * comes back is the 16 bytes of the two sums. */
+static int pile_launch(bwb_hip_ctx *c, const uint8_t *d_reads, const uint16_t *d_lens, uint32_t stride, const uint4 *d_places, uint32_t n, const uint8_t *d_kind, const uint64_t *d_loff,
+                       const uint4 *d_lrecs, const uint8_t *d_mapq, uint32_t mapq_stride, int min_mapq) {
+	if (!n) return BWB_OK; /* (nothing launched: the figures of the last launch stay) */
+	const unsigned nblk = (unsigned)(((size_t)n + BWB_BLOCK - 1) / BWB_BLOCK);
+	const unsigned grid = (unsigned)std::min<size_t>(nblk, (size_t)c->num_cu * 8);
+	const uint32_t n_seq = d_kind ? c->loci_nseq : 0u;
+	HIPCHK(hipMemsetAsync(c->d_pile_stats.p, 0, 16, c->rstream));
+	Timed t(c, c->rstream);
+	RC(t.begin());
+	hipLaunchKernelGGL(k_pile, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, d_reads, d_lens, stride, d_places, n, d_kind, d_loff, d_lrecs, c->d_lstart.as<uint64_t>(), n_seq,
+	                   c->d_text.as<uint4>(), c->text_n, d_mapq, mapq_stride, (uint32_t)min_mapq, c->d_site_base.as<uint32_t>(), c->d_counts.as<uint32_t>(),
+	                   c->d_pile_stats.as<unsigned long long>());
+	HIPCHK(hipGetLastError());
+	RC(t.end());
+	HIPCHK(hipMemcpyAsync(c->h_pile_stats.p, c->d_pile_stats.p, 16, hipMemcpyDeviceToHost, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	float ms = 0;
+	RC(t.ms(&ms));
+	c->pile_ms = ms;
+	c->pile_reads = c->h_pile_stats.as<uint64_t>()[0];
+	c->pile_adds = c->h_pile_stats.as<uint64_t>()[1];
+	return BWB_OK;
+}
+
+static int pile_ready(bwb_hip_ctx *c, const char *who, int max_alt, int lifted, int joined, int min_mapq) {
+	if (min_mapq < 0 || min_mapq > 255) return fail(BWB_E_ARG, std::string(who) + ": min_mapq must be 0..255");
+	if (max_alt < 0 || max_alt > 255) return fail(BWB_E_ARG, std::string(who) + ": max_alt must be 0..255");
+	if (!c->pile_on) return fail(BWB_E_STATE, std::string(who) + ": no site index and counters (bwb_hip_pile_begin)");
+	if (!c->d_SA.p) return fail(BWB_E_STATE, std::string(who) + ": sampled SA not uploaded (bwb_hip_set_sa)");
+	if (lifted) RC(lift_ready(c, who, max_alt));
+	if (joined) {
+		if (!max_alt) return fail(BWB_E_STATE, std::string(who) + ": the joined MAPQ needs the items of max_alt 1..255");
+		RC(join_ready(c, who, max_alt));
+	}
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_slot_pile(bwb_hip_ctx *c, int si, int max_mm, int max_alt, int lifted, int joined, int min_mapq, uint64_t *reads_counted) {
+	if (!c || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_pile: bad argument");
+	RC(pile_ready(c, "slot_pile", max_alt, lifted, joined, min_mapq));
+	if (reads_counted) *reads_counted = 0;
+	/* (each waits for the slot, refuses what slot_place refuses, and leaves its records in the slot's device memory) */
+	const bwb_place *places = nullptr;
+	uint32_t n = 0;
+	RC(bwb_hip_slot_place(c, si, max_mm, &places, &n));
+	Slot &s = c->slots[si];
+	if (s.piled) return BWB_OK; /* (a submission is counted once) */
+	if (lifted) {
+		const uint8_t *kinds = nullptr;
+		const uint64_t *lift_off = nullptr;
+		const bwb_lift *lrecs = nullptr;
+		uint64_t nq = 0;
+		RC(bwb_hip_slot_lift(c, si, max_mm, max_alt, &kinds, &lift_off, &lrecs, &nq));
+	}
+	if (joined) {
+		const uint64_t *alt_off = nullptr;
+		const bwb_alt *alts = nullptr;
+		const bwb_locus *loci = nullptr;
+		const bwb_join *joins = nullptr;
+		RC(bwb_hip_slot_join(c, si, max_mm, max_alt, &places, &alt_off, &alts, &loci, &joins, &n));
+	}
+	n = s.n_reads; /* (not n_tot: a carried read that rides along behind the batch's reads has no record) */
+	if (n) {
+		HIPCHK(hipStreamWaitEvent(c->rstream, s.ev_up.e, 0)); /* (the slot's reads, uploaded on the copy stream) */
+		RC(pile_launch(c, s.d_reads.as<uint8_t>(), s.d_lens.as<uint16_t>(), s.stride, s.d_place.as<uint4>(), n, lifted ? s.lift.d_kind.as<uint8_t>() : nullptr,
+		               s.lift.d_off.as<uint64_t>(), s.lift.d_recs.as<uint4>(), joined ? s.d_join.as<uint8_t>() + offsetof(bwb_join, mapq) : nullptr, (uint32_t)sizeof(bwb_join), min_mapq));
+		if (reads_counted) *reads_counted = c->pile_reads;
+	}
+	s.piled = true;
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_batch_pile(bwb_hip_ctx *c, int max_mm, int max_alt, int lifted, int joined, int min_mapq, uint64_t *reads_counted) {
+	if (!c) return fail(BWB_E_ARG, "batch_pile: null context");
+	RC(pile_ready(c, "batch_pile", max_alt, lifted, joined, min_mapq));
+	if (!c->slots[0].submitted || !c->slots[0].complete) return fail(BWB_E_STATE, "batch_pile: batch_run has not completed");
+	return bwb_hip_slot_pile(c, 0, max_mm, max_alt, lifted, joined, min_mapq, reads_counted);
+}
+
+/* the kernel on reads and records of the caller's instead of a slot's (for parity tests) */
+extern "C" int bwb_hip_pile_records(bwb_hip_ctx *c, const uint8_t *reads_fwd, const uint16_t *lens, uint32_t stride, const bwb_place *places, uint32_t n, const uint8_t *kinds,
+                                    const uint64_t *lift_off, const bwb_lift *lift_recs, const uint8_t *mapq, int min_mapq) {
+	if (!c || (n && (!reads_fwd || !lens || !places)) || n > 0x7FFFFFFFu || stride < 1 || stride > 255) return fail(BWB_E_ARG, "pile_records: bad argument");
+	if ((kinds != nullptr) != (lift_off != nullptr)) return fail(BWB_E_ARG, "pile_records: the lift kinds and offsets come together");
+	if (min_mapq < 0 || min_mapq > 255) return fail(BWB_E_ARG, "pile_records: min_mapq must be 0..255");
+	if (!c->pile_on) return fail(BWB_E_STATE, "pile_records: no site index and counters (bwb_hip_pile_begin)");
+	if (kinds && !c->loci_nseq) return fail(BWB_E_STATE, "pile_records: lift records need the record table (bwb_hip_set_loci)");
+	uint64_t words = 0;
+	if (kinds) {
+		if (lift_off[0] != 0) return fail(BWB_E_ARG, "pile_records: lift_off[0] must be 0");
+		for (uint32_t r = 0; r < n; r++)
+			if (lift_off[r + 1] < lift_off[r]) return fail(BWB_E_ARG, "pile_records: lift_off does not ascend at read " + std::to_string(r));
+		words = lift_off[n];
+		if (words && !lift_recs) return fail(BWB_E_ARG, "pile_records: null argument");
+	}
+	HIPCHK(hipSetDevice(c->device));
+	DevMem d_reads, d_lens, d_places, d_kind, d_loff, d_lrecs, d_mapq;
+	HIPCHK(d_reads.alloc((size_t)n * stride));
+	HIPCHK(d_lens.alloc((size_t)n * 2));
+	HIPCHK(d_places.alloc((size_t)n * sizeof(bwb_place)));
+	if (n) {
+		HIPCHK(hipMemcpyAsync(d_reads.p, reads_fwd, (size_t)n * stride, hipMemcpyHostToDevice, c->rstream));
+		HIPCHK(hipMemcpyAsync(d_lens.p, lens, (size_t)n * 2, hipMemcpyHostToDevice, c->rstream));
+		HIPCHK(hipMemcpyAsync(d_places.p, places, (size_t)n * sizeof(bwb_place), hipMemcpyHostToDevice, c->rstream));
+	}
+	if (kinds) {
+		HIPCHK(d_kind.alloc((size_t)n));
+		HIPCHK(d_loff.alloc(((size_t)n + 1) * 8));
+		HIPCHK(d_lrecs.alloc((size_t)words * sizeof(bwb_lift)));
+		if (n) HIPCHK(hipMemcpyAsync(d_kind.p, kinds, (size_t)n, hipMemcpyHostToDevice, c->rstream));
+		HIPCHK(hipMemcpyAsync(d_loff.p, lift_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->rstream));
+		if (words) HIPCHK(hipMemcpyAsync(d_lrecs.p, lift_recs, (size_t)words * sizeof(bwb_lift), hipMemcpyHostToDevice, c->rstream));
+	}
+	if (mapq && n) {
+		HIPCHK(d_mapq.alloc((size_t)n));
+		HIPCHK(hipMemcpyAsync(d_mapq.p, mapq, (size_t)n, hipMemcpyHostToDevice, c->rstream));
+	}
+	HIPCHK(hipStreamSynchronize(c->rstream)); /* (pageable memory of the caller) */
+	return pile_launch(c, d_reads.as<uint8_t>(), d_lens.as<uint16_t>(), stride, d_places.as<uint4>(), n, kinds ? d_kind.as<uint8_t>() : nullptr, d_loff.as<uint64_t>(), d_lrecs.as<uint4>(),
+	                   mapq && n ? d_mapq.as<uint8_t>() : nullptr, 1u, min_mapq);
+}
+
+extern "C" int bwb_hip_pile_counts(bwb_hip_ctx *c, uint64_t first, uint64_t n, uint32_t *out) {
+	if (!c || (n && !out)) return fail(BWB_E_ARG, "pile_counts: null argument");
+	if (!c->pile_on) return fail(BWB_E_STATE, "pile_counts: no site index and counters (bwb_hip_pile_begin)");
+	if (first > c->pile_sites || n > c->pile_sites - first) return fail(BWB_E_ARG, "pile_counts: the range leaves the " + std::to_string(c->pile_sites) + " sites");
+	HIPCHK(hipSetDevice(c->device));
+	if (n) HIPCHK(hipMemcpyAsync(out, c->d_counts.as<uint32_t>() + first * 4, (size_t)n * 16, hipMemcpyDeviceToHost, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_pile_reset(bwb_hip_ctx *c) {
+	if (!c) return fail(BWB_E_ARG, "pile_reset: null context");
+	if (!c->pile_on) return fail(BWB_E_STATE, "pile_reset: no site index and counters (bwb_hip_pile_begin)");
+	HIPCHK(hipSetDevice(c->device));
+	if (c->pile_sites) HIPCHK(hipMemsetAsync(c->d_counts.p, 0, (size_t)c->pile_sites * 16, c->rstream));
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_pile_site_of(bwb_hip_ctx *c, const uint64_t *pos, size_t n, int64_t *site) {
+	if (!c || (n && (!pos || !site))) return fail(BWB_E_ARG, "pile_site_of: null argument");
+	if (!c->pile_on) return fail(BWB_E_STATE, "pile_site_of: no site index and counters (bwb_hip_pile_begin)");
+	for (size_t i = 0; i < n; i++)
+		if (pos[i] >= c->text_n) return fail(BWB_E_ARG, "pile_site_of: position outside the text");
+	if (n == 0) return BWB_OK;
+	HIPCHK(hipSetDevice(c->device));
+	DevMem dp, dout;
+	HIPCHK(dp.alloc(n * 8));
+	HIPCHK(dout.alloc(n * 8));
+	HIPCHK(hipMemcpyAsync(dp.p, pos, n * 8, hipMemcpyHostToDevice, c->rstream));
+	const unsigned grid = (unsigned)std::min<size_t>((n + BWB_BLOCK - 1) / BWB_BLOCK, (size_t)c->num_cu * 8);
+	hipLaunchKernelGGL(k_site_of, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, c->d_text.as<uint4>(), c->d_site_base.as<uint32_t>(), dp.as<uint64_t>(), (uint64_t)n, dout.as<int64_t>());
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(site, dout.p, n * 8, hipMemcpyDeviceToHost, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	return BWB_OK;
+}
+
+/* the last pile call that launched: reads counted, adds made, and the kernel's HIP-event time */
+extern "C" int bwb_hip_pile_stats(bwb_hip_ctx *c, uint64_t *reads, uint64_t *adds, double *kernel_ms) {
+	if (!c) return fail(BWB_E_ARG, "pile_stats: null context");
+	if (reads) *reads = c->pile_reads;
+	if (adds) *adds = c->pile_adds;
+	if (kernel_ms) *kernel_ms = c->pile_ms;
 	return BWB_OK;
 }
 

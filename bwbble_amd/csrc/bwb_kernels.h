@@ -11,6 +11,7 @@
  *   k_join_items, k_join_reads   a read's other placements that lie where its primary lies, and its MAPQ without them (`bwbble map -J`)
  *   k_lift_count, k_lift         a placement on a bubble record in the chromosome's coordinates: POS and CIGAR (`bwbble map -R`)
  *   k_text_pack, k_md_count, k_md   the forward text at 4 bits per character, and a read's NM and MD text against it (`bwbble map -D`)
+ *   k_site_count, k_site_add, k_site_of, k_pile   the rank structure over the text's IUPAC sites, and the reads' allele counts at them (`bwbble map -A`)
  * The alignment kernels themselves (kl_calc_d, kl_search: one read per lane) are in bwb_lane.h.
  */
 #pragma once
@@ -1016,5 +1017,124 @@ __global__ __launch_bounds__(BWB_BLOCK) void k_md(const uint8_t *reads, const ui
 		MdWalk m = md_begin(text, reads + (size_t)q * stride, lens[q], v, out + o, (uint32_t)cap);
 		md_walk(m, v);
 		m.number(m.run);
+	}
+}
+
+/* ---- allele counts at the text's IUPAC sites (`map -A`) -----------------------------------------------------------------------------
+ * The rule is in include/bwbble_hip.h (bwb_hip_pile_begin).  A SITE is a text position whose code has two or three members; sites are numbered
+ * in text order.  The rank structure over them is one uint32 per 16-byte word of the packed text: site_base[w] = the sites below character
+ * 32 w, so that position i is site site_base[i >> 5] + popcount(site mask of its word & the bits below i & 31).
+ * k_site_count: one lane per 16-byte word - its 32-bit site mask, the popcount, the block's exclusive scan (the scheme of k_scan_blocks, fused
+ * behind the popcount so that no count array exists) into site_base[] and the block's sum into bsum[]; k_scan_sums turns bsum[] into the blocks'
+ * offsets and the 64-bit total; k_site_add adds them.  What lies behind the text in its last word is code 0, no site. */
+#define PILE_SITE_CODES 0x7B74u /* bit c: code c is K 2, S 4, B 5, Y 6, M 8, H 9, V 11, R 12, D 13 or W 14 */
+static_assert(PILE_SITE_CODES == (1u << 2 | 1u << 4 | 1u << 5 | 1u << 6 | 1u << 8 | 1u << 9 | 1u << 11 | 1u << 12 | 1u << 13 | 1u << 14), "the ten codes with two or three members");
+__device__ __forceinline__ uint32_t site_mask8(uint32_t x) { /* bit k: nibble k of x is a site's code */
+	uint32_t m = 0;
+#pragma unroll
+	for (int k = 0; k < 8; k++) m |= ((PILE_SITE_CODES >> ((x >> (4 * k)) & 15u)) & 1u) << k;
+	return m;
+}
+__device__ __forceinline__ uint32_t site_mask32(const uint4 w) { return site_mask8(w.x) | (site_mask8(w.y) << 8) | (site_mask8(w.z) << 16) | (site_mask8(w.w) << 24); }
+__global__ __launch_bounds__(BWB_BLOCK) void k_site_count(const uint4 *text, uint32_t n_words, uint32_t *site_base, uint64_t *bsum) {
+	__shared__ uint32_t s_wave[BWB_BLOCK / 64];
+	const uint32_t i = blockIdx.x * BWB_BLOCK + threadIdx.x;
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	const uint32_t v = i < n_words ? (uint32_t)__popc(site_mask32(text[i])) : 0u;
+	uint32_t inc = v; /* (a block's sum is at most 256 * 32) */
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(inc, d); if (lane >= d) inc += t; }
+	if (lane == 63) s_wave[wv] = inc;
+	__syncthreads();
+	uint32_t before = 0, total = 0;
+#pragma unroll
+	for (int k = 0; k < BWB_BLOCK / 64; k++) { if (k < wv) before += s_wave[k]; total += s_wave[k]; }
+	if (i < n_words) site_base[i] = before + inc - v;
+	if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+}
+/* (the caller has refused a total above 2^32 - 1 before this runs: no sum wraps) */
+__global__ __launch_bounds__(BWB_BLOCK) void k_site_add(uint32_t *site_base, uint32_t n_words, const uint64_t *bsum) {
+	const uint32_t i = blockIdx.x * BWB_BLOCK + threadIdx.x;
+	if (i < n_words) site_base[i] += (uint32_t)bsum[blockIdx.x];
+}
+/* test entry: the site number of every queried text position (< n_fwd, checked by the caller), or -1 */
+__global__ __launch_bounds__(BWB_BLOCK) void k_site_of(const uint4 *text, const uint32_t *site_base, const uint64_t *pos, uint64_t n, int64_t *site) {
+	const uint64_t stride = (uint64_t)gridDim.x * BWB_BLOCK;
+	for (uint64_t q = (uint64_t)blockIdx.x * BWB_BLOCK + threadIdx.x; q < n; q += stride) {
+		const uint64_t wi = pos[q] >> 5;
+		const uint32_t k = (uint32_t)pos[q] & 31u, mask = site_mask32(text[wi]);
+		site[q] = (mask >> k) & 1u ? (int64_t)((uint64_t)site_base[wi] + (uint32_t)__popc(mask & ((1u << k) - 1u))) : -1;
+	}
+}
+
+/* k_pile: one lane per READ, grid-strided; the walk of k_md_count - md_read, the same ops from the same start, the same span and length checks,
+ * the text in 16-byte words held in registers - with one add where k_md compares: for every M base that lies on a site and is A, C, G or T,
+ * counts[site * 4 + column] += 1, the columns A, C, G, T by the letter SAM prints.  The site mask is computed once per word held; site_base[] is
+ * loaded only when a base falls on a site, and the read base only then.  A read counts when its kind would be BWB_MD_OK and its MAPQ - the
+ * placement's, or mapq[q * mapq_stride] (the join record's, or the caller's override) - is at least min_mapq.  The adds are relaxed, agent-scope
+ * atomics to scattered counters (a site sees about as many adds per run as the coverage: no aggregation ahead of them); the reads counted and
+ * the adds made are summed over the block - shuffles, then LDS - and added to stats[0] / stats[1] once per block.  Every text position fetched
+ * lies in [0, n_fwd), every read base in [0, len), every site number below n_sites (the index was built from this text). */
+struct PileWalk {
+	const uint4 *text; uint64_t cur; uint4 w; uint32_t mask;  /* the packed text, the word held and its site mask */
+	const uint32_t *site_base; uint32_t *counts;
+	const uint8_t *seq; uint32_t len; bool reverse;
+	uint32_t ri, adds; uint64_t tp;
+	__device__ __forceinline__ void step(uint32_t op, uint32_t count) { /* op: 0 M, 1 I, 2 D, 4 S */
+		if (op == 0u) {
+			for (uint32_t k = 0; k < count; k++, ri++, tp++) {
+				const uint64_t wi = tp >> 5;
+				if (wi != cur) { w = text[wi]; cur = wi; mask = site_mask32(w); }
+				const uint32_t at = (uint32_t)tp & 31u;
+				if (!((mask >> at) & 1u)) continue;
+				const uint32_t c = reverse ? seq[len - 1u - ri] : seq[ri];
+				if (c > 3u) continue; /* a read N */
+				const uint32_t b = reverse ? 3u - c : c; /* A0 G1 C2 T3 as printed */
+				const uint32_t col = (b == 1u || b == 2u) ? 3u - b : b; /* A C G T */
+				const uint64_t site = (uint64_t)site_base[wi] + (uint32_t)__popc(mask & ((1u << at) - 1u));
+				__hip_atomic_fetch_add(counts + site * 4u + col, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+				adds++;
+			}
+		} else if (op == 2u) tp += count;
+		else ri += count;
+	}
+};
+__global__ __launch_bounds__(BWB_BLOCK) void k_pile(const uint8_t *reads, const uint16_t *lens, uint32_t stride, const uint4 *places, uint32_t n_reads, const uint8_t *lift_kind,
+                                                     const uint64_t *lift_off, const uint4 *lift_recs, const uint64_t *lstart, uint32_t n_seq, const uint4 *text, uint64_t n_fwd,
+                                                     const uint8_t *mapq, uint32_t mapq_stride, uint32_t min_mapq, const uint32_t *site_base, uint32_t *counts,
+                                                     unsigned long long *stats) {
+	__shared__ unsigned long long s_sum[2][BWB_BLOCK / 64];
+	const uint32_t gstride = gridDim.x * BWB_BLOCK;
+	unsigned long long my_reads = 0, my_adds = 0;
+	for (uint32_t q = blockIdx.x * BWB_BLOCK + threadIdx.x; q < n_reads; q += gstride) {
+		const MdRead v = md_read(q, places, lift_kind, lift_off, lift_recs, lstart, n_seq);
+		const uint32_t len = lens[q];
+		if (!(v.mapped && len <= 255u && len <= stride)) continue;
+		const uint32_t mq = mapq ? mapq[(size_t)q * mapq_stride] : (places[(size_t)q * 3 + 1].x >> 16) & 0xFFu;
+		if (mq < min_mapq) continue;
+		uint64_t span = 0, on_read = 0;
+		if (v.lifted) for (uint32_t i = 0; i < v.n_ops; i++) { const uint32_t op = md_rec_op(v.rec, i); if ((op & 15u) == 0u || (op & 15u) == 2u) span += op >> 4; if ((op & 15u) != 2u) on_read += op >> 4; }
+		else for (uint32_t t = 0; t < v.alen; t++) { const uint32_t op = lift_op_at(v.runs, v.alen, v.reverse, t); span += op != 1u; on_read += op != 2u; }
+		if (span > MD_MAX_SPAN || v.start < 0 || (uint64_t)v.start > n_fwd || span > n_fwd - (uint64_t)v.start || on_read != len) continue;
+		PileWalk m;
+		m.text = text; m.cur = ~0ull; m.w = make_uint4(0u, 0u, 0u, 0u); m.mask = 0u;
+		m.site_base = site_base; m.counts = counts;
+		m.seq = reads + (size_t)q * stride; m.len = len; m.reverse = v.reverse;
+		m.ri = 0; m.adds = 0; m.tp = (uint64_t)v.start;
+		if (v.lifted) for (uint32_t i = 0; i < v.n_ops; i++) { const uint32_t op = md_rec_op(v.rec, i); m.step(op & 15u, op >> 4); }
+		else for (uint32_t t = 0; t < v.alen; t++) m.step(lift_op_at(v.runs, v.alen, v.reverse, t), 1u);
+		my_reads++; my_adds += m.adds;
+	}
+	/* (every thread of the block gets here: the loop has no barrier inside) */
+#pragma unroll
+	for (int d = 32; d > 0; d >>= 1) { my_reads += __shfl_down(my_reads, d); my_adds += __shfl_down(my_adds, d); }
+	if ((threadIdx.x & 63) == 0) { s_sum[0][threadIdx.x >> 6] = my_reads; s_sum[1][threadIdx.x >> 6] = my_adds; }
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		unsigned long long r = 0, a = 0;
+#pragma unroll
+		for (int k = 0; k < BWB_BLOCK / 64; k++) { r += s_sum[0][k]; a += s_sum[1][k]; }
+		if (r) atomicAdd(stats, r);
+		if (a) atomicAdd(stats + 1, a);
 	}
 }

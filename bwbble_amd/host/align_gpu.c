@@ -49,7 +49,10 @@ typedef struct {
 	const int32_t *chrom_of;  /* -J, -R (NULL: neither): the chromosome's record of every bubble; needs bub */
 	int join;                 /* -J: a read's placements counted by locus; needs max_alt and bub */
 	int lift;                 /* -R: placements on a bubble record written in chromosome coordinates; needs bub */
-	md_text_t *text;          /* -D (NULL: no tags): the forward text of <seq_fasta>.ref, for the tags NM:i / MD:Z */
+	md_text_t *text;          /* -D, -A (NULL: neither): the forward text of <seq_fasta>.ref */
+	int md;                   /* -D: the tags NM:i / MD:Z against the text */
+	pile_t *pile;             /* -A (NULL: no counts): the allele counts at the text's IUPAC sites; on the GPU unless pile_on_host */
+	int pile_on_host;         /* -A with the host's lift or join records (-R / -J on an .ann that is not ascending and disjoint): the host's rule */
 } map_t;
 
 typedef struct {
@@ -84,6 +87,7 @@ typedef struct {
 	double join_ms; unsigned long long join_items, join_joined, join_mapq; /* map -J: k_join_items + k_join_reads, summed over the chunks; reads whose MAPQ changed */
 	double lift_ms; unsigned long long lift_lifted, lift_unliftable, lift_bytes; /* map -R: k_lift_count + scan + k_lift, summed over the chunks; what came back for them */
 	double md_ms, text_s; unsigned long long md_reads, md_bytes, md_back; /* map -D: k_md_count + scan + k_md, summed over the chunks; set_text's seconds; reads tagged, MD bytes, what came back */
+	double pile_ms, pile_begin_s, pile_fetch_s; unsigned long long pile_reads, pile_adds; /* map -A: k_pile, summed over the chunks; pile_begin's and the final read-back's seconds; reads counted, adds */
 } worker_t;
 
 /* The reader: chunk k+1 is parsed (record boundaries by one sequential scan, bases encoded by all cores: reads.c) while chunk k is on
@@ -226,16 +230,27 @@ static void retire_map(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c) {
 	const uint64_t *md_off = NULL;
 	const char *md_text = NULL;
 	md_set_t *host_md = NULL;
-	if (m->text && !host_lift) {
+	if (m->md && !host_lift) {
 		uint64_t nr = 0, nb = 0; double ms = 0;
 		if (bwb_hip_slot_md(ctx, slot, m->max_mm, m->max_alt, m->lift, &md_recs, &md_off, &md_text, &n)) bwb_die("map_reads: GPU %d: %s", w->gpu, bwb_hip_last_error());
 		bwb_hip_md_stats(ctx, &nr, &nb, &ms); /* (the figures of the last call that LAUNCHED: this one, since a chunk's slot is asked once - a second slot_md on it would return its cached records and leave them) */
 		w->md_ms += ms; w->md_reads += nr; w->md_bytes += nb;
 		w->md_back += (unsigned long long)n * sizeof(bwb_md) + ((unsigned long long)n + 1) * 8 + md_off[n];
-	} else if (m->text) {
+	} else if (m->md) {
 		host_md = md_host(pl, n, c->fq.seq, c->fq.stride, c->fq.len, lift_kind, lift_off, lift_recs, m->ann, m->text);
 		md_recs = host_md->recs; md_off = host_md->off; md_text = host_md->text;
 		w->md_reads += host_md->n_ok; w->md_bytes += host_md->off[n];
+	}
+	/* -A: the allele counts of the slot's reads, added to the context's counters (kernel k_pile behind them on the result stream, on the slot's
+	 * resident reads and cached records; nothing per read comes back); with the host's lift or join records, the host's rule into the table itself */
+	if (m->pile && !m->pile_on_host) {
+		uint64_t nr = 0, na = 0; double ms = 0;
+		if (bwb_hip_slot_pile(ctx, slot, m->max_mm, m->max_alt, m->lift, m->join, m->pile->min_mapq, &nr)) bwb_die("map_reads: GPU %d: %s", w->gpu, bwb_hip_last_error());
+		if (n) { bwb_hip_pile_stats(ctx, NULL, &na, &ms); w->pile_ms += ms; w->pile_reads += nr; w->pile_adds += na; } /* (a chunk without reads launches nothing) */
+	} else if (m->pile) {
+		pthread_mutex_lock(&w->pp->mu); /* (pile_host adds with the whole team: one worker at a time) */
+		pile_host(m->pile, pl, n, c->fq.seq, c->fq.stride, c->fq.len, lift_kind, lift_off, lift_recs, joins, m->ann);
+		pthread_mutex_unlock(&w->pp->mu);
 	}
 	const sam_reads_t rd = { .pl = pl, .seq = c->fq.seq, .stride = c->fq.stride, .len = c->fq.len, .text = c->fq.text,
 	                         .name_off = c->fq.name_off, .qual_off = c->fq.qual_off, .name_len = c->fq.name_len, .first = c->first_read,
@@ -317,11 +332,25 @@ static void *gpu_worker(void *arg) {
 		/* -D: the forward text (n_fwd / 2 bytes in HBM: 1.7 GB at GRCh37 scale), before the first slot_upload sizes the chunk pool as well; its
 		 * bytes are read by the .bwt loader behind the SA (bwt_io.c: load_bwt_start_job, md.c: md_text_read).  Not with the host's lift records: the host's rule then */
 		md_text_wait(pp->map->text);
-		if (pp->map->text && !(pp->map->lift && !pp->map->gpu_loci)) {
+		if (pp->map->pile) { /* -A: the host's own count of the sites, which every context's must equal, and the table (the first worker here makes them) */
+			pthread_mutex_lock(&pp->mu);
+			if (!pp->map->pile->text) pile_set_text(pp->map->pile, pp->map->text, pp->map->pile_on_host);
+			pthread_mutex_unlock(&pp->mu);
+		}
+		const int pile_gpu = pp->map->pile && !pp->map->pile_on_host;
+		if ((pp->map->md && !(pp->map->lift && !pp->map->gpu_loci)) || pile_gpu) {
 			const double t0 = wall();
 			if (bwb_hip_set_text(ctx, pp->map->text->codes, pp->map->text->n_fwd)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
 			w->text_s = wall() - t0;
 			if (dbg) fprintf(stderr, "[bwb host] worker %d: text resident at +%.3f s\n", w->gpu, wall() - tq);
+		}
+		/* -A: the site index (n_fwd / 8 bytes) and the zeroed counters (16 bytes per site) behind the text, before the pool is sized as well */
+		if (pile_gpu) {
+			const double t0 = wall();
+			uint64_t n_sites = 0;
+			if (bwb_hip_pile_begin(ctx, &n_sites)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
+			w->pile_begin_s = wall() - t0;
+			if (n_sites != pp->map->pile->n_sites) bwb_die("map_reads: GPU %d counts %llu IUPAC sites in the text, the host's scan of the .ref %llu", w->device, (unsigned long long)n_sites, (unsigned long long)pp->map->pile->n_sites);
 		}
 	}
 	void (*const hand_over)(worker_t *, bwb_hip_ctx *, int, chunk_t *) = pp->map ? retire_map : retire;
@@ -364,6 +393,21 @@ static void *gpu_worker(void *arg) {
 		w->n_reads += c->fq.n;
 		j++;
 		if (dbg) fprintf(stderr, "[bwb host] worker %d: chunk %zu (%u reads) submitted at +%.3f s\n", w->gpu, c->idx, c->fq.n, wall() - tq);
+	}
+	/* -A: the stream has ended and every chunk of this worker is retired - its counters come back in bounded pieces and are summed on the host */
+	if (pp->map && pp->map->pile && !pp->map->pile_on_host) {
+		const double t0 = wall();
+		const uint64_t PIECE = (uint64_t)1 << 20, n_sites = pp->map->pile->n_sites; /* sites per read-back: 16 MB */
+		uint32_t *buf = (uint32_t *)malloc((size_t)(n_sites < PIECE ? n_sites : PIECE) * 16 + 16);
+		for (uint64_t s0 = 0; s0 < n_sites; s0 += PIECE) {
+			const uint64_t ns = n_sites - s0 < PIECE ? n_sites - s0 : PIECE;
+			if (bwb_hip_pile_counts(ctx, s0, ns, buf)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
+			pthread_mutex_lock(&pp->mu);
+			pile_add(pp->map->pile, s0, ns, buf);
+			pthread_mutex_unlock(&pp->mu);
+		}
+		free(buf);
+		w->pile_fetch_s = wall() - t0;
 	}
 	bwb_stats st;
 	if (bwb_hip_flush(ctx) || bwb_hip_get_stats(ctx, &st)) bwb_die("align_reads_inexact_gpu: GPU %d: %s", w->device, bwb_hip_last_error());
@@ -495,13 +539,22 @@ static int run_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, 
 			if (map->gpu_loci) printf("placements lifted to chromosome coordinates on the GPU: lifted %llu  not liftable %llu  kernels %.3f ms  bytes to the host %llu\n", ll, lu, lms, lb);
 			else printf("placements lifted to chromosome coordinates on the host (the .ann records are not ascending and disjoint): lifted %llu  not liftable %llu\n", ll, lu);
 		}
-		if (map->text) { /* -D */
+		if (map->md) { /* -D */
 			double mms = 0, ts = 0; unsigned long long mr = 0, mb = 0, bk = 0;
 			for (int g = 0; g < n_gpus; g++) { mr += ws[g].md_reads; mb += ws[g].md_bytes; bk += ws[g].md_back; if (ws[g].md_ms > mms) mms = ws[g].md_ms; if (ws[g].text_s > ts) ts = ws[g].text_s; }
 			if (!(map->lift && !map->gpu_loci))
 				printf("NM and MD against the text on the GPU: reads %llu  MD bytes %llu  kernels %.3f ms  bytes to the host %llu  text %llu characters read in %.3f s, set in %.3f s\n", mr, mb, mms, bk,
 				       (unsigned long long)map->text->n_fwd, map->text->seconds, ts);
 			else printf("NM and MD against the text on the host (the .ann records are not ascending and disjoint): reads %llu  MD bytes %llu\n", mr, mb);
+		}
+		if (map->pile) { /* -A */
+			double pms = 0, bs = 0, fs = 0; unsigned long long pr = 0, pa = 0;
+			for (int g = 0; g < n_gpus; g++) { pr += ws[g].pile_reads; pa += ws[g].pile_adds; if (ws[g].pile_ms > pms) pms = ws[g].pile_ms; if (ws[g].pile_begin_s > bs) bs = ws[g].pile_begin_s; if (ws[g].pile_fetch_s > fs) fs = ws[g].pile_fetch_s; }
+			if (!map->pile_on_host)
+				printf("allele counts at the text's IUPAC sites on the GPU: sites %llu  reads counted %llu  adds %llu  k_pile %.3f ms  site index and counters %llu bytes, built in %.3f s  counters read back in %.3f s\n",
+				       (unsigned long long)map->pile->n_sites, pr, pa, pms, (unsigned long long)((map->text->n_fwd + 31) / 32 * 4 + map->pile->n_sites * 16), bs, fs);
+			else printf("allele counts at the text's IUPAC sites on the host (the .ann records are not ascending and disjoint): sites %llu  reads counted %llu  adds %llu\n",
+			            (unsigned long long)map->pile->n_sites, (unsigned long long)map->pile->reads, (unsigned long long)map->pile->adds);
 		}
 		if (map->max_alt) {
 			double ams = 0; unsigned long long ast = 0, ait = 0;
@@ -561,13 +614,15 @@ int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_
 }
 
 /* `bwbble map`: align_reads + alns2sam in one pass.  The .bwt is loaded once, with its SA; the SAM header is written before the first chunk. */
-int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int lift, int md, int n_gpus) {
+int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, int n_gpus) {
 	printf("**** BWBBLE Read Mapping (align + aln2sam in one pass) ****\n");
+	/* -A: the counts file is opened before anything is loaded; until it is written, a run that stops leaves none behind */
+	pile_t *pile = countsFname ? pile_open(countsFname, min_mapq) : NULL;
 	/* -B: the table first (a refused table stops the run before anything is created) */
 	bubble_table_t *bub = bubbleFname ? load_bubbles(bubbleFname) : NULL;
 	if (lift && bub) lift_check_table(bub); /* -R (main.c: only with -B): a bubble the rule refuses is named here */
 	/* -D: a missing <seq_fasta>.ref, or one of another size than the .ann says, stops the run here; the .bwt loader reads its forward half, behind the sampled SA */
-	md_text_t *text = md ? md_text_open(fastaFname, 1) : NULL;
+	md_text_t *text = md || pile ? md_text_open_for(fastaFname, 1, md ? "-D" : "-A") : NULL; /* (-A loads it the same way, with or without -D) */
 	/* before anything is created: without a GPU no SAM file is left behind */
 	if (bwb_hip_device_count() < 1) bwb_die("align_reads_inexact_gpu: no HIP device found (this build has no CPU alignment path)");
 	size_t L = strlen(fastaFname) + 8;
@@ -598,13 +653,20 @@ int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *
 	if (!sam) { perror(samFname); bwb_die("map_reads: Cannot open SAM file: %s!", samFname); }
 	sam_write_header(sam, ann);
 	const map_t m = { .max_mm = max_mm, .max_alt = max_alt, .ann = ann, .ann_sorted = sam_ann_sorted(ann),
-	                  .bub = bub, .bubble_of = bubble_of, .gpu_loci = gpu_loci, .rec_start = rec_start, .rec_end = rec_end, .chrom_of = chrom_of, .join = join, .lift = lift, .text = text };
+	                  .bub = bub, .bubble_of = bubble_of, .gpu_loci = gpu_loci, .rec_start = rec_start, .rec_end = rec_end, .chrom_of = chrom_of, .join = join, .lift = lift, .text = text,
+	                  .md = md, .pile = pile, .pile_on_host = pile && bub && !gpu_loci && (lift || join) };
+
 	t = wall();
 	printf("BWBBLE Inexact Alignment (MI355X)...\n");
 	run_stream(BWT, readsFname, params, sam, samFname, n_gpus, &m);
+	if (pile) { /* -A: the SAM file is complete (run_stream has closed it) */
+		const double tw = wall();
+		const unsigned long long lines = pile_write(pile, ann);
+		printf("allele counts written: %llu sites with a count in %.3f s\n", lines, wall() - tw);
+	}
 	printf("Total read mapping time (index and read loading overlapped): %.2f sec\n", wall() - t);
 	free_bwt(BWT); free_ann(ann);
 	free(bwtFname); free(annFname);
-	free(bubble_of); free(chrom_of); free(rec_start); free(rec_end); free_bubbles(bub); md_text_free(text);
+	free(bubble_of); free(chrom_of); free(rec_start); free(rec_end); free_bubbles(bub); pile_free(pile); md_text_free(text);
 	return 0;
 }

@@ -120,14 +120,14 @@ int aln_path_bytes(const bwb_aln *a, unsigned char *path /* >= 272 bytes */); /*
 void set_default_aln_params(aln_params_t *params);                     /* align.c:22-38 */
 int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_t *params, int n_gpus); /* align.c:40-87 */
 int align_reads_inexact_gpu_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, char *alnFname, int n_gpus); /* the GPU's align_reads_inexact_parallel (inexact_match.h:40) over a streamed FASTQ */
-int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int lift, int md, int n_gpus); /* `bwbble map`: align + aln2sam in one pass, the hits evaluated on the GPU */
+int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, int n_gpus); /* `bwbble map` (countsFname: -A, NULL: no counts; min_mapq: -a): align + aln2sam in one pass, the hits evaluated on the GPU */
 
 /* precalc.c */
 void precalc_sa_intervals(bwt_t *BWT, const aln_params_t *params, const char *preFname); /* align.c:200-224: writes <fasta>.pre */
 int check_precalc_file(const char *preFname); /* the walk of load_precalc_sa_intervals (align.c:226-238) over an existing table: 0 = complete */
 
 /* sam.c */
-void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join, int lift, int md); /* align.c:494-556; max_alt: -X (0: no tags); bubbleFname: -B (NULL: no tags); join: -J; lift: -R; md: -D */
+void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq); /* align.c:494-556; max_alt: -X (0: no tags); bubbleFname: -B (NULL: no tags); join: -J; lift: -R; md: -D; countsFname: -A (NULL: no counts), min_mapq: -a */
 /* the two halves of alns2sam: eval_aln of one read on the host, and the text of a block of reads from placement records (which `map` gets
  * from the GPU instead, bwb_hip_slot_place) */
 #define SAM_BLOCK_READS ((size_t)1 << 14)                              /* reads formatted by one thread at a time */
@@ -152,7 +152,7 @@ uint64_t alt_placements(const bwb_aln *e, uint64_t ne);               /* the row
 void sam_write_header(FILE *sam, const fasta_annotations_t *ann);
 int sam_ann_sorted(const fasta_annotations_t *ann);
 char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_annotations_t *ann, int ann_sorted, size_t *out_len);
-void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join, int lift, int md); /* developer command: records from a file (altsFname: NULL or the items; bubbleFname: NULL or -B's table; join: -J, the items file then ends with one suboptimal byte per item; lift: -R; md: -D) */
+void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq); /* developer command: records from a file (countsFname / min_mapq: -A / -a; (altsFname: NULL or the items; bubbleFname: NULL or -B's table; join: -J, the items file then ends with one suboptimal byte per item; lift: -R; md: -D) */
 
 /* pad.c: bubble hits in reference coordinates (the reference's mg-ref/sam_pad.cpp) */
 typedef struct bubble_table {                                          /* bubble.data (mg-ref/comb.cpp:245-253): the k-th pair of lines is bubble k */
@@ -192,8 +192,9 @@ static inline unsigned lift_op_at(const uint16_t *gap_run, unsigned alen, int re
 }
 
 /* md.c: -D, NM:i and MD:Z against the text of <seq_fasta>.ref (include/bwbble_hip.h: bwb_md) */
-typedef struct md_text { uint8_t *codes; uint64_t n_fwd; double seconds; char *refFname; volatile int ready; } md_text_t; /* the forward text, one code per byte; ready: the bytes are in memory (release/acquire) */
+typedef struct md_text { uint8_t *codes; uint64_t n_fwd; double seconds; char *refFname; volatile int ready; const char *flag; } md_text_t; /* the forward text, one code per byte; ready: the bytes are in memory (release/acquire) */
 md_text_t *md_text_open(const char *fastaFname, int deferred);        /* a missing .ref or one that is not 2 x n_fwd bytes stops the run and names `bwbble fasta2ref`; deferred: the bytes are not read here but by md_text_read */
+md_text_t *md_text_open_for(const char *fastaFname, int deferred, const char *flag); /* the same; flag: the option the messages name ("-D", "-A") */
 void md_text_read(void *text);                                         /* reads the n_fwd bytes of a deferred text (a job of the .bwt loader: load_bwt_start_job) */
 void md_text_wait(md_text_t *t);                                       /* until the n_fwd bytes are in memory */
 void md_text_free(md_text_t *t);
@@ -204,6 +205,20 @@ typedef struct { bwb_md *recs; uint64_t *off; char *text; uint64_t n_ok, n_too_l
 md_set_t *md_host(const bwb_place *pl, size_t n, const uint8_t *seq, uint32_t stride, const uint16_t *len, const uint8_t *lift_kind, const uint64_t *lift_off,
                   const bwb_lift *lift_recs, const fasta_annotations_t *ann, const md_text_t *t);
 void md_free(md_set_t *ms);
+
+/* pile.c: -A, allele counts at the text's IUPAC sites (include/bwbble_hip.h: bwb_hip_pile_begin) */
+typedef struct pile {
+	char *fname; FILE *f; int min_mapq;                               /* the counts file, open since before anything was loaded (NULL: none, a table in memory only); -a */
+	const md_text_t *text; uint64_t n_sites; uint32_t *base;          /* the text, its sites, and - for pile_host - the sites below every 32 characters */
+	uint32_t *counts; uint64_t reads, adds;                           /* n_sites x (A, C, G, T), wrapping; what pile_host has counted */
+} pile_t;
+pile_t *pile_open(const char *countsFname, int min_mapq);             /* a path that cannot be written stops the run; until pile_write has finished, a run that exits leaves no file */
+void pile_set_text(pile_t *p, const md_text_t *t, int index);         /* counts the sites of the text in memory and makes the zeroed table; index: also what pile_host needs */
+uint64_t pile_host(pile_t *p, const bwb_place *pl, size_t n, const uint8_t *seq, uint32_t stride, const uint16_t *len, const uint8_t *lift_kind, const uint64_t *lift_off,
+                   const bwb_lift *lift_recs, const bwb_join *joins, const fasta_annotations_t *ann); /* kernel k_pile on the host: adds into the table, returns the reads counted (joins NULL: the placements' MAPQ) */
+void pile_add(pile_t *p, uint64_t first, uint64_t n, const uint32_t *counts); /* adds a context's counters of n sites from `first` (bwb_hip_pile_counts) */
+uint64_t pile_write(pile_t *p, const fasta_annotations_t *ann);       /* the header line and one line per site with a counter that is not zero; closes the file; returns the lines */
+void pile_free(pile_t *p);
 void sam_pad(const char *dataFname, const char *inFname, const char *outFname); /* `bwbble sampad`: sam_pad.cpp:47-94 over SAM text */
 
 /* The OpenMP teams of the host stages of `align` / `aln2sam` (base encoding, .aln serialisation, SAM text) have at most 32 threads unless

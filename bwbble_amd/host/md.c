@@ -20,32 +20,36 @@ void md_text_read(void *text) {
 	md_text_t *t = (md_text_t *)text;
 	const double t0 = md_wall();
 	FILE *f = fopen(t->refFname, "rb");
-	if (!f) { perror(t->refFname); bwb_die("-D: Cannot open the text: %s (`bwbble fasta2ref <seq_fasta>` writes it)", t->refFname); }
-	if (fread(t->codes, 1, t->n_fwd, f) != t->n_fwd) bwb_die("-D: %s ends before its %llu forward characters", t->refFname, (unsigned long long)t->n_fwd);
+	if (!f) { perror(t->refFname); bwb_die("%s: Cannot open the text: %s (`bwbble fasta2ref <seq_fasta>` writes it)", t->flag, t->refFname); }
+	if (fread(t->codes, 1, t->n_fwd, f) != t->n_fwd) bwb_die("%s: %s ends before its %llu forward characters", t->flag, t->refFname, (unsigned long long)t->n_fwd);
 	fclose(f);
 	t->seconds = md_wall() - t0;
 	__atomic_store_n(&t->ready, 1, __ATOMIC_RELEASE);
 }
 
 /* the forward half of <fastaFname>.ref.  Checked before anything is read: the file is there and holds 2 x n_fwd bytes */
-md_text_t *md_text_open(const char *fastaFname, int deferred) {
+md_text_t *md_text_open(const char *fastaFname, int deferred) { return md_text_open_for(fastaFname, deferred, "-D"); }
+
+/* flag: the option that asks for the text, for the messages (-D, or -A without it) */
+md_text_t *md_text_open_for(const char *fastaFname, int deferred, const char *flag) {
 	const size_t L = strlen(fastaFname) + 8;
 	char *annFname = (char *)malloc(L), *refFname = (char *)malloc(L);
 	snprintf(annFname, L, "%s.ann", fastaFname);
 	snprintf(refFname, L, "%s.ref", fastaFname);
 	FILE *af = fopen(annFname, "r");
 	unsigned long long n_fwd = 0;
-	if (!af || fscanf(af, "%llu", &n_fwd) != 1 || !n_fwd) bwb_die("-D: Cannot read the text length from %s", annFname);
+	if (!af || fscanf(af, "%llu", &n_fwd) != 1 || !n_fwd) bwb_die("%s: Cannot read the text length from %s", flag, annFname);
 	fclose(af);
 	struct stat st;
-	if (stat(refFname, &st) != 0) bwb_die("-D needs the text %s: it is missing (`bwbble fasta2ref %s` writes it)", refFname, fastaFname);
+	if (stat(refFname, &st) != 0) bwb_die("%s needs the text %s: it is missing (`bwbble fasta2ref %s` writes it)", flag, refFname, fastaFname);
 	if ((unsigned long long)st.st_size != 2 * n_fwd)
-		bwb_die("-D needs the text %s: it holds %lld bytes, not 2 x %llu as %s says (`bwbble fasta2ref %s` writes it)", refFname, (long long)st.st_size, n_fwd, annFname, fastaFname);
+		bwb_die("%s needs the text %s: it holds %lld bytes, not 2 x %llu as %s says (`bwbble fasta2ref %s` writes it)", flag, refFname, (long long)st.st_size, n_fwd, annFname, fastaFname);
 	md_text_t *t = (md_text_t *)calloc(1, sizeof(*t));
 	t->n_fwd = n_fwd;
 	t->refFname = refFname;
+	t->flag = flag;
 	t->codes = (uint8_t *)malloc(n_fwd);
-	if (!t->codes) bwb_die("-D: no memory for the %llu characters of %s", n_fwd, refFname);
+	if (!t->codes) bwb_die("%s: no memory for the %llu characters of %s", flag, n_fwd, refFname);
 	free(annFname);
 	if (!deferred) md_text_read(t);
 	return t;

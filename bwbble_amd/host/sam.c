@@ -244,10 +244,11 @@ static bwb_join *host_joins(const bwb_place *pl, const bwb_locus *loci, const ui
 	return joins;
 }
 
-void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join, int lift, int md) {
+void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq) {
 	(void)is_multiref;
 	printf("**** BWBBLE Alignment Evaluation/SAM File Generation ****\n");
-	md_text_t *text = md ? md_text_open(fastaFname, 0) : NULL; /* -D (a missing .ref, or one of another size than the .ann says, stops the run before anything is loaded or created) */
+	pile_t *pile = countsFname ? pile_open(countsFname, min_mapq) : NULL; /* -A (a path that cannot be written stops the run before anything is loaded) */
+	md_text_t *text = md || pile ? md_text_open_for(fastaFname, 0, md ? "-D" : "-A") : NULL; /* -D (a missing .ref, or one of another size than the .ann says, stops the run before anything is loaded or created) */
 	size_t Ln = strlen(fastaFname) + 8;
 	char *bwtFname = (char *)malloc(Ln), *annFname = (char *)malloc(Ln);
 	snprintf(bwtFname, Ln, "%s.bwt", fastaFname);
@@ -335,7 +336,7 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 	bwb_join *joins = join ? host_joins(pl, loci, alt_off, alts, alt_sub, n, ann, ann_sorted, bubble_of, chrom_of, bub, max_diff) : NULL;
 	lift_set_t *ls = lift ? lift_host(pl, loci, n, alt_off, alts, ann, ann_sorted, bubble_of, chrom_of, bub) : NULL;
 	if (ls) printf("placements lifted to chromosome coordinates on the host: %llu  not liftable %llu\n", (unsigned long long)ls->n_lifted, (unsigned long long)ls->n_unliftable);
-	md_set_t *ms = text ? md_host(pl, n, reads->seq, reads->stride, reads->len, ls ? ls->kind : NULL, ls ? ls->off : NULL, ls ? ls->recs : NULL, ann, text) : NULL;
+	md_set_t *ms = md ? md_host(pl, n, reads->seq, reads->stride, reads->len, ls ? ls->kind : NULL, ls ? ls->off : NULL, ls ? ls->recs : NULL, ann, text) : NULL;
 	if (ms) printf("NM and MD against the text on the host: reads %llu  too long %llu  MD bytes %llu\n", (unsigned long long)ms->n_ok, (unsigned long long)ms->n_too_long, (unsigned long long)ms->off[n]);
 	const sam_reads_t rd = { .pl = pl, .seq = reads->seq, .stride = reads->stride, .len = reads->len, .text = reads->raw,
 	                         .name_off = reads->name_off, .qual_off = reads->qual_off, .name_len = reads->name_len, .first = 0,
@@ -361,20 +362,27 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 			free(bufs[bi]); bufs[bi] = NULL;
 		}
 	}
-	free(pl); free(alt_off); free(alts); free(loci); free(bubble_of); free_bubbles(bub);
-	free(alt_sub); free(joins); free(chrom_of); lift_free(ls); md_free(ms); md_text_free(text);
 	free(bufs); free(lens);
 	printf("Processed %zu reads.\n", n);
 	free(rows); free(pos); free(which); free(ref_pos);
 	free(bwtFname); free(annFname);
-	free_bwt(BWT); free_reads(reads); free_alns_batch(alns); free_ann(ann);
 	fclose(sam);
+	if (pile) { /* -A: the host's rule on the same records, written when the SAM file is complete */
+		pile_set_text(pile, text, 1);
+		pile_host(pile, pl, n, reads->seq, reads->stride, reads->len, ls ? ls->kind : NULL, ls ? ls->off : NULL, ls ? ls->recs : NULL, joins, ann);
+		const unsigned long long lines = pile_write(pile, ann);
+		printf("allele counts at the text's IUPAC sites on the host: sites %llu  reads counted %llu  adds %llu  sites written %llu\n", (unsigned long long)pile->n_sites, (unsigned long long)pile->reads, (unsigned long long)pile->adds, lines);
+	}
+	free(pl); free(alt_off); free(alts); free(loci); free(bubble_of); free_bubbles(bub);
+	free(alt_sub); free(joins); free(chrom_of); lift_free(ls); md_free(ms); pile_free(pile); md_text_free(text);
+	free_bwt(BWT); free_reads(reads); free_alns_batch(alns); free_ann(ann);
 }
 
 /* developer command (CPU only, for the tests): raw bwb_place records from a file through sam_format_reads - the formatter `map` uses, on a
  * machine without a GPU (bubbleFname: -B, the loci from the host resolver; join: -J, the join records from the host's rule; lift: -R, the
  * lift records from the host's rule; md: -D, NM and MD from the host's rule) */
-void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join, int lift, int md) {
+void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq) {
+	pile_t *pile = countsFname ? pile_open(countsFname, min_mapq) : NULL; /* -A */
 	size_t Ln = strlen(fastaFname) + 8;
 	char *annFname = (char *)malloc(Ln);
 	snprintf(annFname, Ln, "%s.ann", fastaFname);
@@ -383,7 +391,7 @@ void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *sam
 	int32_t *bubble_of = bub ? ann_bubble_of(ann, bub) : NULL;
 	if (lift) lift_check_table(bub); /* -R (main.c: only with -B) */
 	int32_t *chrom_of = join || lift ? bubble_chrom_of(ann, bubble_of, bub, join ? "-J" : "-R") : NULL; /* -J (main.c: only with -B and an items file), -R */
-	md_text_t *text = md ? md_text_open(fastaFname, 0) : NULL; /* -D */
+	md_text_t *text = md || pile ? md_text_open_for(fastaFname, 0, md ? "-D" : "-A") : NULL; /* -D, -A */
 	reads_t *reads = fastq2reads(readsFname);
 	FILE *pf = fopen(placesFname, "rb");
 	if (!pf) { perror(placesFname); bwb_die("places2sam: Cannot open the placements file: %s!", placesFname); }
@@ -416,7 +424,7 @@ void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *sam
 	bwb_locus *loci = bub ? host_loci(pl, n, ann, ann_sorted, bubble_of, bub) : NULL;
 	bwb_join *joins = join ? host_joins(pl, loci, alt_off, alts, alt_sub, n, ann, ann_sorted, bubble_of, chrom_of, bub, 6) : NULL; /* (aln2sam's default -n: the records carry no max_mm) */
 	lift_set_t *ls = lift ? lift_host(pl, loci, n, alt_off, alts, ann, ann_sorted, bubble_of, chrom_of, bub) : NULL;
-	md_set_t *ms = text ? md_host(pl, n, reads->seq, reads->stride, reads->len, ls ? ls->kind : NULL, ls ? ls->off : NULL, ls ? ls->recs : NULL, ann, text) : NULL;
+	md_set_t *ms = md ? md_host(pl, n, reads->seq, reads->stride, reads->len, ls ? ls->kind : NULL, ls ? ls->off : NULL, ls ? ls->recs : NULL, ann, text) : NULL;
 	const sam_reads_t rd = { .pl = pl, .seq = reads->seq, .stride = reads->stride, .len = reads->len, .text = reads->raw,
 	                         .name_off = reads->name_off, .qual_off = reads->qual_off, .name_len = reads->name_len, .first = 0,
 	                         .alt_off = alt_off, .alts = alts, .loci = loci, .bubbles = bub, .joins = joins,
@@ -429,8 +437,14 @@ void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *sam
 		free(buf);
 	}
 	printf("Processed %zu reads.\n", n);
-	free(pl); free(annFname); free(alt_off); free(alts); free(loci); free(bubble_of); free_bubbles(bub);
-	free(alt_sub); free(joins); free(chrom_of); lift_free(ls); md_free(ms); md_text_free(text);
-	free_reads(reads); free_ann(ann);
 	fclose(sam);
+	if (pile) { /* -A: the host's rule, written when the SAM file is complete */
+		pile_set_text(pile, text, 1);
+		pile_host(pile, pl, n, reads->seq, reads->stride, reads->len, ls ? ls->kind : NULL, ls ? ls->off : NULL, ls ? ls->recs : NULL, joins, ann);
+		const unsigned long long lines = pile_write(pile, ann);
+		printf("allele counts at the text's IUPAC sites on the host: sites %llu  reads counted %llu  adds %llu  sites written %llu\n", (unsigned long long)pile->n_sites, (unsigned long long)pile->reads, (unsigned long long)pile->adds, lines);
+	}
+	free(pl); free(annFname); free(alt_off); free(alts); free(loci); free(bubble_of); free_bubbles(bub);
+	free(alt_sub); free(joins); free(chrom_of); lift_free(ls); md_free(ms); pile_free(pile); md_text_free(text);
+	free_reads(reads); free_ann(ann);
 }

@@ -440,6 +440,53 @@ int bwb_hip_md_records(bwb_hip_ctx *ctx, const uint8_t *reads_fwd, const uint16_
  * (any pointer may be NULL) */
 int bwb_hip_md_stats(bwb_hip_ctx *ctx, uint64_t *reads, uint64_t *md_bytes, double *kernel_ms);
 
+/* Allele counts at the text's IUPAC sites (`bwbble map -A`): which allele of each known variant the reads carry, summed on the device over
+ * every read of a run - the first stage that is a reduction ACROSS reads.  No pileup tool can make the table afterwards: it has neither the
+ * text nor the member rule, and without -R the reads on bubble records lie in coordinates nothing else understands.
+ * The rule:
+ *   sites   a SITE is a position i in [0, n_fwd) of the forward text (bwb_hip_set_text) whose code has two or three members: 2 K, 4 S, 5 B, 6 Y,
+ *           8 M, 9 H, 11 V, 12 R, 13 D, 14 W.  `$`, N and the four plain bases are no sites.  Sites are numbered in text order: site(i) = the
+ *           number of sites below i.  n_sites is 64-bit here; a text with more than 2^32 - 1 sites is refused (BWB_E_ARG).
+ *   reads   read r counts when its bwb_md kind under the same `lifted` argument would be BWB_MD_OK - mapped, the span within [0, n_fwd) and at
+ *           most BWB_MD_MAX_SPAN, the ops consuming exactly the read - and its MAPQ is at least min_mapq: bwb_join.mapq when the call is
+ *           `joined`, else bwb_place.mapq.  Primaries only.
+ *   counts  the ops are those bwb_md walks, from the same start: the printed CIGAR from bwb_place.pos, or for a primary whose lift kind is
+ *           BWB_LIFT_LIFTED the ops of its lift record from start[rec.seqid] + rec.pos - 1.  For every M base whose text position is a site and
+ *           whose read base (SEQ as SAM prints it) is A, C, G or T: counts[site][column] += 1, the columns A, C, G, T by the printed letter.  A
+ *           base that is no member of the code counts under its own letter (a novel allele or an error: the table is there to show it).  A read
+ *           N, and the ops I, S and D, count nothing.  The counters are uint32 and wrap modulo 2^32.
+ *   where   with `lifted` a read on a bubble record is walked on the chromosome: its flank bases land on the chromosome's sites, the allele's
+ *           bases (I) nowhere.  Without it the read counts on the bubble record's own positions.
+ * The adds are integer and commute: the table does not depend on chunking, slot order, parked reads or the number of contexts whose tables are
+ * summed.  Kernels: k_site_count (one lane per 16-byte word of the packed text: the word's site mask and popcount, scanned into one uint32 per
+ * word, n_fwd / 8 bytes resident), k_pile (one lane per read behind k_place / k_lift / the join kernels on the result stream; relaxed
+ * agent-scope atomic adds), k_site_of (test entry).  (Added without a version change: no structure or existing entry point changed.) */
+/* After set_text and before the first slot_upload sizes the pool: builds the site index, allocates and zeroes n_sites x 4 counters.  BWB_E_STATE
+ * without a text.  *n_sites may be 0: the pile calls then count nothing.  A later set_text forgets the index and the counters. */
+int bwb_hip_pile_begin(bwb_hip_ctx *ctx, uint64_t *n_sites);
+/* slot_place, then slot_lift with lifted != 0 and slot_join with joined != 0 (their cached records where they exist), then k_pile over the
+ * slot's n_reads resident reads (a carried read has no record).  Nothing per read comes back; *reads_counted (may be NULL) = the reads this
+ * call counted.  A SUBMISSION IS PILED ONCE: a second slot_pile on the same submission returns BWB_OK, launches nothing and reports 0; the flag
+ * clears at the slot's next upload.  BWB_E_ARG for min_mapq or max_alt outside 0..255.  BWB_E_STATE without pile_begin, without set_sa, on a
+ * slot that has not been submitted, with lifted != 0 without set_loci / set_bubble_chrom, and with joined != 0 without them or with
+ * max_alt == 0; the context stays usable after each.  batch_pile is the one-batch form (slot 0 after batch_run). */
+int bwb_hip_slot_pile(bwb_hip_ctx *ctx, int slot, int max_mm, int max_alt, int lifted, int joined, int min_mapq, uint64_t *reads_counted);
+int bwb_hip_batch_pile(bwb_hip_ctx *ctx, int max_mm, int max_alt, int lifted, int joined, int min_mapq, uint64_t *reads_counted);
+/* The same kernel on records of the caller's, laid out as for md_records; mapq: NULL, or one value per read that stands in for the joined MAPQ.
+ * Accumulates into the context's counters; touches no slot.  Needs pile_begin, and set_loci with the lift arguments (BWB_E_STATE). */
+int bwb_hip_pile_records(bwb_hip_ctx *ctx, const uint8_t *reads_fwd, const uint16_t *lens, uint32_t stride, const bwb_place *places, uint32_t n,
+                         const uint8_t *kinds, const uint64_t *lift_off, const bwb_lift *lift_recs, const uint8_t *mapq, int min_mapq);
+/* Synchronises the result stream and copies the 4 n counters of the sites first .. first + n - 1 to out (A, C, G, T per site).  BWB_E_ARG when
+ * the range leaves n_sites; BWB_E_STATE without pile_begin. */
+int bwb_hip_pile_counts(bwb_hip_ctx *ctx, uint64_t first, uint64_t n, uint32_t *out);
+/* zeroes the counters */
+int bwb_hip_pile_reset(bwb_hip_ctx *ctx);
+/* the site number of each text position pos[q] < n_fwd (BWB_E_ARG beyond), or -1 where it is no site: for parity tests, like rank16 */
+int bwb_hip_pile_site_of(bwb_hip_ctx *ctx, const uint64_t *pos, size_t n, int64_t *site);
+/* the last pile call on the context that launched the kernel: reads counted, adds made, and the kernel's HIP-event time (any pointer may be
+ * NULL) */
+int bwb_hip_pile_stats(bwb_hip_ctx *ctx, uint64_t *reads, uint64_t *adds, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
