@@ -29,6 +29,7 @@ EXPORTS = [
     "bwb_hip_slot_lift", "bwb_hip_batch_lift", "bwb_hip_lift_records", "bwb_hip_lift_stats",
     "bwb_hip_set_text", "bwb_hip_slot_md", "bwb_hip_batch_md", "bwb_hip_md_records", "bwb_hip_md_stats",
     "bwb_hip_pile_begin", "bwb_hip_slot_pile", "bwb_hip_batch_pile", "bwb_hip_pile_records", "bwb_hip_pile_counts", "bwb_hip_pile_reset", "bwb_hip_pile_site_of", "bwb_hip_pile_stats",
+    "bwb_hip_indel_begin", "bwb_hip_slot_indel", "bwb_hip_batch_indel", "bwb_hip_indel_records", "bwb_hip_indel_counts", "bwb_hip_indel_reset", "bwb_hip_indel_stats",
 ]
 ABI_VERSION = 3  # BWB_HIP_ABI_VERSION (include/bwbble_hip.h)
 MAX_SLOTS = 8  # BWB_MAX_SLOTS
@@ -170,6 +171,13 @@ def lib():
         L.bwb_hip_pile_reset.argtypes = [C.c_void_p]
         L.bwb_hip_pile_site_of.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.bwb_hip_pile_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.bwb_hip_indel_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
+        L.bwb_hip_slot_indel.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+        L.bwb_hip_batch_indel.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+        L.bwb_hip_indel_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int]
+        L.bwb_hip_indel_counts.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        L.bwb_hip_indel_reset.argtypes = [C.c_void_p]
+        L.bwb_hip_indel_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -670,6 +678,52 @@ class Context:
     def pile_stats(self):
         """(reads counted, adds, kernel ms) of the last pile call that launched"""
         return self._count_steps_ms(lib().bwb_hip_pile_stats)
+
+    # -- ref / alt read support per indel bubble (-I): device-resident counters, n_bub x (ref, alt, ref_gapped, alt_gapped), summed over every
+    #    indel call (needs set_loci, set_bubble_chrom and indel_begin; the slot forms set_sa) --
+    def indel_begin(self, anchor=1):
+        """builds the sorted table of the bubbles eligible at this anchor and zeroed counters -> their number.  Before the first upload"""
+        n = C.c_uint64()
+        _chk(lib().bwb_hip_indel_begin(self._h, anchor, C.byref(n)))
+        return n.value
+
+    def slot_indel(self, slot, max_mm=6, max_alt=5, joined=False, min_mapq=0):
+        """counts the slot's reads -> the reads counted; a second call on the same submission counts nothing and returns 0"""
+        n = C.c_uint64()
+        _chk(lib().bwb_hip_slot_indel(self._h, slot, max_mm, max_alt, int(bool(joined)), min_mapq, C.byref(n)))
+        return n.value
+
+    def batch_indel(self, max_mm=6, max_alt=5, joined=False, min_mapq=0):
+        """the same for the one-batch interface (after run() / align())"""
+        n = C.c_uint64()
+        _chk(lib().bwb_hip_batch_indel(self._h, max_mm, max_alt, int(bool(joined)), min_mapq, C.byref(n)))
+        return n.value
+
+    def indel_records(self, places, mapq=None, min_mapq=0):
+        """the same kernel on placement records of the caller's; mapq: one value per read in place of the records' own"""
+        places = np.ascontiguousarray(places, dtype=PLACE_DTYPE)
+        if mapq is not None:
+            mapq = np.ascontiguousarray(mapq, dtype=np.uint8)
+            if len(mapq) != len(places):
+                raise ValueError("one MAPQ per read")
+        _chk(lib().bwb_hip_indel_records(self._h, places.ctypes.data, len(places), mapq.ctypes.data if mapq is not None else None, min_mapq))
+
+    def indel_counts(self, first=0, n=None, n_bub=None):
+        """the counters of the bubbles first .. first + n - 1 as an (n, 4) uint32 array: ref, alt, ref_gapped, alt_gapped (n None: up to n_bub)"""
+        if n is None:
+            n = n_bub - first
+        out = np.zeros((n, 4), dtype=np.uint32)
+        _chk(lib().bwb_hip_indel_counts(self._h, first, n, out.ctypes.data))
+        return out
+
+    def indel_reset(self):
+        _chk(lib().bwb_hip_indel_reset(self._h))
+
+    def indel_stats(self):
+        """(reads counted, adds, candidates examined, kernel ms) of the last indel call that launched"""
+        r, a, k, ms = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_double()
+        _chk(lib().bwb_hip_indel_stats(self._h, C.byref(r), C.byref(a), C.byref(k), C.byref(ms)))
+        return r.value, a.value, k.value, ms.value
 
     def dtab_info(self):
         """the context's calculate_d table: {K (0: none), build seconds, bytes}"""

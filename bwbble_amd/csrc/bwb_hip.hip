@@ -147,6 +147,7 @@ struct Slot {
 	MdBufs md;                    /* bwb_hip_slot_md */
 	int md_mm = -1, md_alt = -1, md_lifted = -1; /* md holds the records for this max_mm, and with lifted for this max_alt (-1: none) */
 	bool piled = false;           /* bwb_hip_slot_pile has counted this submission (cleared at the next upload) */
+	bool indeled = false;         /* bwb_hip_slot_indel has counted this submission (cleared at the next upload) */
 	std::vector<uint8_t> h_status;
 	std::vector<uint64_t> h_aln_off;
 	std::vector<bwb_aln> h_alns;
@@ -212,6 +213,11 @@ struct bwb_hip_ctx {
 	PinMem h_pile_stats;
 	bool pile_on = false; uint64_t pile_sites = 0; /* pile_begin has run on this text; its sites */
 	double pile_ms = 0; uint64_t pile_reads = 0, pile_adds = 0; /* the last pile call that launched */
+	std::vector<bwb_bubble> loci_bubbles; std::vector<int32_t> chrom_of; /* the host's copies of set_loci's bubble table and set_bubble_chrom's records (bwb_hip_indel_begin) */
+	DevMem d_indel_tab, d_indel_elig, d_indel_counts, d_indel_stats; /* k_indel: the eligible bubbles sorted by (chrom_of, lo, bubble), one byte per bubble, the n_bub x 4 counters, three sums of one launch */
+	PinMem h_indel_stats;
+	bool indel_on = false; uint32_t indel_anchor = 0, indel_ntab = 0, indel_trips = 0; /* indel_begin has run on these tables */
+	double indel_ms = 0; uint64_t indel_reads = 0, indel_adds = 0, indel_cands = 0; /* the last indel call that launched */
 	bool force_slices = false;          /* BWB_FORCE_SLICES: the one-batch API parks and resumes too (tests) */
 	bool dbg = false, dbg_iters = false;
 	const char *launch_log = nullptr;   /* BWB_LAUNCH_LOG=<file>: one JSON line per class-0 kernel launch (synchronises after every launch: a profiling aid) */
@@ -784,7 +790,7 @@ extern "C" int bwb_hip_slot_upload(bwb_hip_ctx *c, int si, const bwb_params *p, 
 	/* (pageable source: the runtime stages it before returning, so h_descs may change again right away) */
 	HIPCHK(hipMemcpyAsync(c->d_descs.as<SlotDesc>() + si, &d, sizeof(SlotDesc), hipMemcpyHostToDevice, c->cstream));
 	HIPCHK(hipEventRecord(s.ev_up.e, c->cstream));
-	s.uploaded = true; s.submitted = false; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.join_mm = -1; s.lift_mm = -1; s.md_mm = -1; s.piled = false;
+	s.uploaded = true; s.submitted = false; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.join_mm = -1; s.lift_mm = -1; s.md_mm = -1; s.piled = false; s.indeled = false;
 	return ensure_class(c, 0);
 }
 
@@ -1032,7 +1038,7 @@ static int submit(bwb_hip_ctx *c, int si, bool suspend) {
 		HIPCHK(hipStreamWaitEvent(c->stream, s.ev_calcd.e, 0));
 	}
 	HIPCHK(hipMemsetAsync(s.d_ctl.p, 0, 256, c->stream));
-	s.submitted = true; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.join_mm = -1; s.lift_mm = -1; s.md_mm = -1; s.piled = false; s.launch = 0;
+	s.submitted = true; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.join_mm = -1; s.lift_mm = -1; s.md_mm = -1; s.piled = false; s.indeled = false; s.launch = 0;
 	if (s.n_reads == 0) { s.complete = true; s.launch = c->n_launches; return BWB_OK; }
 	HIPCHK(hipMemsetAsync(s.d_n.p, 0, (size_t)s.n_reads * 4, c->stream));
 	if (!ahead) {
@@ -1765,6 +1771,7 @@ extern "C" int bwb_hip_set_loci(bwb_hip_ctx *c, const uint64_t *start, const uin
 	c->loci_nseq = 0; /* (no tables until all four are resident) */
 	c->chrom_set = false;
 	for (auto &s : c->slots) { s.locus_mm = -1; s.join_mm = -1; s.lift_mm = -1; s.md_mm = -1; }
+	c->indel_on = false; /* (the table and the counters were these bubbles') */
 	c->lift_refusal = lift_table_refusal(bubbles, n_bub);
 	HIPCHK(c->d_lstart.alloc((size_t)n_seq * 8));
 	HIPCHK(c->d_lend.alloc((size_t)n_seq * 8));
@@ -1780,6 +1787,7 @@ extern "C" int bwb_hip_set_loci(bwb_hip_ctx *c, const uint64_t *start, const uin
 	while (((uint64_t)1 << trips) < n_seq) trips++;
 	c->loci_trips = trips;
 	c->loci_bub_of.assign(bubble_of, bubble_of + n_seq);
+	c->loci_bubbles.assign(bubbles, bubbles + n_bub);
 	c->loci_nbub = n_bub;
 	c->loci_nseq = n_seq;
 	return BWB_OK;
@@ -1865,6 +1873,8 @@ extern "C" int bwb_hip_set_bubble_chrom(bwb_hip_ctx *c, const int32_t *chrom_of,
 	HIPCHK(hipSetDevice(c->device));
 	c->chrom_set = false;
 	for (auto &s : c->slots) { s.join_mm = -1; s.lift_mm = -1; s.md_mm = -1; }
+	c->indel_on = false;
+	c->chrom_of.assign(chrom_of, chrom_of + n_bub);
 	HIPCHK(c->d_chrom.alloc((size_t)n_bub * 4));
 	if (n_bub) {
 		HIPCHK(hipMemcpyAsync(c->d_chrom.p, chrom_of, (size_t)n_bub * 4, hipMemcpyHostToDevice, c->rstream));
@@ -2505,6 +2515,174 @@ extern "C" int bwb_hip_pile_stats(bwb_hip_ctx *c, uint64_t *reads, uint64_t *add
 	if (reads) *reads = c->pile_reads;
 	if (adds) *adds = c->pile_adds;
 	if (kernel_ms) *kernel_ms = c->pile_ms;
+	return BWB_OK;
+}
+
+/* ---- ref / alt read support per indel bubble (k_indel) ------------------------------------------------------------------------------------ */
+struct IndelEntry { int64_t lo; int32_t chrom; uint32_t bubble; }; /* one 16-byte word of k_indel's table */
+static_assert(sizeof(IndelEntry) == 16, "an entry of the indel table is one 16-byte word (k_indel)");
+/* the rule's eligibility (include/bwbble_hip.h), in the wrapping 64-bit arithmetic of the kernels */
+static bool indel_eligible(const bwb_bubble &b, int64_t w) {
+	const __int128 gap = (__int128)b.C - (__int128)b.A - (__int128)b.B_minus_A;
+	if (b.B_minus_A < 0 || b.D_minus_C < -1 || b.alt_len < 0 || gap < 0 || gap >= ((__int128)1 << 28)) return false;
+	return b.B_minus_A >= w && b.D_minus_C + 1 >= w && (int64_t)((uint64_t)b.A + (uint64_t)b.B_minus_A - (uint64_t)w) >= 1;
+}
+extern "C" int bwb_hip_indel_begin(bwb_hip_ctx *c, int anchor, uint64_t *n_eligible) {
+	if (!c || !n_eligible) return fail(BWB_E_ARG, "indel_begin: null argument");
+	if (anchor < 1 || anchor > 255) return fail(BWB_E_ARG, "indel_begin: the anchor must be 1..255");
+	if (!c->loci_nseq) return fail(BWB_E_STATE, "indel_begin: record and bubble tables not uploaded (bwb_hip_set_loci)");
+	if (!c->chrom_set) return fail(BWB_E_STATE, "indel_begin: the bubbles' chromosome records not uploaded (bwb_hip_set_bubble_chrom)");
+	HIPCHK(hipSetDevice(c->device));
+	HIPCHK(hipStreamSynchronize(c->rstream)); /* (a kernel of an earlier call may still read the table and add to the counters that are replaced) */
+	c->indel_on = false;
+	const uint32_t n_bub = c->loci_nbub;
+	std::vector<IndelEntry> tab;
+	std::vector<uint8_t> elig(n_bub ? n_bub : 1, 0);
+	for (uint32_t b = 0; b < n_bub; b++) {
+		const bwb_bubble &v = c->loci_bubbles[b];
+		if (!indel_eligible(v, anchor)) continue;
+		elig[b] = 1;
+		tab.push_back(IndelEntry{ (int64_t)((uint64_t)v.A + (uint64_t)v.B_minus_A - (uint64_t)anchor), c->chrom_of[b], b });
+	}
+	std::sort(tab.begin(), tab.end(), [](const IndelEntry &x, const IndelEntry &y) {
+		return x.chrom != y.chrom ? x.chrom < y.chrom : x.lo != y.lo ? x.lo < y.lo : x.bubble < y.bubble; });
+	HIPCHK(c->d_indel_tab.alloc(tab.size() * sizeof(IndelEntry)));
+	HIPCHK(c->d_indel_elig.alloc(elig.size()));
+	HIPCHK(c->d_indel_counts.alloc((size_t)n_bub * 16));
+	HIPCHK(c->d_indel_stats.alloc(24));
+	HIPCHK(c->h_indel_stats.reserve(24));
+	if (!tab.empty()) HIPCHK(hipMemcpyAsync(c->d_indel_tab.p, tab.data(), tab.size() * sizeof(IndelEntry), hipMemcpyHostToDevice, c->rstream));
+	HIPCHK(hipMemcpyAsync(c->d_indel_elig.p, elig.data(), elig.size(), hipMemcpyHostToDevice, c->rstream));
+	if (n_bub) HIPCHK(hipMemsetAsync(c->d_indel_counts.p, 0, (size_t)n_bub * 16, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream)); /* (pageable memory of this function) */
+	uint32_t trips = 0;
+	while (((uint64_t)1 << trips) <= tab.size()) trips++;
+	c->indel_anchor = (uint32_t)anchor; c->indel_ntab = (uint32_t)tab.size(); c->indel_trips = trips;
+	c->indel_ms = 0; c->indel_reads = 0; c->indel_adds = 0; c->indel_cands = 0;
+	c->indel_on = true;
+	*n_eligible = tab.size();
+	return BWB_OK;
+}
+
+/* k_indel over n placement and locus records (device memory; d_lens NULL: no read lengths; d_mapq NULL: the placement's own MAPQ, else one byte
+ * every mapq_stride bytes) into the context's counters; sets indel_ms / indel_reads / indel_adds / indel_cands.  On the result stream, behind the
+ * kernels that wrote the records.  What comes back is the 24 bytes of the three sums. */
+static int indel_launch(bwb_hip_ctx *c, const uint4 *d_places, const uint4 *d_loci, uint32_t n, const uint16_t *d_lens, const uint8_t *d_mapq, uint32_t mapq_stride, int min_mapq) {
+	if (!n) return BWB_OK; /* (nothing launched: the figures of the last launch stay) */
+	const unsigned nblk = (unsigned)(((size_t)n + BWB_BLOCK - 1) / BWB_BLOCK);
+	const unsigned grid = (unsigned)std::min<size_t>(nblk, (size_t)c->num_cu * 8);
+	HIPCHK(hipMemsetAsync(c->d_indel_stats.p, 0, 24, c->rstream));
+	Timed t(c, c->rstream);
+	RC(t.begin());
+	hipLaunchKernelGGL(k_indel, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, d_places, d_loci, n, d_lens, d_mapq, mapq_stride, (uint32_t)min_mapq, c->d_bubbles.as<uint64_t>(),
+	                   c->d_indel_elig.as<uint8_t>(), c->indel_anchor, c->d_indel_tab.as<uint4>(), c->indel_ntab, c->indel_trips, c->d_indel_counts.as<uint32_t>(),
+	                   c->d_indel_stats.as<unsigned long long>());
+	HIPCHK(hipGetLastError());
+	RC(t.end());
+	HIPCHK(hipMemcpyAsync(c->h_indel_stats.p, c->d_indel_stats.p, 24, hipMemcpyDeviceToHost, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	float ms = 0;
+	RC(t.ms(&ms));
+	c->indel_ms = ms;
+	c->indel_reads = c->h_indel_stats.as<uint64_t>()[0];
+	c->indel_adds = c->h_indel_stats.as<uint64_t>()[1];
+	c->indel_cands = c->h_indel_stats.as<uint64_t>()[2];
+	return BWB_OK;
+}
+
+static int indel_ready(bwb_hip_ctx *c, const char *who, int max_alt, int joined, int min_mapq) {
+	if (min_mapq < 0 || min_mapq > 255) return fail(BWB_E_ARG, std::string(who) + ": min_mapq must be 0..255");
+	if (max_alt < 0 || max_alt > 255) return fail(BWB_E_ARG, std::string(who) + ": max_alt must be 0..255");
+	if (!c->indel_on) return fail(BWB_E_STATE, std::string(who) + ": no bubble table and counters (bwb_hip_indel_begin)");
+	if (!c->d_SA.p) return fail(BWB_E_STATE, std::string(who) + ": sampled SA not uploaded (bwb_hip_set_sa)");
+	if (joined) {
+		if (!max_alt) return fail(BWB_E_STATE, std::string(who) + ": the joined MAPQ needs the items of max_alt 1..255");
+		RC(join_ready(c, who, max_alt));
+	}
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_slot_indel(bwb_hip_ctx *c, int si, int max_mm, int max_alt, int joined, int min_mapq, uint64_t *reads_counted) {
+	if (!c || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_indel: bad argument");
+	RC(indel_ready(c, "slot_indel", max_alt, joined, min_mapq));
+	if (reads_counted) *reads_counted = 0;
+	/* (each waits for the slot, refuses what slot_place refuses, and leaves its records in the slot's device memory) */
+	const bwb_place *places = nullptr;
+	const bwb_locus *loci = nullptr;
+	uint32_t n = 0;
+	RC(bwb_hip_slot_locus(c, si, max_mm, &places, &loci, &n));
+	Slot &s = c->slots[si];
+	if (s.indeled) return BWB_OK; /* (a submission is counted once) */
+	if (joined) {
+		const uint64_t *alt_off = nullptr;
+		const bwb_alt *alts = nullptr;
+		const bwb_join *joins = nullptr;
+		RC(bwb_hip_slot_join(c, si, max_mm, max_alt, &places, &alt_off, &alts, &loci, &joins, &n));
+	}
+	n = s.n_reads; /* (not n_tot: a carried read that rides along behind the batch's reads has no record) */
+	if (n) {
+		HIPCHK(hipStreamWaitEvent(c->rstream, s.ev_up.e, 0)); /* (the slot's read lengths, uploaded on the copy stream) */
+		RC(indel_launch(c, s.d_place.as<uint4>(), s.d_locus.as<uint4>(), n, s.d_lens.as<uint16_t>(), joined ? s.d_join.as<uint8_t>() + offsetof(bwb_join, mapq) : nullptr,
+		                (uint32_t)sizeof(bwb_join), min_mapq));
+		if (reads_counted) *reads_counted = c->indel_reads;
+	}
+	s.indeled = true;
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_batch_indel(bwb_hip_ctx *c, int max_mm, int max_alt, int joined, int min_mapq, uint64_t *reads_counted) {
+	if (!c) return fail(BWB_E_ARG, "batch_indel: null context");
+	RC(indel_ready(c, "batch_indel", max_alt, joined, min_mapq));
+	if (!c->slots[0].submitted || !c->slots[0].complete) return fail(BWB_E_STATE, "batch_indel: batch_run has not completed");
+	return bwb_hip_slot_indel(c, 0, max_mm, max_alt, joined, min_mapq, reads_counted);
+}
+
+/* the kernel on placement records of the caller's instead of a slot's (for parity tests): k_locus for their loci, then k_indel */
+extern "C" int bwb_hip_indel_records(bwb_hip_ctx *c, const bwb_place *places, uint32_t n, const uint8_t *mapq, int min_mapq) {
+	if (!c || (n && !places) || n > 0x7FFFFFFFu) return fail(BWB_E_ARG, "indel_records: bad argument");
+	if (min_mapq < 0 || min_mapq > 255) return fail(BWB_E_ARG, "indel_records: min_mapq must be 0..255");
+	if (!c->indel_on) return fail(BWB_E_STATE, "indel_records: no bubble table and counters (bwb_hip_indel_begin)");
+	if (!n) return BWB_OK;
+	HIPCHK(hipSetDevice(c->device));
+	DevMem d_places, d_loci, d_mapq;
+	HIPCHK(d_places.alloc((size_t)n * sizeof(bwb_place)));
+	HIPCHK(d_loci.alloc((size_t)n * sizeof(bwb_locus)));
+	HIPCHK(hipMemcpyAsync(d_places.p, places, (size_t)n * sizeof(bwb_place), hipMemcpyHostToDevice, c->rstream));
+	if (mapq) {
+		HIPCHK(d_mapq.alloc((size_t)n));
+		HIPCHK(hipMemcpyAsync(d_mapq.p, mapq, (size_t)n, hipMemcpyHostToDevice, c->rstream));
+	}
+	HIPCHK(hipStreamSynchronize(c->rstream)); /* (pageable memory of the caller) */
+	std::vector<bwb_locus> h_loci(n);
+	RC(locus_launch(c, d_places.as<uint4>(), n, d_loci.as<uint4>(), h_loci.data()));
+	return indel_launch(c, d_places.as<uint4>(), d_loci.as<uint4>(), n, nullptr, mapq ? d_mapq.as<uint8_t>() : nullptr, 1u, min_mapq);
+}
+
+extern "C" int bwb_hip_indel_counts(bwb_hip_ctx *c, uint64_t first, uint64_t n, uint32_t *out) {
+	if (!c || (n && !out)) return fail(BWB_E_ARG, "indel_counts: null argument");
+	if (!c->indel_on) return fail(BWB_E_STATE, "indel_counts: no bubble table and counters (bwb_hip_indel_begin)");
+	if (first > c->loci_nbub || n > c->loci_nbub - first) return fail(BWB_E_ARG, "indel_counts: the range leaves the " + std::to_string(c->loci_nbub) + " bubbles");
+	HIPCHK(hipSetDevice(c->device));
+	if (n) HIPCHK(hipMemcpyAsync(out, c->d_indel_counts.as<uint32_t>() + first * 4, (size_t)n * 16, hipMemcpyDeviceToHost, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_indel_reset(bwb_hip_ctx *c) {
+	if (!c) return fail(BWB_E_ARG, "indel_reset: null context");
+	if (!c->indel_on) return fail(BWB_E_STATE, "indel_reset: no bubble table and counters (bwb_hip_indel_begin)");
+	HIPCHK(hipSetDevice(c->device));
+	if (c->loci_nbub) HIPCHK(hipMemsetAsync(c->d_indel_counts.p, 0, (size_t)c->loci_nbub * 16, c->rstream));
+	return BWB_OK;
+}
+
+/* the last indel call that launched: reads counted, adds made, candidates examined, and the kernel's HIP-event time */
+extern "C" int bwb_hip_indel_stats(bwb_hip_ctx *c, uint64_t *reads, uint64_t *adds, uint64_t *candidates, double *kernel_ms) {
+	if (!c) return fail(BWB_E_ARG, "indel_stats: null context");
+	if (reads) *reads = c->indel_reads;
+	if (adds) *adds = c->indel_adds;
+	if (candidates) *candidates = c->indel_cands;
+	if (kernel_ms) *kernel_ms = c->indel_ms;
 	return BWB_OK;
 }
 

@@ -12,6 +12,7 @@
  *   k_lift_count, k_lift         a placement on a bubble record in the chromosome's coordinates: POS and CIGAR (`bwbble map -R`)
  *   k_text_pack, k_md_count, k_md   the forward text at 4 bits per character, and a read's NM and MD text against it (`bwbble map -D`)
  *   k_site_count, k_site_add, k_site_of, k_pile   the rank structure over the text's IUPAC sites, and the reads' allele counts at them (`bwbble map -A`)
+ *   k_indel                      ref / alt read support per indel bubble, against a sorted table of the eligible bubbles (`bwbble map -I`)
  * The alignment kernels themselves (kl_calc_d, kl_search: one read per lane) are in bwb_lane.h.
  */
 #pragma once
@@ -1136,5 +1137,106 @@ __global__ __launch_bounds__(BWB_BLOCK) void k_pile(const uint8_t *reads, const 
 		for (int k = 0; k < BWB_BLOCK / 64; k++) { r += s_sum[0][k]; a += s_sum[1][k]; }
 		if (r) atomicAdd(stats, r);
 		if (a) atomicAdd(stats + 1, a);
+	}
+}
+
+/* ---- ref / alt read support per indel bubble (`map -I`) --------------------------------------------------------------------------------
+ * The rule is in include/bwbble_hip.h (bwb_hip_indel_begin).  k_indel: one lane per READ, grid-strided, over the placement records of k_place
+ * and the locus records of k_locus.  A read's printed CIGAR is walked one text position at a time (lift_op_at: at most 8 gap runs compared per
+ * position), once for the bases it consumes and its first and last M, then once per window it is classed against - that walk ends at the
+ * window's hi.  A read on bubble b's record has one window (elig[b] says whether b is eligible).  A read on a chromosome record c bisects
+ * tab[] - the eligible bubbles ascending by (c, lo, bubble), one 16-byte word lo | c | bubble each - for the first entry not below (c, its first
+ * M), `trips` steps for every lane (2^trips > n_tab, a kernel argument: selects, no divergent while), and walks on while the entry's c is its
+ * own and lo does not exceed its last M: the loop is bounded by the table alone.  An entry whose hi = C + w - 1 (from bub[]) lies behind the
+ * last M is skipped.  The adds are relaxed, agent-scope atomics into counts[bubble * 4 + ref 0 | alt 1 | ref_gapped 2 | alt_gapped 3]; reads
+ * counted, adds made and candidates examined are summed over the block - shuffles, then LDS - into stats[0..2] once per block.  Every index is
+ * bounded: tab[] below n_tab, a locus record's bubble below the table's size (bwb_hip_set_loci checked bubble_of), an entry's bubble likewise. */
+struct IndelRead { int64_t pos1; bool reverse; uint32_t alen; uint4 runs; };
+/* 0 not covering, 1 clean, 2 gapped (lo < hi: a window is at least two positions wide) */
+__device__ __forceinline__ uint32_t indel_class(const IndelRead &v, int64_t lo, int64_t hi) {
+	int64_t x = v.pos1;
+	bool at_lo = false, at_hi = false, dirty = false;
+	for (uint32_t t = 0; t < v.alen && x <= hi; t++) {
+		const uint32_t op = lift_op_at(v.runs, v.alen, v.reverse, t);
+		if (op == 1u) { dirty = dirty || at_lo; continue; } /* (the M at hi ends the walk: an I behind it is not seen) */
+		if (x >= lo) {
+			if (op == 0u) { at_lo = at_lo || x == lo; at_hi = at_hi || x == hi; }
+			else dirty = true;
+		}
+		x++;
+	}
+	return at_lo && at_hi ? (dirty ? 2u : 1u) : 0u;
+}
+__global__ __launch_bounds__(BWB_BLOCK) void k_indel(const uint4 *places, const uint4 *loci, uint32_t n_reads, const uint16_t *lens, const uint8_t *mapq, uint32_t mapq_stride,
+                                                      uint32_t min_mapq, const uint64_t *bub, const uint8_t *elig, uint32_t anchor, const uint4 *tab, uint32_t n_tab, uint32_t trips,
+                                                      uint32_t *counts, unsigned long long *stats) {
+	__shared__ unsigned long long s_sum[3][BWB_BLOCK / 64];
+	const uint32_t gstride = gridDim.x * BWB_BLOCK;
+	unsigned long long my_reads = 0, my_adds = 0, my_cand = 0;
+	for (uint32_t q = blockIdx.x * BWB_BLOCK + threadIdx.x; q < n_reads; q += gstride) {
+		const uint4 p1 = places[(size_t)q * 3 + 1], l0 = loci[(size_t)q * 2];
+		if (!((p1.x >> 24) & PLACE_F_MAPPED) || l0.x == 0xFFFFFFFFu) continue;
+		const uint32_t mq = mapq ? mapq[(size_t)q * mapq_stride] : (p1.x >> 16) & 0xFFu;
+		if (mq < min_mapq) continue;
+		IndelRead v;
+		v.pos1 = (int64_t)(int32_t)l0.y; v.reverse = ((p1.x >> 24) & PLACE_F_REVERSE) != 0; v.alen = p1.z & 0xFFFFu; v.runs = places[(size_t)q * 3 + 2];
+		int64_t x = v.pos1, xf = 0, xl = -1;
+		uint32_t on_read = 0;
+		bool any = false;
+		for (uint32_t t = 0; t < v.alen; t++) {
+			const uint32_t op = lift_op_at(v.runs, v.alen, v.reverse, t);
+			on_read += op != 2u;
+			if (op == 1u) continue;
+			if (op == 0u) { xf = any ? xf : x; any = true; xl = x; }
+			x++;
+		}
+		if (lens && on_read != lens[q]) continue;
+		my_reads++;
+		const int32_t b = (int32_t)l0.z;
+		if (b >= 0) {
+			if (!elig[b]) continue;
+			const uint64_t *e = bub + (size_t)b * 5;
+			const int64_t Bm = (int64_t)e[1], alt = (int64_t)(int32_t)(uint32_t)(e[4] >> 32);
+			my_cand++;
+			const uint32_t cls = indel_class(v, Bm - (int64_t)anchor + 1, Bm + alt + (int64_t)anchor);
+			if (cls) { __hip_atomic_fetch_add(counts + (size_t)b * 4 + (cls == 1u ? 1u : 3u), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); my_adds++; }
+			continue;
+		}
+		if (!any) continue;
+		const int32_t c = (int32_t)l0.x;
+		uint32_t at = 0; /* the entries below (c, xf) */
+		for (uint32_t t = trips; t-- > 0;) {
+			const uint32_t s = 1u << t;
+			bool below = false;
+			if (s <= n_tab - at) { /* (at <= n_tab throughout) */
+				const uint4 k = tab[at + s - 1u];
+				const int64_t klo = (int64_t)((uint64_t)k.x | ((uint64_t)k.y << 32));
+				below = (int32_t)k.z < c || ((int32_t)k.z == c && klo < xf);
+			}
+			at = below ? at + s : at;
+		}
+		for (; at < n_tab; at++) {
+			const uint4 k = tab[at];
+			const int64_t klo = (int64_t)((uint64_t)k.x | ((uint64_t)k.y << 32));
+			if ((int32_t)k.z != c || klo > xl) break;
+			my_cand++;
+			const int64_t khi = (int64_t)(bub[(size_t)k.w * 5 + 2] + (uint64_t)anchor - 1u);
+			if (khi > xl) continue;
+			const uint32_t cls = indel_class(v, klo, khi);
+			if (cls) { __hip_atomic_fetch_add(counts + (size_t)k.w * 4 + (cls == 1u ? 0u : 2u), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); my_adds++; }
+		}
+	}
+	/* (every thread of the block gets here: the loop has no barrier inside) */
+#pragma unroll
+	for (int d = 32; d > 0; d >>= 1) { my_reads += __shfl_down(my_reads, d); my_adds += __shfl_down(my_adds, d); my_cand += __shfl_down(my_cand, d); }
+	if ((threadIdx.x & 63) == 0) { s_sum[0][threadIdx.x >> 6] = my_reads; s_sum[1][threadIdx.x >> 6] = my_adds; s_sum[2][threadIdx.x >> 6] = my_cand; }
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		unsigned long long r = 0, a = 0, k = 0;
+#pragma unroll
+		for (int i = 0; i < BWB_BLOCK / 64; i++) { r += s_sum[0][i]; a += s_sum[1][i]; k += s_sum[2][i]; }
+		if (r) atomicAdd(stats, r);
+		if (a) atomicAdd(stats + 1, a);
+		if (k) atomicAdd(stats + 2, k);
 	}
 }

@@ -53,6 +53,7 @@ typedef struct {
 	int md;                   /* -D: the tags NM:i / MD:Z against the text */
 	pile_t *pile;             /* -A (NULL: no counts): the allele counts at the text's IUPAC sites; on the GPU unless pile_on_host */
 	int pile_on_host;         /* -A with the host's lift or join records (-R / -J on an .ann that is not ascending and disjoint): the host's rule */
+	indel_t *indel;           /* -I (NULL: no table): the read support per indel bubble; needs bub and chrom_of; on the GPU when gpu_loci, else the host's rule */
 } map_t;
 
 typedef struct {
@@ -88,6 +89,7 @@ typedef struct {
 	double lift_ms; unsigned long long lift_lifted, lift_unliftable, lift_bytes; /* map -R: k_lift_count + scan + k_lift, summed over the chunks; what came back for them */
 	double md_ms, text_s; unsigned long long md_reads, md_bytes, md_back; /* map -D: k_md_count + scan + k_md, summed over the chunks; set_text's seconds; reads tagged, MD bytes, what came back */
 	double pile_ms, pile_begin_s, pile_fetch_s; unsigned long long pile_reads, pile_adds; /* map -A: k_pile, summed over the chunks; pile_begin's and the final read-back's seconds; reads counted, adds */
+	double indel_ms, indel_begin_s, indel_fetch_s; unsigned long long indel_reads, indel_adds, indel_cands; /* map -I: k_indel, summed over the chunks; indel_begin's and the final read-back's seconds; reads counted, adds, candidates */
 } worker_t;
 
 /* The reader: chunk k+1 is parsed (record boundaries by one sequential scan, bases encoded by all cores: reads.c) while chunk k is on
@@ -252,6 +254,17 @@ static void retire_map(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c) {
 		pile_host(m->pile, pl, n, c->fq.seq, c->fq.stride, c->fq.len, lift_kind, lift_off, lift_recs, joins, m->ann);
 		pthread_mutex_unlock(&w->pp->mu);
 	}
+	/* -I: the read support per indel bubble of the slot's reads, added to the context's counters (kernel k_indel behind them on the result stream,
+	 * on the slot's cached placement, locus and join records; nothing per read comes back); with the host's loci, the host's rule into the table itself */
+	if (m->indel && m->gpu_loci) {
+		uint64_t nr = 0, na = 0, nc = 0; double ms = 0;
+		if (bwb_hip_slot_indel(ctx, slot, m->max_mm, m->max_alt, m->join, m->indel->min_mapq, &nr)) bwb_die("map_reads: GPU %d: %s", w->gpu, bwb_hip_last_error());
+		if (n) { bwb_hip_indel_stats(ctx, NULL, &na, &nc, &ms); w->indel_ms += ms; w->indel_reads += nr; w->indel_adds += na; w->indel_cands += nc; } /* (a chunk without reads launches nothing) */
+	} else if (m->indel) {
+		pthread_mutex_lock(&w->pp->mu); /* (indel_host adds with the whole team: one worker at a time) */
+		indel_host(m->indel, pl, loci, n, c->fq.len, joins);
+		pthread_mutex_unlock(&w->pp->mu);
+	}
 	const sam_reads_t rd = { .pl = pl, .seq = c->fq.seq, .stride = c->fq.stride, .len = c->fq.len, .text = c->fq.text,
 	                         .name_off = c->fq.name_off, .qual_off = c->fq.qual_off, .name_len = c->fq.name_len, .first = c->first_read,
 	                         .alt_off = alt_off, .alts = alts, .loci = loci, .bubbles = m->bub, .joins = joins,
@@ -329,6 +342,14 @@ static void *gpu_worker(void *arg) {
 		/* -J, -R: the chromosome's record of every bubble, beside them */
 		if (pp->map->chrom_of && pp->map->gpu_loci && bwb_hip_set_bubble_chrom(ctx, pp->map->chrom_of, (uint32_t)pp->map->bub->n))
 			bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
+		/* -I: the sorted table of the eligible bubbles (16 bytes each, one more per bubble) and the zeroed counters (16 bytes per bubble), before the pool is sized as well */
+		if (pp->map->indel && pp->map->gpu_loci) {
+			const double t0 = wall();
+			uint64_t n_elig = 0;
+			if (bwb_hip_indel_begin(ctx, pp->map->indel->anchor, &n_elig)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
+			w->indel_begin_s = wall() - t0;
+			if (n_elig != pp->map->indel->n_tab) bwb_die("map_reads: GPU %d finds %llu eligible bubbles, the host %llu", w->device, (unsigned long long)n_elig, (unsigned long long)pp->map->indel->n_tab);
+		}
 		/* -D: the forward text (n_fwd / 2 bytes in HBM: 1.7 GB at GRCh37 scale), before the first slot_upload sizes the chunk pool as well; its
 		 * bytes are read by the .bwt loader behind the SA (bwt_io.c: load_bwt_start_job, md.c: md_text_read).  Not with the host's lift records: the host's rule then */
 		md_text_wait(pp->map->text);
@@ -408,6 +429,21 @@ static void *gpu_worker(void *arg) {
 		}
 		free(buf);
 		w->pile_fetch_s = wall() - t0;
+	}
+	/* -I: the same for the bubbles' counters */
+	if (pp->map && pp->map->indel && pp->map->gpu_loci) {
+		const double t0 = wall();
+		const uint64_t PIECE = (uint64_t)1 << 20, n_bub = (uint64_t)pp->map->bub->n;
+		uint32_t *buf = (uint32_t *)malloc((size_t)(n_bub < PIECE ? n_bub : PIECE) * 16 + 16);
+		for (uint64_t s0 = 0; s0 < n_bub; s0 += PIECE) {
+			const uint64_t ns = n_bub - s0 < PIECE ? n_bub - s0 : PIECE;
+			if (bwb_hip_indel_counts(ctx, s0, ns, buf)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
+			pthread_mutex_lock(&pp->mu);
+			indel_add(pp->map->indel, s0, ns, buf);
+			pthread_mutex_unlock(&pp->mu);
+		}
+		free(buf);
+		w->indel_fetch_s = wall() - t0;
 	}
 	bwb_stats st;
 	if (bwb_hip_flush(ctx) || bwb_hip_get_stats(ctx, &st)) bwb_die("align_reads_inexact_gpu: GPU %d: %s", w->device, bwb_hip_last_error());
@@ -556,6 +592,16 @@ static int run_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, 
 			else printf("allele counts at the text's IUPAC sites on the host (the .ann records are not ascending and disjoint): sites %llu  reads counted %llu  adds %llu\n",
 			            (unsigned long long)map->pile->n_sites, (unsigned long long)map->pile->reads, (unsigned long long)map->pile->adds);
 		}
+		if (map->indel) { /* -I */
+			double ims = 0, bs = 0, fs = 0; unsigned long long ir = 0, ia = 0, ic = 0;
+			for (int g = 0; g < n_gpus; g++) { ir += ws[g].indel_reads; ia += ws[g].indel_adds; ic += ws[g].indel_cands; if (ws[g].indel_ms > ims) ims = ws[g].indel_ms; if (ws[g].indel_begin_s > bs) bs = ws[g].indel_begin_s; if (ws[g].indel_fetch_s > fs) fs = ws[g].indel_fetch_s; }
+			if (map->gpu_loci)
+				printf("read support per indel bubble on the GPU: anchor %d  eligible bubbles %llu  refused and skipped %llu  reads counted %llu  adds %llu  candidates %llu  k_indel %.3f ms  table and counters %llu bytes, sorted in %.3f s, resident in %.3f s  counters read back in %.3f s\n",
+				       map->indel->anchor, (unsigned long long)map->indel->n_tab, (unsigned long long)map->indel->n_refused, ir, ia, ic, ims,
+				       (unsigned long long)(map->indel->n_tab * 16 + (uint64_t)map->bub->n * 17), map->indel->sort_s, bs, fs);
+			else printf("read support per indel bubble on the host (the .ann records are not ascending and disjoint): anchor %d  eligible bubbles %llu  refused and skipped %llu  reads counted %llu  adds %llu  candidates %llu\n",
+			            map->indel->anchor, (unsigned long long)map->indel->n_tab, (unsigned long long)map->indel->n_refused, (unsigned long long)map->indel->reads, (unsigned long long)map->indel->adds, (unsigned long long)map->indel->cands);
+		}
 		if (map->max_alt) {
 			double ams = 0; unsigned long long ast = 0, ait = 0;
 			for (int g = 0; g < n_gpus; g++) { ast += ws[g].alt_steps; ait += ws[g].alt_items; if (ws[g].alt_ms > ams) ams = ws[g].alt_ms; }
@@ -614,10 +660,11 @@ int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_
 }
 
 /* `bwbble map`: align_reads + alns2sam in one pass.  The .bwt is loaded once, with its SA; the SAM header is written before the first chunk. */
-int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, int n_gpus) {
+int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor, int n_gpus) {
 	printf("**** BWBBLE Read Mapping (align + aln2sam in one pass) ****\n");
 	/* -A: the counts file is opened before anything is loaded; until it is written, a run that stops leaves none behind */
 	pile_t *pile = countsFname ? pile_open(countsFname, min_mapq) : NULL;
+	indel_t *indel = indelFname ? indel_open(indelFname, min_mapq, anchor) : NULL; /* -I (main.c: only with -B): the same */
 	/* -B: the table first (a refused table stops the run before anything is created) */
 	bubble_table_t *bub = bubbleFname ? load_bubbles(bubbleFname) : NULL;
 	if (lift && bub) lift_check_table(bub); /* -R (main.c: only with -B): a bubble the rule refuses is named here */
@@ -636,7 +683,8 @@ int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *
 	int32_t *bubble_of = bub ? ann_bubble_of(ann, bub) : NULL;
 	/* -J (main.c: only with -X and -B): the chromosome's record of every bubble; one without a chromosome leaves no SAM file behind either */
 	join = join && bub && max_alt; lift = lift && bub;
-	int32_t *chrom_of = join || lift ? bubble_chrom_of(ann, bubble_of, bub, join ? "-J" : "-R") : NULL;
+	int32_t *chrom_of = join || lift || indel ? bubble_chrom_of(ann, bubble_of, bub, join ? "-J" : lift ? "-R" : "-I") : NULL;
+	if (indel) indel_set_table(indel, bub, chrom_of); /* -I: the eligible bubbles, sorted; a refused bubble is skipped, not named */
 	uint64_t *rec_start = NULL, *rec_end = NULL;
 	int gpu_loci = bub && ann->num_seq > 0 && sam_ann_sorted(ann) && bub->n <= INT32_MAX;
 	if (bub) {
@@ -654,7 +702,7 @@ int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *
 	sam_write_header(sam, ann);
 	const map_t m = { .max_mm = max_mm, .max_alt = max_alt, .ann = ann, .ann_sorted = sam_ann_sorted(ann),
 	                  .bub = bub, .bubble_of = bubble_of, .gpu_loci = gpu_loci, .rec_start = rec_start, .rec_end = rec_end, .chrom_of = chrom_of, .join = join, .lift = lift, .text = text,
-	                  .md = md, .pile = pile, .pile_on_host = pile && bub && !gpu_loci && (lift || join) };
+	                  .md = md, .pile = pile, .pile_on_host = pile && bub && !gpu_loci && (lift || join), .indel = indel };
 
 	t = wall();
 	printf("BWBBLE Inexact Alignment (MI355X)...\n");
@@ -664,9 +712,14 @@ int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *
 		const unsigned long long lines = pile_write(pile, ann);
 		printf("allele counts written: %llu sites with a count in %.3f s\n", lines, wall() - tw);
 	}
+	if (indel) { /* -I: likewise */
+		const double tw = wall();
+		const unsigned long long lines = indel_write(indel);
+		printf("read support per indel bubble written: %llu bubbles with a count in %.3f s\n", lines, wall() - tw);
+	}
 	printf("Total read mapping time (index and read loading overlapped): %.2f sec\n", wall() - t);
 	free_bwt(BWT); free_ann(ann);
 	free(bwtFname); free(annFname);
-	free(bubble_of); free(chrom_of); free(rec_start); free(rec_end); free_bubbles(bub); pile_free(pile); md_text_free(text);
+	free(bubble_of); free(chrom_of); free(rec_start); free(rec_end); free_bubbles(bub); pile_free(pile); indel_free(indel); md_text_free(text);
 	return 0;
 }

@@ -120,14 +120,14 @@ int aln_path_bytes(const bwb_aln *a, unsigned char *path /* >= 272 bytes */); /*
 void set_default_aln_params(aln_params_t *params);                     /* align.c:22-38 */
 int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_t *params, int n_gpus); /* align.c:40-87 */
 int align_reads_inexact_gpu_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, char *alnFname, int n_gpus); /* the GPU's align_reads_inexact_parallel (inexact_match.h:40) over a streamed FASTQ */
-int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, int n_gpus); /* `bwbble map` (countsFname: -A, NULL: no counts; min_mapq: -a): align + aln2sam in one pass, the hits evaluated on the GPU */
+int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor, int n_gpus); /* `bwbble map` (countsFname: -A, NULL: no counts; min_mapq: -a; indelFname: -I, NULL: no table; anchor: -w): align + aln2sam in one pass, the hits evaluated on the GPU */
 
 /* precalc.c */
 void precalc_sa_intervals(bwt_t *BWT, const aln_params_t *params, const char *preFname); /* align.c:200-224: writes <fasta>.pre */
 int check_precalc_file(const char *preFname); /* the walk of load_precalc_sa_intervals (align.c:226-238) over an existing table: 0 = complete */
 
 /* sam.c */
-void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq); /* align.c:494-556; max_alt: -X (0: no tags); bubbleFname: -B (NULL: no tags); join: -J; lift: -R; md: -D; countsFname: -A (NULL: no counts), min_mapq: -a */
+void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor); /* align.c:494-556; max_alt: -X (0: no tags); bubbleFname: -B (NULL: no tags); join: -J; lift: -R; md: -D; countsFname: -A (NULL: no counts), min_mapq: -a; indelFname: -I (NULL: no table), anchor: -w */
 /* the two halves of alns2sam: eval_aln of one read on the host, and the text of a block of reads from placement records (which `map` gets
  * from the GPU instead, bwb_hip_slot_place) */
 #define SAM_BLOCK_READS ((size_t)1 << 14)                              /* reads formatted by one thread at a time */
@@ -152,7 +152,7 @@ uint64_t alt_placements(const bwb_aln *e, uint64_t ne);               /* the row
 void sam_write_header(FILE *sam, const fasta_annotations_t *ann);
 int sam_ann_sorted(const fasta_annotations_t *ann);
 char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_annotations_t *ann, int ann_sorted, size_t *out_len);
-void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq); /* developer command: records from a file (countsFname / min_mapq: -A / -a; (altsFname: NULL or the items; bubbleFname: NULL or -B's table; join: -J, the items file then ends with one suboptimal byte per item; lift: -R; md: -D) */
+void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor); /* developer command: records from a file (countsFname / min_mapq: -A / -a; indelFname / anchor: -I / -w; (altsFname: NULL or the items; bubbleFname: NULL or -B's table; join: -J, the items file then ends with one suboptimal byte per item; lift: -R; md: -D) */
 
 /* pad.c: bubble hits in reference coordinates (the reference's mg-ref/sam_pad.cpp) */
 typedef struct bubble_table {                                          /* bubble.data (mg-ref/comb.cpp:245-253): the k-th pair of lines is bubble k */
@@ -219,6 +219,23 @@ uint64_t pile_host(pile_t *p, const bwb_place *pl, size_t n, const uint8_t *seq,
 void pile_add(pile_t *p, uint64_t first, uint64_t n, const uint32_t *counts); /* adds a context's counters of n sites from `first` (bwb_hip_pile_counts) */
 uint64_t pile_write(pile_t *p, const fasta_annotations_t *ann);       /* the header line and one line per site with a counter that is not zero; closes the file; returns the lines */
 void pile_free(pile_t *p);
+
+/* indel.c: -I, ref / alt read support per indel bubble (include/bwbble_hip.h: bwb_hip_indel_begin) */
+typedef struct { int64_t lo; int32_t chrom; uint32_t bubble; } indel_entry_t; /* an eligible bubble: A + Bm - w, chrom_of, its number */
+typedef struct indel {
+	char *fname; FILE *f; int min_mapq, anchor;                       /* the file, open since before anything was loaded (NULL: none, a table in memory only); -a; -w */
+	const bubble_table_t *bub; uint8_t *elig;                         /* the bubble table and, per bubble, whether it is eligible at this anchor */
+	indel_entry_t *tab; uint64_t n_tab, n_refused; double sort_s;     /* the eligible bubbles ascending by (chrom, lo, bubble); the bubbles lift_bubble_refusal refuses; qsort's seconds */
+	uint32_t *counts; uint64_t reads, adds, cands;                    /* n x (ref, alt, ref_gapped, alt_gapped), wrapping; what indel_host has counted */
+} indel_t;
+indel_t *indel_open(const char *indelFname, int min_mapq, int anchor); /* a path that cannot be written stops the run; until indel_write has finished, a run that exits leaves no file */
+int indel_eligible(const bwb_bubble *b, int anchor);
+void indel_set_table(indel_t *p, const bubble_table_t *t, const int32_t *chrom_of); /* the sorted table of the eligible bubbles and the zeroed counters */
+unsigned indel_resolve(int64_t pos1, int reverse, unsigned alen, const uint16_t *gap_run, int64_t lo, int64_t hi); /* one placement against one window: 0 not covering, 1 clean, 2 gapped */
+uint64_t indel_host(indel_t *p, const bwb_place *pl, const bwb_locus *loci, size_t n, const uint16_t *len, const bwb_join *joins); /* kernel k_indel on the host: adds into the table, returns the reads counted (joins NULL: the placements' MAPQ) */
+void indel_add(indel_t *p, uint64_t first, uint64_t n, const uint32_t *counts); /* adds a context's counters of n bubbles from `first` (bwb_hip_indel_counts) */
+uint64_t indel_write(indel_t *p);                                     /* the header line and one line per bubble with a counter that is not zero; closes the file; returns the lines */
+void indel_free(indel_t *p);
 void sam_pad(const char *dataFname, const char *inFname, const char *outFname); /* `bwbble sampad`: sam_pad.cpp:47-94 over SAM text */
 
 /* The OpenMP teams of the host stages of `align` / `aln2sam` (base encoding, .aln serialisation, SAM text) have at most 32 threads unless

@@ -487,6 +487,58 @@ int bwb_hip_pile_site_of(bwb_hip_ctx *ctx, const uint64_t *pos, size_t n, int64_
  * NULL) */
 int bwb_hip_pile_stats(bwb_hip_ctx *ctx, uint64_t *reads, uint64_t *adds, double *kernel_ms);
 
+/* Ref / alt read support per indel bubble (`bwbble map -B table -I <indels.tsv>`): how many reads carry a bubble's alternate allele and how
+ * many the chromosome's own, summed on the device over every read of a run - the second reduction across reads, beside the pile family.  No
+ * stock tool can make the table afterwards: an alt-supporting read lies on a bubble record, a ref-supporting read at a site only bubble.data
+ * names, and the MAPQ that decides is -J's.
+ * The rule.  Bubble b = (A, Bm, C, Dm, ref_len, alt_len) with gap = C - A - Bm, c = chrom_of[b] and the zones L / V / R of bwb_lift; w is the
+ * ANCHOR, 1..255: the flank bases a read must cover with M on either side.
+ *   eligible  b is eligible when the rule of bwb_lift does not refuse it (Bm >= 0, Dm >= -1, alt_len >= 0, 0 <= gap < 2^28) and Bm >= w,
+ *             Dm + 1 >= w and A + Bm - w >= 1.  An ineligible bubble is never counted, for either allele.  A table with refused bubbles does
+ *             not stop anything: they are skipped.
+ *   windows   in the 1-based coordinates of the record the read lies on (bwb_locus.pos1):
+ *             on b's own record       [lo, hi] = [Bm - w + 1, Bm + alt_len + w]
+ *             on the chromosome's c   [lo, hi] = [A + Bm - w, C + w - 1]
+ *   reads     a read counts when it is mapped and its locus has seqid >= 0, its printed ops consume exactly the read's length (M and I; the
+ *             records form has no reads and does not ask), and its MAPQ is at least min_mapq: bwb_join.mapq when the call is `joined`, else
+ *             bwb_place.mapq.  Primaries only.  The ops are always the placement's PRINTED CIGAR - lift_op_at over gap_run, walked with x from
+ *             pos1; M and D consume x, I does not -, never the lift record: the table is the same with and without -R.
+ *   classes   of a read against a window: COVERING - lo and hi are each consumed by an M; CLEAN - covering, every x in [lo, hi] is consumed by
+ *             an M, and no I lies between the M at lo and the M at hi; GAPPED - covering, not clean.  A read that is not covering adds nothing.
+ *   counters  four uint32 per bubble, in the order ref, alt, ref_gapped, alt_gapped; they wrap modulo 2^32.  A read whose locus lies on b's
+ *             record is classed against b's own window only: alt += 1 when clean, alt_gapped += 1 when gapped.  A read on a non-bubble record
+ *             c is classed against the window of EVERY eligible bubble with chrom_of == c: ref += 1 or ref_gapped += 1.  Mismatches under M
+ *             do not matter.
+ * Not here: other bubbles' sites inside a bubble record's flanks, XA items, base qualities, genotypes, left-alignment (a read that fits both
+ * alleles equally well counts for whichever placement is its primary).
+ * The adds are integer and commute: the table does not depend on chunking, slot order, parked reads or the number of contexts whose tables are
+ * summed.  Kernel k_indel: one lane per read behind k_place / k_locus / the join kernels on the result stream; a read on a chromosome bisects
+ * a table of the eligible bubbles sorted by (chrom_of, A + Bm - w, bubble number) - 16 bytes per bubble, built on the host by indel_begin - and
+ * walks the candidates whose lo lies within its first and last M; relaxed agent-scope atomic adds.  (Added without a version change: no
+ * structure or existing entry point changed.) */
+/* After set_loci and set_bubble_chrom and before the first slot_upload sizes the pool: builds and uploads the sorted table of the bubbles
+ * eligible at this anchor, allocates and zeroes n_bub x 4 counters.  *n_eligible may be 0.  BWB_E_STATE without set_loci or set_bubble_chrom;
+ * BWB_E_ARG for an anchor outside 1..255.  A later set_loci or set_bubble_chrom forgets the table and the counters. */
+int bwb_hip_indel_begin(bwb_hip_ctx *ctx, int anchor, uint64_t *n_eligible);
+/* slot_locus, and slot_join with joined != 0 (their cached records where they exist), then k_indel over the slot's n_reads resident reads.
+ * Nothing per read comes back; *reads_counted (may be NULL) = the reads this call counted.  A SUBMISSION IS COUNTED ONCE: a second slot_indel
+ * on the same submission returns BWB_OK, launches nothing and reports 0; the flag clears at the slot's next upload.  BWB_E_ARG for min_mapq or
+ * max_alt outside 0..255.  BWB_E_STATE without indel_begin, without set_sa, on a slot that has not been submitted, and with joined != 0 and
+ * max_alt == 0; the context stays usable after each.  batch_indel is the one-batch form (slot 0 after batch_run). */
+int bwb_hip_slot_indel(bwb_hip_ctx *ctx, int slot, int max_mm, int max_alt, int joined, int min_mapq, uint64_t *reads_counted);
+int bwb_hip_batch_indel(bwb_hip_ctx *ctx, int max_mm, int max_alt, int joined, int min_mapq, uint64_t *reads_counted);
+/* The same kernel on n placement records of the caller's (k_locus runs on them first, as in lift_records); mapq: NULL, or one value per read
+ * that stands in for the joined MAPQ.  Accumulates into the context's counters; touches no slot.  Needs indel_begin (BWB_E_STATE). */
+int bwb_hip_indel_records(bwb_hip_ctx *ctx, const bwb_place *places, uint32_t n, const uint8_t *mapq, int min_mapq);
+/* Synchronises the result stream and copies the 4 n counters of the bubbles first .. first + n - 1 to out (ref, alt, ref_gapped, alt_gapped
+ * per bubble).  BWB_E_ARG when the range leaves the bubble table; BWB_E_STATE without indel_begin. */
+int bwb_hip_indel_counts(bwb_hip_ctx *ctx, uint64_t first, uint64_t n, uint32_t *out);
+/* zeroes the counters */
+int bwb_hip_indel_reset(bwb_hip_ctx *ctx);
+/* the last indel call on the context that launched the kernel: reads counted, adds made, candidate windows examined (a chromosome read's
+ * table entries with lo within its M span, a bubble read's own eligible window) and the kernel's HIP-event time (any pointer may be NULL) */
+int bwb_hip_indel_stats(bwb_hip_ctx *ctx, uint64_t *reads, uint64_t *adds, uint64_t *candidates, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
