@@ -310,6 +310,15 @@ static void pin_to_device_node(int device, int dbg) {
 	if (any && pthread_setaffinity_np(pthread_self(), sizeof(set), &set) == 0 && dbg) fprintf(stderr, "[bwb host] device %d: worker thread on NUMA node %d (cpus %s", device, node, buf);
 }
 
+/* counters (of -A's sites, of -I's bubbles) per read-back of a worker: 2^20, 16 MB.  BWB_COUNT_PIECE: a test knob - pieces of a few counters
+ * make the loops below take many turns on a small text; a value below 1 is 1 */
+static uint64_t count_piece(void) {
+	const char *e = getenv("BWB_COUNT_PIECE");
+	if (!e) return (uint64_t)1 << 20;
+	const long long v = strtoll(e, NULL, 10);
+	return v < 1 ? 1 : (uint64_t)v;
+}
+
 /* One host thread per GPU.  Chunks are streamed through the slots of the context: while the search slice of chunk j runs,
  * chunk j+1 is already uploaded and queued behind it and the hits of chunk j-1 are on their way back; a slice parks its
  * unfinished reads for the next one instead of draining (include/bwbble_hip.h), so the GPU never runs a batch's tail alone. */
@@ -418,9 +427,10 @@ static void *gpu_worker(void *arg) {
 	/* -A: the stream has ended and every chunk of this worker is retired - its counters come back in bounded pieces and are summed on the host */
 	if (pp->map && pp->map->pile && !pp->map->pile_on_host) {
 		const double t0 = wall();
-		const uint64_t PIECE = (uint64_t)1 << 20, n_sites = pp->map->pile->n_sites; /* sites per read-back: 16 MB */
+		const uint64_t PIECE = count_piece(), n_sites = pp->map->pile->n_sites; /* sites per read-back */
 		uint32_t *buf = (uint32_t *)malloc((size_t)(n_sites < PIECE ? n_sites : PIECE) * 16 + 16);
-		for (uint64_t s0 = 0; s0 < n_sites; s0 += PIECE) {
+		uint64_t turns = 0;
+		for (uint64_t s0 = 0; s0 < n_sites; s0 += PIECE, turns++) {
 			const uint64_t ns = n_sites - s0 < PIECE ? n_sites - s0 : PIECE;
 			if (bwb_hip_pile_counts(ctx, s0, ns, buf)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
 			pthread_mutex_lock(&pp->mu);
@@ -429,13 +439,15 @@ static void *gpu_worker(void *arg) {
 		}
 		free(buf);
 		w->pile_fetch_s = wall() - t0;
+		if (dbg) fprintf(stderr, "[bwb host] worker %d: the counters of %llu sites read back in %llu pieces\n", w->gpu, (unsigned long long)n_sites, (unsigned long long)turns);
 	}
 	/* -I: the same for the bubbles' counters */
 	if (pp->map && pp->map->indel && pp->map->gpu_loci) {
 		const double t0 = wall();
-		const uint64_t PIECE = (uint64_t)1 << 20, n_bub = (uint64_t)pp->map->bub->n;
+		const uint64_t PIECE = count_piece(), n_bub = (uint64_t)pp->map->bub->n;
 		uint32_t *buf = (uint32_t *)malloc((size_t)(n_bub < PIECE ? n_bub : PIECE) * 16 + 16);
-		for (uint64_t s0 = 0; s0 < n_bub; s0 += PIECE) {
+		uint64_t turns = 0;
+		for (uint64_t s0 = 0; s0 < n_bub; s0 += PIECE, turns++) {
 			const uint64_t ns = n_bub - s0 < PIECE ? n_bub - s0 : PIECE;
 			if (bwb_hip_indel_counts(ctx, s0, ns, buf)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
 			pthread_mutex_lock(&pp->mu);
@@ -444,6 +456,7 @@ static void *gpu_worker(void *arg) {
 		}
 		free(buf);
 		w->indel_fetch_s = wall() - t0;
+		if (dbg) fprintf(stderr, "[bwb host] worker %d: the counters of %llu bubbles read back in %llu pieces\n", w->gpu, (unsigned long long)n_bub, (unsigned long long)turns);
 	}
 	bwb_stats st;
 	if (bwb_hip_flush(ctx) || bwb_hip_get_stats(ctx, &st)) bwb_die("align_reads_inexact_gpu: GPU %d: %s", w->device, bwb_hip_last_error());

@@ -115,7 +115,9 @@ int aln_path_bytes(const bwb_aln *a, unsigned char *path /* >= 272 bytes */); /*
 /* align_gpu.c */
 /* reads per GPU batch (BWB_CHUNK).  Batches are streamed as slices that park their unfinished reads for the next slice, so the
  * size no longer decides how much of the GPU idles at the end of a batch; it trades launch overhead against the balance
- * between GPUs and the memory of a slot (about 1 KB per read). */
+ * between GPUs and the memory of a slot (about 1 KB per read).
+ * Test knobs beside it: BWB_FQ_REGION (reads.c: bytes per region of the FASTQ scan) and BWB_COUNT_PIECE (align_gpu.c: the sites of -A, or the
+ * bubbles of -I, whose counters a worker of `map` reads back at a time; default 2^20, a value below 1 is 1). */
 #define GPU_CHUNK_DEFAULT (1u << 21)
 void set_default_aln_params(aln_params_t *params);                     /* align.c:22-38 */
 int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_t *params, int n_gpus); /* align.c:40-87 */

@@ -1,7 +1,8 @@
 """Ref / alt read support per indel bubble (`bwbble map -I`, kernel k_indel) on the GPU, judged by tests/indel_model.py: Context.indel_records on
 injected placement records over constructed record and bubble tables - the eligibility edges, windows at every edge, D and I at and beside lo
 and hi, CIGARs of up to eight gap runs, both strands, 300 bubbles that share a left flank, two chromosomes with bubbles at equal positions, a
-refused bubble beside good ones, MAPQ thresholds with and without the override -; 70 000 reads on one bubble; more reads than twice the grid's
+refused bubble beside good ones, MAPQ thresholds with and without the override -; tables of 0, 1 and around every power of two up to 257
+entries, one chromosome of three without any; 70 000 reads on one bubble; more reads than twice the grid's
 lanes; the generated genome mapped in one batch and streamed through the slots (tests/indel_slots_worker.py); the state and argument errors;
 and the command line against the model's bytes and against `align` + `aln2sam -I`."""
 import os
@@ -141,6 +142,84 @@ def test_three_hundred_bubbles_share_a_left_flank(toy_ctx):
     got = toy_ctx.indel_counts(0, 300)
     assert np.array_equal(got, want) and (want[:, 0] >= 6).all() and (want[:, 2] >= 3).all() and not want[:, 1].any()
     assert toy_ctx.indel_stats()[:3] == (reads, adds, 300 * 12)  # (the reads on chromosome 3 have no candidate; the 5M read begins at every lo and ends before every hi: a candidate each time, never counted)
+
+
+def edge_bubbles(n_elig):
+    """a list with exactly n_elig bubbles eligible at anchor W and, in every fourth place and behind them, bubbles that are not (a left flank one
+    short; flanks that overlap: refused); with table() bubble b lies on chromosome record 3 * (b % 3), at a position that ascends with b // 3"""
+    out, made = [], 0
+    while made < n_elig or len(out) < 2:
+        A, k = 200 + 20 * (len(out) // 3), len(out)
+        if k % 4 == 1 or made == n_elig:
+            out.append((b"x", A, W - 1, A + W - 1, 9, 0, 1) if k % 8 == 1 else (b"x", A, 10, A + 9, 9, 0, 2))
+        else:
+            out.append((b"t", A, 10, A + 10 + made % 2, 9, made % 2, 1 + made % 3))
+            made += 1
+    return out
+
+
+def edge_reads(t, bubbles, seed):
+    """per chromosome record 0, 3 and 6, on alternating strands: with entries - a read that begins before the first entry's lo, one whose window is
+    the first entry's and one whose window is the last entry's, one behind the last entry, one that spans the last entry, a CIGAR of three gap runs
+    over the first window, one with a D inside it, and reads of 250 positions over the whole stretch; without entries - reads where the other
+    chromosomes have theirs"""
+    rng = np.random.default_rng(seed)
+    by_chrom = {}
+    for k, b in enumerate(bubbles):
+        if indel_model.eligible(b, W):
+            by_chrom.setdefault(int(t.chrom[k]), []).append(indel_model.windows(b, W)[1])
+    placed, census = [], {"chromosomes with entries": 0, "without": 0}
+
+    def put(rec, pos1, cig):
+        placed.append((int(t.start[rec]) + pos1 - 1, len(placed) % 2 == 1, cig))
+
+    for rec in (0, 3, 6):
+        wins = sorted(by_chrom.get(rec, []))
+        for pos1 in range(1, 200 + 20 * (len(bubbles) // 3) + 60, 200):
+            put(rec, pos1, "250M")
+        if not wins:
+            census["without"] += 1
+            put(rec, 191, "60M")
+            put(rec, 206, "9M")
+            continue
+        census["chromosomes with entries"] += 1
+        (lo0, hi0), (lo1, hi1) = wins[0], wins[-1]
+        put(rec, lo0 - 5, "60M")
+        put(rec, lo0, f"{hi0 - lo0 + 1}M")
+        put(rec, lo1, f"{hi1 - lo1 + 1}M")
+        put(rec, hi1 + 1, "50M")
+        put(rec, lo1 - 20, "60M")
+        put(rec, lo0 - 3, gapped(rng, 3, hi0 - lo0 + 7))
+        put(rec, lo0 - 5, "7M1D50M")  # (a D inside the first window: gapped, whatever the CIGAR before drew)
+    return lift_model.place_records(placed), census
+
+
+@pytest.mark.parametrize("none_on_record_3", [False, True])
+@pytest.mark.parametrize("n_tab", [0, 1, 2, 3, 4, 7, 8, 9, 255, 256, 257])
+def test_table_sizes_at_and_beside_the_powers_of_two(toy_ctx, n_tab, none_on_record_3):
+    """the bisection's step count is chosen so that 2^trips > n_tab: tables of no entry, one, a power of two and one either side, spread over
+    chromosome records 0, 3 and 6 - or over 0 and 6 only, so that the chromosome in the middle owns no entry and two bubbles of record 0 share a
+    lo -, with bubbles that are not eligible between the others"""
+    bubbles = edge_bubbles(n_tab)
+    t = table(9, len(bubbles))
+    if none_on_record_3:
+        t.chrom[t.chrom == 3] = 0
+    places, census = edge_reads(t, bubbles, n_tab)
+    want, reads, adds = expected(t, bubbles, places)
+    assert load(toy_ctx, t, bubbles) == n_tab == sum(indel_model.eligible(b, W) for b in bubbles) < len(bubbles)
+    toy_ctx.indel_records(places)
+    got = toy_ctx.indel_counts(0, len(bubbles))
+    assert np.array_equal(got, want), (n_tab, np.flatnonzero((got != want).any(axis=1))[:5], got[(got != want).any(axis=1)][:3], want[(got != want).any(axis=1)][:3])
+    st = toy_ctx.indel_stats()
+    assert st[:2] == (reads, adds) and st[2] >= adds and reads == len(places)
+    elig = np.array([indel_model.eligible(b, W) for b in bubbles])
+    assert not want[~elig].any() and want[elig][:, 0].all()  # every entry is counted by a read on its chromosome, the first and the last of each among them
+    assert census["chromosomes with entries"] + census["without"] == 3 and (census["without"] > 0) == (none_on_record_3 or n_tab < 4)
+    assert n_tab < 4 or census["chromosomes with entries"] == (2 if none_on_record_3 else 3)
+    if n_tab == 0:
+        assert st[2] == 0 and not want.any()
+    else:
+        assert want[:, 2].any()
 
 
 def test_mapq_threshold_with_and_without_the_override(toy_ctx, bubbles, rel):
