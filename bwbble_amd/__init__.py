@@ -30,6 +30,7 @@ EXPORTS = [
     "bwb_hip_set_text", "bwb_hip_slot_md", "bwb_hip_batch_md", "bwb_hip_md_records", "bwb_hip_md_stats",
     "bwb_hip_pile_begin", "bwb_hip_slot_pile", "bwb_hip_batch_pile", "bwb_hip_pile_records", "bwb_hip_pile_counts", "bwb_hip_pile_reset", "bwb_hip_pile_site_of", "bwb_hip_pile_stats",
     "bwb_hip_indel_begin", "bwb_hip_slot_indel", "bwb_hip_batch_indel", "bwb_hip_indel_records", "bwb_hip_indel_counts", "bwb_hip_indel_reset", "bwb_hip_indel_stats",
+    "bwb_hip_geno_begin", "bwb_hip_pile_put", "bwb_hip_indel_put", "bwb_hip_geno_sites", "bwb_hip_geno_bubbles", "bwb_hip_geno_stats",
 ]
 ABI_VERSION = 3  # BWB_HIP_ABI_VERSION (include/bwbble_hip.h)
 MAX_SLOTS = 8  # BWB_MAX_SLOTS
@@ -84,6 +85,10 @@ assert LIFT_DTYPE.itemsize == 16
 LIFT_M, LIFT_I, LIFT_D, LIFT_S, LIFT_MAX_OPS = 0, 1, 2, 4, 20
 LIFT_NONE, LIFT_LIFTED, LIFT_UNLIFTABLE = 0, 1, 2
 # bwb_md: a read's NM and the length of its MD text against the index's text (kernels k_md_count / k_md)
+# bwb_geno_site / bwb_geno_bubble (include/bwbble_hip.h): the called sites' and bubbles' records of the geno family
+GENO_SITE_DTYPE = np.dtype([("pos", "<u8"), ("site", "<u8"), ("n", "<u4", (4,)), ("code", "u1"), ("n_geno", "u1"), ("gt", "u1"), ("gq", "u1"), ("reserved", "<u4"), ("pl", "<u4", (6,))])
+GENO_BUBBLE_DTYPE = np.dtype([("bubble", "<u4"), ("n", "<u4", (4,)), ("gt", "u1"), ("gq", "u1"), ("reserved", "<u2"), ("pl", "<u4", (3,)), ("pad", "<u4", (3,))])
+assert GENO_SITE_DTYPE.itemsize == 64 and GENO_BUBBLE_DTYPE.itemsize == 48
 MD_DTYPE = np.dtype([("nm", "<u4"), ("md_len", "<u2"), ("kind", "u1"), ("reserved", "u1")])
 assert MD_DTYPE.itemsize == 8
 MD_NONE, MD_OK, MD_TOO_LONG, MD_MAX_SPAN = 0, 1, 2, 4096
@@ -178,6 +183,12 @@ def lib():
         L.bwb_hip_indel_counts.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
         L.bwb_hip_indel_reset.argtypes = [C.c_void_p]
         L.bwb_hip_indel_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.bwb_hip_geno_begin.argtypes = [C.c_void_p, C.c_uint32]
+        L.bwb_hip_pile_put.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        L.bwb_hip_indel_put.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        L.bwb_hip_geno_sites.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.bwb_hip_geno_bubbles.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.bwb_hip_geno_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -724,6 +735,41 @@ class Context:
         r, a, k, ms = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_double()
         _chk(lib().bwb_hip_indel_stats(self._h, C.byref(r), C.byref(a), C.byref(k), C.byref(ms)))
         return r.value, a.value, k.value, ms.value
+
+    # -- genotype calls at the IUPAC sites and the indel bubbles (-G): from the pile and indel counters that live on the device (needs pile_begin,
+    #    for bubbles indel_begin, then geno_begin) --
+    def geno_begin(self, piece):
+        """scratch and pinned output for `piece` sites (and, after indel_begin, min(piece, n_bub) bubbles).  Before the first upload"""
+        _chk(lib().bwb_hip_geno_begin(self._h, piece))
+
+    def pile_put(self, first, counts):
+        """overwrites the counters of the sites first .. with an (n, 4) uint32 array: A, C, G, T"""
+        counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1, 4)
+        _chk(lib().bwb_hip_pile_put(self._h, first, len(counts), counts.ctypes.data))
+
+    def indel_put(self, first, counts):
+        """overwrites the counters of the bubbles first .. with an (n, 4) uint32 array: ref, alt, ref_gapped, alt_gapped"""
+        counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1, 4)
+        _chk(lib().bwb_hip_indel_put(self._h, first, len(counts), counts.ctypes.data))
+
+    def _geno(self, fn, dtype, first, n, err, min_depth):
+        out, k = C.c_void_p(), C.c_uint64()
+        _chk(fn(self._h, first, n, err, min_depth, C.byref(out), C.byref(k)))
+        if not k.value:
+            return np.zeros(0, dtype=dtype)
+        return np.frombuffer(C.string_at(out.value, k.value * dtype.itemsize), dtype=dtype).copy()
+
+    def geno_sites(self, first, n, err=20, min_depth=1):
+        """the records (GENO_SITE_DTYPE, a copy) of the called sites among first .. first + n - 1, in site order"""
+        return self._geno(lib().bwb_hip_geno_sites, GENO_SITE_DTYPE, first, n, err, min_depth)
+
+    def geno_bubbles(self, first, n, err=20, min_depth=1):
+        """the records (GENO_BUBBLE_DTYPE, a copy) of the called bubbles among first .. first + n - 1, in bubble order"""
+        return self._geno(lib().bwb_hip_geno_bubbles, GENO_BUBBLE_DTYPE, first, n, err, min_depth)
+
+    def geno_stats(self):
+        """(sites the last geno_sites called, bubbles the last geno_bubbles called, kernel ms of whichever launched last)"""
+        return self._count_steps_ms(lib().bwb_hip_geno_stats)
 
     def dtab_info(self):
         """the context's calculate_d table: {K (0: none), build seconds, bytes}"""

@@ -218,6 +218,10 @@ struct bwb_hip_ctx {
 	PinMem h_indel_stats;
 	bool indel_on = false; uint32_t indel_anchor = 0, indel_ntab = 0, indel_trips = 0; /* indel_begin has run on these tables */
 	double indel_ms = 0; uint64_t indel_reads = 0, indel_adds = 0, indel_cands = 0; /* the last indel call that launched */
+	DevMem d_geno_cnt, d_geno_word, d_geno_off, d_geno_bsum, d_geno_sites, d_geno_bubs; /* the geno kernels: per entry of a piece the called flag, the site's word and the scan; the called records */
+	PinMem h_geno_sites, h_geno_bubs, h_geno_n;
+	bool geno_on = false, geno_bub = false; uint32_t geno_piece = 0, geno_piece_bub = 0; /* geno_begin has run on this site index (and on this bubble table) */
+	double geno_ms = 0; uint64_t geno_sites_called = 0, geno_bubs_called = 0; /* the last geno_sites / geno_bubbles call: its kernels' time; the entries each called last */
 	bool force_slices = false;          /* BWB_FORCE_SLICES: the one-batch API parks and resumes too (tests) */
 	bool dbg = false, dbg_iters = false;
 	const char *launch_log = nullptr;   /* BWB_LAUNCH_LOG=<file>: one JSON line per class-0 kernel launch (synchronises after every launch: a profiling aid) */
@@ -2147,6 +2151,7 @@ extern "C" int bwb_hip_set_text(bwb_hip_ctx *c, const uint8_t *codes, uint64_t n
 	for (auto &s : c->slots) s.md_mm = -1;
 	c->pile_on = false; c->pile_sites = 0; /* (the site index and the counters were this text's) */
 	c->d_site_base.release(); c->d_counts.release();
+	c->geno_on = false; c->geno_bub = false;
 	const uint64_t CH = 1ull << BWB_TEXT_CHUNK_SHIFT, n_words = (n_fwd + 31) / 32;
 	HIPCHK(c->d_text.alloc((size_t)n_words * 16));
 	DevMem d_stage, d_bad;
@@ -2322,6 +2327,7 @@ extern "C" int bwb_hip_pile_begin(bwb_hip_ctx *c, uint64_t *n_sites) {
 	HIPCHK(hipSetDevice(c->device));
 	HIPCHK(hipStreamSynchronize(c->rstream)); /* (a pile kernel of an earlier call may still add to the counters that are replaced) */
 	c->pile_on = false; c->pile_sites = 0;
+	c->geno_on = false; c->geno_bub = false; /* (the calls were for this index and these counters) */
 	const unsigned nblk = (unsigned)((n_words + BWB_BLOCK - 1) / BWB_BLOCK);
 	DevMem d_bsum, d_total;
 	HIPCHK(c->d_site_base.alloc((size_t)n_words * 4));
@@ -2535,6 +2541,7 @@ extern "C" int bwb_hip_indel_begin(bwb_hip_ctx *c, int anchor, uint64_t *n_eligi
 	HIPCHK(hipSetDevice(c->device));
 	HIPCHK(hipStreamSynchronize(c->rstream)); /* (a kernel of an earlier call may still read the table and add to the counters that are replaced) */
 	c->indel_on = false;
+	c->geno_bub = false; /* (geno_begin sized its bubble output for the table that is replaced) */
 	const uint32_t n_bub = c->loci_nbub;
 	std::vector<IndelEntry> tab;
 	std::vector<uint8_t> elig(n_bub ? n_bub : 1, 0);
@@ -2683,6 +2690,147 @@ extern "C" int bwb_hip_indel_stats(bwb_hip_ctx *c, uint64_t *reads, uint64_t *ad
 	if (adds) *adds = c->indel_adds;
 	if (candidates) *candidates = c->indel_cands;
 	if (kernel_ms) *kernel_ms = c->indel_ms;
+	return BWB_OK;
+}
+
+/* ---- genotype calls at IUPAC sites and indel bubbles (k_geno_count, k_geno_emit, k_geno_bubbles) ------------------------------------------- */
+static_assert(sizeof(bwb_geno_site) == 64 && offsetof(bwb_geno_site, n) == 16 && offsetof(bwb_geno_site, code) == 32 && offsetof(bwb_geno_site, pl) == 40, "k_geno_emit writes this layout");
+static_assert(sizeof(bwb_geno_bubble) == 48 && offsetof(bwb_geno_bubble, gt) == 20 && offsetof(bwb_geno_bubble, pl) == 24, "k_geno_bubbles writes this layout");
+extern "C" int bwb_hip_geno_begin(bwb_hip_ctx *c, uint32_t piece) {
+	if (!c) return fail(BWB_E_ARG, "geno_begin: null context");
+	if (piece < 1 || piece > (1u << 24)) return fail(BWB_E_ARG, "geno_begin: the piece must be 1..2^24");
+	if (!c->pile_on) return fail(BWB_E_STATE, "geno_begin: no site index and counters (bwb_hip_pile_begin)");
+	HIPCHK(hipSetDevice(c->device));
+	HIPCHK(hipStreamSynchronize(c->rstream)); /* (a geno kernel of an earlier call may still use the buffers that are replaced) */
+	c->geno_on = false; c->geno_bub = false;
+	const size_t nblk = ((size_t)piece + BWB_BLOCK - 1) / BWB_BLOCK;
+	HIPCHK(c->d_geno_cnt.alloc((size_t)piece * 4));
+	HIPCHK(c->d_geno_word.alloc((size_t)piece * 4));
+	HIPCHK(c->d_geno_off.alloc(((size_t)piece + 1) * 8));
+	HIPCHK(c->d_geno_bsum.alloc(nblk * 8));
+	HIPCHK(c->d_geno_sites.alloc((size_t)piece * sizeof(bwb_geno_site)));
+	HIPCHK(c->h_geno_sites.reserve((size_t)piece * sizeof(bwb_geno_site)));
+	HIPCHK(c->h_geno_n.reserve(8));
+	c->geno_piece = piece;
+	if (c->indel_on) {
+		const uint32_t pb = std::min(piece, std::max(c->loci_nbub, 1u));
+		HIPCHK(c->d_geno_bubs.alloc((size_t)pb * sizeof(bwb_geno_bubble)));
+		HIPCHK(c->h_geno_bubs.reserve((size_t)pb * sizeof(bwb_geno_bubble)));
+		c->geno_piece_bub = pb; c->geno_bub = true;
+	}
+	c->geno_ms = 0; c->geno_sites_called = 0; c->geno_bubs_called = 0;
+	c->geno_on = true;
+	return BWB_OK;
+}
+
+/* the mirrors of pile_counts / indel_counts: overwrite the counters of a range (several workers' sums meet on one device; tests inject counts) */
+extern "C" int bwb_hip_pile_put(bwb_hip_ctx *c, uint64_t first, uint64_t n, const uint32_t *counts) {
+	if (!c || (n && !counts)) return fail(BWB_E_ARG, "pile_put: null argument");
+	if (!c->pile_on) return fail(BWB_E_STATE, "pile_put: no site index and counters (bwb_hip_pile_begin)");
+	if (first > c->pile_sites || n > c->pile_sites - first) return fail(BWB_E_ARG, "pile_put: the range leaves the " + std::to_string(c->pile_sites) + " sites");
+	HIPCHK(hipSetDevice(c->device));
+	if (n) HIPCHK(hipMemcpyAsync(c->d_counts.as<uint32_t>() + first * 4, counts, (size_t)n * 16, hipMemcpyHostToDevice, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream)); /* (pageable memory of the caller) */
+	return BWB_OK;
+}
+extern "C" int bwb_hip_indel_put(bwb_hip_ctx *c, uint64_t first, uint64_t n, const uint32_t *counts) {
+	if (!c || (n && !counts)) return fail(BWB_E_ARG, "indel_put: null argument");
+	if (!c->indel_on) return fail(BWB_E_STATE, "indel_put: no bubble table and counters (bwb_hip_indel_begin)");
+	if (first > c->loci_nbub || n > c->loci_nbub - first) return fail(BWB_E_ARG, "indel_put: the range leaves the " + std::to_string(c->loci_nbub) + " bubbles");
+	HIPCHK(hipSetDevice(c->device));
+	if (n) HIPCHK(hipMemcpyAsync(c->d_indel_counts.as<uint32_t>() + first * 4, counts, (size_t)n * 16, hipMemcpyHostToDevice, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	return BWB_OK;
+}
+
+static int geno_args(bwb_hip_ctx *c, const char *who, uint64_t first, uint64_t n, int err, int64_t min_depth, uint64_t table, uint32_t piece) {
+	if (err < 4 || err > 93) return fail(BWB_E_ARG, std::string(who) + ": the error phred must be 4..93");
+	if (min_depth < 1 || min_depth > 0x7FFFFFFFll) return fail(BWB_E_ARG, std::string(who) + ": the minimum depth must be 1..2^31 - 1");
+	if (first > table || n > table - first) return fail(BWB_E_ARG, std::string(who) + ": the range leaves the table of " + std::to_string(table));
+	if (n > piece) return fail(BWB_E_ARG, std::string(who) + ": more than the piece of " + std::to_string(piece) + " (bwb_hip_geno_begin)");
+	(void)c;
+	return BWB_OK;
+}
+/* the scan of cnt[0 .. n) and the read-back of what the emit kernel wrote: the total first (8 bytes), then that many records */
+static int geno_scan(bwb_hip_ctx *c, uint32_t n) {
+	const unsigned nblk = (unsigned)(((size_t)n + BWB_BLOCK - 1) / BWB_BLOCK);
+	uint64_t *d_off = c->d_geno_off.as<uint64_t>();
+	hipLaunchKernelGGL(k_scan_blocks, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, c->d_geno_cnt.as<uint32_t>(), n, d_off, c->d_geno_bsum.as<uint64_t>());
+	hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(BWB_BLOCK), 0, c->rstream, c->d_geno_bsum.as<uint64_t>(), (uint32_t)nblk, d_off + n);
+	hipLaunchKernelGGL(k_scan_add, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, d_off, n, c->d_geno_bsum.as<uint64_t>());
+	HIPCHK(hipGetLastError());
+	return BWB_OK;
+}
+static int geno_fetch(bwb_hip_ctx *c, Timed &t, uint32_t n, const void *d_recs, void *h_recs, size_t rec_bytes, uint64_t *n_out) {
+	HIPCHK(hipMemcpyAsync(c->h_geno_n.p, c->d_geno_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	const uint64_t called = c->h_geno_n.as<uint64_t>()[0];
+	if (called > n) return fail(BWB_E_HIP, "geno: the scan counts more called entries than the range has");
+	if (called) HIPCHK(hipMemcpyAsync(h_recs, d_recs, (size_t)called * rec_bytes, hipMemcpyDeviceToHost, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	float ms = 0;
+	RC(t.ms(&ms));
+	c->geno_ms = ms;
+	*n_out = called;
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_geno_sites(bwb_hip_ctx *c, uint64_t first, uint64_t n, int err, int64_t min_depth, const bwb_geno_site **out, uint64_t *n_out) {
+	if (!c || !out || !n_out) return fail(BWB_E_ARG, "geno_sites: null argument");
+	if (!c->geno_on || !c->pile_on) return fail(BWB_E_STATE, "geno_sites: no scratch and output (bwb_hip_geno_begin)");
+	RC(geno_args(c, "geno_sites", first, n, err, min_depth, c->pile_sites, c->geno_piece));
+	*out = c->h_geno_sites.as<bwb_geno_site>(); *n_out = 0;
+	if (!n) return BWB_OK; /* (nothing launched: the figures of the last launch stay) */
+	HIPCHK(hipSetDevice(c->device));
+	const uint64_t n_words64 = (c->text_n + 31) / 32;
+	const uint32_t n_words = (uint32_t)n_words64, nn = (uint32_t)n;
+	uint32_t trips = 0;
+	while (((uint64_t)1 << trips) < n_words64) trips++;
+	const unsigned grid = (unsigned)std::min<size_t>(((size_t)nn + BWB_BLOCK - 1) / BWB_BLOCK, (size_t)c->num_cu * 8);
+	Timed t(c, c->rstream);
+	RC(t.begin());
+	hipLaunchKernelGGL(k_geno_count, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, c->d_text.as<uint4>(), c->d_site_base.as<uint32_t>(), n_words, trips, c->d_counts.as<uint4>(), first, nn,
+	                   (uint64_t)min_depth, c->d_geno_cnt.as<uint32_t>(), c->d_geno_word.as<uint32_t>());
+	RC(geno_scan(c, nn));
+	hipLaunchKernelGGL(k_geno_emit, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, c->d_text.as<uint4>(), c->d_site_base.as<uint32_t>(), n_words, c->d_counts.as<uint4>(), first, nn,
+	                   (uint64_t)min_depth, (uint32_t)err, c->d_geno_cnt.as<uint32_t>(), c->d_geno_word.as<uint32_t>(), c->d_geno_off.as<uint64_t>(), c->d_geno_sites.as<uint4>());
+	HIPCHK(hipGetLastError());
+	RC(t.end());
+	RC(geno_fetch(c, t, nn, c->d_geno_sites.p, c->h_geno_sites.p, sizeof(bwb_geno_site), n_out));
+	c->geno_sites_called = *n_out;
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_geno_bubbles(bwb_hip_ctx *c, uint64_t first, uint64_t n, int err, int64_t min_depth, const bwb_geno_bubble **out, uint64_t *n_out) {
+	if (!c || !out || !n_out) return fail(BWB_E_ARG, "geno_bubbles: null argument");
+	if (!c->geno_on) return fail(BWB_E_STATE, "geno_bubbles: no scratch and output (bwb_hip_geno_begin)");
+	if (!c->indel_on || !c->geno_bub) return fail(BWB_E_STATE, "geno_bubbles: no bubble table and counters before geno_begin (bwb_hip_indel_begin)");
+	RC(geno_args(c, "geno_bubbles", first, n, err, min_depth, c->loci_nbub, c->geno_piece_bub));
+	*out = c->h_geno_bubs.as<bwb_geno_bubble>(); *n_out = 0;
+	if (!n) return BWB_OK;
+	HIPCHK(hipSetDevice(c->device));
+	const uint32_t nn = (uint32_t)n;
+	const unsigned grid = (unsigned)std::min<size_t>(((size_t)nn + BWB_BLOCK - 1) / BWB_BLOCK, (size_t)c->num_cu * 8);
+	Timed t(c, c->rstream);
+	RC(t.begin());
+	hipLaunchKernelGGL(k_geno_bubbles, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, c->d_indel_elig.as<uint8_t>(), c->d_indel_counts.as<uint4>(), (uint32_t)first, nn, (uint64_t)min_depth,
+	                   (uint32_t)err, c->d_geno_cnt.as<uint32_t>(), (const uint64_t *)nullptr, (uint4 *)nullptr);
+	RC(geno_scan(c, nn));
+	hipLaunchKernelGGL(k_geno_bubbles, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, c->d_indel_elig.as<uint8_t>(), c->d_indel_counts.as<uint4>(), (uint32_t)first, nn, (uint64_t)min_depth,
+	                   (uint32_t)err, c->d_geno_cnt.as<uint32_t>(), (const uint64_t *)c->d_geno_off.as<uint64_t>(), c->d_geno_bubs.as<uint4>());
+	HIPCHK(hipGetLastError());
+	RC(t.end());
+	RC(geno_fetch(c, t, nn, c->d_geno_bubs.p, c->h_geno_bubs.p, sizeof(bwb_geno_bubble), n_out));
+	c->geno_bubs_called = *n_out;
+	return BWB_OK;
+}
+
+/* the entries the last geno_sites and the last geno_bubbles call called, and the HIP-event time of the kernels of whichever came last */
+extern "C" int bwb_hip_geno_stats(bwb_hip_ctx *c, uint64_t *sites_called, uint64_t *bubbles_called, double *kernel_ms) {
+	if (!c) return fail(BWB_E_ARG, "geno_stats: null context");
+	if (sites_called) *sites_called = c->geno_sites_called;
+	if (bubbles_called) *bubbles_called = c->geno_bubs_called;
+	if (kernel_ms) *kernel_ms = c->geno_ms;
 	return BWB_OK;
 }
 

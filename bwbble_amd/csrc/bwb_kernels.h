@@ -1240,3 +1240,136 @@ __global__ __launch_bounds__(BWB_BLOCK) void k_indel(const uint4 *places, const 
 		if (k) atomicAdd(stats + 2, k);
 	}
 }
+
+/* ---- genotype calls at IUPAC sites and indel bubbles (`map -G`) ---------------------------------------------------------------------------
+ * The rule is in include/bwbble_hip.h (bwb_hip_geno_begin); all of it is integer arithmetic.  geno_rule: the raw costs of the 3 (k == 2) or 6
+ * genotypes in VCF order from the allele counts n0, n1, n2 and the depth, the first smallest, GQ and the saturated PLs.  Every array index is a
+ * constant after unrolling: the costs live in registers, nothing in scratch. */
+#define GENO_HET 3u /* the cost of a base under a heterozygous genotype that carries it: 10 log10 2, rounded */
+#define GENO_MEMBERS 0x09D570B30AE60C00ull /* nibble c: the members of code c as columns, bit 0 A, 1 C, 2 G, 3 T (0: no site) */
+static_assert(((GENO_MEMBERS >> 8) & 15u) == 12u && ((GENO_MEMBERS >> 32) & 15u) == 3u && ((GENO_MEMBERS >> 56) & 15u) == 9u, "K is G, T; M is A, C; W is A, T");
+struct GenoCall { uint32_t gt, gq; uint32_t pl[6]; };
+__device__ __forceinline__ GenoCall geno_rule(uint64_t n0, uint64_t n1, uint64_t n2, uint32_t k, uint64_t depth, uint64_t err) {
+	uint64_t raw[6];
+	raw[0] = err * (depth - n0);
+	raw[1] = GENO_HET * (n0 + n1) + err * (depth - n0 - n1);
+	raw[2] = err * (depth - n1);
+	raw[3] = GENO_HET * (n0 + n2) + err * (depth - n0 - n2);
+	raw[4] = GENO_HET * (n1 + n2) + err * (depth - n1 - n2);
+	raw[5] = err * (depth - n2);
+	const uint32_t ng = k == 3u ? 6u : 3u;
+	uint32_t gt = 0;
+	uint64_t best = raw[0];
+#pragma unroll
+	for (uint32_t j = 1; j < 6; j++) { const bool lower = j < ng && raw[j] < best; gt = lower ? j : gt; best = lower ? raw[j] : best; }
+	uint64_t second = ~0ull;
+#pragma unroll
+	for (uint32_t j = 0; j < 6; j++) { const bool in = j < ng && j != gt && raw[j] - best < second; second = in ? raw[j] - best : second; }
+	GenoCall g;
+	g.gt = gt; g.gq = second > 99ull ? 99u : (uint32_t)second;
+#pragma unroll
+	for (uint32_t j = 0; j < 6; j++) { const uint64_t d = raw[j] - best; g.pl[j] = j < ng ? (d > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)d) : 0u; }
+	return g;
+}
+/* Site s (< n_sites, checked by the caller) -> its word: the last w with site_base[w] <= s, by `trips` halving steps for every lane (2^trips >=
+ * n_words, a kernel argument: selects, no divergent while; site_base[] does not descend and site_base[0] = 0).  The lanes of a wave hold 64
+ * consecutive sites, which lie in a handful of neighbouring words: all but the last few steps load the same address in every lane, one
+ * request each, and the top of the tree stays in L2 for the whole grid.  Every index is bounded: site_base[] below n_words. */
+__device__ __forceinline__ uint32_t geno_word(uint64_t s, const uint32_t *site_base, uint32_t n_words, uint32_t trips) {
+	uint32_t w = 0;
+	for (uint32_t t = trips; t-- > 0;) {
+		const uint32_t step = 1u << t;
+		bool go = false;
+		if (step < n_words - w) go = (uint64_t)site_base[w + step] <= s; /* (w < n_words throughout) */
+		w = go ? w + step : w;
+	}
+	return w;
+}
+/* the character of the r-th site of a word (r < 32: at most 31 bits cleared), or 32 when the word has no such site - impossible on the index
+ * built from this text, and then nothing is called - and the code there */
+__device__ __forceinline__ uint32_t geno_char(const uint4 tw, uint32_t r, uint32_t *code) {
+	uint32_t m = site_mask32(tw);
+	for (uint32_t i = 0; i < r && m; i++) m &= m - 1u;
+	const uint32_t at = m && r < 32u ? (uint32_t)__ffs((int)m) - 1u : 32u;
+	const uint32_t q = (at & 31u) >> 3, x = q == 0u ? tw.x : q == 1u ? tw.y : q == 2u ? tw.z : tw.w;
+	*code = (x >> (4u * (at & 7u))) & 15u;
+	return at;
+}
+/* k_geno_count: one lane per site of [first, first + n) (first + n <= n_sites, checked by the caller: counts[] below n_sites), grid-strided:
+ * cnt[i] = 1 when site first + i is called - depth, the sum of its four counters in one 16-byte load, >= min_depth - and its word kept in word[i]
+ * so that k_geno_emit does not bisect again.  The scan of k_place_alt (k_scan_blocks / k_scan_sums / k_scan_add) turns cnt[] into off[0 .. n],
+ * off[n] = the called sites. */
+__global__ __launch_bounds__(BWB_BLOCK) void k_geno_count(const uint4 *text, const uint32_t *site_base, uint32_t n_words, uint32_t trips, const uint4 *counts, uint64_t first, uint32_t n,
+                                                           uint64_t min_depth, uint32_t *cnt, uint32_t *word) {
+	const uint32_t gstride = gridDim.x * BWB_BLOCK;
+	for (uint32_t i = blockIdx.x * BWB_BLOCK + threadIdx.x; i < n; i += gstride) {
+		const uint64_t s = first + i;
+		const uint32_t w = geno_word(s, site_base, n_words, trips);
+		uint32_t code;
+		const uint64_t r = s - (uint64_t)site_base[w];
+		const uint32_t at = geno_char(text[w], r < 32u ? (uint32_t)r : 32u, &code);
+		const uint4 c = counts[s];
+		word[i] = w;
+		cnt[i] = at < 32u && (uint64_t)c.x + c.y + c.z + c.w >= min_depth ? 1u : 0u;
+	}
+}
+/* k_geno_emit: the same lanes; a called site makes its call and writes its 64-byte bwb_geno_site record at out[off[i]] (off[i] < off[n] <= n: the
+ * output holds n records) as four 16-byte vector stores back to back.  The called lanes of a wave write neighbouring records, so the wave's four
+ * stores fill the same run of whole 64-byte lines, which L2 combines: no transpose through LDS (1.05 M sites, 787 k records: 0.09 ms for the
+ * count pass, the scan and this kernel together). */
+__global__ __launch_bounds__(BWB_BLOCK) void k_geno_emit(const uint4 *text, const uint32_t *site_base, uint32_t n_words, const uint4 *counts, uint64_t first, uint32_t n, uint64_t min_depth,
+                                                          uint32_t err, const uint32_t *cnt, const uint32_t *word, const uint64_t *off, uint4 *out) {
+	const uint32_t gstride = gridDim.x * BWB_BLOCK;
+	for (uint32_t i = blockIdx.x * BWB_BLOCK + threadIdx.x; i < n; i += gstride) {
+		if (!cnt[i]) continue;
+		const uint64_t s = first + i, o = off[i];
+		const uint32_t w = word[i];
+		if (w >= n_words || o >= (uint64_t)n) continue; /* (k_geno_count wrote both: never) */
+		uint32_t code;
+		const uint64_t r = s - (uint64_t)site_base[w];
+		const uint32_t at = geno_char(text[w], r < 32u ? (uint32_t)r : 32u, &code) & 31u; /* (k_geno_count found it below 32) */
+		const uint32_t mem = (uint32_t)(GENO_MEMBERS >> (4u * code)) & 15u;
+		const uint4 c = counts[s];
+		const uint64_t depth = (uint64_t)c.x + c.y + c.z + c.w;
+		/* the members in column order: the counters of the set bits of mem, lowest first (two or three of them) */
+		uint64_t a[3] = { 0, 0, 0 };
+		uint32_t k = 0;
+#pragma unroll
+		for (uint32_t col = 0; col < 4; col++) {
+			const uint32_t v = col == 0u ? c.x : col == 1u ? c.y : col == 2u ? c.z : c.w;
+			const bool in = (mem >> col) & 1u;
+			a[0] = in && k == 0u ? v : a[0]; a[1] = in && k == 1u ? v : a[1]; a[2] = in && k == 2u ? v : a[2];
+			k += in ? 1u : 0u;
+		}
+		const GenoCall g = geno_rule(a[0], a[1], a[2], k, depth, err);
+		const uint64_t pos = (uint64_t)w * 32u + at;
+		uint4 *dst = out + o * 4u;
+		dst[0] = make_uint4((uint32_t)pos, (uint32_t)(pos >> 32), (uint32_t)s, (uint32_t)(s >> 32));
+		dst[1] = c;
+		dst[2] = make_uint4(code | (k == 3u ? 6u : 3u) << 8 | g.gt << 16 | g.gq << 24, 0u, g.pl[0], g.pl[1]);
+		dst[3] = make_uint4(g.pl[2], g.pl[3], g.pl[4], g.pl[5]);
+	}
+}
+/* k_geno_bubbles: one lane per bubble of [first, first + n) (first + n <= n_bub, checked by the caller), grid-strided.  off NULL, the count pass:
+ * cnt[i] = 1 when the bubble is eligible (elig[], one byte per bubble from bwb_hip_indel_begin) and depth = ref + alt + ref_gapped + alt_gapped >=
+ * min_depth; the same scan; then with off[] the emit pass: the call over R / V with other = the two gapped counters, and the 48-byte
+ * bwb_geno_bubble record at out[off[i]] (off[i] < n) as three 16-byte vector stores. */
+__global__ __launch_bounds__(BWB_BLOCK) void k_geno_bubbles(const uint8_t *elig, const uint4 *counts, uint32_t first, uint32_t n, uint64_t min_depth, uint32_t err, uint32_t *cnt,
+                                                             const uint64_t *off, uint4 *out) {
+	const uint32_t gstride = gridDim.x * BWB_BLOCK;
+	for (uint32_t i = blockIdx.x * BWB_BLOCK + threadIdx.x; i < n; i += gstride) {
+		const uint32_t b = first + i;
+		const uint4 c = counts[b];
+		const uint64_t depth = (uint64_t)c.x + c.y + c.z + c.w;
+		const bool called = elig[b] && depth >= min_depth;
+		if (!off) { cnt[i] = called ? 1u : 0u; continue; }
+		if (!called) continue;
+		const uint64_t o = off[i];
+		if (o >= (uint64_t)n) continue; /* (the scan of the same predicate: never) */
+		const GenoCall g = geno_rule(c.x, c.y, 0ull, 2u, depth, err);
+		uint4 *dst = out + o * 3u;
+		dst[0] = make_uint4(b, c.x, c.y, c.z);
+		dst[1] = make_uint4(c.w, g.gt | g.gq << 8, g.pl[0], g.pl[1]);
+		dst[2] = make_uint4(g.pl[2], 0u, 0u, 0u);
+	}
+}

@@ -54,6 +54,7 @@ typedef struct {
 	pile_t *pile;             /* -A (NULL: no counts): the allele counts at the text's IUPAC sites; on the GPU unless pile_on_host */
 	int pile_on_host;         /* -A with the host's lift or join records (-R / -J on an .ann that is not ascending and disjoint): the host's rule */
 	indel_t *indel;           /* -I (NULL: no table): the read support per indel bubble; needs bub and chrom_of; on the GPU when gpu_loci, else the host's rule */
+	geno_t *geno;             /* -G (NULL: no calls): the genotype calls from both tables - pile is there then, and with bub indel; each half on the GPU where its counters are */
 } map_t;
 
 typedef struct {
@@ -63,6 +64,7 @@ typedef struct {
 	chunk_t *unclaimed;            /* the first chunk no worker has taken yet */
 	size_t n_parsed, n_written, max_ahead;
 	int reader_done;
+	int n_workers, n_finished;     /* map -G: the workers, and those whose counters have all been summed on the host; the one that completes the count calls the genotypes */
 	uint64_t n_reads;
 	/* reader */
 	const char *readsFname;
@@ -319,6 +321,16 @@ static uint64_t count_piece(void) {
 	return v < 1 ? 1 : (uint64_t)v;
 }
 
+/* -G: the entries per geno_sites / geno_bubbles call - count_piece(), at most the library's 2^24 and no more than the larger table has */
+static uint32_t geno_piece(const map_t *m) {
+	uint64_t most = m->pile->n_sites;
+	if (m->indel && m->gpu_loci && (uint64_t)m->bub->n > most) most = (uint64_t)m->bub->n;
+	uint64_t p = count_piece();
+	if (p > most) p = most;
+	if (p > ((uint64_t)1 << 24)) p = (uint64_t)1 << 24;
+	return p < 1 ? 1u : (uint32_t)p;
+}
+
 /* One host thread per GPU.  Chunks are streamed through the slots of the context: while the search slice of chunk j runs,
  * chunk j+1 is already uploaded and queued behind it and the hits of chunk j-1 are on their way back; a slice parks its
  * unfinished reads for the next one instead of draining (include/bwbble_hip.h), so the GPU never runs a batch's tail alone. */
@@ -382,6 +394,9 @@ static void *gpu_worker(void *arg) {
 			w->pile_begin_s = wall() - t0;
 			if (n_sites != pp->map->pile->n_sites) bwb_die("map_reads: GPU %d counts %llu IUPAC sites in the text, the host's scan of the .ref %llu", w->device, (unsigned long long)n_sites, (unsigned long long)pp->map->pile->n_sites);
 		}
+		/* -G: the scratch and the pinned output of one piece of calls (92 bytes per site of the piece, 48 more per bubble), in every context - which worker
+		 * finishes last is not known yet -, before the pool is sized as well */
+		if (pp->map->geno && pile_gpu && bwb_hip_geno_begin(ctx, geno_piece(pp->map))) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
 	}
 	void (*const hand_over)(worker_t *, bwb_hip_ctx *, int, chunk_t *) = pp->map ? retire_map : retire;
 	enum { NS = BWB_MAX_SLOTS }; /* chunks in flight: the heaviest reads of a chunk take several slices' time (they are parked and resumed), and
@@ -458,6 +473,49 @@ static void *gpu_worker(void *arg) {
 		w->indel_fetch_s = wall() - t0;
 		if (dbg) fprintf(stderr, "[bwb host] worker %d: the counters of %llu bubbles read back in %llu pieces\n", w->gpu, (unsigned long long)n_bub, (unsigned long long)turns);
 	}
+	/* -G: this worker's counters are in the host's sums.  The worker that completes the count calls the genotypes on its own context: with several
+	 * workers it first puts the host's summed tables back over its counters, with one its counters are the sums already and nothing is uploaded.  Then
+	 * the sites and the bubbles are walked in pieces; what comes back is the called entries' records alone, which geno.c keeps for the writer. */
+	if (pp->map && pp->map->geno) {
+		const map_t *m = pp->map;
+		geno_t *G = m->geno;
+		pthread_mutex_lock(&pp->mu);
+		const int last = ++pp->n_finished == pp->n_workers;
+		pthread_mutex_unlock(&pp->mu);
+		const int sites_gpu = !m->pile_on_host, bubs_gpu = sites_gpu && m->indel && m->gpu_loci;
+		if (last && sites_gpu) {
+			const uint64_t PIECE = count_piece(), GP = geno_piece(m), n_sites = m->pile->n_sites, n_bub = bubs_gpu ? (uint64_t)m->bub->n : 0;
+			double t0 = wall();
+			if (pp->n_workers > 1) {
+				for (uint64_t s0 = 0; s0 < n_sites; s0 += PIECE, G->put_pieces++)
+					if (bwb_hip_pile_put(ctx, s0, n_sites - s0 < PIECE ? n_sites - s0 : PIECE, m->pile->counts + s0 * 4)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
+				for (uint64_t s0 = 0; s0 < n_bub; s0 += PIECE, G->put_pieces++)
+					if (bwb_hip_indel_put(ctx, s0, n_bub - s0 < PIECE ? n_bub - s0 : PIECE, m->indel->counts + s0 * 4)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
+			}
+			G->put_s = wall() - t0;
+			t0 = wall();
+			double ms = 0;
+			for (uint64_t s0 = 0; s0 < n_sites; s0 += GP, G->pieces++) {
+				const bwb_geno_site *recs = NULL; uint64_t k = 0;
+				if (bwb_hip_geno_sites(ctx, s0, n_sites - s0 < GP ? n_sites - s0 : GP, G->err, G->min_depth, &recs, &k)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
+				bwb_hip_geno_stats(ctx, NULL, NULL, &ms);
+				G->kernel_ms += ms;
+				geno_take_sites(G, recs, k);
+			}
+			const uint64_t GB = GP < n_bub ? GP : n_bub;
+			for (uint64_t s0 = 0; s0 < n_bub; s0 += GB, G->pieces++) {
+				const bwb_geno_bubble *recs = NULL; uint64_t k = 0;
+				if (bwb_hip_geno_bubbles(ctx, s0, n_bub - s0 < GB ? n_bub - s0 : GB, G->err, G->min_depth, &recs, &k)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
+				bwb_hip_geno_stats(ctx, NULL, NULL, &ms);
+				G->kernel_ms += ms;
+				geno_take_bubbles(G, recs, k);
+			}
+			G->call_s = wall() - t0;
+			G->worker = w->gpu;
+			if (dbg) fprintf(stderr, "[bwb host] worker %d: genotypes called by this worker, the last of %d: %llu pieces of tables put back in %.3f s, %llu pieces called in %.3f s: sites %llu  bubbles %llu  kernels %.3f ms\n",
+			                 w->gpu, pp->n_workers, (unsigned long long)G->put_pieces, G->put_s, (unsigned long long)G->pieces, G->call_s, (unsigned long long)G->n_sites, (unsigned long long)G->n_bubs, G->kernel_ms);
+		}
+	}
 	bwb_stats st;
 	if (bwb_hip_flush(ctx) || bwb_hip_get_stats(ctx, &st)) bwb_die("align_reads_inexact_gpu: GPU %d: %s", w->device, bwb_hip_last_error());
 	w->total = st;
@@ -505,6 +563,7 @@ static int run_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, 
 	pthread_mutex_init(&pp.mu, NULL);
 	pthread_cond_init(&pp.cv_work, NULL); pthread_cond_init(&pp.cv_done, NULL); pthread_cond_init(&pp.cv_space, NULL);
 	pp.readsFname = readsFname; pp.params = params; pp.map = map;
+	pp.n_workers = n_gpus;
 	pp.chunk_reads = GPU_CHUNK_DEFAULT;
 	if (getenv("BWB_CHUNK")) pp.chunk_reads = (uint32_t)strtoul(getenv("BWB_CHUNK"), NULL, 10);
 	if (pp.chunk_reads < 1) pp.chunk_reads = 1;
@@ -615,6 +674,11 @@ static int run_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, 
 			else printf("read support per indel bubble on the host (the .ann records are not ascending and disjoint): anchor %d  eligible bubbles %llu  refused and skipped %llu  reads counted %llu  adds %llu  candidates %llu\n",
 			            map->indel->anchor, (unsigned long long)map->indel->n_tab, (unsigned long long)map->indel->n_refused, (unsigned long long)map->indel->reads, (unsigned long long)map->indel->adds, (unsigned long long)map->indel->cands);
 		}
+		if (map->geno && !map->pile_on_host) /* -G */
+			printf("genotype calls on the GPU (worker %d): error phred %d  minimum depth %lld  sites called %llu%s  bubbles called %llu  kernels %.3f ms  pieces %llu  bytes to the host %llu  tables put back in %llu pieces, %.3f s  called in %.3f s\n",
+			       map->geno->worker, map->geno->err, (long long)map->geno->min_depth, (unsigned long long)map->geno->n_sites, map->indel && !map->gpu_loci ? " (the bubbles follow on the host)" : "",
+			       (unsigned long long)map->geno->n_bubs, map->geno->kernel_ms, (unsigned long long)map->geno->pieces,
+			       (unsigned long long)(map->geno->n_sites * sizeof(bwb_geno_site) + map->geno->n_bubs * sizeof(bwb_geno_bubble) + map->geno->pieces * 8), (unsigned long long)map->geno->put_pieces, map->geno->put_s, map->geno->call_s);
 		if (map->max_alt) {
 			double ams = 0; unsigned long long ast = 0, ait = 0;
 			for (int g = 0; g < n_gpus; g++) { ast += ws[g].alt_steps; ait += ws[g].alt_items; if (ws[g].alt_ms > ams) ams = ws[g].alt_ms; }
@@ -673,16 +737,17 @@ int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_
 }
 
 /* `bwbble map`: align_reads + alns2sam in one pass.  The .bwt is loaded once, with its SA; the SAM header is written before the first chunk. */
-int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor, int n_gpus) {
+int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor, const char *genoFname, int geno_err, int64_t geno_depth, int n_gpus) {
 	printf("**** BWBBLE Read Mapping (align + aln2sam in one pass) ****\n");
 	/* -A: the counts file is opened before anything is loaded; until it is written, a run that stops leaves none behind */
-	pile_t *pile = countsFname ? pile_open(countsFname, min_mapq) : NULL;
-	indel_t *indel = indelFname ? indel_open(indelFname, min_mapq, anchor) : NULL; /* -I (main.c: only with -B): the same */
+	pile_t *pile = countsFname || genoFname ? pile_open(countsFname, min_mapq) : NULL; /* (-G: the table without a file) */
+	indel_t *indel = indelFname || (genoFname && bubbleFname) ? indel_open(indelFname, min_mapq, anchor) : NULL; /* -I (main.c: only with -B): the same; -G with -B: the table without a file */
+	geno_t *geno = genoFname ? geno_open(genoFname, geno_err, geno_depth) : NULL; /* -G: the same */
 	/* -B: the table first (a refused table stops the run before anything is created) */
 	bubble_table_t *bub = bubbleFname ? load_bubbles(bubbleFname) : NULL;
 	if (lift && bub) lift_check_table(bub); /* -R (main.c: only with -B): a bubble the rule refuses is named here */
 	/* -D: a missing <seq_fasta>.ref, or one of another size than the .ann says, stops the run here; the .bwt loader reads its forward half, behind the sampled SA */
-	md_text_t *text = md || pile ? md_text_open_for(fastaFname, 1, md ? "-D" : "-A") : NULL; /* (-A loads it the same way, with or without -D) */
+	md_text_t *text = md || pile ? md_text_open_for(fastaFname, 1, md ? "-D" : countsFname ? "-A" : "-G") : NULL; /* (-A loads it the same way, with or without -D) */
 	/* before anything is created: without a GPU no SAM file is left behind */
 	if (bwb_hip_device_count() < 1) bwb_die("align_reads_inexact_gpu: no HIP device found (this build has no CPU alignment path)");
 	size_t L = strlen(fastaFname) + 8;
@@ -696,7 +761,7 @@ int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *
 	int32_t *bubble_of = bub ? ann_bubble_of(ann, bub) : NULL;
 	/* -J (main.c: only with -X and -B): the chromosome's record of every bubble; one without a chromosome leaves no SAM file behind either */
 	join = join && bub && max_alt; lift = lift && bub;
-	int32_t *chrom_of = join || lift || indel ? bubble_chrom_of(ann, bubble_of, bub, join ? "-J" : lift ? "-R" : "-I") : NULL;
+	int32_t *chrom_of = join || lift || indel ? bubble_chrom_of(ann, bubble_of, bub, join ? "-J" : lift ? "-R" : indelFname ? "-I" : "-G") : NULL;
 	if (indel) indel_set_table(indel, bub, chrom_of); /* -I: the eligible bubbles, sorted; a refused bubble is skipped, not named */
 	uint64_t *rec_start = NULL, *rec_end = NULL;
 	int gpu_loci = bub && ann->num_seq > 0 && sam_ann_sorted(ann) && bub->n <= INT32_MAX;
@@ -715,24 +780,34 @@ int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *
 	sam_write_header(sam, ann);
 	const map_t m = { .max_mm = max_mm, .max_alt = max_alt, .ann = ann, .ann_sorted = sam_ann_sorted(ann),
 	                  .bub = bub, .bubble_of = bubble_of, .gpu_loci = gpu_loci, .rec_start = rec_start, .rec_end = rec_end, .chrom_of = chrom_of, .join = join, .lift = lift, .text = text,
-	                  .md = md, .pile = pile, .pile_on_host = pile && bub && !gpu_loci && (lift || join), .indel = indel };
+	                  .md = md, .pile = pile, .pile_on_host = pile && bub && !gpu_loci && (lift || join), .indel = indel, .geno = geno };
 
 	t = wall();
 	printf("BWBBLE Inexact Alignment (MI355X)...\n");
 	run_stream(BWT, readsFname, params, sam, samFname, n_gpus, &m);
-	if (pile) { /* -A: the SAM file is complete (run_stream has closed it) */
+	if (pile && pile->f) { /* -A: the SAM file is complete (run_stream has closed it) */
 		const double tw = wall();
 		const unsigned long long lines = pile_write(pile, ann);
 		printf("allele counts written: %llu sites with a count in %.3f s\n", lines, wall() - tw);
 	}
-	if (indel) { /* -I: likewise */
+	if (indel && indel->f) { /* -I: likewise */
 		const double tw = wall();
 		const unsigned long long lines = indel_write(indel);
 		printf("read support per indel bubble written: %llu bubbles with a count in %.3f s\n", lines, wall() - tw);
 	}
+	if (geno) { /* -G: last; what was counted on the host is called there, by the same rule */
+		const double tw = wall();
+		if (m.pile_on_host || (indel && !gpu_loci)) {
+			const unsigned long long s0 = geno->n_sites, b0 = geno->n_bubs;
+			geno_host(geno, m.pile_on_host ? pile : NULL, indel && !gpu_loci ? indel : NULL);
+			printf("genotype calls on the host (the .ann records are not ascending and disjoint): sites called %llu  bubbles called %llu\n", (unsigned long long)geno->n_sites - s0, (unsigned long long)geno->n_bubs - b0);
+		}
+		const unsigned long long lines = geno_write(geno, ann, bub);
+		printf("genotype calls written: %llu lines in %.3f s\n", lines, wall() - tw);
+	}
 	printf("Total read mapping time (index and read loading overlapped): %.2f sec\n", wall() - t);
 	free_bwt(BWT); free_ann(ann);
 	free(bwtFname); free(annFname);
-	free(bubble_of); free(chrom_of); free(rec_start); free(rec_end); free_bubbles(bub); pile_free(pile); indel_free(indel); md_text_free(text);
+	free(bubble_of); free(chrom_of); free(rec_start); free(rec_end); free_bubbles(bub); pile_free(pile); indel_free(indel); geno_free(geno); md_text_free(text);
 	return 0;
 }

@@ -122,14 +122,14 @@ int aln_path_bytes(const bwb_aln *a, unsigned char *path /* >= 272 bytes */); /*
 void set_default_aln_params(aln_params_t *params);                     /* align.c:22-38 */
 int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_t *params, int n_gpus); /* align.c:40-87 */
 int align_reads_inexact_gpu_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, char *alnFname, int n_gpus); /* the GPU's align_reads_inexact_parallel (inexact_match.h:40) over a streamed FASTQ */
-int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor, int n_gpus); /* `bwbble map` (countsFname: -A, NULL: no counts; min_mapq: -a; indelFname: -I, NULL: no table; anchor: -w): align + aln2sam in one pass, the hits evaluated on the GPU */
+int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor, const char *genoFname, int geno_err, int64_t geno_depth, int n_gpus); /* `bwbble map` (countsFname: -A, NULL: no counts; min_mapq: -a; indelFname: -I, NULL: no table; anchor: -w; genoFname: -G, NULL: no calls; geno_err: -q; geno_depth: -d): align + aln2sam in one pass, the hits evaluated on the GPU */
 
 /* precalc.c */
 void precalc_sa_intervals(bwt_t *BWT, const aln_params_t *params, const char *preFname); /* align.c:200-224: writes <fasta>.pre */
 int check_precalc_file(const char *preFname); /* the walk of load_precalc_sa_intervals (align.c:226-238) over an existing table: 0 = complete */
 
 /* sam.c */
-void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor); /* align.c:494-556; max_alt: -X (0: no tags); bubbleFname: -B (NULL: no tags); join: -J; lift: -R; md: -D; countsFname: -A (NULL: no counts), min_mapq: -a; indelFname: -I (NULL: no table), anchor: -w */
+void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor, const char *genoFname, int geno_err, int64_t geno_depth); /* align.c:494-556; genoFname / geno_err / geno_depth: -G / -q / -d; max_alt: -X (0: no tags); bubbleFname: -B (NULL: no tags); join: -J; lift: -R; md: -D; countsFname: -A (NULL: no counts), min_mapq: -a; indelFname: -I (NULL: no table), anchor: -w */
 /* the two halves of alns2sam: eval_aln of one read on the host, and the text of a block of reads from placement records (which `map` gets
  * from the GPU instead, bwb_hip_slot_place) */
 #define SAM_BLOCK_READS ((size_t)1 << 14)                              /* reads formatted by one thread at a time */
@@ -154,7 +154,7 @@ uint64_t alt_placements(const bwb_aln *e, uint64_t ne);               /* the row
 void sam_write_header(FILE *sam, const fasta_annotations_t *ann);
 int sam_ann_sorted(const fasta_annotations_t *ann);
 char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_annotations_t *ann, int ann_sorted, size_t *out_len);
-void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor); /* developer command: records from a file (countsFname / min_mapq: -A / -a; indelFname / anchor: -I / -w; (altsFname: NULL or the items; bubbleFname: NULL or -B's table; join: -J, the items file then ends with one suboptimal byte per item; lift: -R; md: -D) */
+void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor, const char *genoFname, int geno_err, int64_t geno_depth); /* developer command: records from a file (genoFname / geno_err / geno_depth: -G / -q / -d; countsFname / min_mapq: -A / -a; indelFname / anchor: -I / -w; (altsFname: NULL or the items; bubbleFname: NULL or -B's table; join: -J, the items file then ends with one suboptimal byte per item; lift: -R; md: -D) */
 
 /* pad.c: bubble hits in reference coordinates (the reference's mg-ref/sam_pad.cpp) */
 typedef struct bubble_table {                                          /* bubble.data (mg-ref/comb.cpp:245-253): the k-th pair of lines is bubble k */
@@ -238,6 +238,21 @@ uint64_t indel_host(indel_t *p, const bwb_place *pl, const bwb_locus *loci, size
 void indel_add(indel_t *p, uint64_t first, uint64_t n, const uint32_t *counts); /* adds a context's counters of n bubbles from `first` (bwb_hip_indel_counts) */
 uint64_t indel_write(indel_t *p);                                     /* the header line and one line per bubble with a counter that is not zero; closes the file; returns the lines */
 void indel_free(indel_t *p);
+
+/* geno.c: -G, genotype calls at the IUPAC sites and the indel bubbles (include/bwbble_hip.h: bwb_hip_geno_begin) */
+typedef struct geno {
+	char *fname; FILE *f; int err; int64_t min_depth;                  /* the calls file, open since before anything was loaded (NULL: none, records in memory only); -q; -d */
+	bwb_geno_site *sites; uint64_t n_sites, cap_sites;                /* the called sites' records, in site order */
+	bwb_geno_bubble *bubs; uint64_t n_bubs, cap_bubs;                 /* the called bubbles' records, in bubble order */
+	int worker; uint64_t pieces, put_pieces; double kernel_ms, put_s, call_s; /* map: the worker that called, its geno_sites / geno_bubbles calls, its pile_put / indel_put calls, the kernels' time summed, the seconds of both */
+} geno_t;
+geno_t *geno_open(const char *genoFname, int err, int64_t min_depth); /* a path that cannot be written stops the run; until geno_write has finished, a run that exits leaves no file */
+void geno_rule(const uint32_t *n, unsigned k, uint64_t depth, unsigned err, uint8_t *gt, uint8_t *gq, uint32_t *pl /* 6 */); /* the rule from the k = 2 or 3 alleles' counts and the depth */
+void geno_take_sites(geno_t *g, const bwb_geno_site *recs, uint64_t n); /* keeps a piece's records for the writer (bwb_hip_geno_sites) */
+void geno_take_bubbles(geno_t *g, const bwb_geno_bubble *recs, uint64_t n); /* (bwb_hip_geno_bubbles) */
+void geno_host(geno_t *g, const pile_t *pile, const indel_t *indel);  /* the geno kernels on the host: the same records from the host's tables (either may be NULL) */
+uint64_t geno_write(geno_t *g, const fasta_annotations_t *ann, const bubble_table_t *bub); /* the header line, the called sites, the called bubbles (bub NULL: none); closes the file; returns the lines */
+void geno_free(geno_t *g);
 void sam_pad(const char *dataFname, const char *inFname, const char *outFname); /* `bwbble sampad`: sam_pad.cpp:47-94 over SAM text */
 
 /* The OpenMP teams of the host stages of `align` / `aln2sam` (base encoding, .aln serialisation, SAM text) have at most 32 threads unless

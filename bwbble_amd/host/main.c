@@ -1,7 +1,7 @@
 /* main.c - `bwbble` command line, same commands and flags as the reference (mg-aligner/main.c:38-160),
  * plus -g <n_gpus> on align / aln2sam, `map` = align + aln2sam in one pass, and `sampad` = mg-ref/sam_pad (-B on map / aln2sam: the same
- * tags without a second pass; -J, -R, -D, -A and -I, the project's own: placements counted by locus, written in chromosome coordinates, the tags
- * NM:i / MD:Z against the text, the allele counts at the text's IUPAC sites, and the read support per indel bubble). */
+ * tags without a second pass; -J, -R, -D, -A, -I and -G, the project's own: placements counted by locus, written in chromosome coordinates, the tags
+ * NM:i / MD:Z against the text, the allele counts at the text's IUPAC sites, the read support per indel bubble, and the genotype calls from both). */
 #define _GNU_SOURCE
 #include <getopt.h>
 #include <time.h>
@@ -32,7 +32,7 @@ static int align_usage(void) {
 }
 
 static int map_usage(void) {
-	printf("Usage: bwbble map [align options] [-Q <int>] [-X <int>] [-B <bubble.data>] [-J] [-R] [-D] [-A <counts.tsv> [-a <int>]] [-I <indels.tsv> [-w <int>]] [-g <gpus>] <seq_fasta> <reads_fastq> <out_sam> \n");
+	printf("Usage: bwbble map [align options] [-Q <int>] [-X <int>] [-B <bubble.data>] [-J] [-R] [-D] [-A <counts.tsv> [-a <int>]] [-I <indels.tsv> [-w <int>]] [-G <calls.tsv> [-q <int>] [-d <int>]] [-g <gpus>] <seq_fasta> <reads_fastq> <out_sam> \n");
 	printf("         writes the SAM file that `bwbble align [align options]` followed by `bwbble aln2sam [-n <Q>] [-X <N>]` writes, without the .aln file\n");
 	printf("Options: the options of align, and\n");
 	printf("         Q    the mismatch count at which a unique hit gets MAPQ 25 (aln2sam's -n; default: 6)\n");
@@ -43,19 +43,22 @@ static int map_usage(void) {
 	printf("         D    mapped reads get the tags NM:i:<n> MD:Z:<text> directly behind QUAL, computed on the GPU against the text of <seq_fasta>.ref (`bwbble fasta2ref <seq_fasta>` writes it): a read base that is a member of the text's IUPAC code is a match, a mismatch or deleted position prints the text's letter; with -R a lifted line is described by its chromosome CIGAR; XA items keep their NM (default: no tags)\n");
 	printf("         A    writes the allele counts at the IUPAC sites of the text of <seq_fasta>.ref, summed on the GPU over every mapped read: a line `record<TAB>pos<TAB>code<TAB>A<TAB>C<TAB>G<TAB>T` per site that a read base covers under an M of its CIGAR; with -R reads on bubble records count on the chromosome, with -J the joined MAPQ is the one -a sees; the SAM file is the one written without -A (default: no counts)\n");
 	printf("         I    with -B: writes the read support per indel bubble, summed on the GPU over every mapped read: a line `bubble<TAB>chrom<TAB>pos<TAB>ref_len<TAB>alt_len<TAB>ref<TAB>alt<TAB>ref_gapped<TAB>alt_gapped` per bubble with a count - reads on the bubble's record that cover the alternate allele and w bases of either flank with M count as alt, reads on the chromosome that cover the site the same way as ref, with an I or D inside as gapped; with -J the joined MAPQ is the one -a sees; the SAM file is the one written without -I (default: no table)\n");
-	printf("         w    with -I: the anchor, the flank bases a read must cover on either side, 1..255 (default: 1)\n");
-	printf("         a    with -A or -I: only reads with MAPQ >= a count, 0..255 (default: 0)\n\n");
+	printf("         G    writes the genotype calls, made on the GPU from the counters of -A and - with -B - of -I, whether or not those files are asked for: after the line `#kind<TAB>record<TAB>pos<TAB>id<TAB>alleles<TAB>AD<TAB>other<TAB>GT<TAB>GQ<TAB>PL` one line S per IUPAC site and one line I per eligible indel bubble with a depth of at least d - the alleles (a site's code members, a bubble's R,V), their read counts, the other bases or gapped reads, the genotype, its quality 0..99 and the phred-scaled likelihoods in VCF order; the SAM, -A and -I files are those written without -G (default: no calls)\n");
+	printf("         q    with -G: the error phred, the cost of a base a genotype does not carry, 4..93 (default: 20)\n");
+	printf("         d    with -G: the minimum depth of a call, 1..2147483647 (default: 1)\n");
+	printf("         w    with -I or -G: the anchor, the flank bases a read must cover on either side, 1..255 (default: 1)\n");
+	printf("         a    with -A, -I or -G: only reads with MAPQ >= a count, 0..255 (default: 0)\n\n");
 	return 1;
 }
 static int aln2sam_usage(void) {
-	printf("Usage: bwbble aln2sam [-S, -n, -g, -X, -B, -J, -R, -D, -A, -a, -I, -w] <seq_fasta> <reads_fastq> <alns_aln> <out_sam> \n");
+	printf("Usage: bwbble aln2sam [-S, -n, -g, -X, -B, -J, -R, -D, -A, -a, -I, -w, -G, -q, -d] <seq_fasta> <reads_fastq> <alns_aln> <out_sam> \n");
 	printf("Options: n    the mismatch count at which a unique hit gets MAPQ 25 (default: 6)\n         g    number of GPUs for the SA lookups (default: 1)\n");
 	printf("         X    1..255: the tags X0:i / X1:i / XA:Z: of `bwbble map -X` (default: no tags)\n");
 	printf("         B    the bubble table (bubble.data): the tags bC:Z: / bP:Z: of `bwbble map -B` (default: no tags)\n");
 	printf("         J    with -X and -B: MAPQ and the tag bJ:i: of `bwbble map -J` (default: every placement counts)\n");
 	printf("         R    with -B: RNAME, POS and CIGAR in chromosome coordinates and the tag bO:Z: of `bwbble map -R` (default: bubble coordinates)\n");
 	printf("         D    the tags NM:i: / MD:Z: of `bwbble map -D`, against the text of <seq_fasta>.ref (default: no tags)\n");
-	printf("         A    <counts.tsv>: the allele counts of `bwbble map -A`, from the host's rule (default: no counts)\n         I    <indels.tsv>, with -B: the read support per indel bubble of `bwbble map -I`, from the host's rule (default: no table)\n         w    with -I: the anchor, 1..255 (default: 1)\n         a    with -A or -I: the least MAPQ that counts, 0..255 (default: 0)\n\n");
+	printf("         A    <counts.tsv>: the allele counts of `bwbble map -A`, from the host's rule (default: no counts)\n         I    <indels.tsv>, with -B: the read support per indel bubble of `bwbble map -I`, from the host's rule (default: no table)\n         G    <calls.tsv>: the genotype calls of `bwbble map -G`, from the host's rule (default: no calls)\n         q    with -G: the error phred, 4..93 (default: 20)\n         d    with -G: the minimum depth, 1..2147483647 (default: 1)\n         w    with -I or -G: the anchor, 1..255 (default: 1)\n         a    with -A, -I or -G: the least MAPQ that counts, 0..255 (default: 0)\n\n");
 	return 1;
 }
 /* -a's argument: 0..255, anything else is refused; and -a without -A */
@@ -65,9 +68,9 @@ static int mapq_option(const char *arg) {
 	if (end == arg || *end || v < 0 || v > 255) { printf("Error: -a takes a MAPQ of 0..255, not %s\n", arg); exit(1); }
 	return (int)v;
 }
-static void pile_option_check(const char *countsFname, const char *indelFname, int min_mapq) {
-	if (countsFname || indelFname || min_mapq < 0) return;
-	printf("Error: -a needs -A <counts.tsv> or -I <indels.tsv>\n");
+static void pile_option_check(const char *countsFname, const char *indelFname, const char *genoFname, int min_mapq) {
+	if (countsFname || indelFname || genoFname || min_mapq < 0) return;
+	printf("Error: -a needs -A <counts.tsv>, -I <indels.tsv> or -G <calls.tsv>\n");
 	exit(1);
 }
 /* -w's argument: 1..255, anything else is refused; -I without -B; and -w without -I */
@@ -77,9 +80,27 @@ static int anchor_option(const char *arg) {
 	if (end == arg || *end || v < 1 || v > 255) { printf("Error: -w takes an anchor of 1..255, not %s\n", arg); exit(1); }
 	return (int)v;
 }
-static void indel_option_check(const char *indelFname, int anchor, const char *bubbleFname) {
+static void indel_option_check(const char *indelFname, int anchor, const char *bubbleFname, const char *genoFname) {
 	if (indelFname && !bubbleFname) { printf("Error: -I needs -B <bubble.data>\n"); exit(1); }
-	if (!indelFname && anchor > 0) { printf("Error: -w needs -I <indels.tsv>\n"); exit(1); }
+	if (!indelFname && !genoFname && anchor > 0) { printf("Error: -w needs -I <indels.tsv> or -G <calls.tsv>\n"); exit(1); }
+}
+/* -q's argument: 4..93; -d's: 1..2^31 - 1; anything else is refused; and either without -G (0: not given) */
+static int err_option(const char *arg) {
+	char *end;
+	const long v = strtol(arg, &end, 10);
+	if (end == arg || *end || v < 4 || v > 93) { printf("Error: -q takes an error phred of 4..93, not %s\n", arg); exit(1); }
+	return (int)v;
+}
+static int64_t depth_option(const char *arg) {
+	char *end;
+	const long long v = strtoll(arg, &end, 10);
+	if (end == arg || *end || v < 1 || v > 2147483647ll) { printf("Error: -d takes a minimum depth of 1..2147483647, not %s\n", arg); exit(1); }
+	return (int64_t)v;
+}
+static void geno_option_check(const char *genoFname, int geno_err, int64_t geno_depth) {
+	if (genoFname) return;
+	if (geno_err) { printf("Error: -q needs -G <calls.tsv>\n"); exit(1); }
+	if (geno_depth) { printf("Error: -d needs -G <calls.tsv>\n"); exit(1); }
 }
 /* -X's argument: 1..255, anything else is refused */
 static int alt_option(const char *arg) {
@@ -150,9 +171,10 @@ int main(int argc, char *argv[]) {
 		aln_params_t params;
 		set_default_aln_params(&params);
 		int c, n_gpus = 1, max_mm = 6, max_alt = 0, join = 0, lift = 0, md = 0; /* (aln2sam's default, mg-aligner/main.c:142) */
-		const char *bubbleFname = NULL, *countsFname = NULL, *indelFname = NULL;
-		int min_mapq = -1, anchor = 0; /* (-1: no -a; 0: no -w) */
-		while ((c = getopt(argc - 1, argv + 1, "M:O:E:n:k:o:e:l:m:t:g:SPQ:X:B:JRDA:a:I:w:")) >= 0) {
+		const char *bubbleFname = NULL, *countsFname = NULL, *indelFname = NULL, *genoFname = NULL;
+		int min_mapq = -1, anchor = 0, geno_err = 0; /* (-1: no -a; 0: no -w, no -q) */
+		int64_t geno_depth = 0; /* (0: no -d) */
+		while ((c = getopt(argc - 1, argv + 1, "M:O:E:n:k:o:e:l:m:t:g:SPQ:X:B:JRDA:a:I:w:G:q:d:")) >= 0) {
 			if (align_option(c, &params, &n_gpus)) continue;
 			if (c == 'Q') { max_mm = atoi(optarg); continue; }
 			if (c == 'X') { max_alt = alt_option(optarg); continue; }
@@ -164,15 +186,20 @@ int main(int argc, char *argv[]) {
 			if (c == 'a') { min_mapq = mapq_option(optarg); continue; }
 			if (c == 'I') { indelFname = optarg; continue; }
 			if (c == 'w') { anchor = anchor_option(optarg); continue; }
+			if (c == 'G') { genoFname = optarg; continue; }
+			if (c == 'q') { geno_err = err_option(optarg); continue; }
+			if (c == 'd') { geno_depth = depth_option(optarg); continue; }
 			if (c == '?') { map_usage(); return 1; }
 			return 1;
 		}
 		if (argc - 1 - optind < 3) { map_usage(); exit(1); }
 		join_option_check(join, max_alt, bubbleFname);
 		lift_option_check(lift, bubbleFname);
-		pile_option_check(countsFname, indelFname, min_mapq);
-		indel_option_check(indelFname, anchor, bubbleFname);
-		map_reads(argv[optind + 1], argv[optind + 2], argv[optind + 3], &params, max_mm, max_alt, bubbleFname, join, lift, md, countsFname, min_mapq < 0 ? 0 : min_mapq, indelFname, anchor ? anchor : 1, n_gpus);
+		pile_option_check(countsFname, indelFname, genoFname, min_mapq);
+		indel_option_check(indelFname, anchor, bubbleFname, genoFname);
+		geno_option_check(genoFname, geno_err, geno_depth);
+		map_reads(argv[optind + 1], argv[optind + 2], argv[optind + 3], &params, max_mm, max_alt, bubbleFname, join, lift, md, countsFname, min_mapq < 0 ? 0 : min_mapq, indelFname, anchor ? anchor : 1,
+		          genoFname, geno_err ? geno_err : 20, geno_depth ? geno_depth : 1, n_gpus);
 	} else if (strcmp(argv[1], "places2sam") == 0) {
 		/* developer command (CPU only, used by the tests): placement records (bwb_place, include/bwbble_hip.h) from a file -> SAM text */
 		/* (a sixth argument: u64 alt_off[n + 1] followed by the bwb_alt records - the X tags of `map -X`) */
@@ -182,8 +209,9 @@ int main(int argc, char *argv[]) {
 		 * counts of `map -A`, from the host's rule) */
 		char **a = argv + 2;
 		int na = argc - 2, join = 0, lift = 0, md = 0;
-		const char *bubbleFname = NULL, *countsFname = NULL, *indelFname = NULL;
-		int min_mapq = -1, anchor = 0;
+		const char *bubbleFname = NULL, *countsFname = NULL, *indelFname = NULL, *genoFname = NULL;
+		int min_mapq = -1, anchor = 0, geno_err = 0;
+		int64_t geno_depth = 0;
 		if (na >= 2 && strcmp(a[0], "-B") == 0) { bubbleFname = a[1]; a += 2; na -= 2; }
 		if (na >= 1 && strcmp(a[0], "-J") == 0) { join = 1; a++; na--; }
 		if (na >= 1 && strcmp(a[0], "-R") == 0) { lift = 1; a++; na--; }
@@ -192,12 +220,17 @@ int main(int argc, char *argv[]) {
 		if (na >= 2 && strcmp(a[0], "-a") == 0) { min_mapq = mapq_option(a[1]); a += 2; na -= 2; }
 		if (na >= 2 && strcmp(a[0], "-I") == 0) { indelFname = a[1]; a += 2; na -= 2; }
 		if (na >= 2 && strcmp(a[0], "-w") == 0) { anchor = anchor_option(a[1]); a += 2; na -= 2; }
-		if (na < 4) { printf("Usage: bwbble places2sam [-B <bubble.data>] [-J] [-R] [-D] [-A <counts.tsv>] [-a <MAPQ>] [-I <indels.tsv>] [-w <anchor>] <seq_fasta> <reads_fastq> <places_bin> <out_sam> [<alts_bin>] \n"); exit(1); }
+		if (na >= 2 && strcmp(a[0], "-G") == 0) { genoFname = a[1]; a += 2; na -= 2; }
+		if (na >= 2 && strcmp(a[0], "-q") == 0) { geno_err = err_option(a[1]); a += 2; na -= 2; }
+		if (na >= 2 && strcmp(a[0], "-d") == 0) { geno_depth = depth_option(a[1]); a += 2; na -= 2; }
+		if (na < 4) { printf("Usage: bwbble places2sam [-B <bubble.data>] [-J] [-R] [-D] [-A <counts.tsv>] [-a <MAPQ>] [-I <indels.tsv>] [-w <anchor>] [-G <calls.tsv>] [-q <err>] [-d <depth>] <seq_fasta> <reads_fastq> <places_bin> <out_sam> [<alts_bin>] \n"); exit(1); }
 		join_option_check(join, na >= 5, bubbleFname);
 		lift_option_check(lift, bubbleFname);
-		pile_option_check(countsFname, indelFname, min_mapq);
-		indel_option_check(indelFname, anchor, bubbleFname);
-		places2sam(a[0], a[1], a[2], a[3], na >= 5 ? a[4] : NULL, bubbleFname, join, lift, md, countsFname, min_mapq < 0 ? 0 : min_mapq, indelFname, anchor ? anchor : 1);
+		pile_option_check(countsFname, indelFname, genoFname, min_mapq);
+		indel_option_check(indelFname, anchor, bubbleFname, genoFname);
+		geno_option_check(genoFname, geno_err, geno_depth);
+		places2sam(a[0], a[1], a[2], a[3], na >= 5 ? a[4] : NULL, bubbleFname, join, lift, md, countsFname, min_mapq < 0 ? 0 : min_mapq, indelFname, anchor ? anchor : 1, genoFname, geno_err ? geno_err : 20,
+		           geno_depth ? geno_depth : 1);
 	} else if (strcmp(argv[1], "sampad") == 0) {
 		if (argc < 5) { printf("Usage: bwbble sampad <bubble.data> <in_sam> <out_sam> \n"); exit(1); }
 		sam_pad(argv[2], argv[3], argv[4]);
@@ -214,9 +247,10 @@ int main(int argc, char *argv[]) {
 	} else if (strcmp(argv[1], "aln2sam") == 0) {
 		if (argc < 6) { aln2sam_usage(); exit(1); }
 		int is_multiref = 1, max_diff = 6, n_gpus = 1, max_alt = 0, join = 0, lift = 0, md = 0, c;
-		const char *bubbleFname = NULL, *countsFname = NULL, *indelFname = NULL;
-		int min_mapq = -1, anchor = 0;
-		while ((c = getopt(argc - 1, argv + 1, "n:g:SX:B:JRDA:a:I:w:")) >= 0) {
+		const char *bubbleFname = NULL, *countsFname = NULL, *indelFname = NULL, *genoFname = NULL;
+		int min_mapq = -1, anchor = 0, geno_err = 0;
+		int64_t geno_depth = 0;
+		while ((c = getopt(argc - 1, argv + 1, "n:g:SX:B:JRDA:a:I:w:G:q:d:")) >= 0) {
 			switch (c) {
 			case 'X': max_alt = alt_option(optarg); break;
 			case 'B': bubbleFname = optarg; break;
@@ -227,6 +261,9 @@ int main(int argc, char *argv[]) {
 			case 'a': min_mapq = mapq_option(optarg); break;
 			case 'I': indelFname = optarg; break;
 			case 'w': anchor = anchor_option(optarg); break;
+			case 'G': genoFname = optarg; break;
+			case 'q': geno_err = err_option(optarg); break;
+			case 'd': geno_depth = depth_option(optarg); break;
 			case 'S': is_multiref = 0; break;
 			case 'n': max_diff = atoi(optarg); break;
 			case 'g': n_gpus = atoi(optarg); break;
@@ -237,9 +274,11 @@ int main(int argc, char *argv[]) {
 		if (argc - 1 - optind < 4) { aln2sam_usage(); exit(1); }
 		join_option_check(join, max_alt, bubbleFname);
 		lift_option_check(lift, bubbleFname);
-		pile_option_check(countsFname, indelFname, min_mapq);
-		indel_option_check(indelFname, anchor, bubbleFname);
-		alns2sam(argv[optind + 1], argv[optind + 2], argv[optind + 3], argv[optind + 4], is_multiref, max_diff, n_gpus, max_alt, bubbleFname, join, lift, md, countsFname, min_mapq < 0 ? 0 : min_mapq, indelFname, anchor ? anchor : 1);
+		pile_option_check(countsFname, indelFname, genoFname, min_mapq);
+		indel_option_check(indelFname, anchor, bubbleFname, genoFname);
+		geno_option_check(genoFname, geno_err, geno_depth);
+		alns2sam(argv[optind + 1], argv[optind + 2], argv[optind + 3], argv[optind + 4], is_multiref, max_diff, n_gpus, max_alt, bubbleFname, join, lift, md, countsFname, min_mapq < 0 ? 0 : min_mapq, indelFname, anchor ? anchor : 1,
+		         genoFname, geno_err ? geno_err : 20, geno_depth ? geno_depth : 1);
 	} else if (strcmp(argv[1], "dumpreads") == 0) {
 		/* developer command (CPU only, used by the tests): what fastq2reads made of a FASTQ - per read "name<TAB>codes<TAB>quality" */
 		if (argc < 4) { printf("Usage: bwbble dumpreads <reads_fastq> <out_tsv> [chunk_reads [text]] \n"); exit(1); }

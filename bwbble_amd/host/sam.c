@@ -244,12 +244,13 @@ static bwb_join *host_joins(const bwb_place *pl, const bwb_locus *loci, const ui
 	return joins;
 }
 
-void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor) {
+void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor, const char *genoFname, int geno_err, int64_t geno_depth) {
 	(void)is_multiref;
 	printf("**** BWBBLE Alignment Evaluation/SAM File Generation ****\n");
-	pile_t *pile = countsFname ? pile_open(countsFname, min_mapq) : NULL; /* -A (a path that cannot be written stops the run before anything is loaded) */
-	indel_t *indel = indelFname ? indel_open(indelFname, min_mapq, anchor) : NULL; /* -I (main.c: only with -B; the same) */
-	md_text_t *text = md || pile ? md_text_open_for(fastaFname, 0, md ? "-D" : "-A") : NULL; /* -D (a missing .ref, or one of another size than the .ann says, stops the run before anything is loaded or created) */
+	pile_t *pile = countsFname || genoFname ? pile_open(countsFname, min_mapq) : NULL; /* -A (a path that cannot be written stops the run before anything is loaded); -G: the table without a file */
+	indel_t *indel = indelFname || (genoFname && bubbleFname) ? indel_open(indelFname, min_mapq, anchor) : NULL; /* -I (main.c: only with -B; the same); -G with -B: the table without a file */
+	geno_t *geno = genoFname ? geno_open(genoFname, geno_err, geno_depth) : NULL; /* -G (the same) */
+	md_text_t *text = md || pile ? md_text_open_for(fastaFname, 0, md ? "-D" : countsFname ? "-A" : "-G") : NULL; /* -D (a missing .ref, or one of another size than the .ann says, stops the run before anything is loaded or created) */
 	size_t Ln = strlen(fastaFname) + 8;
 	char *bwtFname = (char *)malloc(Ln), *annFname = (char *)malloc(Ln);
 	snprintf(bwtFname, Ln, "%s.bwt", fastaFname);
@@ -259,7 +260,7 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 	bubble_table_t *bub = bubbleFname ? load_bubbles(bubbleFname) : NULL; /* (refused tables stop the run before the SAM file exists) */
 	int32_t *bubble_of = bub ? ann_bubble_of(ann, bub) : NULL;
 	if (lift) lift_check_table(bub); /* -R (main.c: only with -B) */
-	int32_t *chrom_of = join || lift || indel ? bubble_chrom_of(ann, bubble_of, bub, join ? "-J" : lift ? "-R" : "-I") : NULL; /* -J (main.c: only with -X and -B), -R */
+	int32_t *chrom_of = join || lift || indel ? bubble_chrom_of(ann, bubble_of, bub, join ? "-J" : lift ? "-R" : indelFname ? "-I" : "-G") : NULL; /* -J (main.c: only with -X and -B), -R */
 	alns_batch_t *alns = alnsf2alns_bin(alnsFname);
 	reads_t *reads = fastq2reads(readsFname);
 	FILE *sam = fopen(samFname, "w");
@@ -371,27 +372,37 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 	if (pile) { /* -A: the host's rule on the same records, written when the SAM file is complete */
 		pile_set_text(pile, text, 1);
 		pile_host(pile, pl, n, reads->seq, reads->stride, reads->len, ls ? ls->kind : NULL, ls ? ls->off : NULL, ls ? ls->recs : NULL, joins, ann);
+	}
+	if (pile && pile->f) {
 		const unsigned long long lines = pile_write(pile, ann);
 		printf("allele counts at the text's IUPAC sites on the host: sites %llu  reads counted %llu  adds %llu  sites written %llu\n", (unsigned long long)pile->n_sites, (unsigned long long)pile->reads, (unsigned long long)pile->adds, lines);
 	}
 	if (indel) { /* -I: the host's rule on the same records (the printed CIGAR, with or without -R), written when the SAM file is complete */
 		indel_set_table(indel, bub, chrom_of);
 		indel_host(indel, pl, loci, n, reads->len, joins);
+	}
+	if (indel && indel->f) {
 		const unsigned long long lines = indel_write(indel);
 		printf("read support per indel bubble on the host: anchor %d  eligible bubbles %llu  refused and skipped %llu  reads counted %llu  adds %llu  candidates %llu  lines written %llu\n", indel->anchor,
 		       (unsigned long long)indel->n_tab, (unsigned long long)indel->n_refused, (unsigned long long)indel->reads, (unsigned long long)indel->adds, (unsigned long long)indel->cands, lines);
 	}
+	if (geno) { /* -G: the calls from the two tables, written last */
+		geno_host(geno, pile, indel);
+		const unsigned long long sites = geno->n_sites, bubs = geno->n_bubs, lines = geno_write(geno, ann, bub);
+		printf("genotype calls on the host: error phred %d  minimum depth %lld  sites called %llu  bubbles called %llu  lines written %llu\n", geno->err, (long long)geno->min_depth, sites, bubs, lines);
+	}
 	free(pl); free(alt_off); free(alts); free(loci); free(bubble_of); free_bubbles(bub);
-	free(alt_sub); free(joins); free(chrom_of); lift_free(ls); md_free(ms); pile_free(pile); indel_free(indel); md_text_free(text);
+	free(alt_sub); free(joins); free(chrom_of); lift_free(ls); md_free(ms); pile_free(pile); indel_free(indel); geno_free(geno); md_text_free(text);
 	free_bwt(BWT); free_reads(reads); free_alns_batch(alns); free_ann(ann);
 }
 
 /* developer command (CPU only, for the tests): raw bwb_place records from a file through sam_format_reads - the formatter `map` uses, on a
  * machine without a GPU (bubbleFname: -B, the loci from the host resolver; join: -J, the join records from the host's rule; lift: -R, the
  * lift records from the host's rule; md: -D, NM and MD from the host's rule) */
-void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor) {
-	pile_t *pile = countsFname ? pile_open(countsFname, min_mapq) : NULL; /* -A */
-	indel_t *indel = indelFname ? indel_open(indelFname, min_mapq, anchor) : NULL; /* -I (main.c: only with -B) */
+void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor, const char *genoFname, int geno_err, int64_t geno_depth) {
+	pile_t *pile = countsFname || genoFname ? pile_open(countsFname, min_mapq) : NULL; /* -A; -G: the table without a file */
+	indel_t *indel = indelFname || (genoFname && bubbleFname) ? indel_open(indelFname, min_mapq, anchor) : NULL; /* -I (main.c: only with -B); -G with -B: the table without a file */
+	geno_t *geno = genoFname ? geno_open(genoFname, geno_err, geno_depth) : NULL; /* -G */
 	size_t Ln = strlen(fastaFname) + 8;
 	char *annFname = (char *)malloc(Ln);
 	snprintf(annFname, Ln, "%s.ann", fastaFname);
@@ -399,8 +410,8 @@ void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *sam
 	bubble_table_t *bub = bubbleFname ? load_bubbles(bubbleFname) : NULL;
 	int32_t *bubble_of = bub ? ann_bubble_of(ann, bub) : NULL;
 	if (lift) lift_check_table(bub); /* -R (main.c: only with -B) */
-	int32_t *chrom_of = join || lift || indel ? bubble_chrom_of(ann, bubble_of, bub, join ? "-J" : lift ? "-R" : "-I") : NULL; /* -J (main.c: only with -B and an items file), -R */
-	md_text_t *text = md || pile ? md_text_open_for(fastaFname, 0, md ? "-D" : "-A") : NULL; /* -D, -A */
+	int32_t *chrom_of = join || lift || indel ? bubble_chrom_of(ann, bubble_of, bub, join ? "-J" : lift ? "-R" : indelFname ? "-I" : "-G") : NULL; /* -J (main.c: only with -B and an items file), -R */
+	md_text_t *text = md || pile ? md_text_open_for(fastaFname, 0, md ? "-D" : countsFname ? "-A" : "-G") : NULL; /* -D, -A, -G */
 	reads_t *reads = fastq2reads(readsFname);
 	FILE *pf = fopen(placesFname, "rb");
 	if (!pf) { perror(placesFname); bwb_die("places2sam: Cannot open the placements file: %s!", placesFname); }
@@ -450,17 +461,26 @@ void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *sam
 	if (pile) { /* -A: the host's rule, written when the SAM file is complete */
 		pile_set_text(pile, text, 1);
 		pile_host(pile, pl, n, reads->seq, reads->stride, reads->len, ls ? ls->kind : NULL, ls ? ls->off : NULL, ls ? ls->recs : NULL, joins, ann);
+	}
+	if (pile && pile->f) {
 		const unsigned long long lines = pile_write(pile, ann);
 		printf("allele counts at the text's IUPAC sites on the host: sites %llu  reads counted %llu  adds %llu  sites written %llu\n", (unsigned long long)pile->n_sites, (unsigned long long)pile->reads, (unsigned long long)pile->adds, lines);
 	}
 	if (indel) { /* -I: the host's rule on the same records (the printed CIGAR, with or without -R), written when the SAM file is complete */
 		indel_set_table(indel, bub, chrom_of);
 		indel_host(indel, pl, loci, n, reads->len, joins);
+	}
+	if (indel && indel->f) {
 		const unsigned long long lines = indel_write(indel);
 		printf("read support per indel bubble on the host: anchor %d  eligible bubbles %llu  refused and skipped %llu  reads counted %llu  adds %llu  candidates %llu  lines written %llu\n", indel->anchor,
 		       (unsigned long long)indel->n_tab, (unsigned long long)indel->n_refused, (unsigned long long)indel->reads, (unsigned long long)indel->adds, (unsigned long long)indel->cands, lines);
 	}
+	if (geno) { /* -G: the calls from the two tables, written last */
+		geno_host(geno, pile, indel);
+		const unsigned long long sites = geno->n_sites, bubs = geno->n_bubs, lines = geno_write(geno, ann, bub);
+		printf("genotype calls on the host: error phred %d  minimum depth %lld  sites called %llu  bubbles called %llu  lines written %llu\n", geno->err, (long long)geno->min_depth, sites, bubs, lines);
+	}
 	free(pl); free(annFname); free(alt_off); free(alts); free(loci); free(bubble_of); free_bubbles(bub);
-	free(alt_sub); free(joins); free(chrom_of); lift_free(ls); md_free(ms); pile_free(pile); indel_free(indel); md_text_free(text);
+	free(alt_sub); free(joins); free(chrom_of); lift_free(ls); md_free(ms); pile_free(pile); indel_free(indel); geno_free(geno); md_text_free(text);
 	free_reads(reads); free_ann(ann);
 }

@@ -539,6 +539,65 @@ int bwb_hip_indel_reset(bwb_hip_ctx *ctx);
  * table entries with lo within its M span, a bubble read's own eligible window) and the kernel's HIP-event time (any pointer may be NULL) */
 int bwb_hip_indel_stats(bwb_hip_ctx *ctx, uint64_t *reads, uint64_t *adds, uint64_t *candidates, double *kernel_ms);
 
+/* Genotype calls at IUPAC sites and indel bubbles (`bwbble map -G <calls.tsv>`): the last link behind the pile and indel counters - a genotype,
+ * a quality and phred-scaled likelihoods for every known SNP site and indel bubble the reads cover.  No stock tool can make the call afterwards:
+ * the text holds IUPAC codes and no reference base, the alt-supporting reads of an indel lie on bubble records, and the MAPQ that decides is -J's.
+ * The rule - stated here once; the kernels, host/geno.c and tests/geno_model.py implement it and agree bit for bit.  Integer arithmetic only.
+ *   parameters  E, the error phred, 4..93 (-q, default 20); d, the minimum depth, 1..2^31 - 1 (-d, default 1); H = 3, the cost of a base under a
+ *               heterozygous genotype that carries it (10 log10 2, rounded).
+ *   site        one of the pile family's sites, in the same numbering.  Its alleles are the members of the text's code in the column order A, C,
+ *               G, T: a0 < a1 (< a2), k = 2 or 3.  n_i = the pile counter of a_i's column; depth = the sum of all four columns, in 64 bits (the
+ *               counters are uint32 and wrap, as they do); other = depth - sum n_i.  The site is CALLED when depth >= d.
+ *   genotypes   in VCF order, j = (0,0), (0,1), (1,1), (0,2), (1,2), (2,2); a two-member code has the first three.
+ *                 raw(x,x) = E (depth - n_x)          raw(x,y) = H (n_x + n_y) + E (depth - n_x - n_y)          in uint64
+ *               GT = the first j with the smallest raw; GQ = min(99, the smallest raw over j != GT, minus raw_GT); PL_j = min(raw_j - raw_GT,
+ *               2^32 - 1).  A site whose bases are all non-members is still called: a0/a0 with GQ 0 - the table shows it, as the pile shows such
+ *               bases.
+ *   bubble      only the bubbles ELIGIBLE at indel_begin's anchor.  The alleles are R (the chromosome's) and V (the record's): n_R = ref, n_V =
+ *               alt, the clean counts; other = ref_gapped + alt_gapped, depth = n_R + n_V + other, both in 64 bits.  Called when depth >= d, by
+ *               the same formulas over R/R, R/V, V/V.  Bubbles that share a site are called each on its own, biallelic, with the shared ref count,
+ *               exactly as the indel family counts them.
+ * Which reads count is entirely the pile and indel families' rule; nothing here walks a read.  Not here: base qualities, priors, multi-allelic
+ * indel sites, XA items, left-alignment, and VCF itself - the text has no reference allele to put in REF.
+ * Kernels: k_geno_count (one lane per site of a range: the inverse of the site index - the site's word by bisection over the one uint32 per word,
+ * its character as the r-th set bit of the word's site mask - and the four counters in one 16-byte load), the scan of the alt family, k_geno_emit
+ * (the call, and the called sites' records compacted in site order); k_geno_bubbles, count and emit pass, for a range of bubbles.  On the result
+ * stream.  (Added without a version change: no structure or existing entry point changed.) */
+typedef struct {
+	uint64_t pos;           /* 0-based position in the forward text */
+	uint64_t site;          /* the site's number */
+	uint32_t n[4];          /* the counters: A, C, G, T */
+	uint8_t code, n_geno;   /* the text's code there; 3 or 6 genotypes */
+	uint8_t gt, gq;         /* GT as the index j in VCF order; GQ 0..99 */
+	uint32_t reserved;      /* 0 */
+	uint32_t pl[6];         /* PL per genotype, unused entries 0 */
+} bwb_geno_site;            /* 64 bytes */
+typedef struct {
+	uint32_t bubble;        /* the bubble's number */
+	uint32_t n[4];          /* the counters: ref, alt, ref_gapped, alt_gapped */
+	uint8_t gt, gq;         /* 0 R/R, 1 R/V, 2 V/V; GQ 0..99 */
+	uint16_t reserved;      /* 0 */
+	uint32_t pl[3];
+	uint32_t pad[3];        /* 0 */
+} bwb_geno_bubble;          /* 48 bytes */
+/* After pile_begin (BWB_E_STATE without) and, where bubbles are to be called, after indel_begin; before the first slot_upload sizes the pool:
+ * allocates the scratch and the pinned output for `piece` sites (1..2^24, else BWB_E_ARG) and, when indel_begin has run, for min(piece, n_bub)
+ * bubbles.  A later pile_begin, set_text or indel_begin forgets what was sized for the tables they replace. */
+int bwb_hip_geno_begin(bwb_hip_ctx *ctx, uint32_t piece);
+/* The mirrors of pile_counts / indel_counts, with their argument checks: overwrite the 4 n counters from `first` with the caller's.  `map` needs
+ * them when several workers' counters must meet on one device, the tests to inject crafted counts. */
+int bwb_hip_pile_put(bwb_hip_ctx *ctx, uint64_t first, uint64_t n, const uint32_t *counts);
+int bwb_hip_indel_put(bwb_hip_ctx *ctx, uint64_t first, uint64_t n, const uint32_t *counts);
+/* Calls the sites (the bubbles) first .. first + n - 1, n <= piece (for bubbles min(piece, n_bub)): *out = the *n_out called entries' records in
+ * ascending order, in pinned memory of the context's that stays valid until the next call of the same function.  BWB_E_ARG for err outside 4..93,
+ * min_depth outside 1..2^31 - 1, a range that leaves the table or exceeds the piece.  BWB_E_STATE without geno_begin, and for bubbles without
+ * an indel_begin before it. */
+int bwb_hip_geno_sites(bwb_hip_ctx *ctx, uint64_t first, uint64_t n, int err, int64_t min_depth, const bwb_geno_site **out, uint64_t *n_out);
+int bwb_hip_geno_bubbles(bwb_hip_ctx *ctx, uint64_t first, uint64_t n, int err, int64_t min_depth, const bwb_geno_bubble **out, uint64_t *n_out);
+/* the entries the last geno_sites and the last geno_bubbles call that launched have called, and the HIP-event time of the kernels of whichever
+ * of the two launched last (any pointer may be NULL) */
+int bwb_hip_geno_stats(bwb_hip_ctx *ctx, uint64_t *sites_called, uint64_t *bubbles_called, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
