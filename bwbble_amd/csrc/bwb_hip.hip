@@ -121,6 +121,24 @@ struct ScratchClass {
 	bool ready = false;
 };
 
+/* Which records a slot's result-stream stages hold: the arguments each was launched with last (-1: none).  A stage re-launches when its key differs;
+ * what else it reads is invalidated here, by name, and nowhere else:
+ *   place        key max_mm                                reads the hit log and the SA
+ *   alt          key max_alt                               reads the hit log and the SA
+ *   locus        key max_mm                                reads place and the tables of set_loci
+ *   join         key max_mm, max_alt                       reads place, alt, locus, the hit log and the table of set_bubble_chrom
+ *   lift         key max_mm, max_alt                       reads place, locus, alt (max_alt > 0), the tables of set_loci and set_bubble_chrom
+ *   md           key max_mm, lifted, max_alt when lifted   reads the slot's reads, place, lift (lifted) and the text
+ *   pile, indel  once per submission */
+struct StageCache {
+	int place_mm = -1, alt_max = -1, locus_mm = -1, join_mm = -1, join_alt = -1, lift_mm = -1, lift_alt = -1, md_mm = -1, md_alt = -1, md_lifted = -1;
+	bool piled = false, indeled = false;
+	void reset() { *this = StageCache(); }                                /* new reads or a new hit log: slot_upload, submit */
+	void loci_replaced() { locus_mm = join_mm = lift_mm = md_mm = -1; }   /* set_loci (md reads lift) */
+	void chrom_replaced() { join_mm = lift_mm = md_mm = -1; }             /* set_bubble_chrom */
+	void text_replaced() { md_mm = -1; }                                  /* set_text */
+};
+
 /* one resident batch */
 struct Slot {
 	bool uploaded = false, submitted = false, complete = false, fetched = false;
@@ -133,21 +151,14 @@ struct Slot {
 	PinMem h_reads, h_lens, h_cnt, h_off, h_log, h_ctl;
 	DevMem d_place;               /* bwb_hip_slot_place: one bwb_place per read */
 	PinMem h_place;
-	int placed_mm = -1;           /* h_place holds the records for this max_mm (-1: none) */
 	AltBufs alt;                  /* bwb_hip_slot_place_alt: the items of the slot's reads */
-	int placed_alt = -1;          /* alt holds the items for this max_alt (-1: none) */
 	DevMem d_locus;               /* bwb_hip_slot_locus: one bwb_locus per read */
 	PinMem h_locus;
-	int locus_mm = -1;            /* h_locus holds the records of the placement records for this max_mm (-1: none) */
 	DevMem d_cls, d_join;         /* bwb_hip_slot_join: one class byte per item, one bwb_join per read */
 	PinMem h_join;
-	int join_mm = -1, join_alt = -1; /* h_join holds the records for this max_mm and max_alt (-1: none) */
 	LiftBufs lift;                /* bwb_hip_slot_lift */
-	int lift_mm = -1, lift_alt = -1; /* lift holds the records for this max_mm and max_alt (-1: none) */
 	MdBufs md;                    /* bwb_hip_slot_md */
-	int md_mm = -1, md_alt = -1, md_lifted = -1; /* md holds the records for this max_mm, and with lifted for this max_alt (-1: none) */
-	bool piled = false;           /* bwb_hip_slot_pile has counted this submission (cleared at the next upload) */
-	bool indeled = false;         /* bwb_hip_slot_indel has counted this submission (cleared at the next upload) */
+	StageCache stage;             /* which arguments the records above were made for */
 	std::vector<uint8_t> h_status;
 	std::vector<uint64_t> h_aln_off;
 	std::vector<bwb_aln> h_alns;
@@ -259,6 +270,13 @@ template <typename F> static auto with_pos(const bwb_hip_ctx *c, F &&f) { return
 template <typename F> static auto with_flag(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 /* grid of a kernel that works in octets of lanes, one item per octet (k_rank16, k_locate, k_place, k_place_alt) */
 static unsigned oct_grid(const bwb_hip_ctx *c, size_t n) { return (unsigned)std::min<size_t>((n + BWB_OCTS_PER_BLOCK - 1) / BWB_OCTS_PER_BLOCK, (size_t)c->num_cu * 8); }
+
+/* blocks that give every one of n items a lane; and the grid of a kernel whose lanes stride over the items, eight blocks per CU at the most (the
+ * kernels behind k_place: a lane's walk is a chain of dependent loads, and the waves beside it are what hides their latency) */
+static unsigned blocks_of(size_t n) { return (unsigned)((n + BWB_BLOCK - 1) / BWB_BLOCK); }
+static unsigned lane_grid(const bwb_hip_ctx *c, size_t n) { return (unsigned)std::min<size_t>(blocks_of(n), (size_t)c->num_cu * 8); }
+/* the steps of a bisection over n entries: ceil(log2(n)), 0 for n <= 1 */
+static uint32_t ceil_log2(uint64_t n) { uint32_t t = 0; while (((uint64_t)1 << t) < n) t++; return t; }
 
 extern "C" const char *bwb_hip_last_error(void) { return g_err.c_str(); }
 static_assert(sizeof(bwb_aln) == 16 * ALN_U4, "bwb_aln is ALN_U4 16-byte words (bwb_lane.h)");
@@ -794,7 +812,8 @@ extern "C" int bwb_hip_slot_upload(bwb_hip_ctx *c, int si, const bwb_params *p, 
 	/* (pageable source: the runtime stages it before returning, so h_descs may change again right away) */
 	HIPCHK(hipMemcpyAsync(c->d_descs.as<SlotDesc>() + si, &d, sizeof(SlotDesc), hipMemcpyHostToDevice, c->cstream));
 	HIPCHK(hipEventRecord(s.ev_up.e, c->cstream));
-	s.uploaded = true; s.submitted = false; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.join_mm = -1; s.lift_mm = -1; s.md_mm = -1; s.piled = false; s.indeled = false;
+	s.uploaded = true; s.submitted = false; s.complete = false; s.fetched = false;
+	s.stage.reset();
 	return ensure_class(c, 0);
 }
 
@@ -1042,7 +1061,8 @@ static int submit(bwb_hip_ctx *c, int si, bool suspend) {
 		HIPCHK(hipStreamWaitEvent(c->stream, s.ev_calcd.e, 0));
 	}
 	HIPCHK(hipMemsetAsync(s.d_ctl.p, 0, 256, c->stream));
-	s.submitted = true; s.complete = false; s.fetched = false; s.placed_mm = -1; s.placed_alt = -1; s.locus_mm = -1; s.join_mm = -1; s.lift_mm = -1; s.md_mm = -1; s.piled = false; s.indeled = false; s.launch = 0;
+	s.submitted = true; s.complete = false; s.fetched = false; s.launch = 0;
+	s.stage.reset();
 	if (s.n_reads == 0) { s.complete = true; s.launch = c->n_launches; return BWB_OK; }
 	HIPCHK(hipMemsetAsync(s.d_n.p, 0, (size_t)s.n_reads * 4, c->stream));
 	if (!ahead) {
@@ -1540,6 +1560,36 @@ static int ensure_qtab(bwb_hip_ctx *c) { /* mapq's table (k_place, k_join_reads)
 	HIPCHK(hipStreamSynchronize(c->rstream));
 	return BWB_OK;
 }
+/* an array of the caller's (pageable memory) into a fresh allocation, on the result stream: the caller synchronises once, after its last one */
+static int stage_in(bwb_hip_ctx *c, DevMem &d, const void *src, size_t bytes) {
+	HIPCHK(d.alloc(bytes));
+	if (bytes) HIPCHK(hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, c->rstream));
+	return BWB_OK;
+}
+/* the exclusive scan of cnt[0 .. n) into off[0 .. n], the total last, on the result stream; bsum holds blocks_of(n) block sums */
+static void scan_offsets(bwb_hip_ctx *c, const uint32_t *d_cnt, uint32_t n, uint64_t *d_off, uint64_t *d_bsum) {
+	const unsigned nblk = blocks_of(n);
+	hipLaunchKernelGGL(k_scan_blocks, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, d_cnt, n, d_off, d_bsum);
+	hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(BWB_BLOCK), 0, c->rstream, d_bsum, (uint32_t)nblk, d_off + n);
+	hipLaunchKernelGGL(k_scan_add, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, d_off, n, d_bsum);
+}
+/* off[0 .. n] of a caller's records: starts at 0, ascends, and - max_per_read below NO_LIMIT - no read owns more */
+static const uint64_t NO_LIMIT = ~0ull;
+static int check_offsets(const char *who, const char *what, const uint64_t *off, uint32_t n, uint64_t max_per_read) {
+	if (off[0] != 0) return fail(BWB_E_ARG, std::string(who) + ": " + what + "[0] must be 0");
+	for (uint32_t r = 0; r < n; r++) {
+		if (off[r + 1] >= off[r] && off[r + 1] - off[r] <= max_per_read) continue;
+		if (max_per_read == NO_LIMIT) return fail(BWB_E_ARG, std::string(who) + ": " + what + " does not ascend at read " + std::to_string(r));
+		return fail(BWB_E_ARG, std::string(who) + ": read " + std::to_string(r) + " does not own 0.." + std::to_string(max_per_read) + " items");
+	}
+	return BWB_OK;
+}
+/* what every bwb_hip_batch_* stage call asks before it forwards to slot 0 */
+static int batch_ready(bwb_hip_ctx *c, const char *who) {
+	if (!c->d_SA.p) return fail(BWB_E_STATE, std::string(who) + ": sampled SA not uploaded (bwb_hip_set_sa)");
+	if (!c->slots[0].submitted || !c->slots[0].complete) return fail(BWB_E_STATE, std::string(who) + ": batch_run has not completed");
+	return BWB_OK;
+}
 /* k_place over n reads whose hits are log[off[r] .. off[r] + cnt[r]) (all device memory, log_n hits in the log) -> n records in d_out, copied to
  * h_out; sets the context's place_ms / place_steps.  On the result stream.  Shared by slot_place (the slot's hit log) and place_hits (a hit
  * list of the caller's): the same kernel, the same launch. */
@@ -1578,26 +1628,34 @@ static int slot_log_n(bwb_hip_ctx *c, Slot &s, uint64_t *log_n) {
 	return BWB_OK;
 }
 
-extern "C" int bwb_hip_slot_place(bwb_hip_ctx *c, int si, int max_mm, const bwb_place **out, uint32_t *n_reads) {
-	if (!c || !out || !n_reads || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_place: bad argument");
+/* The chain behind the bwb_hip_slot_* calls.  ensure_X leaves stage X's records for these arguments in the slot, in device memory and in the pinned
+ * buffers, and calls ensure_* on the stages X reads; it refuses, under the name slot_X, what bwb_hip_slot_X refuses.  A stage whose key matches
+ * (StageCache) launches nothing and leaves the *_stats figures where the last launch put them; a slot of 0 reads always takes the launch path, which
+ * reserves the buffers and returns.  Every chain begins with ensure_place: it selects the device and waits for the slot. */
+static int ensure_place(bwb_hip_ctx *c, int si, int max_mm) {
 	HIPCHK(hipSetDevice(c->device));
 	Slot &s = c->slots[si];
 	if (!c->d_SA.p) return fail(BWB_E_STATE, "slot_place: sampled SA not uploaded (bwb_hip_set_sa)");
 	if (!s.submitted) return fail(BWB_E_STATE, "slot_place: the slot has not been submitted");
 	RC(slot_wait(c, si));
 	const uint32_t n = s.n_reads;
-	if (s.placed_mm != max_mm || !n) {
-		HIPCHK(s.h_place.reserve((size_t)n * sizeof(bwb_place)));
-		uint64_t log_n = 0;
-		if (n) {
-			HIPCHK(s.d_place.reserve((size_t)n * sizeof(bwb_place)));
-			RC(slot_log_n(c, s, &log_n));
-		}
-		RC(place_launch(c, "slot_place", s.d_log.as<uint4>(), log_n, s.d_off.as<uint64_t>(), s.d_n.as<uint32_t>(), n, max_mm, s.d_place.as<uint4>(), s.h_place.as<bwb_place>()));
-		s.placed_mm = max_mm;
+	if (s.stage.place_mm == max_mm && n) return BWB_OK;
+	HIPCHK(s.h_place.reserve((size_t)n * sizeof(bwb_place)));
+	uint64_t log_n = 0;
+	if (n) {
+		HIPCHK(s.d_place.reserve((size_t)n * sizeof(bwb_place)));
+		RC(slot_log_n(c, s, &log_n));
 	}
-	*out = s.h_place.as<bwb_place>();
-	*n_reads = n;
+	RC(place_launch(c, "slot_place", s.d_log.as<uint4>(), log_n, s.d_off.as<uint64_t>(), s.d_n.as<uint32_t>(), n, max_mm, s.d_place.as<uint4>(), s.h_place.as<bwb_place>()));
+	s.stage.place_mm = max_mm;
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_slot_place(bwb_hip_ctx *c, int si, int max_mm, const bwb_place **out, uint32_t *n_reads) {
+	if (!c || !out || !n_reads || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_place: bad argument");
+	RC(ensure_place(c, si, max_mm));
+	*out = c->slots[si].h_place.as<bwb_place>();
+	*n_reads = c->slots[si].n_reads;
 	return BWB_OK;
 }
 
@@ -1618,16 +1676,11 @@ static int place_hits_impl(bwb_hip_ctx *c, const std::string &who, const bwb_aln
 	RC(index_ready(c));
 	static_assert(sizeof(bwb_aln) == 48, "bwb_aln is the hit log's three 16-byte words");
 	DevMem d_log, d_off, d_cnt, d_out;
-	HIPCHK(d_log.alloc((size_t)total * sizeof(bwb_aln)));
-	HIPCHK(d_off.alloc((size_t)n_reads * 8));
-	HIPCHK(d_cnt.alloc((size_t)n_reads * 4));
+	RC(stage_in(c, d_log, total ? alns + base : nullptr, (size_t)total * sizeof(bwb_aln)));
+	RC(stage_in(c, d_off, off.data(), (size_t)n_reads * 8));
+	RC(stage_in(c, d_cnt, cnt.data(), (size_t)n_reads * 4));
 	HIPCHK(d_out.alloc((size_t)n_reads * sizeof(bwb_place)));
-	if (total) HIPCHK(hipMemcpyAsync(d_log.p, alns + base, (size_t)total * sizeof(bwb_aln), hipMemcpyHostToDevice, c->rstream));
-	if (n_reads) {
-		HIPCHK(hipMemcpyAsync(d_off.p, off.data(), (size_t)n_reads * 8, hipMemcpyHostToDevice, c->rstream));
-		HIPCHK(hipMemcpyAsync(d_cnt.p, cnt.data(), (size_t)n_reads * 4, hipMemcpyHostToDevice, c->rstream));
-		HIPCHK(hipStreamSynchronize(c->rstream)); /* (off / cnt are pageable memory of this call) */
-	}
+	if (n_reads) HIPCHK(hipStreamSynchronize(c->rstream));
 	const int rc = place_launch(c, who.c_str(), d_log.as<uint4>(), total, d_off.as<uint64_t>(), d_cnt.as<uint32_t>(), n_reads, max_mm, d_out.as<uint4>(), out);
 	if (rc || !max_alt) return rc;
 	return alt_launch(c, who.c_str(), d_log.as<uint4>(), total, d_off.as<uint64_t>(), d_cnt.as<uint32_t>(), n_reads, max_alt, c->hits_alt);
@@ -1650,8 +1703,7 @@ extern "C" int bwb_hip_place_hits_alt(bwb_hip_ctx *c, const bwb_aln *alns, const
 
 extern "C" int bwb_hip_batch_place(bwb_hip_ctx *c, int max_mm, const bwb_place **out, uint32_t *n_reads) {
 	if (!c || !out || !n_reads) return fail(BWB_E_ARG, "batch_place: null argument");
-	if (!c->d_SA.p) return fail(BWB_E_STATE, "batch_place: sampled SA not uploaded (bwb_hip_set_sa)");
-	if (!c->slots[0].submitted || !c->slots[0].complete) return fail(BWB_E_STATE, "batch_place: batch_run has not completed");
+	RC(batch_ready(c, "batch_place"));
 	return bwb_hip_slot_place(c, 0, max_mm, out, n_reads);
 }
 
@@ -1674,7 +1726,7 @@ static int alt_launch(bwb_hip_ctx *c, const char *who, const uint4 *d_log, uint6
 	HIPCHK(ab.h_off.reserve(((size_t)n + 1) * 8));
 	ab.h_off.as<uint64_t>()[0] = 0;
 	if (!n) return BWB_OK;
-	const unsigned nblk = (unsigned)(((size_t)n + BWB_BLOCK - 1) / BWB_BLOCK);
+	const unsigned nblk = blocks_of(n);
 	HIPCHK(ab.d_cnt.reserve((size_t)n * 4));
 	HIPCHK(ab.d_off.reserve(((size_t)n + 1) * 8));
 	HIPCHK(ab.d_bsum.reserve((size_t)nblk * 8));
@@ -1685,9 +1737,7 @@ static int alt_launch(bwb_hip_ctx *c, const char *who, const uint4 *d_log, uint6
 	HIPCHK(hipMemsetAsync(ctl, 0, 16, c->rstream));
 	RC(t_count.begin());
 	hipLaunchKernelGGL(k_alt_count, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, d_log, log_n, d_off, d_cnt, n, (uint32_t)max_alt, ab.d_cnt.as<uint32_t>());
-	hipLaunchKernelGGL(k_scan_blocks, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, ab.d_cnt.as<uint32_t>(), n, d_altoff, ab.d_bsum.as<uint64_t>());
-	hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(BWB_BLOCK), 0, c->rstream, ab.d_bsum.as<uint64_t>(), (uint32_t)nblk, d_altoff + n);
-	hipLaunchKernelGGL(k_scan_add, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, d_altoff, n, ab.d_bsum.as<uint64_t>());
+	scan_offsets(c, ab.d_cnt.as<uint32_t>(), n, d_altoff, ab.d_bsum.as<uint64_t>());
 	HIPCHK(hipGetLastError());
 	RC(t_count.end());
 	HIPCHK(hipMemcpyAsync(ab.h_off.p, d_altoff, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, c->rstream));
@@ -1715,28 +1765,36 @@ static int alt_launch(bwb_hip_ctx *c, const char *who, const uint4 *d_log, uint6
 	return BWB_OK;
 }
 
+static int ensure_alt(bwb_hip_ctx *c, int si, int max_mm, int max_alt) {
+	RC(ensure_place(c, si, max_mm));
+	Slot &s = c->slots[si];
+	const uint32_t n = s.n_reads;
+	if (s.stage.alt_max == max_alt && n) return BWB_OK;
+	uint64_t log_n = 0;
+	if (n) RC(slot_log_n(c, s, &log_n));
+	RC(alt_launch(c, "slot_place_alt", s.d_log.as<uint4>(), log_n, s.d_off.as<uint64_t>(), s.d_n.as<uint32_t>(), n, max_alt, s.alt));
+	s.stage.alt_max = max_alt;
+	return BWB_OK;
+}
+/* how many items the slot's alt holds (max_alt 0: the caller has not asked for any) */
+static uint64_t slot_items(const Slot &s, int max_alt) { return max_alt && s.n_reads ? s.alt.h_off.as<uint64_t>()[s.n_reads] : 0; }
+
 extern "C" int bwb_hip_slot_place_alt(bwb_hip_ctx *c, int si, int max_mm, int max_alt, const bwb_place **places, const uint64_t **alt_off, const bwb_alt **alts, uint32_t *n_reads) {
 	if (!c || !places || !alt_off || !alts || !n_reads || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_place_alt: bad argument");
 	if (max_alt < 1 || max_alt > 255) return fail(BWB_E_ARG, "slot_place_alt: max_alt must be 1..255");
-	RC(bwb_hip_slot_place(c, si, max_mm, places, n_reads)); /* (waits for the slot; refuses what slot_place refuses) */
-	Slot &s = c->slots[si];
-	const uint32_t n = s.n_reads;
-	if (s.placed_alt != max_alt || !n) {
-		uint64_t log_n = 0;
-		if (n) RC(slot_log_n(c, s, &log_n));
-		RC(alt_launch(c, "slot_place_alt", s.d_log.as<uint4>(), log_n, s.d_off.as<uint64_t>(), s.d_n.as<uint32_t>(), n, max_alt, s.alt));
-		s.placed_alt = max_alt;
-	}
+	RC(ensure_alt(c, si, max_mm, max_alt));
+	const Slot &s = c->slots[si];
+	*places = s.h_place.as<bwb_place>();
 	*alt_off = s.alt.h_off.as<uint64_t>();
 	*alts = s.alt.h_alts.as<bwb_alt>();
+	*n_reads = s.n_reads;
 	return BWB_OK;
 }
 
 extern "C" int bwb_hip_batch_place_alt(bwb_hip_ctx *c, int max_mm, int max_alt, const bwb_place **places, const uint64_t **alt_off, const bwb_alt **alts, uint32_t *n_reads) {
 	if (!c || !places || !alt_off || !alts || !n_reads) return fail(BWB_E_ARG, "batch_place_alt: null argument");
 	if (max_alt < 1 || max_alt > 255) return fail(BWB_E_ARG, "batch_place_alt: max_alt must be 1..255");
-	if (!c->d_SA.p) return fail(BWB_E_STATE, "batch_place_alt: sampled SA not uploaded (bwb_hip_set_sa)");
-	if (!c->slots[0].submitted || !c->slots[0].complete) return fail(BWB_E_STATE, "batch_place_alt: batch_run has not completed");
+	RC(batch_ready(c, "batch_place_alt"));
 	return bwb_hip_slot_place_alt(c, 0, max_mm, max_alt, places, alt_off, alts, n_reads);
 }
 
@@ -1774,7 +1832,7 @@ extern "C" int bwb_hip_set_loci(bwb_hip_ctx *c, const uint64_t *start, const uin
 	HIPCHK(hipSetDevice(c->device));
 	c->loci_nseq = 0; /* (no tables until all four are resident) */
 	c->chrom_set = false;
-	for (auto &s : c->slots) { s.locus_mm = -1; s.join_mm = -1; s.lift_mm = -1; s.md_mm = -1; }
+	for (auto &s : c->slots) s.stage.loci_replaced();
 	c->indel_on = false; /* (the table and the counters were these bubbles') */
 	c->lift_refusal = lift_table_refusal(bubbles, n_bub);
 	HIPCHK(c->d_lstart.alloc((size_t)n_seq * 8));
@@ -1787,9 +1845,7 @@ extern "C" int bwb_hip_set_loci(bwb_hip_ctx *c, const uint64_t *start, const uin
 	HIPCHK(hipMemcpyAsync(c->d_lbub.p, bubble_of, (size_t)n_seq * 4, hipMemcpyHostToDevice, c->rstream));
 	if (n_bub) HIPCHK(hipMemcpyAsync(c->d_bubbles.p, bubbles, (size_t)n_bub * sizeof(bwb_bubble), hipMemcpyHostToDevice, c->rstream));
 	HIPCHK(hipStreamSynchronize(c->rstream));
-	uint32_t trips = 0;
-	while (((uint64_t)1 << trips) < n_seq) trips++;
-	c->loci_trips = trips;
+	c->loci_trips = ceil_log2(n_seq);
 	c->loci_bub_of.assign(bubble_of, bubble_of + n_seq);
 	c->loci_bubbles.assign(bubbles, bubbles + n_bub);
 	c->loci_nbub = n_bub;
@@ -1803,9 +1859,8 @@ static int locus_launch(bwb_hip_ctx *c, const uint4 *d_places, uint32_t n, uint4
 	c->locus_ms = 0; c->locus_reads = n;
 	if (!n) return BWB_OK;
 	Timed t(c, c->rstream);
-	const unsigned grid = (unsigned)std::min<size_t>(((size_t)n + BWB_BLOCK - 1) / BWB_BLOCK, (size_t)c->num_cu * 8);
 	RC(t.begin());
-	hipLaunchKernelGGL(k_locus, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, d_places, n, c->d_lstart.as<uint64_t>(), c->d_lend.as<uint64_t>(), c->d_lbub.as<int32_t>(),
+	hipLaunchKernelGGL(k_locus, dim3(lane_grid(c, n)), dim3(BWB_BLOCK), 0, c->rstream, d_places, n, c->d_lstart.as<uint64_t>(), c->d_lend.as<uint64_t>(), c->d_lbub.as<int32_t>(),
 	                   c->loci_nseq, c->loci_trips, c->d_bubbles.as<uint64_t>(), d_out);
 	HIPCHK(hipGetLastError());
 	RC(t.end());
@@ -1817,27 +1872,33 @@ static int locus_launch(bwb_hip_ctx *c, const uint4 *d_places, uint32_t n, uint4
 	return BWB_OK;
 }
 
-extern "C" int bwb_hip_slot_locus(bwb_hip_ctx *c, int si, int max_mm, const bwb_place **places, const bwb_locus **loci, uint32_t *n_reads) {
-	if (!c || !places || !loci || !n_reads || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_locus: bad argument");
+static int ensure_locus(bwb_hip_ctx *c, int si, int max_mm) {
 	if (!c->loci_nseq) return fail(BWB_E_STATE, "slot_locus: record and bubble tables not uploaded (bwb_hip_set_loci)");
-	RC(bwb_hip_slot_place(c, si, max_mm, places, n_reads)); /* (waits for the slot; refuses what slot_place refuses; leaves the records in d_place) */
+	RC(ensure_place(c, si, max_mm));
 	Slot &s = c->slots[si];
 	const uint32_t n = s.n_reads;
-	if (s.locus_mm != max_mm || !n) {
-		HIPCHK(s.h_locus.reserve((size_t)n * sizeof(bwb_locus)));
-		if (n) HIPCHK(s.d_locus.reserve((size_t)n * sizeof(bwb_locus)));
-		RC(locus_launch(c, s.d_place.as<uint4>(), n, s.d_locus.as<uint4>(), s.h_locus.as<bwb_locus>()));
-		s.locus_mm = max_mm;
-	}
+	if (s.stage.locus_mm == max_mm && n) return BWB_OK;
+	HIPCHK(s.h_locus.reserve((size_t)n * sizeof(bwb_locus)));
+	if (n) HIPCHK(s.d_locus.reserve((size_t)n * sizeof(bwb_locus)));
+	RC(locus_launch(c, s.d_place.as<uint4>(), n, s.d_locus.as<uint4>(), s.h_locus.as<bwb_locus>()));
+	s.stage.locus_mm = max_mm;
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_slot_locus(bwb_hip_ctx *c, int si, int max_mm, const bwb_place **places, const bwb_locus **loci, uint32_t *n_reads) {
+	if (!c || !places || !loci || !n_reads || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_locus: bad argument");
+	RC(ensure_locus(c, si, max_mm));
+	const Slot &s = c->slots[si];
+	*places = s.h_place.as<bwb_place>();
 	*loci = s.h_locus.as<bwb_locus>();
+	*n_reads = s.n_reads;
 	return BWB_OK;
 }
 
 extern "C" int bwb_hip_batch_locus(bwb_hip_ctx *c, int max_mm, const bwb_place **places, const bwb_locus **loci, uint32_t *n_reads) {
 	if (!c || !places || !loci || !n_reads) return fail(BWB_E_ARG, "batch_locus: null argument");
 	if (!c->loci_nseq) return fail(BWB_E_STATE, "batch_locus: record and bubble tables not uploaded (bwb_hip_set_loci)");
-	if (!c->d_SA.p) return fail(BWB_E_STATE, "batch_locus: sampled SA not uploaded (bwb_hip_set_sa)");
-	if (!c->slots[0].submitted || !c->slots[0].complete) return fail(BWB_E_STATE, "batch_locus: batch_run has not completed");
+	RC(batch_ready(c, "batch_locus"));
 	return bwb_hip_slot_locus(c, 0, max_mm, places, loci, n_reads);
 }
 
@@ -1847,12 +1908,9 @@ extern "C" int bwb_hip_locus_places(bwb_hip_ctx *c, const bwb_place *places, uin
 	if (!c->loci_nseq) return fail(BWB_E_STATE, "locus_places: record and bubble tables not uploaded (bwb_hip_set_loci)");
 	HIPCHK(hipSetDevice(c->device));
 	DevMem d_in, d_out;
-	HIPCHK(d_in.alloc((size_t)n * sizeof(bwb_place)));
+	RC(stage_in(c, d_in, places, (size_t)n * sizeof(bwb_place)));
 	HIPCHK(d_out.alloc((size_t)n * sizeof(bwb_locus)));
-	if (n) {
-		HIPCHK(hipMemcpyAsync(d_in.p, places, (size_t)n * sizeof(bwb_place), hipMemcpyHostToDevice, c->rstream));
-		HIPCHK(hipStreamSynchronize(c->rstream)); /* (pageable memory of the caller) */
-	}
+	if (n) HIPCHK(hipStreamSynchronize(c->rstream));
 	return locus_launch(c, d_in.as<uint4>(), n, d_out.as<uint4>(), out);
 }
 
@@ -1876,7 +1934,7 @@ extern "C" int bwb_hip_set_bubble_chrom(bwb_hip_ctx *c, const int32_t *chrom_of,
 			                           std::to_string(c->loci_nseq) + " records");
 	HIPCHK(hipSetDevice(c->device));
 	c->chrom_set = false;
-	for (auto &s : c->slots) { s.join_mm = -1; s.lift_mm = -1; s.md_mm = -1; }
+	for (auto &s : c->slots) s.stage.chrom_replaced();
 	c->indel_on = false;
 	c->chrom_of.assign(chrom_of, chrom_of + n_bub);
 	HIPCHK(c->d_chrom.alloc((size_t)n_bub * 4));
@@ -1901,16 +1959,13 @@ static int join_launch(bwb_hip_ctx *c, const JoinIn &in, int max_mm, DevMem &d_c
 	if (!in.n) return BWB_OK;
 	RC(ensure_qtab(c));
 	HIPCHK(d_cls.reserve((size_t)in.n_items));
-	uint32_t owner_trips = 0;
-	while (((uint64_t)1 << owner_trips) < in.n) owner_trips++;
-	const size_t cap = (size_t)c->num_cu * 8;
 	Timed t(c, c->rstream);
 	RC(t.begin());
 	if (in.n_items)
-		hipLaunchKernelGGL(k_join_items, dim3((unsigned)std::min<size_t>((size_t)((in.n_items + BWB_BLOCK - 1) / BWB_BLOCK), cap)), dim3(BWB_BLOCK), 0, c->rstream,
-		                   in.places, in.n, owner_trips, in.alt_off, in.alts, in.n_items, in.loci, c->d_lstart.as<uint64_t>(), c->d_lend.as<uint64_t>(), c->d_lbub.as<int32_t>(),
+		hipLaunchKernelGGL(k_join_items, dim3(lane_grid(c, in.n_items)), dim3(BWB_BLOCK), 0, c->rstream,
+		                   in.places, in.n, ceil_log2(in.n), in.alt_off, in.alts, in.n_items, in.loci, c->d_lstart.as<uint64_t>(), c->d_lend.as<uint64_t>(), c->d_lbub.as<int32_t>(),
 		                   c->loci_nseq, c->loci_trips, c->d_bubbles.as<uint64_t>(), c->d_chrom.as<int32_t>(), in.log, in.log_n, in.off, in.cnt, in.sub, d_cls.as<uint8_t>());
-	hipLaunchKernelGGL(k_join_reads, dim3((unsigned)std::min<size_t>(((size_t)in.n + BWB_BLOCK - 1) / BWB_BLOCK, cap)), dim3(BWB_BLOCK), 0, c->rstream,
+	hipLaunchKernelGGL(k_join_reads, dim3(lane_grid(c, in.n)), dim3(BWB_BLOCK), 0, c->rstream,
 	                   in.places, in.n, in.alt_off, d_cls.as<uint8_t>(), max_mm, c->d_qtab.as<uint8_t>(), d_out);
 	HIPCHK(hipGetLastError());
 	RC(t.end());
@@ -1930,28 +1985,37 @@ static int join_ready(bwb_hip_ctx *c, const char *who, int max_alt) {
 	return BWB_OK;
 }
 
+static int ensure_join(bwb_hip_ctx *c, int si, int max_mm, int max_alt) {
+	RC(join_ready(c, "slot_join", max_alt));
+	RC(ensure_alt(c, si, max_mm, max_alt));
+	RC(ensure_locus(c, si, max_mm));
+	Slot &s = c->slots[si];
+	const uint32_t n = s.n_reads;
+	if (s.stage.join_mm == max_mm && s.stage.join_alt == max_alt && n) return BWB_OK;
+	HIPCHK(s.h_join.reserve((size_t)n * sizeof(bwb_join)));
+	uint64_t log_n = 0;
+	if (n) {
+		HIPCHK(s.d_join.reserve((size_t)n * sizeof(bwb_join)));
+		RC(slot_log_n(c, s, &log_n));
+	}
+	const JoinIn in = { s.d_place.as<uint4>(), n, s.d_locus.as<uint4>(), s.alt.d_off.as<uint64_t>(), s.alt.d_alts.as<uint4>(), slot_items(s, max_alt),
+	                    s.d_log.as<uint4>(), log_n, s.d_off.as<uint64_t>(), s.d_n.as<uint32_t>(), nullptr };
+	RC(join_launch(c, in, max_mm, s.d_cls, s.d_join.as<uint4>(), s.h_join.as<bwb_join>()));
+	s.stage.join_mm = max_mm; s.stage.join_alt = max_alt;
+	return BWB_OK;
+}
+
 extern "C" int bwb_hip_slot_join(bwb_hip_ctx *c, int si, int max_mm, int max_alt, const bwb_place **places, const uint64_t **alt_off, const bwb_alt **alts,
                                  const bwb_locus **loci, const bwb_join **joins, uint32_t *n_reads) {
 	if (!c || !places || !alt_off || !alts || !loci || !joins || !n_reads || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_join: bad argument");
-	RC(join_ready(c, "slot_join", max_alt));
-	/* (both wait for the slot, refuse what slot_place refuses, and leave their records in the slot's device memory) */
-	RC(bwb_hip_slot_place_alt(c, si, max_mm, max_alt, places, alt_off, alts, n_reads));
-	RC(bwb_hip_slot_locus(c, si, max_mm, places, loci, n_reads));
-	Slot &s = c->slots[si];
-	const uint32_t n = s.n_reads;
-	if (s.join_mm != max_mm || s.join_alt != max_alt || !n) {
-		HIPCHK(s.h_join.reserve((size_t)n * sizeof(bwb_join)));
-		uint64_t log_n = 0;
-		if (n) {
-			HIPCHK(s.d_join.reserve((size_t)n * sizeof(bwb_join)));
-			RC(slot_log_n(c, s, &log_n));
-		}
-		const JoinIn in = { s.d_place.as<uint4>(), n, s.d_locus.as<uint4>(), s.alt.d_off.as<uint64_t>(), s.alt.d_alts.as<uint4>(), n ? (*alt_off)[n] : 0,
-		                    s.d_log.as<uint4>(), log_n, s.d_off.as<uint64_t>(), s.d_n.as<uint32_t>(), nullptr };
-		RC(join_launch(c, in, max_mm, s.d_cls, s.d_join.as<uint4>(), s.h_join.as<bwb_join>()));
-		s.join_mm = max_mm; s.join_alt = max_alt;
-	}
+	RC(ensure_join(c, si, max_mm, max_alt));
+	const Slot &s = c->slots[si];
+	*places = s.h_place.as<bwb_place>();
+	*alt_off = s.alt.h_off.as<uint64_t>();
+	*alts = s.alt.h_alts.as<bwb_alt>();
+	*loci = s.h_locus.as<bwb_locus>();
 	*joins = s.h_join.as<bwb_join>();
+	*n_reads = s.n_reads;
 	return BWB_OK;
 }
 
@@ -1959,8 +2023,7 @@ extern "C" int bwb_hip_batch_join(bwb_hip_ctx *c, int max_mm, int max_alt, const
                                   const bwb_locus **loci, const bwb_join **joins, uint32_t *n_reads) {
 	if (!c || !places || !alt_off || !alts || !loci || !joins || !n_reads) return fail(BWB_E_ARG, "batch_join: null argument");
 	RC(join_ready(c, "batch_join", max_alt));
-	if (!c->d_SA.p) return fail(BWB_E_STATE, "batch_join: sampled SA not uploaded (bwb_hip_set_sa)");
-	if (!c->slots[0].submitted || !c->slots[0].complete) return fail(BWB_E_STATE, "batch_join: batch_run has not completed");
+	RC(batch_ready(c, "batch_join"));
 	return bwb_hip_slot_join(c, 0, max_mm, max_alt, places, alt_off, alts, loci, joins, n_reads);
 }
 
@@ -1969,26 +2032,18 @@ extern "C" int bwb_hip_join_records(bwb_hip_ctx *c, const bwb_place *places, uin
                                     bwb_join *out) {
 	if (!c || !alt_off || (n && (!places || !out)) || n > 0x7FFFFFFFu) return fail(BWB_E_ARG, "join_records: bad argument");
 	RC(join_ready(c, "join_records", 1));
-	if (alt_off[0] != 0) return fail(BWB_E_ARG, "join_records: alt_off[0] must be 0");
-	for (uint32_t r = 0; r < n; r++)
-		if (alt_off[r + 1] < alt_off[r] || alt_off[r + 1] - alt_off[r] > 255) return fail(BWB_E_ARG, "join_records: read " + std::to_string(r) + " does not own 0..255 items");
+	RC(check_offsets("join_records", "alt_off", alt_off, n, 255));
 	const uint64_t n_items = alt_off[n];
 	if (n_items && (!alts || !alt_sub)) return fail(BWB_E_ARG, "join_records: null argument");
 	HIPCHK(hipSetDevice(c->device));
 	DevMem d_places, d_loci, d_off, d_alts, d_sub, d_cls, d_out;
-	HIPCHK(d_places.alloc((size_t)n * sizeof(bwb_place)));
+	RC(stage_in(c, d_places, places, (size_t)n * sizeof(bwb_place)));
+	RC(stage_in(c, d_off, alt_off, ((size_t)n + 1) * 8));
+	RC(stage_in(c, d_alts, alts, (size_t)n_items * sizeof(bwb_alt)));
+	RC(stage_in(c, d_sub, alt_sub, (size_t)n_items));
 	HIPCHK(d_loci.alloc((size_t)n * sizeof(bwb_locus)));
-	HIPCHK(d_off.alloc(((size_t)n + 1) * 8));
-	HIPCHK(d_alts.alloc((size_t)n_items * sizeof(bwb_alt)));
-	HIPCHK(d_sub.alloc((size_t)n_items));
 	HIPCHK(d_out.alloc((size_t)n * sizeof(bwb_join)));
-	if (n) HIPCHK(hipMemcpyAsync(d_places.p, places, (size_t)n * sizeof(bwb_place), hipMemcpyHostToDevice, c->rstream));
-	HIPCHK(hipMemcpyAsync(d_off.p, alt_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->rstream));
-	if (n_items) {
-		HIPCHK(hipMemcpyAsync(d_alts.p, alts, (size_t)n_items * sizeof(bwb_alt), hipMemcpyHostToDevice, c->rstream));
-		HIPCHK(hipMemcpyAsync(d_sub.p, alt_sub, (size_t)n_items, hipMemcpyHostToDevice, c->rstream));
-	}
-	HIPCHK(hipStreamSynchronize(c->rstream)); /* (pageable memory of the caller) */
+	HIPCHK(hipStreamSynchronize(c->rstream));
 	std::vector<bwb_locus> h_loci(n ? n : 1);
 	RC(locus_launch(c, d_places.as<uint4>(), n, d_loci.as<uint4>(), h_loci.data()));
 	const JoinIn in = { d_places.as<uint4>(), n, d_loci.as<uint4>(), d_off.as<uint64_t>(), d_alts.as<uint4>(), n_items, nullptr, 0, nullptr, nullptr, d_sub.as<uint8_t>() };
@@ -2026,20 +2081,17 @@ static int lift_launch(bwb_hip_ctx *c, const char *who, const uint4 *d_places, u
 	HIPCHK(lb.h_recs.reserve(sizeof(bwb_lift)));
 	lb.h_off.as<uint64_t>()[0] = 0;
 	if (!n_q) return BWB_OK;
-	const unsigned nblk = (unsigned)((n_q + BWB_BLOCK - 1) / BWB_BLOCK);
-	const unsigned grid = (unsigned)std::min<size_t>(nblk, (size_t)c->num_cu * 8);
+	const unsigned grid = lane_grid(c, n_q);
 	HIPCHK(lb.d_kind.reserve((size_t)n_q));
 	HIPCHK(lb.d_cnt.reserve((size_t)n_q * 4));
 	HIPCHK(lb.d_off.reserve(((size_t)n_q + 1) * 8));
-	HIPCHK(lb.d_bsum.reserve((size_t)nblk * 8));
+	HIPCHK(lb.d_bsum.reserve((size_t)blocks_of(n_q) * 8));
 	uint64_t *d_off = lb.d_off.as<uint64_t>();
 	Timed t_count(c, c->rstream), t_lift(c, c->rstream); /* k_lift_count and the scan; k_lift */
 	RC(t_count.begin());
 	hipLaunchKernelGGL(k_lift_count, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, d_places, n, d_loci, d_alts, n_q, c->d_lstart.as<uint64_t>(), c->d_lend.as<uint64_t>(),
 	                   c->d_lbub.as<int32_t>(), c->loci_nseq, c->loci_trips, c->d_bubbles.as<uint64_t>(), lb.d_kind.as<uint8_t>(), lb.d_cnt.as<uint32_t>());
-	hipLaunchKernelGGL(k_scan_blocks, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, lb.d_cnt.as<uint32_t>(), (uint32_t)n_q, d_off, lb.d_bsum.as<uint64_t>());
-	hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(BWB_BLOCK), 0, c->rstream, lb.d_bsum.as<uint64_t>(), (uint32_t)nblk, d_off + n_q);
-	hipLaunchKernelGGL(k_scan_add, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, d_off, (uint32_t)n_q, lb.d_bsum.as<uint64_t>());
+	scan_offsets(c, lb.d_cnt.as<uint32_t>(), (uint32_t)n_q, d_off, lb.d_bsum.as<uint64_t>());
 	HIPCHK(hipGetLastError());
 	RC(t_count.end());
 	HIPCHK(hipMemcpyAsync(lb.h_off.p, d_off, ((size_t)n_q + 1) * 8, hipMemcpyDeviceToHost, c->rstream));
@@ -2067,36 +2119,32 @@ static int lift_launch(bwb_hip_ctx *c, const char *who, const uint4 *d_places, u
 	return BWB_OK;
 }
 
+static int ensure_lift(bwb_hip_ctx *c, int si, int max_mm, int max_alt) {
+	RC(lift_ready(c, "slot_lift", max_alt));
+	if (max_alt) RC(ensure_alt(c, si, max_mm, max_alt));
+	RC(ensure_locus(c, si, max_mm));
+	Slot &s = c->slots[si];
+	if (s.stage.lift_mm == max_mm && s.stage.lift_alt == max_alt && s.n_reads) return BWB_OK;
+	RC(lift_launch(c, "slot_lift", s.d_place.as<uint4>(), s.n_reads, s.d_locus.as<uint4>(), s.alt.d_alts.as<uint4>(), slot_items(s, max_alt), s.lift));
+	s.stage.lift_mm = max_mm; s.stage.lift_alt = max_alt;
+	return BWB_OK;
+}
+
 extern "C" int bwb_hip_slot_lift(bwb_hip_ctx *c, int si, int max_mm, int max_alt, const uint8_t **kinds, const uint64_t **lift_off, const bwb_lift **recs, uint64_t *n_placements) {
 	if (!c || !kinds || !lift_off || !recs || !n_placements || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_lift: bad argument");
-	RC(lift_ready(c, "slot_lift", max_alt));
-	/* (both wait for the slot, refuse what slot_place refuses, and leave their records in the slot's device memory) */
-	const bwb_place *places = nullptr;
-	const uint64_t *alt_off = nullptr;
-	const bwb_alt *alts = nullptr;
-	const bwb_locus *loci = nullptr;
-	uint32_t n = 0;
-	if (max_alt) RC(bwb_hip_slot_place_alt(c, si, max_mm, max_alt, &places, &alt_off, &alts, &n));
-	RC(bwb_hip_slot_locus(c, si, max_mm, &places, &loci, &n));
-	Slot &s = c->slots[si];
-	n = s.n_reads;
-	const uint64_t n_items = max_alt && n ? alt_off[n] : 0;
-	if (s.lift_mm != max_mm || s.lift_alt != max_alt || !n) {
-		RC(lift_launch(c, "slot_lift", s.d_place.as<uint4>(), n, s.d_locus.as<uint4>(), s.alt.d_alts.as<uint4>(), n_items, s.lift));
-		s.lift_mm = max_mm; s.lift_alt = max_alt;
-	}
+	RC(ensure_lift(c, si, max_mm, max_alt));
+	const Slot &s = c->slots[si];
 	*kinds = s.lift.h_kind.as<uint8_t>();
 	*lift_off = s.lift.h_off.as<uint64_t>();
 	*recs = s.lift.h_recs.as<bwb_lift>();
-	*n_placements = (uint64_t)n + n_items;
+	*n_placements = (uint64_t)s.n_reads + slot_items(s, max_alt);
 	return BWB_OK;
 }
 
 extern "C" int bwb_hip_batch_lift(bwb_hip_ctx *c, int max_mm, int max_alt, const uint8_t **kinds, const uint64_t **lift_off, const bwb_lift **recs, uint64_t *n_placements) {
 	if (!c || !kinds || !lift_off || !recs || !n_placements) return fail(BWB_E_ARG, "batch_lift: null argument");
 	RC(lift_ready(c, "batch_lift", max_alt));
-	if (!c->d_SA.p) return fail(BWB_E_STATE, "batch_lift: sampled SA not uploaded (bwb_hip_set_sa)");
-	if (!c->slots[0].submitted || !c->slots[0].complete) return fail(BWB_E_STATE, "batch_lift: batch_run has not completed");
+	RC(batch_ready(c, "batch_lift"));
 	return bwb_hip_slot_lift(c, 0, max_mm, max_alt, kinds, lift_off, recs, n_placements);
 }
 
@@ -2105,20 +2153,16 @@ extern "C" int bwb_hip_lift_records(bwb_hip_ctx *c, const bwb_place *places, uin
                                     const uint64_t **lift_off, const bwb_lift **recs) {
 	if (!c || !alt_off || !kinds || !lift_off || !recs || (n && !places) || n > 0x7FFFFFFFu) return fail(BWB_E_ARG, "lift_records: bad argument");
 	RC(lift_ready(c, "lift_records", 1));
-	if (alt_off[0] != 0) return fail(BWB_E_ARG, "lift_records: alt_off[0] must be 0");
-	for (uint32_t r = 0; r < n; r++)
-		if (alt_off[r + 1] < alt_off[r]) return fail(BWB_E_ARG, "lift_records: alt_off does not ascend at read " + std::to_string(r));
+	RC(check_offsets("lift_records", "alt_off", alt_off, n, NO_LIMIT));
 	const uint64_t n_items = alt_off[n];
 	if (n_items && !alts) return fail(BWB_E_ARG, "lift_records: null argument");
 	if ((uint64_t)n + n_items > 0x7FFFFFFFu) return fail(BWB_E_ARG, "lift_records: more than 2^31 - 1 placements");
 	HIPCHK(hipSetDevice(c->device));
 	DevMem d_places, d_loci, d_alts;
-	HIPCHK(d_places.alloc((size_t)n * sizeof(bwb_place)));
+	RC(stage_in(c, d_places, places, (size_t)n * sizeof(bwb_place)));
+	RC(stage_in(c, d_alts, alts, (size_t)n_items * sizeof(bwb_alt)));
 	HIPCHK(d_loci.alloc((size_t)n * sizeof(bwb_locus)));
-	HIPCHK(d_alts.alloc((size_t)n_items * sizeof(bwb_alt)));
-	if (n) HIPCHK(hipMemcpyAsync(d_places.p, places, (size_t)n * sizeof(bwb_place), hipMemcpyHostToDevice, c->rstream));
-	if (n_items) HIPCHK(hipMemcpyAsync(d_alts.p, alts, (size_t)n_items * sizeof(bwb_alt), hipMemcpyHostToDevice, c->rstream));
-	HIPCHK(hipStreamSynchronize(c->rstream)); /* (pageable memory of the caller) */
+	HIPCHK(hipStreamSynchronize(c->rstream));
 	std::vector<bwb_locus> h_loci(n ? n : 1);
 	RC(locus_launch(c, d_places.as<uint4>(), n, d_loci.as<uint4>(), h_loci.data()));
 	RC(lift_launch(c, "lift_records", d_places.as<uint4>(), n, d_loci.as<uint4>(), d_alts.as<uint4>(), n_items, c->lift_rec));
@@ -2148,7 +2192,7 @@ extern "C" int bwb_hip_set_text(bwb_hip_ctx *c, const uint8_t *codes, uint64_t n
 	HIPCHK(hipSetDevice(c->device));
 	HIPCHK(hipStreamSynchronize(c->rstream)); /* (a kernel of an earlier md call may still read the text that is replaced) */
 	c->text_n = 0;
-	for (auto &s : c->slots) s.md_mm = -1;
+	for (auto &s : c->slots) s.stage.text_replaced();
 	c->pile_on = false; c->pile_sites = 0; /* (the site index and the counters were this text's) */
 	c->d_site_base.release(); c->d_counts.release();
 	c->geno_on = false; c->geno_bub = false;
@@ -2161,8 +2205,7 @@ extern "C" int bwb_hip_set_text(bwb_hip_ctx *c, const uint8_t *codes, uint64_t n
 	for (uint64_t c0 = 0; c0 < n_fwd; c0 += CH) { /* (CH is a multiple of 32: every chunk begins a 16-byte word of the packed text) */
 		const uint64_t nc = std::min<uint64_t>(CH, n_fwd - c0), nw = (nc + 31) / 32;
 		HIPCHK(hipMemcpyAsync(d_stage.p, codes + c0, (size_t)nc, hipMemcpyHostToDevice, c->rstream));
-		const unsigned grid = (unsigned)std::min<uint64_t>((nw + BWB_BLOCK - 1) / BWB_BLOCK, (uint64_t)c->num_cu * 8);
-		hipLaunchKernelGGL(k_text_pack, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, d_stage.as<uint8_t>(), nc, c->d_text.as<uint4>() + c0 / 32, d_bad.as<uint32_t>());
+		hipLaunchKernelGGL(k_text_pack, dim3(lane_grid(c, nw)), dim3(BWB_BLOCK), 0, c->rstream, d_stage.as<uint8_t>(), nc, c->d_text.as<uint4>() + c0 / 32, d_bad.as<uint32_t>());
 		HIPCHK(hipGetLastError());
 	}
 	uint32_t bad = 0;
@@ -2186,21 +2229,18 @@ static int md_launch(bwb_hip_ctx *c, const uint8_t *d_reads, const uint16_t *d_l
 	HIPCHK(mb.h_text.reserve(1));
 	mb.h_off.as<uint64_t>()[0] = 0;
 	if (!n) return BWB_OK;
-	const unsigned nblk = (unsigned)(((size_t)n + BWB_BLOCK - 1) / BWB_BLOCK);
-	const unsigned grid = (unsigned)std::min<size_t>(nblk, (size_t)c->num_cu * 8);
+	const unsigned grid = lane_grid(c, n);
 	HIPCHK(mb.d_recs.reserve((size_t)n * sizeof(bwb_md)));
 	HIPCHK(mb.d_cnt.reserve((size_t)n * 4));
 	HIPCHK(mb.d_off.reserve(((size_t)n + 1) * 8));
-	HIPCHK(mb.d_bsum.reserve((size_t)nblk * 8));
+	HIPCHK(mb.d_bsum.reserve((size_t)blocks_of(n) * 8));
 	uint64_t *d_off = mb.d_off.as<uint64_t>();
 	const uint32_t n_seq = d_kind ? c->loci_nseq : 0u;
 	Timed t_count(c, c->rstream), t_md(c, c->rstream); /* k_md_count and the scan; k_md */
 	RC(t_count.begin());
 	hipLaunchKernelGGL(k_md_count, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, d_reads, d_lens, stride, d_places, n, d_kind, d_loff, d_lrecs, c->d_lstart.as<uint64_t>(), n_seq,
 	                   c->d_text.as<uint4>(), c->text_n, mb.d_recs.as<uint2>(), mb.d_cnt.as<uint32_t>());
-	hipLaunchKernelGGL(k_scan_blocks, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, mb.d_cnt.as<uint32_t>(), n, d_off, mb.d_bsum.as<uint64_t>());
-	hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(BWB_BLOCK), 0, c->rstream, mb.d_bsum.as<uint64_t>(), (uint32_t)nblk, d_off + n);
-	hipLaunchKernelGGL(k_scan_add, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, d_off, n, mb.d_bsum.as<uint64_t>());
+	scan_offsets(c, mb.d_cnt.as<uint32_t>(), n, d_off, mb.d_bsum.as<uint64_t>());
 	HIPCHK(hipGetLastError());
 	RC(t_count.end());
 	HIPCHK(hipMemcpyAsync(mb.h_off.p, d_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, c->rstream));
@@ -2228,44 +2268,57 @@ static int md_launch(bwb_hip_ctx *c, const uint8_t *d_reads, const uint16_t *d_l
 	return BWB_OK;
 }
 
+/* (a cached call leaves md_stats at the last launch's figures, whichever slot's: a caller that sums them - retire_map - asks every slot once) */
+static int ensure_md(bwb_hip_ctx *c, int si, int max_mm, int max_alt, bool lifted) {
+	RC(lifted ? ensure_lift(c, si, max_mm, max_alt) : ensure_place(c, si, max_mm));
+	Slot &s = c->slots[si];
+	const uint32_t n = s.n_reads; /* (not n_tot: a carried read that rides along behind the batch's reads has no record) */
+	if (s.stage.md_mm == max_mm && s.stage.md_lifted == (int)lifted && (!lifted || s.stage.md_alt == max_alt) && n) return BWB_OK;
+	HIPCHK(hipStreamWaitEvent(c->rstream, s.ev_up.e, 0)); /* (the slot's reads, uploaded on the copy stream) */
+	/* (a slot whose every placement lies on no bubble record has no lift records at all: d_recs may be NULL, and no lane reads it) */
+	RC(md_launch(c, s.d_reads.as<uint8_t>(), s.d_lens.as<uint16_t>(), s.stride, s.d_place.as<uint4>(), n, lifted ? s.lift.d_kind.as<uint8_t>() : nullptr,
+	             s.lift.d_off.as<uint64_t>(), s.lift.d_recs.as<uint4>(), s.md));
+	s.stage.md_mm = max_mm; s.stage.md_alt = max_alt; s.stage.md_lifted = (int)lifted;
+	return BWB_OK;
+}
+
 extern "C" int bwb_hip_slot_md(bwb_hip_ctx *c, int si, int max_mm, int max_alt, int lifted, const bwb_md **recs, const uint64_t **md_off, const char **md_text, uint32_t *n_reads) {
 	if (!c || !recs || !md_off || !md_text || !n_reads || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_md: bad argument");
 	if (!c->text_n) return fail(BWB_E_STATE, "slot_md: the text has not been uploaded (bwb_hip_set_text)");
 	if (!c->d_SA.p) return fail(BWB_E_STATE, "slot_md: sampled SA not uploaded (bwb_hip_set_sa)");
-	/* (both wait for the slot, refuse what slot_place refuses, and leave their records in the slot's device memory) */
-	const bwb_place *places = nullptr;
-	uint32_t n = 0;
-	if (lifted) {
-		const uint8_t *kinds = nullptr;
-		const uint64_t *lift_off = nullptr;
-		const bwb_lift *lrecs = nullptr;
-		uint64_t nq = 0;
-		RC(bwb_hip_slot_lift(c, si, max_mm, max_alt, &kinds, &lift_off, &lrecs, &nq));
-	} else RC(bwb_hip_slot_place(c, si, max_mm, &places, &n));
-	Slot &s = c->slots[si];
-	n = s.n_reads; /* (not n_tot: a carried read that rides along behind the batch's reads has no record) */
-	/* (cached records launch nothing and leave md_stats at the last launch's figures, whichever slot's: a caller that sums them - retire_map -
-	 * asks every slot once) */
-	if (s.md_mm != max_mm || s.md_lifted != (lifted ? 1 : 0) || (lifted && s.md_alt != max_alt) || !n) {
-		HIPCHK(hipStreamWaitEvent(c->rstream, s.ev_up.e, 0)); /* (the slot's reads, uploaded on the copy stream) */
-		/* (a slot whose every placement lies on no bubble record has no lift records at all: d_recs may be NULL, and no lane reads it) */
-		RC(md_launch(c, s.d_reads.as<uint8_t>(), s.d_lens.as<uint16_t>(), s.stride, s.d_place.as<uint4>(), n, lifted ? s.lift.d_kind.as<uint8_t>() : nullptr,
-		             s.lift.d_off.as<uint64_t>(), s.lift.d_recs.as<uint4>(), s.md));
-		s.md_mm = max_mm; s.md_alt = max_alt; s.md_lifted = lifted ? 1 : 0;
-	}
+	RC(ensure_md(c, si, max_mm, max_alt, lifted != 0));
+	const Slot &s = c->slots[si];
 	*recs = s.md.h_recs.as<bwb_md>();
 	*md_off = s.md.h_off.as<uint64_t>();
 	*md_text = s.md.h_text.as<char>();
-	*n_reads = n;
+	*n_reads = s.n_reads;
 	return BWB_OK;
 }
 
 extern "C" int bwb_hip_batch_md(bwb_hip_ctx *c, int max_mm, int max_alt, int lifted, const bwb_md **recs, const uint64_t **md_off, const char **md_text, uint32_t *n_reads) {
 	if (!c || !recs || !md_off || !md_text || !n_reads) return fail(BWB_E_ARG, "batch_md: null argument");
 	if (!c->text_n) return fail(BWB_E_STATE, "batch_md: the text has not been uploaded (bwb_hip_set_text)");
-	if (!c->d_SA.p) return fail(BWB_E_STATE, "batch_md: sampled SA not uploaded (bwb_hip_set_sa)");
-	if (!c->slots[0].submitted || !c->slots[0].complete) return fail(BWB_E_STATE, "batch_md: batch_run has not completed");
+	RC(batch_ready(c, "batch_md"));
 	return bwb_hip_slot_md(c, 0, max_mm, max_alt, lifted, recs, md_off, md_text, n_reads);
+}
+
+/* what md_records and pile_records are given, in device memory: n reads, their lengths and placement records, and - kinds NULL: none, and kind, loff
+ * and lrecs stay NULL - their lift records.  Checks the lift arrays under the caller's name; the caller synchronises (stage_in). */
+struct StagedReads { DevMem reads, lens, places, kind, loff, lrecs; };
+static int stage_reads(bwb_hip_ctx *c, const char *who, const uint8_t *reads_fwd, const uint16_t *lens, uint32_t stride, const bwb_place *places, uint32_t n, const uint8_t *kinds,
+                       const uint64_t *lift_off, const bwb_lift *lift_recs, StagedReads &in) {
+	if (kinds && !c->loci_nseq) return fail(BWB_E_STATE, std::string(who) + ": lift records need the record table (bwb_hip_set_loci)");
+	if (kinds) RC(check_offsets(who, "lift_off", lift_off, n, NO_LIMIT));
+	const uint64_t words = kinds ? lift_off[n] : 0;
+	if (words && !lift_recs) return fail(BWB_E_ARG, std::string(who) + ": null argument");
+	HIPCHK(hipSetDevice(c->device));
+	RC(stage_in(c, in.reads, reads_fwd, (size_t)n * stride));
+	RC(stage_in(c, in.lens, lens, (size_t)n * 2));
+	RC(stage_in(c, in.places, places, (size_t)n * sizeof(bwb_place)));
+	if (!kinds) return BWB_OK;
+	RC(stage_in(c, in.kind, kinds, (size_t)n));
+	RC(stage_in(c, in.loff, lift_off, ((size_t)n + 1) * 8));
+	return stage_in(c, in.lrecs, lift_recs, (size_t)words * sizeof(bwb_lift));
 }
 
 /* the kernels on reads and records of the caller's instead of a slot's (for parity tests) */
@@ -2274,35 +2327,10 @@ extern "C" int bwb_hip_md_records(bwb_hip_ctx *c, const uint8_t *reads_fwd, cons
 	if (!c || !recs || !md_off || !md_text || (n && (!reads_fwd || !lens || !places)) || n > 0x7FFFFFFFu || stride < 1 || stride > 255) return fail(BWB_E_ARG, "md_records: bad argument");
 	if ((kinds != nullptr) != (lift_off != nullptr)) return fail(BWB_E_ARG, "md_records: the lift kinds and offsets come together");
 	if (!c->text_n) return fail(BWB_E_STATE, "md_records: the text has not been uploaded (bwb_hip_set_text)");
-	if (kinds && !c->loci_nseq) return fail(BWB_E_STATE, "md_records: lift records need the record table (bwb_hip_set_loci)");
-	uint64_t words = 0;
-	if (kinds) {
-		if (lift_off[0] != 0) return fail(BWB_E_ARG, "md_records: lift_off[0] must be 0");
-		for (uint32_t r = 0; r < n; r++)
-			if (lift_off[r + 1] < lift_off[r]) return fail(BWB_E_ARG, "md_records: lift_off does not ascend at read " + std::to_string(r));
-		words = lift_off[n];
-		if (words && !lift_recs) return fail(BWB_E_ARG, "md_records: null argument");
-	}
-	HIPCHK(hipSetDevice(c->device));
-	DevMem d_reads, d_lens, d_places, d_kind, d_loff, d_lrecs;
-	HIPCHK(d_reads.alloc((size_t)n * stride));
-	HIPCHK(d_lens.alloc((size_t)n * 2));
-	HIPCHK(d_places.alloc((size_t)n * sizeof(bwb_place)));
-	if (n) {
-		HIPCHK(hipMemcpyAsync(d_reads.p, reads_fwd, (size_t)n * stride, hipMemcpyHostToDevice, c->rstream));
-		HIPCHK(hipMemcpyAsync(d_lens.p, lens, (size_t)n * 2, hipMemcpyHostToDevice, c->rstream));
-		HIPCHK(hipMemcpyAsync(d_places.p, places, (size_t)n * sizeof(bwb_place), hipMemcpyHostToDevice, c->rstream));
-	}
-	if (kinds) {
-		HIPCHK(d_kind.alloc((size_t)n));
-		HIPCHK(d_loff.alloc(((size_t)n + 1) * 8));
-		HIPCHK(d_lrecs.alloc((size_t)words * sizeof(bwb_lift)));
-		if (n) HIPCHK(hipMemcpyAsync(d_kind.p, kinds, (size_t)n, hipMemcpyHostToDevice, c->rstream));
-		HIPCHK(hipMemcpyAsync(d_loff.p, lift_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->rstream));
-		if (words) HIPCHK(hipMemcpyAsync(d_lrecs.p, lift_recs, (size_t)words * sizeof(bwb_lift), hipMemcpyHostToDevice, c->rstream));
-	}
-	HIPCHK(hipStreamSynchronize(c->rstream)); /* (pageable memory of the caller) */
-	RC(md_launch(c, d_reads.as<uint8_t>(), d_lens.as<uint16_t>(), stride, d_places.as<uint4>(), n, kinds ? d_kind.as<uint8_t>() : nullptr, d_loff.as<uint64_t>(), d_lrecs.as<uint4>(), c->md_rec));
+	StagedReads in;
+	RC(stage_reads(c, "md_records", reads_fwd, lens, stride, places, n, kinds, lift_off, lift_recs, in));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	RC(md_launch(c, in.reads.as<uint8_t>(), in.lens.as<uint16_t>(), stride, in.places.as<uint4>(), n, in.kind.as<uint8_t>(), in.loff.as<uint64_t>(), in.lrecs.as<uint4>(), c->md_rec));
 	*recs = c->md_rec.h_recs.as<bwb_md>();
 	*md_off = c->md_rec.h_off.as<uint64_t>();
 	*md_text = c->md_rec.h_text.as<char>();
@@ -2328,7 +2356,7 @@ extern "C" int bwb_hip_pile_begin(bwb_hip_ctx *c, uint64_t *n_sites) {
 	HIPCHK(hipStreamSynchronize(c->rstream)); /* (a pile kernel of an earlier call may still add to the counters that are replaced) */
 	c->pile_on = false; c->pile_sites = 0;
 	c->geno_on = false; c->geno_bub = false; /* (the calls were for this index and these counters) */
-	const unsigned nblk = (unsigned)((n_words + BWB_BLOCK - 1) / BWB_BLOCK);
+	const unsigned nblk = blocks_of(n_words);
 	DevMem d_bsum, d_total;
 	HIPCHK(c->d_site_base.alloc((size_t)n_words * 4));
 	HIPCHK(d_bsum.alloc((size_t)nblk * 8));
@@ -2359,13 +2387,11 @@ extern "C" int bwb_hip_pile_begin(bwb_hip_ctx *c, uint64_t *n_sites) {
 static int pile_launch(bwb_hip_ctx *c, const uint8_t *d_reads, const uint16_t *d_lens, uint32_t stride, const uint4 *d_places, uint32_t n, const uint8_t *d_kind, const uint64_t *d_loff,
                        const uint4 *d_lrecs, const uint8_t *d_mapq, uint32_t mapq_stride, int min_mapq) {
 	if (!n) return BWB_OK; /* (nothing launched: the figures of the last launch stay) */
-	const unsigned nblk = (unsigned)(((size_t)n + BWB_BLOCK - 1) / BWB_BLOCK);
-	const unsigned grid = (unsigned)std::min<size_t>(nblk, (size_t)c->num_cu * 8);
 	const uint32_t n_seq = d_kind ? c->loci_nseq : 0u;
 	HIPCHK(hipMemsetAsync(c->d_pile_stats.p, 0, 16, c->rstream));
 	Timed t(c, c->rstream);
 	RC(t.begin());
-	hipLaunchKernelGGL(k_pile, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, d_reads, d_lens, stride, d_places, n, d_kind, d_loff, d_lrecs, c->d_lstart.as<uint64_t>(), n_seq,
+	hipLaunchKernelGGL(k_pile, dim3(lane_grid(c, n)), dim3(BWB_BLOCK), 0, c->rstream, d_reads, d_lens, stride, d_places, n, d_kind, d_loff, d_lrecs, c->d_lstart.as<uint64_t>(), n_seq,
 	                   c->d_text.as<uint4>(), c->text_n, d_mapq, mapq_stride, (uint32_t)min_mapq, c->d_site_base.as<uint32_t>(), c->d_counts.as<uint32_t>(),
 	                   c->d_pile_stats.as<unsigned long long>());
 	HIPCHK(hipGetLastError());
@@ -2397,41 +2423,26 @@ extern "C" int bwb_hip_slot_pile(bwb_hip_ctx *c, int si, int max_mm, int max_alt
 	if (!c || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_pile: bad argument");
 	RC(pile_ready(c, "slot_pile", max_alt, lifted, joined, min_mapq));
 	if (reads_counted) *reads_counted = 0;
-	/* (each waits for the slot, refuses what slot_place refuses, and leaves its records in the slot's device memory) */
-	const bwb_place *places = nullptr;
-	uint32_t n = 0;
-	RC(bwb_hip_slot_place(c, si, max_mm, &places, &n));
+	RC(ensure_place(c, si, max_mm));
 	Slot &s = c->slots[si];
-	if (s.piled) return BWB_OK; /* (a submission is counted once) */
-	if (lifted) {
-		const uint8_t *kinds = nullptr;
-		const uint64_t *lift_off = nullptr;
-		const bwb_lift *lrecs = nullptr;
-		uint64_t nq = 0;
-		RC(bwb_hip_slot_lift(c, si, max_mm, max_alt, &kinds, &lift_off, &lrecs, &nq));
-	}
-	if (joined) {
-		const uint64_t *alt_off = nullptr;
-		const bwb_alt *alts = nullptr;
-		const bwb_locus *loci = nullptr;
-		const bwb_join *joins = nullptr;
-		RC(bwb_hip_slot_join(c, si, max_mm, max_alt, &places, &alt_off, &alts, &loci, &joins, &n));
-	}
-	n = s.n_reads; /* (not n_tot: a carried read that rides along behind the batch's reads has no record) */
+	if (s.stage.piled) return BWB_OK; /* (a submission is counted once) */
+	if (lifted) RC(ensure_lift(c, si, max_mm, max_alt));
+	if (joined) RC(ensure_join(c, si, max_mm, max_alt));
+	const uint32_t n = s.n_reads; /* (not n_tot: a carried read that rides along behind the batch's reads has no record) */
 	if (n) {
 		HIPCHK(hipStreamWaitEvent(c->rstream, s.ev_up.e, 0)); /* (the slot's reads, uploaded on the copy stream) */
 		RC(pile_launch(c, s.d_reads.as<uint8_t>(), s.d_lens.as<uint16_t>(), s.stride, s.d_place.as<uint4>(), n, lifted ? s.lift.d_kind.as<uint8_t>() : nullptr,
 		               s.lift.d_off.as<uint64_t>(), s.lift.d_recs.as<uint4>(), joined ? s.d_join.as<uint8_t>() + offsetof(bwb_join, mapq) : nullptr, (uint32_t)sizeof(bwb_join), min_mapq));
 		if (reads_counted) *reads_counted = c->pile_reads;
 	}
-	s.piled = true;
+	s.stage.piled = true;
 	return BWB_OK;
 }
 
 extern "C" int bwb_hip_batch_pile(bwb_hip_ctx *c, int max_mm, int max_alt, int lifted, int joined, int min_mapq, uint64_t *reads_counted) {
 	if (!c) return fail(BWB_E_ARG, "batch_pile: null context");
 	RC(pile_ready(c, "batch_pile", max_alt, lifted, joined, min_mapq));
-	if (!c->slots[0].submitted || !c->slots[0].complete) return fail(BWB_E_STATE, "batch_pile: batch_run has not completed");
+	RC(batch_ready(c, "batch_pile"));
 	return bwb_hip_slot_pile(c, 0, max_mm, max_alt, lifted, joined, min_mapq, reads_counted);
 }
 
@@ -2442,58 +2453,47 @@ extern "C" int bwb_hip_pile_records(bwb_hip_ctx *c, const uint8_t *reads_fwd, co
 	if ((kinds != nullptr) != (lift_off != nullptr)) return fail(BWB_E_ARG, "pile_records: the lift kinds and offsets come together");
 	if (min_mapq < 0 || min_mapq > 255) return fail(BWB_E_ARG, "pile_records: min_mapq must be 0..255");
 	if (!c->pile_on) return fail(BWB_E_STATE, "pile_records: no site index and counters (bwb_hip_pile_begin)");
-	if (kinds && !c->loci_nseq) return fail(BWB_E_STATE, "pile_records: lift records need the record table (bwb_hip_set_loci)");
-	uint64_t words = 0;
-	if (kinds) {
-		if (lift_off[0] != 0) return fail(BWB_E_ARG, "pile_records: lift_off[0] must be 0");
-		for (uint32_t r = 0; r < n; r++)
-			if (lift_off[r + 1] < lift_off[r]) return fail(BWB_E_ARG, "pile_records: lift_off does not ascend at read " + std::to_string(r));
-		words = lift_off[n];
-		if (words && !lift_recs) return fail(BWB_E_ARG, "pile_records: null argument");
-	}
+	StagedReads in;
+	DevMem d_mapq; /* (stays NULL without a MAPQ array, and without reads) */
+	RC(stage_reads(c, "pile_records", reads_fwd, lens, stride, places, n, kinds, lift_off, lift_recs, in));
+	if (mapq && n) RC(stage_in(c, d_mapq, mapq, (size_t)n));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	return pile_launch(c, in.reads.as<uint8_t>(), in.lens.as<uint16_t>(), stride, in.places.as<uint4>(), n, in.kind.as<uint8_t>(), in.loff.as<uint64_t>(), in.lrecs.as<uint4>(),
+	                   d_mapq.as<uint8_t>(), 1u, min_mapq);
+}
+
+/* The two counter tables, four 32-bit counters per entry: the sites' (pile_begin) and the bubbles' (indel_begin).  What the counts / put / reset calls
+ * of either need: the buffer, its entries, whether its *_begin has run, and the words of the messages. */
+struct CounterTable { const DevMem &buf; uint64_t entries; bool on; const char *missing, *unit; };
+static CounterTable site_counters(const bwb_hip_ctx *c) { return { c->d_counts, c->pile_sites, c->pile_on, "no site index and counters (bwb_hip_pile_begin)", "sites" }; }
+static CounterTable bubble_counters(const bwb_hip_ctx *c) { return { c->d_indel_counts, c->loci_nbub, c->indel_on, "no bubble table and counters (bwb_hip_indel_begin)", "bubbles" }; }
+/* n entries from `first` on, device to host or host to device (pageable memory of the caller: waits for the copy) */
+static int counters_copy(bwb_hip_ctx *c, const char *who, const CounterTable &t, uint64_t first, uint64_t n, const void *host, hipMemcpyKind kind) {
+	if (n && !host) return fail(BWB_E_ARG, std::string(who) + ": null argument");
+	if (!t.on) return fail(BWB_E_STATE, std::string(who) + ": " + t.missing);
+	if (first > t.entries || n > t.entries - first) return fail(BWB_E_ARG, std::string(who) + ": the range leaves the " + std::to_string(t.entries) + " " + t.unit);
 	HIPCHK(hipSetDevice(c->device));
-	DevMem d_reads, d_lens, d_places, d_kind, d_loff, d_lrecs, d_mapq;
-	HIPCHK(d_reads.alloc((size_t)n * stride));
-	HIPCHK(d_lens.alloc((size_t)n * 2));
-	HIPCHK(d_places.alloc((size_t)n * sizeof(bwb_place)));
-	if (n) {
-		HIPCHK(hipMemcpyAsync(d_reads.p, reads_fwd, (size_t)n * stride, hipMemcpyHostToDevice, c->rstream));
-		HIPCHK(hipMemcpyAsync(d_lens.p, lens, (size_t)n * 2, hipMemcpyHostToDevice, c->rstream));
-		HIPCHK(hipMemcpyAsync(d_places.p, places, (size_t)n * sizeof(bwb_place), hipMemcpyHostToDevice, c->rstream));
-	}
-	if (kinds) {
-		HIPCHK(d_kind.alloc((size_t)n));
-		HIPCHK(d_loff.alloc(((size_t)n + 1) * 8));
-		HIPCHK(d_lrecs.alloc((size_t)words * sizeof(bwb_lift)));
-		if (n) HIPCHK(hipMemcpyAsync(d_kind.p, kinds, (size_t)n, hipMemcpyHostToDevice, c->rstream));
-		HIPCHK(hipMemcpyAsync(d_loff.p, lift_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->rstream));
-		if (words) HIPCHK(hipMemcpyAsync(d_lrecs.p, lift_recs, (size_t)words * sizeof(bwb_lift), hipMemcpyHostToDevice, c->rstream));
-	}
-	if (mapq && n) {
-		HIPCHK(d_mapq.alloc((size_t)n));
-		HIPCHK(hipMemcpyAsync(d_mapq.p, mapq, (size_t)n, hipMemcpyHostToDevice, c->rstream));
-	}
-	HIPCHK(hipStreamSynchronize(c->rstream)); /* (pageable memory of the caller) */
-	return pile_launch(c, d_reads.as<uint8_t>(), d_lens.as<uint16_t>(), stride, d_places.as<uint4>(), n, kinds ? d_kind.as<uint8_t>() : nullptr, d_loff.as<uint64_t>(), d_lrecs.as<uint4>(),
-	                   mapq && n ? d_mapq.as<uint8_t>() : nullptr, 1u, min_mapq);
+	void *dev = t.buf.as<uint32_t>() + first * 4, *h = const_cast<void *>(host); /* (written device to host only: the counts calls' pointer is not const) */
+	const bool put = kind == hipMemcpyHostToDevice;
+	if (n) HIPCHK(hipMemcpyAsync(put ? dev : h, put ? h : dev, (size_t)n * 16, kind, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	return BWB_OK;
+}
+static int counters_reset(bwb_hip_ctx *c, const char *who, const CounterTable &t) {
+	if (!t.on) return fail(BWB_E_STATE, std::string(who) + ": " + t.missing);
+	HIPCHK(hipSetDevice(c->device));
+	if (t.entries) HIPCHK(hipMemsetAsync(t.buf.p, 0, (size_t)t.entries * 16, c->rstream));
+	return BWB_OK;
 }
 
 extern "C" int bwb_hip_pile_counts(bwb_hip_ctx *c, uint64_t first, uint64_t n, uint32_t *out) {
-	if (!c || (n && !out)) return fail(BWB_E_ARG, "pile_counts: null argument");
-	if (!c->pile_on) return fail(BWB_E_STATE, "pile_counts: no site index and counters (bwb_hip_pile_begin)");
-	if (first > c->pile_sites || n > c->pile_sites - first) return fail(BWB_E_ARG, "pile_counts: the range leaves the " + std::to_string(c->pile_sites) + " sites");
-	HIPCHK(hipSetDevice(c->device));
-	if (n) HIPCHK(hipMemcpyAsync(out, c->d_counts.as<uint32_t>() + first * 4, (size_t)n * 16, hipMemcpyDeviceToHost, c->rstream));
-	HIPCHK(hipStreamSynchronize(c->rstream));
-	return BWB_OK;
+	if (!c) return fail(BWB_E_ARG, "pile_counts: null argument");
+	return counters_copy(c, "pile_counts", site_counters(c), first, n, out, hipMemcpyDeviceToHost);
 }
 
 extern "C" int bwb_hip_pile_reset(bwb_hip_ctx *c) {
 	if (!c) return fail(BWB_E_ARG, "pile_reset: null context");
-	if (!c->pile_on) return fail(BWB_E_STATE, "pile_reset: no site index and counters (bwb_hip_pile_begin)");
-	HIPCHK(hipSetDevice(c->device));
-	if (c->pile_sites) HIPCHK(hipMemsetAsync(c->d_counts.p, 0, (size_t)c->pile_sites * 16, c->rstream));
-	return BWB_OK;
+	return counters_reset(c, "pile_reset", site_counters(c));
 }
 
 extern "C" int bwb_hip_pile_site_of(bwb_hip_ctx *c, const uint64_t *pos, size_t n, int64_t *site) {
@@ -2507,8 +2507,7 @@ extern "C" int bwb_hip_pile_site_of(bwb_hip_ctx *c, const uint64_t *pos, size_t 
 	HIPCHK(dp.alloc(n * 8));
 	HIPCHK(dout.alloc(n * 8));
 	HIPCHK(hipMemcpyAsync(dp.p, pos, n * 8, hipMemcpyHostToDevice, c->rstream));
-	const unsigned grid = (unsigned)std::min<size_t>((n + BWB_BLOCK - 1) / BWB_BLOCK, (size_t)c->num_cu * 8);
-	hipLaunchKernelGGL(k_site_of, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, c->d_text.as<uint4>(), c->d_site_base.as<uint32_t>(), dp.as<uint64_t>(), (uint64_t)n, dout.as<int64_t>());
+	hipLaunchKernelGGL(k_site_of, dim3(lane_grid(c, n)), dim3(BWB_BLOCK), 0, c->rstream, c->d_text.as<uint4>(), c->d_site_base.as<uint32_t>(), dp.as<uint64_t>(), (uint64_t)n, dout.as<int64_t>());
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(site, dout.p, n * 8, hipMemcpyDeviceToHost, c->rstream));
 	HIPCHK(hipStreamSynchronize(c->rstream));
@@ -2562,9 +2561,8 @@ extern "C" int bwb_hip_indel_begin(bwb_hip_ctx *c, int anchor, uint64_t *n_eligi
 	HIPCHK(hipMemcpyAsync(c->d_indel_elig.p, elig.data(), elig.size(), hipMemcpyHostToDevice, c->rstream));
 	if (n_bub) HIPCHK(hipMemsetAsync(c->d_indel_counts.p, 0, (size_t)n_bub * 16, c->rstream));
 	HIPCHK(hipStreamSynchronize(c->rstream)); /* (pageable memory of this function) */
-	uint32_t trips = 0;
-	while (((uint64_t)1 << trips) <= tab.size()) trips++;
-	c->indel_anchor = (uint32_t)anchor; c->indel_ntab = (uint32_t)tab.size(); c->indel_trips = trips;
+	/* (one step more than a bisection over the entries when their number is a power of two: the first power of two ABOVE it) */
+	c->indel_anchor = (uint32_t)anchor; c->indel_ntab = (uint32_t)tab.size(); c->indel_trips = ceil_log2((uint64_t)tab.size() + 1);
 	c->indel_ms = 0; c->indel_reads = 0; c->indel_adds = 0; c->indel_cands = 0;
 	c->indel_on = true;
 	*n_eligible = tab.size();
@@ -2576,12 +2574,10 @@ extern "C" int bwb_hip_indel_begin(bwb_hip_ctx *c, int anchor, uint64_t *n_eligi
  * kernels that wrote the records.  What comes back is the 24 bytes of the three sums. */
 static int indel_launch(bwb_hip_ctx *c, const uint4 *d_places, const uint4 *d_loci, uint32_t n, const uint16_t *d_lens, const uint8_t *d_mapq, uint32_t mapq_stride, int min_mapq) {
 	if (!n) return BWB_OK; /* (nothing launched: the figures of the last launch stay) */
-	const unsigned nblk = (unsigned)(((size_t)n + BWB_BLOCK - 1) / BWB_BLOCK);
-	const unsigned grid = (unsigned)std::min<size_t>(nblk, (size_t)c->num_cu * 8);
 	HIPCHK(hipMemsetAsync(c->d_indel_stats.p, 0, 24, c->rstream));
 	Timed t(c, c->rstream);
 	RC(t.begin());
-	hipLaunchKernelGGL(k_indel, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, d_places, d_loci, n, d_lens, d_mapq, mapq_stride, (uint32_t)min_mapq, c->d_bubbles.as<uint64_t>(),
+	hipLaunchKernelGGL(k_indel, dim3(lane_grid(c, n)), dim3(BWB_BLOCK), 0, c->rstream, d_places, d_loci, n, d_lens, d_mapq, mapq_stride, (uint32_t)min_mapq, c->d_bubbles.as<uint64_t>(),
 	                   c->d_indel_elig.as<uint8_t>(), c->indel_anchor, c->d_indel_tab.as<uint4>(), c->indel_ntab, c->indel_trips, c->d_indel_counts.as<uint32_t>(),
 	                   c->d_indel_stats.as<unsigned long long>());
 	HIPCHK(hipGetLastError());
@@ -2613,34 +2609,25 @@ extern "C" int bwb_hip_slot_indel(bwb_hip_ctx *c, int si, int max_mm, int max_al
 	if (!c || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_indel: bad argument");
 	RC(indel_ready(c, "slot_indel", max_alt, joined, min_mapq));
 	if (reads_counted) *reads_counted = 0;
-	/* (each waits for the slot, refuses what slot_place refuses, and leaves its records in the slot's device memory) */
-	const bwb_place *places = nullptr;
-	const bwb_locus *loci = nullptr;
-	uint32_t n = 0;
-	RC(bwb_hip_slot_locus(c, si, max_mm, &places, &loci, &n));
+	RC(ensure_locus(c, si, max_mm));
 	Slot &s = c->slots[si];
-	if (s.indeled) return BWB_OK; /* (a submission is counted once) */
-	if (joined) {
-		const uint64_t *alt_off = nullptr;
-		const bwb_alt *alts = nullptr;
-		const bwb_join *joins = nullptr;
-		RC(bwb_hip_slot_join(c, si, max_mm, max_alt, &places, &alt_off, &alts, &loci, &joins, &n));
-	}
-	n = s.n_reads; /* (not n_tot: a carried read that rides along behind the batch's reads has no record) */
+	if (s.stage.indeled) return BWB_OK; /* (a submission is counted once) */
+	if (joined) RC(ensure_join(c, si, max_mm, max_alt));
+	const uint32_t n = s.n_reads; /* (not n_tot: a carried read that rides along behind the batch's reads has no record) */
 	if (n) {
 		HIPCHK(hipStreamWaitEvent(c->rstream, s.ev_up.e, 0)); /* (the slot's read lengths, uploaded on the copy stream) */
 		RC(indel_launch(c, s.d_place.as<uint4>(), s.d_locus.as<uint4>(), n, s.d_lens.as<uint16_t>(), joined ? s.d_join.as<uint8_t>() + offsetof(bwb_join, mapq) : nullptr,
 		                (uint32_t)sizeof(bwb_join), min_mapq));
 		if (reads_counted) *reads_counted = c->indel_reads;
 	}
-	s.indeled = true;
+	s.stage.indeled = true;
 	return BWB_OK;
 }
 
 extern "C" int bwb_hip_batch_indel(bwb_hip_ctx *c, int max_mm, int max_alt, int joined, int min_mapq, uint64_t *reads_counted) {
 	if (!c) return fail(BWB_E_ARG, "batch_indel: null context");
 	RC(indel_ready(c, "batch_indel", max_alt, joined, min_mapq));
-	if (!c->slots[0].submitted || !c->slots[0].complete) return fail(BWB_E_STATE, "batch_indel: batch_run has not completed");
+	RC(batch_ready(c, "batch_indel"));
 	return bwb_hip_slot_indel(c, 0, max_mm, max_alt, joined, min_mapq, reads_counted);
 }
 
@@ -2652,35 +2639,23 @@ extern "C" int bwb_hip_indel_records(bwb_hip_ctx *c, const bwb_place *places, ui
 	if (!n) return BWB_OK;
 	HIPCHK(hipSetDevice(c->device));
 	DevMem d_places, d_loci, d_mapq;
-	HIPCHK(d_places.alloc((size_t)n * sizeof(bwb_place)));
+	RC(stage_in(c, d_places, places, (size_t)n * sizeof(bwb_place)));
+	if (mapq) RC(stage_in(c, d_mapq, mapq, (size_t)n));
 	HIPCHK(d_loci.alloc((size_t)n * sizeof(bwb_locus)));
-	HIPCHK(hipMemcpyAsync(d_places.p, places, (size_t)n * sizeof(bwb_place), hipMemcpyHostToDevice, c->rstream));
-	if (mapq) {
-		HIPCHK(d_mapq.alloc((size_t)n));
-		HIPCHK(hipMemcpyAsync(d_mapq.p, mapq, (size_t)n, hipMemcpyHostToDevice, c->rstream));
-	}
-	HIPCHK(hipStreamSynchronize(c->rstream)); /* (pageable memory of the caller) */
+	HIPCHK(hipStreamSynchronize(c->rstream));
 	std::vector<bwb_locus> h_loci(n);
 	RC(locus_launch(c, d_places.as<uint4>(), n, d_loci.as<uint4>(), h_loci.data()));
-	return indel_launch(c, d_places.as<uint4>(), d_loci.as<uint4>(), n, nullptr, mapq ? d_mapq.as<uint8_t>() : nullptr, 1u, min_mapq);
+	return indel_launch(c, d_places.as<uint4>(), d_loci.as<uint4>(), n, nullptr, d_mapq.as<uint8_t>(), 1u, min_mapq);
 }
 
 extern "C" int bwb_hip_indel_counts(bwb_hip_ctx *c, uint64_t first, uint64_t n, uint32_t *out) {
-	if (!c || (n && !out)) return fail(BWB_E_ARG, "indel_counts: null argument");
-	if (!c->indel_on) return fail(BWB_E_STATE, "indel_counts: no bubble table and counters (bwb_hip_indel_begin)");
-	if (first > c->loci_nbub || n > c->loci_nbub - first) return fail(BWB_E_ARG, "indel_counts: the range leaves the " + std::to_string(c->loci_nbub) + " bubbles");
-	HIPCHK(hipSetDevice(c->device));
-	if (n) HIPCHK(hipMemcpyAsync(out, c->d_indel_counts.as<uint32_t>() + first * 4, (size_t)n * 16, hipMemcpyDeviceToHost, c->rstream));
-	HIPCHK(hipStreamSynchronize(c->rstream));
-	return BWB_OK;
+	if (!c) return fail(BWB_E_ARG, "indel_counts: null argument");
+	return counters_copy(c, "indel_counts", bubble_counters(c), first, n, out, hipMemcpyDeviceToHost);
 }
 
 extern "C" int bwb_hip_indel_reset(bwb_hip_ctx *c) {
 	if (!c) return fail(BWB_E_ARG, "indel_reset: null context");
-	if (!c->indel_on) return fail(BWB_E_STATE, "indel_reset: no bubble table and counters (bwb_hip_indel_begin)");
-	HIPCHK(hipSetDevice(c->device));
-	if (c->loci_nbub) HIPCHK(hipMemsetAsync(c->d_indel_counts.p, 0, (size_t)c->loci_nbub * 16, c->rstream));
-	return BWB_OK;
+	return counters_reset(c, "indel_reset", bubble_counters(c));
 }
 
 /* the last indel call that launched: reads counted, adds made, candidates examined, and the kernel's HIP-event time */
@@ -2703,11 +2678,10 @@ extern "C" int bwb_hip_geno_begin(bwb_hip_ctx *c, uint32_t piece) {
 	HIPCHK(hipSetDevice(c->device));
 	HIPCHK(hipStreamSynchronize(c->rstream)); /* (a geno kernel of an earlier call may still use the buffers that are replaced) */
 	c->geno_on = false; c->geno_bub = false;
-	const size_t nblk = ((size_t)piece + BWB_BLOCK - 1) / BWB_BLOCK;
 	HIPCHK(c->d_geno_cnt.alloc((size_t)piece * 4));
 	HIPCHK(c->d_geno_word.alloc((size_t)piece * 4));
 	HIPCHK(c->d_geno_off.alloc(((size_t)piece + 1) * 8));
-	HIPCHK(c->d_geno_bsum.alloc(nblk * 8));
+	HIPCHK(c->d_geno_bsum.alloc((size_t)blocks_of(piece) * 8));
 	HIPCHK(c->d_geno_sites.alloc((size_t)piece * sizeof(bwb_geno_site)));
 	HIPCHK(c->h_geno_sites.reserve((size_t)piece * sizeof(bwb_geno_site)));
 	HIPCHK(c->h_geno_n.reserve(8));
@@ -2725,22 +2699,12 @@ extern "C" int bwb_hip_geno_begin(bwb_hip_ctx *c, uint32_t piece) {
 
 /* the mirrors of pile_counts / indel_counts: overwrite the counters of a range (several workers' sums meet on one device; tests inject counts) */
 extern "C" int bwb_hip_pile_put(bwb_hip_ctx *c, uint64_t first, uint64_t n, const uint32_t *counts) {
-	if (!c || (n && !counts)) return fail(BWB_E_ARG, "pile_put: null argument");
-	if (!c->pile_on) return fail(BWB_E_STATE, "pile_put: no site index and counters (bwb_hip_pile_begin)");
-	if (first > c->pile_sites || n > c->pile_sites - first) return fail(BWB_E_ARG, "pile_put: the range leaves the " + std::to_string(c->pile_sites) + " sites");
-	HIPCHK(hipSetDevice(c->device));
-	if (n) HIPCHK(hipMemcpyAsync(c->d_counts.as<uint32_t>() + first * 4, counts, (size_t)n * 16, hipMemcpyHostToDevice, c->rstream));
-	HIPCHK(hipStreamSynchronize(c->rstream)); /* (pageable memory of the caller) */
-	return BWB_OK;
+	if (!c) return fail(BWB_E_ARG, "pile_put: null argument");
+	return counters_copy(c, "pile_put", site_counters(c), first, n, counts, hipMemcpyHostToDevice);
 }
 extern "C" int bwb_hip_indel_put(bwb_hip_ctx *c, uint64_t first, uint64_t n, const uint32_t *counts) {
-	if (!c || (n && !counts)) return fail(BWB_E_ARG, "indel_put: null argument");
-	if (!c->indel_on) return fail(BWB_E_STATE, "indel_put: no bubble table and counters (bwb_hip_indel_begin)");
-	if (first > c->loci_nbub || n > c->loci_nbub - first) return fail(BWB_E_ARG, "indel_put: the range leaves the " + std::to_string(c->loci_nbub) + " bubbles");
-	HIPCHK(hipSetDevice(c->device));
-	if (n) HIPCHK(hipMemcpyAsync(c->d_indel_counts.as<uint32_t>() + first * 4, counts, (size_t)n * 16, hipMemcpyHostToDevice, c->rstream));
-	HIPCHK(hipStreamSynchronize(c->rstream));
-	return BWB_OK;
+	if (!c) return fail(BWB_E_ARG, "indel_put: null argument");
+	return counters_copy(c, "indel_put", bubble_counters(c), first, n, counts, hipMemcpyHostToDevice);
 }
 
 static int geno_args(bwb_hip_ctx *c, const char *who, uint64_t first, uint64_t n, int err, int64_t min_depth, uint64_t table, uint32_t piece) {
@@ -2752,15 +2716,7 @@ static int geno_args(bwb_hip_ctx *c, const char *who, uint64_t first, uint64_t n
 	return BWB_OK;
 }
 /* the scan of cnt[0 .. n) and the read-back of what the emit kernel wrote: the total first (8 bytes), then that many records */
-static int geno_scan(bwb_hip_ctx *c, uint32_t n) {
-	const unsigned nblk = (unsigned)(((size_t)n + BWB_BLOCK - 1) / BWB_BLOCK);
-	uint64_t *d_off = c->d_geno_off.as<uint64_t>();
-	hipLaunchKernelGGL(k_scan_blocks, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, c->d_geno_cnt.as<uint32_t>(), n, d_off, c->d_geno_bsum.as<uint64_t>());
-	hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(BWB_BLOCK), 0, c->rstream, c->d_geno_bsum.as<uint64_t>(), (uint32_t)nblk, d_off + n);
-	hipLaunchKernelGGL(k_scan_add, dim3(nblk), dim3(BWB_BLOCK), 0, c->rstream, d_off, n, c->d_geno_bsum.as<uint64_t>());
-	HIPCHK(hipGetLastError());
-	return BWB_OK;
-}
+static void geno_scan(bwb_hip_ctx *c, uint32_t n) { scan_offsets(c, c->d_geno_cnt.as<uint32_t>(), n, c->d_geno_off.as<uint64_t>(), c->d_geno_bsum.as<uint64_t>()); }
 static int geno_fetch(bwb_hip_ctx *c, Timed &t, uint32_t n, const void *d_recs, void *h_recs, size_t rec_bytes, uint64_t *n_out) {
 	HIPCHK(hipMemcpyAsync(c->h_geno_n.p, c->d_geno_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, c->rstream));
 	HIPCHK(hipStreamSynchronize(c->rstream));
@@ -2784,14 +2740,12 @@ extern "C" int bwb_hip_geno_sites(bwb_hip_ctx *c, uint64_t first, uint64_t n, in
 	HIPCHK(hipSetDevice(c->device));
 	const uint64_t n_words64 = (c->text_n + 31) / 32;
 	const uint32_t n_words = (uint32_t)n_words64, nn = (uint32_t)n;
-	uint32_t trips = 0;
-	while (((uint64_t)1 << trips) < n_words64) trips++;
-	const unsigned grid = (unsigned)std::min<size_t>(((size_t)nn + BWB_BLOCK - 1) / BWB_BLOCK, (size_t)c->num_cu * 8);
+	const unsigned grid = lane_grid(c, nn);
 	Timed t(c, c->rstream);
 	RC(t.begin());
-	hipLaunchKernelGGL(k_geno_count, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, c->d_text.as<uint4>(), c->d_site_base.as<uint32_t>(), n_words, trips, c->d_counts.as<uint4>(), first, nn,
+	hipLaunchKernelGGL(k_geno_count, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, c->d_text.as<uint4>(), c->d_site_base.as<uint32_t>(), n_words, ceil_log2(n_words64), c->d_counts.as<uint4>(), first, nn,
 	                   (uint64_t)min_depth, c->d_geno_cnt.as<uint32_t>(), c->d_geno_word.as<uint32_t>());
-	RC(geno_scan(c, nn));
+	geno_scan(c, nn);
 	hipLaunchKernelGGL(k_geno_emit, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, c->d_text.as<uint4>(), c->d_site_base.as<uint32_t>(), n_words, c->d_counts.as<uint4>(), first, nn,
 	                   (uint64_t)min_depth, (uint32_t)err, c->d_geno_cnt.as<uint32_t>(), c->d_geno_word.as<uint32_t>(), c->d_geno_off.as<uint64_t>(), c->d_geno_sites.as<uint4>());
 	HIPCHK(hipGetLastError());
@@ -2810,12 +2764,12 @@ extern "C" int bwb_hip_geno_bubbles(bwb_hip_ctx *c, uint64_t first, uint64_t n, 
 	if (!n) return BWB_OK;
 	HIPCHK(hipSetDevice(c->device));
 	const uint32_t nn = (uint32_t)n;
-	const unsigned grid = (unsigned)std::min<size_t>(((size_t)nn + BWB_BLOCK - 1) / BWB_BLOCK, (size_t)c->num_cu * 8);
+	const unsigned grid = lane_grid(c, nn);
 	Timed t(c, c->rstream);
 	RC(t.begin());
 	hipLaunchKernelGGL(k_geno_bubbles, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, c->d_indel_elig.as<uint8_t>(), c->d_indel_counts.as<uint4>(), (uint32_t)first, nn, (uint64_t)min_depth,
 	                   (uint32_t)err, c->d_geno_cnt.as<uint32_t>(), (const uint64_t *)nullptr, (uint4 *)nullptr);
-	RC(geno_scan(c, nn));
+	geno_scan(c, nn);
 	hipLaunchKernelGGL(k_geno_bubbles, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, c->d_indel_elig.as<uint8_t>(), c->d_indel_counts.as<uint4>(), (uint32_t)first, nn, (uint64_t)min_depth,
 	                   (uint32_t)err, c->d_geno_cnt.as<uint32_t>(), (const uint64_t *)c->d_geno_off.as<uint64_t>(), c->d_geno_bubs.as<uint4>());
 	HIPCHK(hipGetLastError());
