@@ -35,6 +35,7 @@ typedef struct chunk {
 	uint8_t *carry; uint32_t carry_len; /* the last read before the chunk that computes a D_seed (NULL: none), a copy */
 	unsigned char *buf; size_t buf_len; uint32_t n; /* the chunk's .aln records, serialised by the worker that received its hits */
 	char **sam; size_t *sam_len; size_t n_sam;      /* map: the chunk's SAM text instead, in blocks of SAM_BLOCK_READS reads */
+	host_recs_t host;                               /* map: what the host's stages allocated for the chunk's records, until its text is formatted */
 	size_t first_read;                              /* number of the chunk's first read in the file */
 	int ready;
 	struct chunk *next;            /* production order */
@@ -42,11 +43,13 @@ typedef struct chunk {
 
 /* what `map` adds to the pipeline (NULL: align) */
 typedef struct {
-	int max_mm; int max_alt /* -X (0: no tags) */; const fasta_annotations_t *ann; int ann_sorted;
-	/* -B (bub NULL: no tags): the bubble table, every .ann record's bubble number, and - when the records are ascending and disjoint, so that
-	 * kernel k_locus can search them (gpu_loci) - their first and last positions as the arrays bwb_hip_set_loci takes */
-	const bubble_table_t *bub; const int32_t *bubble_of; int gpu_loci; const uint64_t *rec_start, *rec_end;
-	const int32_t *chrom_of;  /* -J, -R (NULL: neither): the chromosome's record of every bubble; needs bub */
+	int max_mm; int max_alt /* -X (0: no tags) */;
+	/* the .ann records; -B (T.bub NULL: no tags): the bubble table and every record's bubble number; -J, -R, -I (T.chrom_of NULL: none of them):
+	 * the chromosome's record of every bubble */
+	host_tables_t T;
+	/* -B: when the records are ascending and disjoint, so that kernel k_locus can search them (gpu_loci) - their first and last positions as
+	 * the arrays bwb_hip_set_loci takes */
+	int gpu_loci; const uint64_t *rec_start, *rec_end;
 	int join;                 /* -J: a read's placements counted by locus; needs max_alt and bub */
 	int lift;                 /* -R: placements on a bubble record written in chromosome coordinates; needs bub */
 	md_text_t *text;          /* -D, -A (NULL: neither): the forward text of <seq_fasta>.ref */
@@ -148,140 +151,152 @@ static void chunk_ready(pipe_t *pp, chunk_t *c) {
 	pthread_mutex_unlock(&pp->mu);
 }
 
+/* a C-ABI call of a worker: on failure the run ends with the caller's prefix, the worker's number (retire, retire_map: w->gpu) or its device
+ * (gpu_worker: w->device), and the library's message */
+static void gpu_ok(int failed, const char *who, int id) {
+	if (failed) bwb_die("%s: GPU %d: %s", who, id, bwb_hip_last_error());
+}
+
 /* hands the finished chunk in `slot` to the writer */
 static void retire(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c) {
 	bwb_result r;
-	if (bwb_hip_slot_result(ctx, slot, &r)) bwb_die("align_reads_inexact_gpu: GPU %d: %s", w->gpu, bwb_hip_last_error());
+	gpu_ok(bwb_hip_slot_result(ctx, slot, &r), "align_reads_inexact_gpu", w->gpu);
 	c->n = r.n_reads;
 	c->buf = alns2alnf_buf(r.alns, r.aln_off, r.n_reads, &c->buf_len); /* (with all cores; the library's result buffers stay valid until the slot is uploaded again) */
 	chunk_ready(w->pp, c);
 }
 
-/* map: the same hand-over with the chunk's SAM text.  The reads are evaluated where their hits lie (kernel k_place); what comes back is one
- * placement record per read, and the worker's team formats the text. */
-static void retire_map(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c) {
+/* map: the stages of a finished chunk on the result stream, one per flag.  Each takes the worker, its context, the slot, the chunk and the
+ * carrier of the chunk's records (rd: a stage reads what the stages before it put there), holds the GPU's branch and the host's - the slot's
+ * records are cached, so nothing is evaluated twice; what the host allocates the chunk keeps (c->host) - and adds to the worker's figures. */
+
+/* the reads are evaluated where their hits lie (kernel k_place; -X: with their other placements): one placement record per read comes back */
+static void stage_place(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c, sam_reads_t *rd) {
 	const map_t *m = w->pp->map;
-	const bwb_place *pl = NULL;
-	uint32_t n = 0;
-	const uint64_t *alt_off = NULL;
-	const bwb_alt *alts = NULL;
-	if (m->max_alt ? bwb_hip_slot_place_alt(ctx, slot, m->max_mm, m->max_alt, &pl, &alt_off, &alts, &n) : bwb_hip_slot_place(ctx, slot, m->max_mm, &pl, &n))
-		bwb_die("map_reads: GPU %d: %s", w->gpu, bwb_hip_last_error());
+	gpu_ok(m->max_alt ? bwb_hip_slot_place_alt(ctx, slot, m->max_mm, m->max_alt, &rd->pl, &rd->alt_off, &rd->alts, &c->n) : bwb_hip_slot_place(ctx, slot, m->max_mm, &rd->pl, &c->n), "map_reads", w->gpu);
+	rd->lift_n = c->n;
 	{ uint64_t st = 0; double ms = 0; bwb_hip_place_stats(ctx, NULL, &st, &ms); w->place_ms += ms; w->place_steps += st; }
 	if (m->max_alt) { uint64_t it = 0, st = 0; double ms = 0; bwb_hip_place_alt_stats(ctx, &it, &st, &ms); w->alt_ms += ms; w->alt_steps += st; w->alt_items += it; }
-	/* -B: the loci of the same records, resolved where they lie (kernel k_locus behind k_place on the result stream; the slot's placement
-	 * records are cached, so nothing is evaluated twice); on an .ann that is not ascending and disjoint, by the host's resolver */
-	const bwb_locus *loci = NULL;
-	bwb_locus *host_loci = NULL;
-	if (m->bub && m->gpu_loci) {
-		if (bwb_hip_slot_locus(ctx, slot, m->max_mm, &pl, &loci, &n)) bwb_die("map_reads: GPU %d: %s", w->gpu, bwb_hip_last_error());
-		uint64_t nr = 0; double ms = 0;
-		bwb_hip_locus_stats(ctx, &nr, &ms);
-		w->locus_ms += ms; w->locus_reads += nr;
-	} else if (m->bub) {
-		loci = host_loci = (bwb_locus *)malloc((n ? n : 1) * sizeof(bwb_locus));
-#pragma omp parallel for schedule(static) num_threads(bwb_host_team())
-		for (long r = 0; r < (long)n; r++) locus_resolve(&pl[r], m->ann, m->ann_sorted, m->bubble_of, m->bub, &host_loci[r]);
-	}
-	/* -J: the items that lie where the primary lies, from the items and loci the slot already holds (kernels k_join_items / k_join_reads behind
-	 * k_locus on the result stream); with the host's loci, the host's rule - the suboptimal bit then needs the hits' scores (slot_result) */
-	const bwb_join *joins = NULL;
-	bwb_join *host_joins = NULL;
-	if (m->join && m->gpu_loci) {
-		if (bwb_hip_slot_join(ctx, slot, m->max_mm, m->max_alt, &pl, &alt_off, &alts, &loci, &joins, &n)) bwb_die("map_reads: GPU %d: %s", w->gpu, bwb_hip_last_error());
+}
+
+/* -B: the loci of the same records, resolved where they lie (kernel k_locus behind k_place); on an .ann that is not ascending and disjoint, by
+ * the host's resolver */
+static void stage_locus(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c, sam_reads_t *rd) {
+	const map_t *m = w->pp->map;
+	if (!m->gpu_loci) { rd->loci = c->host.loci = host_loci(rd, c->n, &m->T); return; }
+	uint64_t nr = 0; double ms = 0;
+	gpu_ok(bwb_hip_slot_locus(ctx, slot, m->max_mm, &rd->pl, &rd->loci, &c->n), "map_reads", w->gpu);
+	bwb_hip_locus_stats(ctx, &nr, &ms);
+	w->locus_ms += ms; w->locus_reads += nr;
+}
+
+/* -J: the items that lie where the primary lies, from the items and loci the slot already holds (kernels k_join_items / k_join_reads behind
+ * k_locus); with the host's loci, the host's rule - the suboptimal byte then needs the hits' scores (slot_result) */
+static void stage_join(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c, sam_reads_t *rd) {
+	const map_t *m = w->pp->map;
+	if (m->gpu_loci) {
 		uint64_t it = 0, jn = 0; double ms = 0;
+		gpu_ok(bwb_hip_slot_join(ctx, slot, m->max_mm, m->max_alt, &rd->pl, &rd->alt_off, &rd->alts, &rd->loci, &rd->joins, &c->n), "map_reads", w->gpu);
 		bwb_hip_join_stats(ctx, &it, &jn, &ms);
 		w->join_ms += ms; w->join_items += it; w->join_joined += jn;
-	} else if (m->join) {
+	} else {
 		bwb_result res;
-		if (bwb_hip_slot_result(ctx, slot, &res)) bwb_die("map_reads: GPU %d: %s", w->gpu, bwb_hip_last_error());
-		uint8_t *sub = (uint8_t *)malloc(alt_off[n] ? alt_off[n] : 1);
-		joins = host_joins = (bwb_join *)malloc((n ? n : 1) * sizeof(bwb_join));
-#pragma omp parallel for schedule(static) num_threads(bwb_host_team())
-		for (long r = 0; r < (long)n; r++) {
-			for (uint64_t q = alt_off[r]; q < alt_off[r + 1]; q++) sub[q] = res.alns[res.aln_off[r] + alts[q].hit].score > res.alns[res.aln_off[r]].score;
-			join_resolve(&pl[r], &loci[r], alts + alt_off[r], sub + alt_off[r], alt_off[r + 1] - alt_off[r], m->ann, m->ann_sorted, m->bubble_of, m->chrom_of, m->bub, m->max_mm, &host_joins[r]);
-		}
-		free(sub);
+		gpu_ok(bwb_hip_slot_result(ctx, slot, &res), "map_reads", w->gpu);
+		rd->joins = c->host.joins = host_joins(rd, c->n, &m->T, m->max_mm, NULL, res.alns, res.aln_off);
 	}
-	if (joins) { /* the log line's counts, with the team */
-		unsigned long long changed = 0, joined = 0;
+	unsigned long long changed = 0, joined = 0; /* the log line's counts, with the team */
 #pragma omp parallel for schedule(static) reduction(+ : changed, joined) num_threads(bwb_host_team())
-		for (long r = 0; r < (long)n; r++) { changed += joins[r].mapq != pl[r].mapq; joined += joins[r].joined; }
-		w->join_mapq += changed;
-		if (!m->gpu_loci) w->join_joined += joined; /* (on the GPU path join_stats has counted them) */
-	}
-	/* -R: RNAME, POS and CIGAR of the placements on bubble records, from the records and loci the slot already holds (kernels k_lift_count / k_lift
-	 * behind them on the result stream); with the host's loci, the host's rule */
-	const uint8_t *lift_kind = NULL;
-	const uint64_t *lift_off = NULL;
-	const bwb_lift *lift_recs = NULL;
-	lift_set_t *host_lift = NULL;
-	if (m->lift && m->gpu_loci) {
+	for (long r = 0; r < (long)c->n; r++) { changed += rd->joins[r].mapq != rd->pl[r].mapq; joined += rd->joins[r].joined; }
+	w->join_mapq += changed;
+	if (!m->gpu_loci) w->join_joined += joined; /* (on the GPU path join_stats has counted them) */
+}
+
+/* -R: RNAME, POS and CIGAR of the placements on bubble records, from the records and loci the slot already holds (kernels k_lift_count / k_lift
+ * behind them); with the host's loci, the host's rule */
+static void stage_lift(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c, sam_reads_t *rd) {
+	const map_t *m = w->pp->map;
+	if (m->gpu_loci) {
 		uint64_t nq = 0, nl = 0, nu = 0; double ms = 0;
-		if (bwb_hip_slot_lift(ctx, slot, m->max_mm, m->max_alt, &lift_kind, &lift_off, &lift_recs, &nq)) bwb_die("map_reads: GPU %d: %s", w->gpu, bwb_hip_last_error());
+		gpu_ok(bwb_hip_slot_lift(ctx, slot, m->max_mm, m->max_alt, &rd->lift_kind, &rd->lift_off, &rd->lift_recs, &nq), "map_reads", w->gpu);
 		bwb_hip_lift_stats(ctx, &nl, &nu, &ms);
 		w->lift_ms += ms; w->lift_lifted += nl; w->lift_unliftable += nu;
-		w->lift_bytes += nq + (nq + 1) * 8 + lift_off[nq] * sizeof(bwb_lift);
-	} else if (m->lift) {
-		host_lift = lift_host(pl, loci, n, alt_off, alts, m->ann, m->ann_sorted, m->bubble_of, m->chrom_of, m->bub);
-		lift_kind = host_lift->kind; lift_off = host_lift->off; lift_recs = host_lift->recs;
-		w->lift_lifted += host_lift->n_lifted; w->lift_unliftable += host_lift->n_unliftable;
+		w->lift_bytes += nq + (nq + 1) * 8 + rd->lift_off[nq] * sizeof(bwb_lift);
+	} else {
+		c->host.lift = lift_host(rd->pl, rd->loci, c->n, rd->alt_off, rd->alts, m->T.ann, m->T.ann_sorted, m->T.bubble_of, m->T.chrom_of, m->T.bub);
+		sam_reads_set_lift(rd, c->host.lift);
+		w->lift_lifted += c->host.lift->n_lifted; w->lift_unliftable += c->host.lift->n_unliftable;
 	}
-	/* -D: NM and the MD text of every mapped read against the text in HBM (kernels k_md_count / k_md behind them on the result stream, on the
-	 * slot's resident reads); with the host's lift records, the host's rule */
-	const bwb_md *md_recs = NULL;
-	const uint64_t *md_off = NULL;
-	const char *md_text = NULL;
-	md_set_t *host_md = NULL;
-	if (m->md && !host_lift) {
+}
+
+/* -D: NM and the MD text of every mapped read against the text in HBM (kernels k_md_count / k_md behind them, on the slot's resident reads);
+ * with the host's lift records, the host's rule */
+static void stage_md(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c, sam_reads_t *rd) {
+	const map_t *m = w->pp->map;
+	if (!c->host.lift) {
 		uint64_t nr = 0, nb = 0; double ms = 0;
-		if (bwb_hip_slot_md(ctx, slot, m->max_mm, m->max_alt, m->lift, &md_recs, &md_off, &md_text, &n)) bwb_die("map_reads: GPU %d: %s", w->gpu, bwb_hip_last_error());
+		gpu_ok(bwb_hip_slot_md(ctx, slot, m->max_mm, m->max_alt, m->lift, &rd->md, &rd->md_off, &rd->md_text, &c->n), "map_reads", w->gpu);
 		bwb_hip_md_stats(ctx, &nr, &nb, &ms); /* (the figures of the last call that LAUNCHED: this one, since a chunk's slot is asked once - a second slot_md on it would return its cached records and leave them) */
 		w->md_ms += ms; w->md_reads += nr; w->md_bytes += nb;
-		w->md_back += (unsigned long long)n * sizeof(bwb_md) + ((unsigned long long)n + 1) * 8 + md_off[n];
-	} else if (m->md) {
-		host_md = md_host(pl, n, c->fq.seq, c->fq.stride, c->fq.len, lift_kind, lift_off, lift_recs, m->ann, m->text);
-		md_recs = host_md->recs; md_off = host_md->off; md_text = host_md->text;
-		w->md_reads += host_md->n_ok; w->md_bytes += host_md->off[n];
+		w->md_back += (unsigned long long)c->n * sizeof(bwb_md) + ((unsigned long long)c->n + 1) * 8 + rd->md_off[c->n];
+	} else {
+		c->host.md = md_host(rd->pl, c->n, rd->seq, rd->stride, rd->len, rd->lift_kind, rd->lift_off, rd->lift_recs, m->T.ann, m->text);
+		sam_reads_set_md(rd, c->host.md);
+		w->md_reads += c->host.md->n_ok; w->md_bytes += c->host.md->off[c->n];
 	}
-	/* -A: the allele counts of the slot's reads, added to the context's counters (kernel k_pile behind them on the result stream, on the slot's
-	 * resident reads and cached records; nothing per read comes back); with the host's lift or join records, the host's rule into the table itself */
-	if (m->pile && !m->pile_on_host) {
+}
+
+/* -A: the allele counts of the slot's reads, added to the context's counters (kernel k_pile behind them, on the slot's resident reads and
+ * cached records; nothing per read comes back); with the host's lift or join records, the host's rule into the table itself */
+static void stage_pile(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c, sam_reads_t *rd) {
+	const map_t *m = w->pp->map;
+	if (!m->pile_on_host) {
 		uint64_t nr = 0, na = 0; double ms = 0;
-		if (bwb_hip_slot_pile(ctx, slot, m->max_mm, m->max_alt, m->lift, m->join, m->pile->min_mapq, &nr)) bwb_die("map_reads: GPU %d: %s", w->gpu, bwb_hip_last_error());
-		if (n) { bwb_hip_pile_stats(ctx, NULL, &na, &ms); w->pile_ms += ms; w->pile_reads += nr; w->pile_adds += na; } /* (a chunk without reads launches nothing) */
-	} else if (m->pile) {
+		gpu_ok(bwb_hip_slot_pile(ctx, slot, m->max_mm, m->max_alt, m->lift, m->join, m->pile->min_mapq, &nr), "map_reads", w->gpu);
+		if (c->n) { bwb_hip_pile_stats(ctx, NULL, &na, &ms); w->pile_ms += ms; w->pile_reads += nr; w->pile_adds += na; } /* (a chunk without reads launches nothing) */
+	} else {
 		pthread_mutex_lock(&w->pp->mu); /* (pile_host adds with the whole team: one worker at a time) */
-		pile_host(m->pile, pl, n, c->fq.seq, c->fq.stride, c->fq.len, lift_kind, lift_off, lift_recs, joins, m->ann);
+		pile_host(m->pile, rd->pl, c->n, rd->seq, rd->stride, rd->len, rd->lift_kind, rd->lift_off, rd->lift_recs, rd->joins, m->T.ann);
 		pthread_mutex_unlock(&w->pp->mu);
 	}
-	/* -I: the read support per indel bubble of the slot's reads, added to the context's counters (kernel k_indel behind them on the result stream,
-	 * on the slot's cached placement, locus and join records; nothing per read comes back); with the host's loci, the host's rule into the table itself */
-	if (m->indel && m->gpu_loci) {
+}
+
+/* -I: the read support per indel bubble of the slot's reads, added to the context's counters (kernel k_indel behind them, on the slot's cached
+ * placement, locus and join records; nothing per read comes back); with the host's loci, the host's rule into the table itself */
+static void stage_indel(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c, sam_reads_t *rd) {
+	const map_t *m = w->pp->map;
+	if (m->gpu_loci) {
 		uint64_t nr = 0, na = 0, nc = 0; double ms = 0;
-		if (bwb_hip_slot_indel(ctx, slot, m->max_mm, m->max_alt, m->join, m->indel->min_mapq, &nr)) bwb_die("map_reads: GPU %d: %s", w->gpu, bwb_hip_last_error());
-		if (n) { bwb_hip_indel_stats(ctx, NULL, &na, &nc, &ms); w->indel_ms += ms; w->indel_reads += nr; w->indel_adds += na; w->indel_cands += nc; } /* (a chunk without reads launches nothing) */
-	} else if (m->indel) {
+		gpu_ok(bwb_hip_slot_indel(ctx, slot, m->max_mm, m->max_alt, m->join, m->indel->min_mapq, &nr), "map_reads", w->gpu);
+		if (c->n) { bwb_hip_indel_stats(ctx, NULL, &na, &nc, &ms); w->indel_ms += ms; w->indel_reads += nr; w->indel_adds += na; w->indel_cands += nc; } /* (a chunk without reads launches nothing) */
+	} else {
 		pthread_mutex_lock(&w->pp->mu); /* (indel_host adds with the whole team: one worker at a time) */
-		indel_host(m->indel, pl, loci, n, c->fq.len, joins);
+		indel_host(m->indel, rd->pl, rd->loci, c->n, rd->len, rd->joins);
 		pthread_mutex_unlock(&w->pp->mu);
 	}
-	const sam_reads_t rd = { .pl = pl, .seq = c->fq.seq, .stride = c->fq.stride, .len = c->fq.len, .text = c->fq.text,
-	                         .name_off = c->fq.name_off, .qual_off = c->fq.qual_off, .name_len = c->fq.name_len, .first = c->first_read,
-	                         .alt_off = alt_off, .alts = alts, .loci = loci, .bubbles = m->bub, .joins = joins,
-	                         .lift_kind = lift_kind, .lift_off = lift_off, .lift_recs = lift_recs, .lift_n = n,
-	                         .md = md_recs, .md_off = md_off, .md_text = md_text };
-	c->n = n;
-	c->n_sam = ((size_t)n + SAM_BLOCK_READS - 1) / SAM_BLOCK_READS;
+}
+
+/* map: the same hand-over with the chunk's SAM text: the records of the stages the flags ask for, then the worker's team formats the text */
+static void retire_map(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c) {
+	const map_t *m = w->pp->map;
+	sam_reads_t rd = { .seq = c->fq.seq, .stride = c->fq.stride, .len = c->fq.len, .text = c->fq.text, .name_off = c->fq.name_off, .qual_off = c->fq.qual_off,
+	                   .name_len = c->fq.name_len, .first = c->first_read, .bubbles = m->T.bub };
+	stage_place(w, ctx, slot, c, &rd);
+	if (m->T.bub) stage_locus(w, ctx, slot, c, &rd);
+	if (m->join) stage_join(w, ctx, slot, c, &rd);
+	if (m->lift) stage_lift(w, ctx, slot, c, &rd);
+	if (m->md) stage_md(w, ctx, slot, c, &rd);
+	if (m->pile) stage_pile(w, ctx, slot, c, &rd);
+	if (m->indel) stage_indel(w, ctx, slot, c, &rd);
+	const size_t n = c->n;
+	c->n_sam = (n + SAM_BLOCK_READS - 1) / SAM_BLOCK_READS;
 	c->sam = (char **)calloc(c->n_sam ? c->n_sam : 1, sizeof(char *));
 	c->sam_len = (size_t *)calloc(c->n_sam ? c->n_sam : 1, sizeof(size_t));
 #pragma omp parallel for schedule(dynamic, 1) num_threads(bwb_host_team())
 	for (long bi = 0; bi < (long)c->n_sam; bi++) {
 		const size_t r0 = (size_t)bi * SAM_BLOCK_READS, r1 = r0 + SAM_BLOCK_READS < n ? r0 + SAM_BLOCK_READS : n;
-		c->sam[bi] = sam_format_reads(&rd, r0, r1, m->ann, m->ann_sorted, &c->sam_len[bi]);
+		c->sam[bi] = sam_format_reads(&rd, r0, r1, m->T.ann, m->T.ann_sorted, &c->sam_len[bi]);
 	}
-	free(host_loci); free(host_joins); lift_free(host_lift); md_free(host_md);
+	host_recs_free(&c->host);
 	free(c->fq.seq); free(c->fq.len); free(c->fq.name_off); free(c->fq.qual_off); free(c->fq.name_len);
 	c->fq.seq = NULL; c->fq.len = NULL; c->fq.name_off = NULL; c->fq.qual_off = NULL; c->fq.name_len = NULL;
 	chunk_ready(w->pp, c);
@@ -324,80 +339,74 @@ static uint64_t count_piece(void) {
 /* -G: the entries per geno_sites / geno_bubbles call - count_piece(), at most the library's 2^24 and no more than the larger table has */
 static uint32_t geno_piece(const map_t *m) {
 	uint64_t most = m->pile->n_sites;
-	if (m->indel && m->gpu_loci && (uint64_t)m->bub->n > most) most = (uint64_t)m->bub->n;
+	if (m->indel && m->gpu_loci && (uint64_t)m->T.bub->n > most) most = (uint64_t)m->T.bub->n;
 	uint64_t p = count_piece();
 	if (p > most) p = most;
 	if (p > ((uint64_t)1 << 24)) p = (uint64_t)1 << 24;
 	return p < 1 ? 1u : (uint32_t)p;
 }
 
-/* One host thread per GPU.  Chunks are streamed through the slots of the context: while the search slice of chunk j runs,
- * chunk j+1 is already uploaded and queued behind it and the hits of chunk j-1 are on their way back; a slice parks its
- * unfinished reads for the next one instead of draining (include/bwbble_hip.h), so the GPU never runs a batch's tail alone. */
-static void *gpu_worker(void *arg) {
-	worker_t *w = (worker_t *)arg;
-	pipe_t *pp = w->pp;
-	bwb_hip_ctx *ctx = NULL;
-	const int dbg = getenv("BWB_DEBUG") != NULL;
-	pin_to_device_node(w->device, dbg);
-	double tq = wall();
-	const bwtint_t hdr[5] = { w->BWT->length, w->BWT->num_words, w->BWT->num_sa, w->BWT->num_occ, w->BWT->sa0_index };
-	/* The index goes to the GPU - on a thread of the library - while the loader threads are still reading the tail of the .bwt file
-	 * (bwt_io.c), and while this thread already uploads its first chunk: that first slot_upload sizes and allocates the context's scratch
-	 * and its heap chunk pool (seconds of hipMalloc at GRCh37 scale, which rounds 3-5 paid AFTER the index upload); slot_submit waits for
-	 * the index by itself. */
-	if (bwb_hip_ctx_create_async(w->device, hdr, w->BWT->C, w->BWT->bwt, w->BWT->O, w->BWT->loader ? &w->BWT->blocks_ready : NULL, &ctx))
-		bwb_die("align_reads_inexact_gpu: GPU %d: %s", w->device, bwb_hip_last_error());
-	if (dbg) fprintf(stderr, "[bwb host] worker %d: context created at +%.3f s (index upload under way)\n", w->gpu, wall() - tq);
-	if (pp->map) {
-		/* The sampled SA (length / 32 x 8 bytes: 1.7 GB at GRCh37 scale) goes to HBM BEFORE the first slot_upload sizes the chunk pool from
-		 * what is free - the loader reads it first (bwt_io.c) - and while the library's thread uploads the index: set_sa uses a stream of
-		 * its own for that (bwb_hip.hip). */
-		while (!__atomic_load_n(&w->BWT->sa_ready, __ATOMIC_ACQUIRE)) { struct timespec ts = { 0, 200000 }; nanosleep(&ts, NULL); }
-		if (bwb_hip_set_sa(ctx, w->BWT->SA, w->BWT->num_sa)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
-		if (dbg) fprintf(stderr, "[bwb host] worker %d: sampled SA resident at +%.3f s\n", w->gpu, wall() - tq);
-		/* -B: the record and bubble tables of k_locus (every worker's context gets them; 30 MB at GRCh37 scale) */
-		if (pp->map->bub && pp->map->gpu_loci &&
-		    bwb_hip_set_loci(ctx, pp->map->rec_start, pp->map->rec_end, pp->map->bubble_of, (uint32_t)pp->map->ann->num_seq, pp->map->bub->b, (uint32_t)pp->map->bub->n))
-			bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
-		/* -J, -R: the chromosome's record of every bubble, beside them */
-		if (pp->map->chrom_of && pp->map->gpu_loci && bwb_hip_set_bubble_chrom(ctx, pp->map->chrom_of, (uint32_t)pp->map->bub->n))
-			bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
-		/* -I: the sorted table of the eligible bubbles (16 bytes each, one more per bubble) and the zeroed counters (16 bytes per bubble), before the pool is sized as well */
-		if (pp->map->indel && pp->map->gpu_loci) {
-			const double t0 = wall();
-			uint64_t n_elig = 0;
-			if (bwb_hip_indel_begin(ctx, pp->map->indel->anchor, &n_elig)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
-			w->indel_begin_s = wall() - t0;
-			if (n_elig != pp->map->indel->n_tab) bwb_die("map_reads: GPU %d finds %llu eligible bubbles, the host %llu", w->device, (unsigned long long)n_elig, (unsigned long long)pp->map->indel->n_tab);
-		}
-		/* -D: the forward text (n_fwd / 2 bytes in HBM: 1.7 GB at GRCh37 scale), before the first slot_upload sizes the chunk pool as well; its
-		 * bytes are read by the .bwt loader behind the SA (bwt_io.c: load_bwt_start_job, md.c: md_text_read).  Not with the host's lift records: the host's rule then */
-		md_text_wait(pp->map->text);
-		if (pp->map->pile) { /* -A: the host's own count of the sites, which every context's must equal, and the table (the first worker here makes them) */
-			pthread_mutex_lock(&pp->mu);
-			if (!pp->map->pile->text) pile_set_text(pp->map->pile, pp->map->text, pp->map->pile_on_host);
-			pthread_mutex_unlock(&pp->mu);
-		}
-		const int pile_gpu = pp->map->pile && !pp->map->pile_on_host;
-		if ((pp->map->md && !(pp->map->lift && !pp->map->gpu_loci)) || pile_gpu) {
-			const double t0 = wall();
-			if (bwb_hip_set_text(ctx, pp->map->text->codes, pp->map->text->n_fwd)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
-			w->text_s = wall() - t0;
-			if (dbg) fprintf(stderr, "[bwb host] worker %d: text resident at +%.3f s\n", w->gpu, wall() - tq);
-		}
-		/* -A: the site index (n_fwd / 8 bytes) and the zeroed counters (16 bytes per site) behind the text, before the pool is sized as well */
-		if (pile_gpu) {
-			const double t0 = wall();
-			uint64_t n_sites = 0;
-			if (bwb_hip_pile_begin(ctx, &n_sites)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
-			w->pile_begin_s = wall() - t0;
-			if (n_sites != pp->map->pile->n_sites) bwb_die("map_reads: GPU %d counts %llu IUPAC sites in the text, the host's scan of the .ref %llu", w->device, (unsigned long long)n_sites, (unsigned long long)pp->map->pile->n_sites);
-		}
-		/* -G: the scratch and the pinned output of one piece of calls (92 bytes per site of the piece, 48 more per bubble), in every context - which worker
-		 * finishes last is not known yet -, before the pool is sized as well */
-		if (pp->map->geno && pile_gpu && bwb_hip_geno_begin(ctx, geno_piece(pp->map))) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
+/* the piece-walker of the counters' loops: the size of the piece of n entries that starts at `first` - at most `piece` -, 0 behind the last.
+ * `for (s0 = 0; (ns = piece_at(s0, n, piece)); s0 += ns)` walks the n entries and takes no turn on none */
+static uint64_t piece_at(uint64_t first, uint64_t n, uint64_t piece) {
+	return first >= n ? 0 : (n - first < piece ? n - first : piece);
+}
+
+/* map: what the worker's context holds before the stream starts.  In this order, and all of it before the first slot_upload: that sizes the
+ * chunk pool from what is free afterwards */
+static void worker_map_setup(worker_t *w, bwb_hip_ctx *ctx, double tq, int dbg) {
+	const map_t *m = w->pp->map;
+	/* The sampled SA (length / 32 x 8 bytes: 1.7 GB at GRCh37 scale) - the loader reads it first (bwt_io.c) - goes up while the library's thread
+	 * uploads the index: set_sa uses a stream of its own for that (bwb_hip.hip). */
+	while (!__atomic_load_n(&w->BWT->sa_ready, __ATOMIC_ACQUIRE)) { struct timespec ts = { 0, 200000 }; nanosleep(&ts, NULL); }
+	gpu_ok(bwb_hip_set_sa(ctx, w->BWT->SA, w->BWT->num_sa), "map_reads", w->device);
+	if (dbg) fprintf(stderr, "[bwb host] worker %d: sampled SA resident at +%.3f s\n", w->gpu, wall() - tq);
+	/* -B: the record and bubble tables of k_locus (every worker's context gets them; 30 MB at GRCh37 scale) */
+	if (m->T.bub && m->gpu_loci)
+		gpu_ok(bwb_hip_set_loci(ctx, m->rec_start, m->rec_end, m->T.bubble_of, (uint32_t)m->T.ann->num_seq, m->T.bub->b, (uint32_t)m->T.bub->n), "map_reads", w->device);
+	/* -J, -R: the chromosome's record of every bubble, beside them */
+	if (m->T.chrom_of && m->gpu_loci) gpu_ok(bwb_hip_set_bubble_chrom(ctx, m->T.chrom_of, (uint32_t)m->T.bub->n), "map_reads", w->device);
+	/* -I: the sorted table of the eligible bubbles (16 bytes each, one more per bubble) and the zeroed counters (16 bytes per bubble) */
+	if (m->indel && m->gpu_loci) {
+		const double t0 = wall();
+		uint64_t n_elig = 0;
+		gpu_ok(bwb_hip_indel_begin(ctx, m->indel->anchor, &n_elig), "map_reads", w->device);
+		w->indel_begin_s = wall() - t0;
+		if (n_elig != m->indel->n_tab) bwb_die("map_reads: GPU %d finds %llu eligible bubbles, the host %llu", w->device, (unsigned long long)n_elig, (unsigned long long)m->indel->n_tab);
 	}
+	/* -D: the forward text (n_fwd / 2 bytes in HBM: 1.7 GB at GRCh37 scale); its bytes are read by the .bwt loader behind the SA (bwt_io.c:
+	 * load_bwt_start_job, md.c: md_text_read).  Not with the host's lift records: the host's rule then */
+	md_text_wait(m->text);
+	if (m->pile) { /* -A: the host's own count of the sites, which every context's must equal, and the table (the first worker here makes them) */
+		pthread_mutex_lock(&w->pp->mu);
+		if (!m->pile->text) pile_set_text(m->pile, m->text, m->pile_on_host);
+		pthread_mutex_unlock(&w->pp->mu);
+	}
+	const int pile_gpu = m->pile && !m->pile_on_host;
+	if ((m->md && !(m->lift && !m->gpu_loci)) || pile_gpu) {
+		const double t0 = wall();
+		gpu_ok(bwb_hip_set_text(ctx, m->text->codes, m->text->n_fwd), "map_reads", w->device);
+		w->text_s = wall() - t0;
+		if (dbg) fprintf(stderr, "[bwb host] worker %d: text resident at +%.3f s\n", w->gpu, wall() - tq);
+	}
+	/* -A: the site index (n_fwd / 8 bytes) and the zeroed counters (16 bytes per site) behind the text */
+	if (pile_gpu) {
+		const double t0 = wall();
+		uint64_t n_sites = 0;
+		gpu_ok(bwb_hip_pile_begin(ctx, &n_sites), "map_reads", w->device);
+		w->pile_begin_s = wall() - t0;
+		if (n_sites != m->pile->n_sites) bwb_die("map_reads: GPU %d counts %llu IUPAC sites in the text, the host's scan of the .ref %llu", w->device, (unsigned long long)n_sites, (unsigned long long)m->pile->n_sites);
+	}
+	/* -G: the scratch and the pinned output of one piece of calls (92 bytes per site of the piece, 48 more per bubble), in every context - which worker
+	 * finishes last is not known yet */
+	if (m->geno && pile_gpu) gpu_ok(bwb_hip_geno_begin(ctx, geno_piece(m)), "map_reads", w->device);
+}
+
+/* The stream.  Chunks go through the slots of the context: while the search slice of chunk j runs, chunk j+1 is already uploaded and queued
+ * behind it and the hits of chunk j-1 are on their way back; a slice parks its unfinished reads for the next one instead of draining
+ * (include/bwbble_hip.h), so the GPU never runs a batch's tail alone. */
+static void worker_stream(worker_t *w, bwb_hip_ctx *ctx, double tq, int dbg) {
+	pipe_t *pp = w->pp;
 	void (*const hand_over)(worker_t *, bwb_hip_ctx *, int, chunk_t *) = pp->map ? retire_map : retire;
 	enum { NS = BWB_MAX_SLOTS }; /* chunks in flight: the heaviest reads of a chunk take several slices' time (they are parked and resumed), and
 	                                a slot can be uploaded again only when its chunk is complete */
@@ -419,18 +428,16 @@ static void *gpu_worker(void *arg) {
 		}
 		const int slot = (int)(j % NS);
 		if (j >= NS && retired + NS <= j) { hand_over(w, ctx, slot, in_slot[slot]); retired++; } /* the slot's previous chunk: NS - 1 slices stay queued while the host waits */
-		if (bwb_hip_slot_upload(ctx, slot, w->params, c->fq.seq, c->fq.len, c->fq.n, c->fq.stride, c->carry, c->carry_len))
-			bwb_die("align_reads_inexact_gpu: GPU %d: %s", w->device, bwb_hip_last_error());
+		gpu_ok(bwb_hip_slot_upload(ctx, slot, w->params, c->fq.seq, c->fq.len, c->fq.n, c->fq.stride, c->carry, c->carry_len), "align_reads_inexact_gpu", w->device);
 		if (j == 0) { /* the first chunk is staged, scratch and pool exist: now the index must be complete */
-			if (bwb_hip_ctx_index_wait(ctx, &w->t_ctx)) bwb_die("align_reads_inexact_gpu: GPU %d: %s", w->device, bwb_hip_last_error());
+			gpu_ok(bwb_hip_ctx_index_wait(ctx, &w->t_ctx), "align_reads_inexact_gpu", w->device);
 			uint64_t pb = 0;
 			bwb_hip_setup_times(ctx, NULL, &w->t_pool, &pb);
 			w->pool_bytes = pb;
 			if (dbg) fprintf(stderr, "[bwb host] worker %d (device %d): index upload %.3f s, chunk pool %.1f GB allocated in %.3f s, first chunk staged at +%.3f s\n", w->gpu, w->device, w->t_ctx,
 			                 (double)pb / (1u << 30), w->t_pool, wall() - tq);
 		}
-		if (bwb_hip_slot_submit(ctx, slot))
-			bwb_die("align_reads_inexact_gpu: GPU %d: %s", w->device, bwb_hip_last_error());
+		gpu_ok(bwb_hip_slot_submit(ctx, slot), "align_reads_inexact_gpu", w->device);
 		if (j == 0) w->t_first_submit = wall() - tq;
 		if (!pp->map) { free(c->fq.seq); free(c->fq.len); c->fq.seq = NULL; c->fq.len = NULL; } /* (staged by the library: the caller's buffers are free; map prints the bases) */
 		free(c->carry); c->carry = NULL;
@@ -439,90 +446,162 @@ static void *gpu_worker(void *arg) {
 		j++;
 		if (dbg) fprintf(stderr, "[bwb host] worker %d: chunk %zu (%u reads) submitted at +%.3f s\n", w->gpu, c->idx, c->fq.n, wall() - tq);
 	}
-	/* -A: the stream has ended and every chunk of this worker is retired - its counters come back in bounded pieces and are summed on the host */
-	if (pp->map && pp->map->pile && !pp->map->pile_on_host) {
-		const double t0 = wall();
-		const uint64_t PIECE = count_piece(), n_sites = pp->map->pile->n_sites; /* sites per read-back */
-		uint32_t *buf = (uint32_t *)malloc((size_t)(n_sites < PIECE ? n_sites : PIECE) * 16 + 16);
-		uint64_t turns = 0;
-		for (uint64_t s0 = 0; s0 < n_sites; s0 += PIECE, turns++) {
-			const uint64_t ns = n_sites - s0 < PIECE ? n_sites - s0 : PIECE;
-			if (bwb_hip_pile_counts(ctx, s0, ns, buf)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
-			pthread_mutex_lock(&pp->mu);
-			pile_add(pp->map->pile, s0, ns, buf);
-			pthread_mutex_unlock(&pp->mu);
-		}
-		free(buf);
-		w->pile_fetch_s = wall() - t0;
-		if (dbg) fprintf(stderr, "[bwb host] worker %d: the counters of %llu sites read back in %llu pieces\n", w->gpu, (unsigned long long)n_sites, (unsigned long long)turns);
-	}
-	/* -I: the same for the bubbles' counters */
-	if (pp->map && pp->map->indel && pp->map->gpu_loci) {
-		const double t0 = wall();
-		const uint64_t PIECE = count_piece(), n_bub = (uint64_t)pp->map->bub->n;
-		uint32_t *buf = (uint32_t *)malloc((size_t)(n_bub < PIECE ? n_bub : PIECE) * 16 + 16);
-		uint64_t turns = 0;
-		for (uint64_t s0 = 0; s0 < n_bub; s0 += PIECE, turns++) {
-			const uint64_t ns = n_bub - s0 < PIECE ? n_bub - s0 : PIECE;
-			if (bwb_hip_indel_counts(ctx, s0, ns, buf)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
-			pthread_mutex_lock(&pp->mu);
-			indel_add(pp->map->indel, s0, ns, buf);
-			pthread_mutex_unlock(&pp->mu);
-		}
-		free(buf);
-		w->indel_fetch_s = wall() - t0;
-		if (dbg) fprintf(stderr, "[bwb host] worker %d: the counters of %llu bubbles read back in %llu pieces\n", w->gpu, (unsigned long long)n_bub, (unsigned long long)turns);
-	}
-	/* -G: this worker's counters are in the host's sums.  The worker that completes the count calls the genotypes on its own context: with several
-	 * workers it first puts the host's summed tables back over its counters, with one its counters are the sums already and nothing is uploaded.  Then
-	 * the sites and the bubbles are walked in pieces; what comes back is the called entries' records alone, which geno.c keeps for the writer. */
-	if (pp->map && pp->map->geno) {
-		const map_t *m = pp->map;
-		geno_t *G = m->geno;
+}
+
+/* map -A, -I: the stream has ended and every chunk of this worker is retired - its counters (bubbles: those of -I's n bubbles, else those of
+ * -A's n sites) come back in bounded pieces and are summed on the host; returns the pieces */
+static uint64_t counters_back(worker_t *w, bwb_hip_ctx *ctx, int bubbles, uint64_t n) {
+	pipe_t *pp = w->pp;
+	const uint64_t PIECE = count_piece();
+	uint32_t *buf = (uint32_t *)malloc((size_t)(n < PIECE ? n : PIECE) * 16 + 16);
+	uint64_t turns = 0, ns;
+	for (uint64_t s0 = 0; (ns = piece_at(s0, n, PIECE)); s0 += ns, turns++) {
+		gpu_ok(bubbles ? bwb_hip_indel_counts(ctx, s0, ns, buf) : bwb_hip_pile_counts(ctx, s0, ns, buf), "map_reads", w->device);
 		pthread_mutex_lock(&pp->mu);
-		const int last = ++pp->n_finished == pp->n_workers;
+		if (bubbles) indel_add(pp->map->indel, s0, ns, buf); else pile_add(pp->map->pile, s0, ns, buf);
 		pthread_mutex_unlock(&pp->mu);
-		const int sites_gpu = !m->pile_on_host, bubs_gpu = sites_gpu && m->indel && m->gpu_loci;
-		if (last && sites_gpu) {
-			const uint64_t PIECE = count_piece(), GP = geno_piece(m), n_sites = m->pile->n_sites, n_bub = bubs_gpu ? (uint64_t)m->bub->n : 0;
-			double t0 = wall();
-			if (pp->n_workers > 1) {
-				for (uint64_t s0 = 0; s0 < n_sites; s0 += PIECE, G->put_pieces++)
-					if (bwb_hip_pile_put(ctx, s0, n_sites - s0 < PIECE ? n_sites - s0 : PIECE, m->pile->counts + s0 * 4)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
-				for (uint64_t s0 = 0; s0 < n_bub; s0 += PIECE, G->put_pieces++)
-					if (bwb_hip_indel_put(ctx, s0, n_bub - s0 < PIECE ? n_bub - s0 : PIECE, m->indel->counts + s0 * 4)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
-			}
-			G->put_s = wall() - t0;
-			t0 = wall();
-			double ms = 0;
-			for (uint64_t s0 = 0; s0 < n_sites; s0 += GP, G->pieces++) {
-				const bwb_geno_site *recs = NULL; uint64_t k = 0;
-				if (bwb_hip_geno_sites(ctx, s0, n_sites - s0 < GP ? n_sites - s0 : GP, G->err, G->min_depth, &recs, &k)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
-				bwb_hip_geno_stats(ctx, NULL, NULL, &ms);
-				G->kernel_ms += ms;
-				geno_take_sites(G, recs, k);
-			}
-			const uint64_t GB = GP < n_bub ? GP : n_bub;
-			for (uint64_t s0 = 0; s0 < n_bub; s0 += GB, G->pieces++) {
-				const bwb_geno_bubble *recs = NULL; uint64_t k = 0;
-				if (bwb_hip_geno_bubbles(ctx, s0, n_bub - s0 < GB ? n_bub - s0 : GB, G->err, G->min_depth, &recs, &k)) bwb_die("map_reads: GPU %d: %s", w->device, bwb_hip_last_error());
-				bwb_hip_geno_stats(ctx, NULL, NULL, &ms);
-				G->kernel_ms += ms;
-				geno_take_bubbles(G, recs, k);
-			}
-			G->call_s = wall() - t0;
-			G->worker = w->gpu;
-			if (dbg) fprintf(stderr, "[bwb host] worker %d: genotypes called by this worker, the last of %d: %llu pieces of tables put back in %.3f s, %llu pieces called in %.3f s: sites %llu  bubbles %llu  kernels %.3f ms\n",
-			                 w->gpu, pp->n_workers, (unsigned long long)G->put_pieces, G->put_s, (unsigned long long)G->pieces, G->call_s, (unsigned long long)G->n_sites, (unsigned long long)G->n_bubs, G->kernel_ms);
-		}
 	}
+	free(buf);
+	return turns;
+}
+static void worker_map_counters(worker_t *w, bwb_hip_ctx *ctx, int dbg) {
+	const map_t *m = w->pp->map;
+	if (m->pile && !m->pile_on_host) {
+		const double t0 = wall();
+		const uint64_t turns = counters_back(w, ctx, 0, m->pile->n_sites);
+		w->pile_fetch_s = wall() - t0;
+		if (dbg) fprintf(stderr, "[bwb host] worker %d: the counters of %llu sites read back in %llu pieces\n", w->gpu, (unsigned long long)m->pile->n_sites, (unsigned long long)turns);
+	}
+	if (m->indel && m->gpu_loci) {
+		const double t0 = wall();
+		const uint64_t turns = counters_back(w, ctx, 1, (uint64_t)m->T.bub->n);
+		w->indel_fetch_s = wall() - t0;
+		if (dbg) fprintf(stderr, "[bwb host] worker %d: the counters of %llu bubbles read back in %llu pieces\n", w->gpu, (unsigned long long)m->T.bub->n, (unsigned long long)turns);
+	}
+}
+
+/* map -G: this worker's counters are in the host's sums.  The worker that completes the count calls the genotypes on its own context: with several
+ * workers it first puts the host's summed tables back over its counters, with one its counters are the sums already and nothing is uploaded.  Then
+ * the sites and the bubbles are walked in pieces; what comes back is the called entries' records alone, which geno.c keeps for the writer. */
+static void worker_map_genotypes(worker_t *w, bwb_hip_ctx *ctx, int dbg) {
+	pipe_t *pp = w->pp;
+	const map_t *m = pp->map;
+	geno_t *G = m->geno;
+	pthread_mutex_lock(&pp->mu);
+	const int last = ++pp->n_finished == pp->n_workers;
+	pthread_mutex_unlock(&pp->mu);
+	const int sites_gpu = !m->pile_on_host, bubs_gpu = sites_gpu && m->indel && m->gpu_loci;
+	if (!last || !sites_gpu) return;
+	const uint64_t PIECE = count_piece(), GP = geno_piece(m), n_sites = m->pile->n_sites, n_bub = bubs_gpu ? (uint64_t)m->T.bub->n : 0;
+	uint64_t ns;
+	double t0 = wall();
+	if (pp->n_workers > 1) {
+		for (uint64_t s0 = 0; (ns = piece_at(s0, n_sites, PIECE)); s0 += ns, G->put_pieces++)
+			gpu_ok(bwb_hip_pile_put(ctx, s0, ns, m->pile->counts + s0 * 4), "map_reads", w->device);
+		for (uint64_t s0 = 0; (ns = piece_at(s0, n_bub, PIECE)); s0 += ns, G->put_pieces++)
+			gpu_ok(bwb_hip_indel_put(ctx, s0, ns, m->indel->counts + s0 * 4), "map_reads", w->device);
+	}
+	G->put_s = wall() - t0;
+	t0 = wall();
+	double ms = 0;
+	for (uint64_t s0 = 0; (ns = piece_at(s0, n_sites, GP)); s0 += ns, G->pieces++) {
+		const bwb_geno_site *recs = NULL; uint64_t k = 0;
+		gpu_ok(bwb_hip_geno_sites(ctx, s0, ns, G->err, G->min_depth, &recs, &k), "map_reads", w->device);
+		bwb_hip_geno_stats(ctx, NULL, NULL, &ms);
+		G->kernel_ms += ms;
+		geno_take_sites(G, recs, k);
+	}
+	for (uint64_t s0 = 0; (ns = piece_at(s0, n_bub, GP)); s0 += ns, G->pieces++) {
+		const bwb_geno_bubble *recs = NULL; uint64_t k = 0;
+		gpu_ok(bwb_hip_geno_bubbles(ctx, s0, ns, G->err, G->min_depth, &recs, &k), "map_reads", w->device);
+		bwb_hip_geno_stats(ctx, NULL, NULL, &ms);
+		G->kernel_ms += ms;
+		geno_take_bubbles(G, recs, k);
+	}
+	G->call_s = wall() - t0;
+	G->worker = w->gpu;
+	if (dbg) fprintf(stderr, "[bwb host] worker %d: genotypes called by this worker, the last of %d: %llu pieces of tables put back in %.3f s, %llu pieces called in %.3f s: sites %llu  bubbles %llu  kernels %.3f ms\n",
+	                 w->gpu, pp->n_workers, (unsigned long long)G->put_pieces, G->put_s, (unsigned long long)G->pieces, G->call_s, (unsigned long long)G->n_sites, (unsigned long long)G->n_bubs, G->kernel_ms);
+}
+
+/* One host thread per GPU: the context, for `map` what it holds beside the index, the stream, for `map` the counters and the calls */
+static void *gpu_worker(void *arg) {
+	worker_t *w = (worker_t *)arg;
+	bwb_hip_ctx *ctx = NULL;
+	const int dbg = getenv("BWB_DEBUG") != NULL;
+	pin_to_device_node(w->device, dbg);
+	const double tq = wall();
+	const bwtint_t hdr[5] = { w->BWT->length, w->BWT->num_words, w->BWT->num_sa, w->BWT->num_occ, w->BWT->sa0_index };
+	/* The index goes to the GPU - on a thread of the library - while the loader threads are still reading the tail of the .bwt file
+	 * (bwt_io.c), and while this thread already uploads its first chunk: that first slot_upload sizes and allocates the context's scratch
+	 * and its heap chunk pool (seconds of hipMalloc at GRCh37 scale, which rounds 3-5 paid AFTER the index upload); slot_submit waits for
+	 * the index by itself. */
+	gpu_ok(bwb_hip_ctx_create_async(w->device, hdr, w->BWT->C, w->BWT->bwt, w->BWT->O, w->BWT->loader ? &w->BWT->blocks_ready : NULL, &ctx), "align_reads_inexact_gpu", w->device);
+	if (dbg) fprintf(stderr, "[bwb host] worker %d: context created at +%.3f s (index upload under way)\n", w->gpu, wall() - tq);
+	if (w->pp->map) worker_map_setup(w, ctx, tq, dbg);
+	worker_stream(w, ctx, tq, dbg);
+	if (w->pp->map) worker_map_counters(w, ctx, dbg);
+	if (w->pp->map && w->pp->map->geno) worker_map_genotypes(w, ctx, dbg);
 	bwb_stats st;
-	if (bwb_hip_flush(ctx) || bwb_hip_get_stats(ctx, &st)) bwb_die("align_reads_inexact_gpu: GPU %d: %s", w->device, bwb_hip_last_error());
+	gpu_ok(bwb_hip_flush(ctx) || bwb_hip_get_stats(ctx, &st), "align_reads_inexact_gpu", w->device);
 	w->total = st;
 	w->kernel_ms = st.ms_calc_d + st.ms_search;
 	bwb_hip_ctx_destroy(ctx);
 	if (dbg) fprintf(stderr, "[bwb host] worker %d: done %.3f s\n", w->gpu, wall() - tq);
 	return NULL;
+}
+
+/* the summary's figures: worker w folded into the total t - times by maximum (the workers run side by side), counts by sum */
+static void max_of(double *t, double v) { if (v > *t) *t = v; }
+static void fold_worker(worker_t *t, const worker_t *w) {
+	max_of(&t->kernel_ms, w->kernel_ms); max_of(&t->t_ctx, w->t_ctx); max_of(&t->t_pool, w->t_pool); max_of(&t->t_first_submit, w->t_first_submit);
+	if (w->pool_bytes > t->pool_bytes) t->pool_bytes = w->pool_bytes;
+	t->total.visits_single += w->total.visits_single; t->total.visits_alphabet += w->total.visits_alphabet;
+	t->total.heap_pops += w->total.heap_pops; t->total.n_alignments += w->total.n_alignments; t->total.n_overflow_reads += w->total.n_overflow_reads;
+	max_of(&t->place_ms, w->place_ms); t->place_steps += w->place_steps;
+	max_of(&t->alt_ms, w->alt_ms); t->alt_steps += w->alt_steps; t->alt_items += w->alt_items;
+	max_of(&t->locus_ms, w->locus_ms); t->locus_reads += w->locus_reads;
+	max_of(&t->join_ms, w->join_ms); t->join_items += w->join_items; t->join_joined += w->join_joined; t->join_mapq += w->join_mapq;
+	max_of(&t->lift_ms, w->lift_ms); t->lift_lifted += w->lift_lifted; t->lift_unliftable += w->lift_unliftable; t->lift_bytes += w->lift_bytes;
+	max_of(&t->md_ms, w->md_ms); max_of(&t->text_s, w->text_s); t->md_reads += w->md_reads; t->md_bytes += w->md_bytes; t->md_back += w->md_back;
+	max_of(&t->pile_ms, w->pile_ms); max_of(&t->pile_begin_s, w->pile_begin_s); max_of(&t->pile_fetch_s, w->pile_fetch_s); t->pile_reads += w->pile_reads; t->pile_adds += w->pile_adds;
+	max_of(&t->indel_ms, w->indel_ms); max_of(&t->indel_begin_s, w->indel_begin_s); max_of(&t->indel_fetch_s, w->indel_fetch_s);
+	t->indel_reads += w->indel_reads; t->indel_adds += w->indel_adds; t->indel_cands += w->indel_cands;
+}
+
+/* map: one line per stage of the result stream, from the folded workers; a stage that ran on the host says so and why */
+static void print_map_summary(const map_t *map, const worker_t *t, uint64_t n_reads) {
+	printf("placements on the GPU: reads %llu  rank-block visits %llu  kernel %.3f ms", (unsigned long long)n_reads, t->place_steps, t->place_ms);
+	if (map->T.bub && map->gpu_loci) printf("  loci resolved %llu  k_locus %.3f ms", t->locus_reads, t->locus_ms); /* -B: the loci of the same reads */
+	else if (map->T.bub) printf("  loci resolved %llu on the host%s (the .ann records are not ascending and disjoint)", (unsigned long long)n_reads, map->join ? " and joined there" : "");
+	printf("\n");
+	if (map->join && map->gpu_loci) printf("placements joined by locus on the GPU: items %llu  joined %llu  reads with another MAPQ %llu  kernels %.3f ms\n", t->join_items, t->join_joined, t->join_mapq, t->join_ms);
+	else if (map->join) printf("placements joined by locus on the host: joined %llu  reads with another MAPQ %llu\n", t->join_joined, t->join_mapq);
+	if (map->lift && map->gpu_loci) printf("placements lifted to chromosome coordinates on the GPU: lifted %llu  not liftable %llu  kernels %.3f ms  bytes to the host %llu\n", t->lift_lifted, t->lift_unliftable, t->lift_ms, t->lift_bytes);
+	else if (map->lift) printf("placements lifted to chromosome coordinates on the host (the .ann records are not ascending and disjoint): lifted %llu  not liftable %llu\n", t->lift_lifted, t->lift_unliftable);
+	if (map->md && !(map->lift && !map->gpu_loci))
+		printf("NM and MD against the text on the GPU: reads %llu  MD bytes %llu  kernels %.3f ms  bytes to the host %llu  text %llu characters read in %.3f s, set in %.3f s\n", t->md_reads, t->md_bytes, t->md_ms, t->md_back,
+		       (unsigned long long)map->text->n_fwd, map->text->seconds, t->text_s);
+	else if (map->md) printf("NM and MD against the text on the host (the .ann records are not ascending and disjoint): reads %llu  MD bytes %llu\n", t->md_reads, t->md_bytes);
+	if (map->pile && !map->pile_on_host)
+		printf("allele counts at the text's IUPAC sites on the GPU: sites %llu  reads counted %llu  adds %llu  k_pile %.3f ms  site index and counters %llu bytes, built in %.3f s  counters read back in %.3f s\n",
+		       (unsigned long long)map->pile->n_sites, t->pile_reads, t->pile_adds, t->pile_ms, (unsigned long long)((map->text->n_fwd + 31) / 32 * 4 + map->pile->n_sites * 16), t->pile_begin_s, t->pile_fetch_s);
+	else if (map->pile) printf("allele counts at the text's IUPAC sites on the host (the .ann records are not ascending and disjoint): sites %llu  reads counted %llu  adds %llu\n",
+		                   (unsigned long long)map->pile->n_sites, (unsigned long long)map->pile->reads, (unsigned long long)map->pile->adds);
+	if (map->indel && map->gpu_loci)
+		printf("read support per indel bubble on the GPU: anchor %d  eligible bubbles %llu  refused and skipped %llu  reads counted %llu  adds %llu  candidates %llu  k_indel %.3f ms  table and counters %llu bytes, sorted in %.3f s, resident in %.3f s  counters read back in %.3f s\n",
+		       map->indel->anchor, (unsigned long long)map->indel->n_tab, (unsigned long long)map->indel->n_refused, t->indel_reads, t->indel_adds, t->indel_cands, t->indel_ms,
+		       (unsigned long long)(map->indel->n_tab * 16 + (uint64_t)map->T.bub->n * 17), map->indel->sort_s, t->indel_begin_s, t->indel_fetch_s);
+	else if (map->indel) printf("read support per indel bubble on the host (the .ann records are not ascending and disjoint): anchor %d  eligible bubbles %llu  refused and skipped %llu  reads counted %llu  adds %llu  candidates %llu\n",
+		                    map->indel->anchor, (unsigned long long)map->indel->n_tab, (unsigned long long)map->indel->n_refused, (unsigned long long)map->indel->reads, (unsigned long long)map->indel->adds, (unsigned long long)map->indel->cands);
+	if (map->geno && !map->pile_on_host) /* -G */
+		printf("genotype calls on the GPU (worker %d): error phred %d  minimum depth %lld  sites called %llu%s  bubbles called %llu  kernels %.3f ms  pieces %llu  bytes to the host %llu  tables put back in %llu pieces, %.3f s  called in %.3f s\n",
+		       map->geno->worker, map->geno->err, (long long)map->geno->min_depth, (unsigned long long)map->geno->n_sites, map->indel && !map->gpu_loci ? " (the bubbles follow on the host)" : "",
+		       (unsigned long long)map->geno->n_bubs, map->geno->kernel_ms, (unsigned long long)map->geno->pieces,
+		       (unsigned long long)(map->geno->n_sites * sizeof(bwb_geno_site) + map->geno->n_bubs * sizeof(bwb_geno_bubble) + map->geno->pieces * 8), (unsigned long long)map->geno->put_pieces, map->geno->put_s, map->geno->call_s);
+	if (map->max_alt)
+		printf("other placements on the GPU (-X %d): items %llu (%.3f per read)  rank-block visits %llu  kernels %.3f ms\n", map->max_alt, t->alt_items,
+		       n_reads ? (double)t->alt_items / (double)n_reads : 0.0, t->alt_steps, t->alt_ms);
 }
 
 /* The GPU replacement for align_reads_inexact_parallel, as a pipeline: reader thread (FASTQ -> chunks) | one worker per GPU | this
@@ -604,18 +683,11 @@ static int run_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, 
 	}
 	pthread_join(rth, NULL);
 	if (pp.fs) fq_close(pp.fs);
-	bwb_stats tot; memset(&tot, 0, sizeof(tot));
-	double kms = 0, tctx = 0, tpool = 0, tfirst = 0;
-	unsigned long long pool_bytes = 0;
+	worker_t tot; /* the workers folded once: times by maximum, counts by sum */
+	memset(&tot, 0, sizeof(tot));
 	for (int g = 0; g < n_gpus; g++) {
 		pthread_join(th[g], NULL);
-		tot.visits_single += ws[g].total.visits_single; tot.visits_alphabet += ws[g].total.visits_alphabet;
-		tot.heap_pops += ws[g].total.heap_pops; tot.n_alignments += ws[g].total.n_alignments; tot.n_overflow_reads += ws[g].total.n_overflow_reads;
-		if (ws[g].kernel_ms > kms) kms = ws[g].kernel_ms;
-		if (ws[g].t_ctx > tctx) tctx = ws[g].t_ctx;
-		if (ws[g].t_pool > tpool) tpool = ws[g].t_pool;
-		if (ws[g].t_first_submit > tfirst) tfirst = ws[g].t_first_submit;
-		if (ws[g].pool_bytes > pool_bytes) pool_bytes = ws[g].pool_bytes;
+		fold_worker(&tot, &ws[g]);
 		if (n_gpus > 1) /* one line per worker: an uneven node (a slow link, a busy socket) shows here, not in the total */
 			printf("  GPU %d (device %d, NUMA node %d): reads %llu  kernel %.1f ms  index to HBM %.2f sec  launches %llu  parked reads %llu  re-run reads %llu\n", g, ws[g].device,
 			       bwb_hip_device_numa_node(ws[g].device), (unsigned long long)ws[g].n_reads, ws[g].kernel_ms, ws[g].t_ctx,
@@ -623,72 +695,12 @@ static int run_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, 
 	}
 	const double dt = wall() - t0;
 	printf("GPUs: %d  reads: %llu  wall: %.3f sec (%.0f reads/s incl. index upload)  kernel: %.1f ms  index to HBM: %.2f sec  first chunk parsed after: %.2f sec  rank-block visits: %llu  hits: %llu  re-run reads: %llu\n",
-	       n_gpus, (unsigned long long)pp.n_reads, dt, pp.n_reads / (dt > 0 ? dt : 1), kms, tctx, pp.t_first_chunk, (unsigned long long)(tot.visits_single + tot.visits_alphabet),
-	       (unsigned long long)tot.n_alignments, (unsigned long long)tot.n_overflow_reads);
-	if (map) {
-		double pms = 0; unsigned long long pst = 0;
-		for (int g = 0; g < n_gpus; g++) { pst += ws[g].place_steps; if (ws[g].place_ms > pms) pms = ws[g].place_ms; }
-		printf("placements on the GPU: reads %llu  rank-block visits %llu  kernel %.3f ms", (unsigned long long)pp.n_reads, pst, pms);
-		if (map->bub && map->gpu_loci) { /* -B: the loci of the same reads */
-			double lms = 0; unsigned long long lrd = 0;
-			for (int g = 0; g < n_gpus; g++) { lrd += ws[g].locus_reads; if (ws[g].locus_ms > lms) lms = ws[g].locus_ms; }
-			printf("  loci resolved %llu  k_locus %.3f ms", lrd, lms);
-		} else if (map->bub) printf("  loci resolved %llu on the host%s (the .ann records are not ascending and disjoint)", (unsigned long long)pp.n_reads, map->join ? " and joined there" : "");
-		printf("\n");
-		if (map->join) { /* -J */
-			double jms = 0; unsigned long long jit = 0, jjn = 0, jmq = 0;
-			for (int g = 0; g < n_gpus; g++) { jit += ws[g].join_items; jjn += ws[g].join_joined; jmq += ws[g].join_mapq; if (ws[g].join_ms > jms) jms = ws[g].join_ms; }
-			if (map->gpu_loci) printf("placements joined by locus on the GPU: items %llu  joined %llu  reads with another MAPQ %llu  kernels %.3f ms\n", jit, jjn, jmq, jms);
-			else printf("placements joined by locus on the host: joined %llu  reads with another MAPQ %llu\n", jjn, jmq);
-		}
-		if (map->lift) { /* -R */
-			double lms = 0; unsigned long long ll = 0, lu = 0, lb = 0;
-			for (int g = 0; g < n_gpus; g++) { ll += ws[g].lift_lifted; lu += ws[g].lift_unliftable; lb += ws[g].lift_bytes; if (ws[g].lift_ms > lms) lms = ws[g].lift_ms; }
-			if (map->gpu_loci) printf("placements lifted to chromosome coordinates on the GPU: lifted %llu  not liftable %llu  kernels %.3f ms  bytes to the host %llu\n", ll, lu, lms, lb);
-			else printf("placements lifted to chromosome coordinates on the host (the .ann records are not ascending and disjoint): lifted %llu  not liftable %llu\n", ll, lu);
-		}
-		if (map->md) { /* -D */
-			double mms = 0, ts = 0; unsigned long long mr = 0, mb = 0, bk = 0;
-			for (int g = 0; g < n_gpus; g++) { mr += ws[g].md_reads; mb += ws[g].md_bytes; bk += ws[g].md_back; if (ws[g].md_ms > mms) mms = ws[g].md_ms; if (ws[g].text_s > ts) ts = ws[g].text_s; }
-			if (!(map->lift && !map->gpu_loci))
-				printf("NM and MD against the text on the GPU: reads %llu  MD bytes %llu  kernels %.3f ms  bytes to the host %llu  text %llu characters read in %.3f s, set in %.3f s\n", mr, mb, mms, bk,
-				       (unsigned long long)map->text->n_fwd, map->text->seconds, ts);
-			else printf("NM and MD against the text on the host (the .ann records are not ascending and disjoint): reads %llu  MD bytes %llu\n", mr, mb);
-		}
-		if (map->pile) { /* -A */
-			double pms = 0, bs = 0, fs = 0; unsigned long long pr = 0, pa = 0;
-			for (int g = 0; g < n_gpus; g++) { pr += ws[g].pile_reads; pa += ws[g].pile_adds; if (ws[g].pile_ms > pms) pms = ws[g].pile_ms; if (ws[g].pile_begin_s > bs) bs = ws[g].pile_begin_s; if (ws[g].pile_fetch_s > fs) fs = ws[g].pile_fetch_s; }
-			if (!map->pile_on_host)
-				printf("allele counts at the text's IUPAC sites on the GPU: sites %llu  reads counted %llu  adds %llu  k_pile %.3f ms  site index and counters %llu bytes, built in %.3f s  counters read back in %.3f s\n",
-				       (unsigned long long)map->pile->n_sites, pr, pa, pms, (unsigned long long)((map->text->n_fwd + 31) / 32 * 4 + map->pile->n_sites * 16), bs, fs);
-			else printf("allele counts at the text's IUPAC sites on the host (the .ann records are not ascending and disjoint): sites %llu  reads counted %llu  adds %llu\n",
-			            (unsigned long long)map->pile->n_sites, (unsigned long long)map->pile->reads, (unsigned long long)map->pile->adds);
-		}
-		if (map->indel) { /* -I */
-			double ims = 0, bs = 0, fs = 0; unsigned long long ir = 0, ia = 0, ic = 0;
-			for (int g = 0; g < n_gpus; g++) { ir += ws[g].indel_reads; ia += ws[g].indel_adds; ic += ws[g].indel_cands; if (ws[g].indel_ms > ims) ims = ws[g].indel_ms; if (ws[g].indel_begin_s > bs) bs = ws[g].indel_begin_s; if (ws[g].indel_fetch_s > fs) fs = ws[g].indel_fetch_s; }
-			if (map->gpu_loci)
-				printf("read support per indel bubble on the GPU: anchor %d  eligible bubbles %llu  refused and skipped %llu  reads counted %llu  adds %llu  candidates %llu  k_indel %.3f ms  table and counters %llu bytes, sorted in %.3f s, resident in %.3f s  counters read back in %.3f s\n",
-				       map->indel->anchor, (unsigned long long)map->indel->n_tab, (unsigned long long)map->indel->n_refused, ir, ia, ic, ims,
-				       (unsigned long long)(map->indel->n_tab * 16 + (uint64_t)map->bub->n * 17), map->indel->sort_s, bs, fs);
-			else printf("read support per indel bubble on the host (the .ann records are not ascending and disjoint): anchor %d  eligible bubbles %llu  refused and skipped %llu  reads counted %llu  adds %llu  candidates %llu\n",
-			            map->indel->anchor, (unsigned long long)map->indel->n_tab, (unsigned long long)map->indel->n_refused, (unsigned long long)map->indel->reads, (unsigned long long)map->indel->adds, (unsigned long long)map->indel->cands);
-		}
-		if (map->geno && !map->pile_on_host) /* -G */
-			printf("genotype calls on the GPU (worker %d): error phred %d  minimum depth %lld  sites called %llu%s  bubbles called %llu  kernels %.3f ms  pieces %llu  bytes to the host %llu  tables put back in %llu pieces, %.3f s  called in %.3f s\n",
-			       map->geno->worker, map->geno->err, (long long)map->geno->min_depth, (unsigned long long)map->geno->n_sites, map->indel && !map->gpu_loci ? " (the bubbles follow on the host)" : "",
-			       (unsigned long long)map->geno->n_bubs, map->geno->kernel_ms, (unsigned long long)map->geno->pieces,
-			       (unsigned long long)(map->geno->n_sites * sizeof(bwb_geno_site) + map->geno->n_bubs * sizeof(bwb_geno_bubble) + map->geno->pieces * 8), (unsigned long long)map->geno->put_pieces, map->geno->put_s, map->geno->call_s);
-		if (map->max_alt) {
-			double ams = 0; unsigned long long ast = 0, ait = 0;
-			for (int g = 0; g < n_gpus; g++) { ast += ws[g].alt_steps; ait += ws[g].alt_items; if (ws[g].alt_ms > ams) ams = ws[g].alt_ms; }
-			printf("other placements on the GPU (-X %d): items %llu (%.3f per read)  rank-block visits %llu  kernels %.3f ms\n", map->max_alt, ait,
-			       pp.n_reads ? (double)ait / (double)pp.n_reads : 0.0, ast, ams);
-		}
-	}
+	       n_gpus, (unsigned long long)pp.n_reads, dt, pp.n_reads / (dt > 0 ? dt : 1), tot.kernel_ms, tot.t_ctx, pp.t_first_chunk, (unsigned long long)(tot.total.visits_single + tot.total.visits_alphabet),
+	       (unsigned long long)tot.total.n_alignments, (unsigned long long)tot.total.n_overflow_reads);
+	if (map) print_map_summary(map, &tot, pp.n_reads);
 	/* where the start-up went (the three overlap): the .bwt file in memory | the index in HBM | the chunk pool's hipMalloc | first slice queued */
 	printf("start-up: .bwt read %.2f sec | index to HBM %.2f sec | chunk pool %.1f GB in %.2f sec | first slice queued after %.2f sec\n",
-	       bwt_load_seconds(BWT), tctx, (double)pool_bytes / (1u << 30), tpool, tfirst);
+	       bwt_load_seconds(BWT), tot.t_ctx, (double)tot.pool_bytes / (1u << 30), tot.t_pool, tot.t_first_submit);
 	free(ws); free(th);
 	pthread_mutex_destroy(&pp.mu); pthread_cond_destroy(&pp.cv_work); pthread_cond_destroy(&pp.cv_done); pthread_cond_destroy(&pp.cv_space);
 	fclose(alnFile);
@@ -737,17 +749,19 @@ int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_
 }
 
 /* `bwbble map`: align_reads + alns2sam in one pass.  The .bwt is loaded once, with its SA; the SAM header is written before the first chunk. */
-int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor, const char *genoFname, int geno_err, int64_t geno_depth, int n_gpus) {
+int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, const map_opts_t *o, int n_gpus) {
 	printf("**** BWBBLE Read Mapping (align + aln2sam in one pass) ****\n");
-	/* -A: the counts file is opened before anything is loaded; until it is written, a run that stops leaves none behind */
-	pile_t *pile = countsFname || genoFname ? pile_open(countsFname, min_mapq) : NULL; /* (-G: the table without a file) */
-	indel_t *indel = indelFname || (genoFname && bubbleFname) ? indel_open(indelFname, min_mapq, anchor) : NULL; /* -I (main.c: only with -B): the same; -G with -B: the table without a file */
-	geno_t *geno = genoFname ? geno_open(genoFname, geno_err, geno_depth) : NULL; /* -G: the same */
+	/* -A, -I, -G: the files are opened before anything is loaded; until they are written, a run that stops leaves none behind */
+	host_outs_t out;
+	host_outs_open(&out, o);
+	pile_t *pile = out.pile;
+	indel_t *indel = out.indel;
+	geno_t *geno = out.geno;
 	/* -B: the table first (a refused table stops the run before anything is created) */
-	bubble_table_t *bub = bubbleFname ? load_bubbles(bubbleFname) : NULL;
-	if (lift && bub) lift_check_table(bub); /* -R (main.c: only with -B): a bubble the rule refuses is named here */
+	bubble_table_t *bub = o->bubbleFname ? load_bubbles(o->bubbleFname) : NULL;
+	if (o->lift && bub) lift_check_table(bub); /* -R (main.c: only with -B): a bubble the rule refuses is named here */
 	/* -D: a missing <seq_fasta>.ref, or one of another size than the .ann says, stops the run here; the .bwt loader reads its forward half, behind the sampled SA */
-	md_text_t *text = md || pile ? md_text_open_for(fastaFname, 1, md ? "-D" : countsFname ? "-A" : "-G") : NULL; /* (-A loads it the same way, with or without -D) */
+	md_text_t *text = host_text_open(fastaFname, o, &out, 1); /* (-A loads it the same way, with or without -D) */
 	/* before anything is created: without a GPU no SAM file is left behind */
 	if (bwb_hip_device_count() < 1) bwb_die("align_reads_inexact_gpu: no HIP device found (this build has no CPU alignment path)");
 	size_t L = strlen(fastaFname) + 8;
@@ -760,8 +774,8 @@ int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *
 	/* -B: every record's bubble number, before the SAM file exists (a record that names a bubble outside the table leaves none behind) */
 	int32_t *bubble_of = bub ? ann_bubble_of(ann, bub) : NULL;
 	/* -J (main.c: only with -X and -B): the chromosome's record of every bubble; one without a chromosome leaves no SAM file behind either */
-	join = join && bub && max_alt; lift = lift && bub;
-	int32_t *chrom_of = join || lift || indel ? bubble_chrom_of(ann, bubble_of, bub, join ? "-J" : lift ? "-R" : indelFname ? "-I" : "-G") : NULL;
+	const int join = o->join && bub && o->max_alt, lift = o->lift && bub;
+	int32_t *chrom_of = join || lift || indel ? bubble_chrom_of(ann, bubble_of, bub, join ? "-J" : lift ? "-R" : o->indelFname ? "-I" : "-G") : NULL;
 	if (indel) indel_set_table(indel, bub, chrom_of); /* -I: the eligible bubbles, sorted; a refused bubble is skipped, not named */
 	uint64_t *rec_start = NULL, *rec_end = NULL;
 	int gpu_loci = bub && ann->num_seq > 0 && sam_ann_sorted(ann) && bub->n <= INT32_MAX;
@@ -778,9 +792,9 @@ int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *
 	FILE *sam = fopen(samFname, "w");
 	if (!sam) { perror(samFname); bwb_die("map_reads: Cannot open SAM file: %s!", samFname); }
 	sam_write_header(sam, ann);
-	const map_t m = { .max_mm = max_mm, .max_alt = max_alt, .ann = ann, .ann_sorted = sam_ann_sorted(ann),
-	                  .bub = bub, .bubble_of = bubble_of, .gpu_loci = gpu_loci, .rec_start = rec_start, .rec_end = rec_end, .chrom_of = chrom_of, .join = join, .lift = lift, .text = text,
-	                  .md = md, .pile = pile, .pile_on_host = pile && bub && !gpu_loci && (lift || join), .indel = indel, .geno = geno };
+	const map_t m = { .max_mm = o->max_mm, .max_alt = o->max_alt, .T = { .ann = ann, .ann_sorted = sam_ann_sorted(ann), .bub = bub, .bubble_of = bubble_of, .chrom_of = chrom_of },
+	                  .gpu_loci = gpu_loci, .rec_start = rec_start, .rec_end = rec_end, .join = join, .lift = lift, .text = text,
+	                  .md = o->md, .pile = pile, .pile_on_host = pile && bub && !gpu_loci && (lift || join), .indel = indel, .geno = geno };
 
 	t = wall();
 	printf("BWBBLE Inexact Alignment (MI355X)...\n");
@@ -808,6 +822,6 @@ int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *
 	printf("Total read mapping time (index and read loading overlapped): %.2f sec\n", wall() - t);
 	free_bwt(BWT); free_ann(ann);
 	free(bwtFname); free(annFname);
-	free(bubble_of); free(chrom_of); free(rec_start); free(rec_end); free_bubbles(bub); pile_free(pile); indel_free(indel); geno_free(geno); md_text_free(text);
+	free(bubble_of); free(chrom_of); free(rec_start); free(rec_end); free_bubbles(bub); host_outs_free(&out); md_text_free(text);
 	return 0;
 }

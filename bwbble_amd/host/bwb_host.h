@@ -122,14 +122,31 @@ int aln_path_bytes(const bwb_aln *a, unsigned char *path /* >= 272 bytes */); /*
 void set_default_aln_params(aln_params_t *params);                     /* align.c:22-38 */
 int align_reads(char *fastaFname, char *readsFname, char *alnsFname, aln_params_t *params, int n_gpus); /* align.c:40-87 */
 int align_reads_inexact_gpu_stream(bwt_t *BWT, const char *readsFname, aln_params_t *params, char *alnFname, int n_gpus); /* the GPU's align_reads_inexact_parallel (inexact_match.h:40) over a streamed FASTQ */
-int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, int max_mm, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor, const char *genoFname, int geno_err, int64_t geno_depth, int n_gpus); /* `bwbble map` (countsFname: -A, NULL: no counts; min_mapq: -a; indelFname: -I, NULL: no table; anchor: -w; genoFname: -G, NULL: no calls; geno_err: -q; geno_depth: -d): align + aln2sam in one pass, the hits evaluated on the GPU */
+/* what the command line asks of the result stream: `map`, `aln2sam` and `places2sam` share the record; main.c fills it letter by letter
+ * (map_option) and checks and completes it (map_opts_finish) before any of them runs */
+typedef struct {
+	int max_mm;                  /* map -Q, aln2sam -n: the mismatch count at which a unique hit gets MAPQ 25 (6; places2sam has no flag for it) */
+	int max_alt;                 /* -X: 1..255, X0:i / X1:i and up to that many other placements as XA:Z: (0: no tags) */
+	const char *bubbleFname;     /* -B: the bubble table, bubble.data - the tags bC:Z: / bP:Z: (NULL: no tags) */
+	int join;                    /* -J: a read's placements counted by locus, MAPQ without the joined ones and the tag bJ:i:; needs -X and -B */
+	int lift;                    /* -R: placements on a bubble record written in chromosome coordinates, the tag bO:Z:; needs -B */
+	int md;                      /* -D: the tags NM:i / MD:Z against the text of <seq_fasta>.ref */
+	const char *countsFname;     /* -A: the file of the allele counts at the text's IUPAC sites (NULL: no counts) */
+	int min_mapq;                /* -a: the least MAPQ that -A, -I and -G count, 0..255 (-1 until finished: not given, then 0) */
+	const char *indelFname;      /* -I: the file of the read support per indel bubble (NULL: no table); needs -B */
+	int anchor;                  /* -w: the flank bases a read must cover on either side for -I and -G, 1..255 (0 until finished: not given, then 1) */
+	const char *genoFname;       /* -G: the file of the genotype calls from both tables (NULL: no calls) */
+	int geno_err;                /* -q: the error phred of -G, 4..93 (0 until finished: not given, then 20) */
+	int64_t geno_depth;          /* -d: the minimum depth of a call of -G, 1..2^31 - 1 (0 until finished: not given, then 1) */
+} map_opts_t;
+int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *params, const map_opts_t *opts, int n_gpus); /* `bwbble map`: align + aln2sam in one pass, the hits evaluated on the GPU */
 
 /* precalc.c */
 void precalc_sa_intervals(bwt_t *BWT, const aln_params_t *params, const char *preFname); /* align.c:200-224: writes <fasta>.pre */
 int check_precalc_file(const char *preFname); /* the walk of load_precalc_sa_intervals (align.c:226-238) over an existing table: 0 = complete */
 
 /* sam.c */
-void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor, const char *genoFname, int geno_err, int64_t geno_depth); /* align.c:494-556; genoFname / geno_err / geno_depth: -G / -q / -d; max_alt: -X (0: no tags); bubbleFname: -B (NULL: no tags); join: -J; lift: -R; md: -D; countsFname: -A (NULL: no counts), min_mapq: -a; indelFname: -I (NULL: no table), anchor: -w */
+void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int n_gpus, const map_opts_t *opts); /* align.c:494-556 */
 /* the two halves of alns2sam: eval_aln of one read on the host, and the text of a block of reads from placement records (which `map` gets
  * from the GPU instead, bwb_hip_slot_place) */
 #define SAM_BLOCK_READS ((size_t)1 << 14)                              /* reads formatted by one thread at a time */
@@ -154,7 +171,7 @@ uint64_t alt_placements(const bwb_aln *e, uint64_t ne);               /* the row
 void sam_write_header(FILE *sam, const fasta_annotations_t *ann);
 int sam_ann_sorted(const fasta_annotations_t *ann);
 char *sam_format_reads(const sam_reads_t *rd, size_t r0, size_t r1, const fasta_annotations_t *ann, int ann_sorted, size_t *out_len);
-void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor, const char *genoFname, int geno_err, int64_t geno_depth); /* developer command: records from a file (genoFname / geno_err / geno_depth: -G / -q / -d; countsFname / min_mapq: -A / -a; indelFname / anchor: -I / -w; (altsFname: NULL or the items; bubbleFname: NULL or -B's table; join: -J, the items file then ends with one suboptimal byte per item; lift: -R; md: -D) */
+void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const map_opts_t *opts); /* developer command: records from a file (altsFname: NULL or the items; with -J the items file ends with one suboptimal byte per item) */
 
 /* pad.c: bubble hits in reference coordinates (the reference's mg-ref/sam_pad.cpp) */
 typedef struct bubble_table {                                          /* bubble.data (mg-ref/comb.cpp:245-253): the k-th pair of lines is bubble k */
@@ -254,6 +271,35 @@ void geno_host(geno_t *g, const pile_t *pile, const indel_t *indel);  /* the gen
 uint64_t geno_write(geno_t *g, const fasta_annotations_t *ann, const bubble_table_t *bub); /* the header line, the called sites, the called bubbles (bub NULL: none); closes the file; returns the lines */
 void geno_free(geno_t *g);
 void sam_pad(const char *dataFname, const char *inFname, const char *outFname); /* `bwbble sampad`: sam_pad.cpp:47-94 over SAM text */
+
+/* host_chain.c: the host's rules behind the placement records, stage by stage - loci, joins, lifts, NM / MD, then the tables of -A, -I and -G.
+ * `aln2sam` and `places2sam` run the whole chain; `map` runs a stage here where it cannot run it on the GPU (align_gpu.c).  The chunk's or
+ * file's records ride in a sam_reads_t: a stage reads what the stages before it put there. */
+typedef struct { pile_t *pile; indel_t *indel; geno_t *geno; } host_outs_t; /* the output trio; -G keeps the tables of -A and (with -B) -I in memory without their files */
+void host_outs_open(host_outs_t *out, const map_opts_t *opts);       /* before anything is loaded: a path that cannot be written stops the run */
+void host_outs_free(host_outs_t *out);
+/* the text of <seq_fasta>.ref that -D, -A and -G need (NULL: none of them), named after the first of them in its messages: a missing .ref, or one of
+ * another size than the .ann says, stops the run; deferred: md_text_open's */
+md_text_t *host_text_open(const char *fastaFname, const map_opts_t *opts, const host_outs_t *out, int deferred);
+typedef struct {                                                     /* what the rules resolve against */
+	const fasta_annotations_t *ann; int ann_sorted;
+	bubble_table_t *bub;                                              /* -B (NULL: none) */
+	int32_t *bubble_of, *chrom_of;                                    /* every .ann record's bubble number; -J, -R, -I, -G with -B: the chromosome's record of every bubble (NULL: not needed) */
+} host_tables_t;
+void host_tables_load(host_tables_t *T, const fasta_annotations_t *ann, const map_opts_t *opts, int indel); /* aln2sam, places2sam: the table, the records' bubbles, -R's check, the bubbles' chromosomes (indel: a table of -I is kept) */
+void host_tables_free(host_tables_t *T);                             /* (not ann: the caller's) */
+typedef struct { bwb_locus *loci; bwb_join *joins; lift_set_t *lift; md_set_t *md; } host_recs_t; /* what the host's stages allocated for a sam_reads_t */
+void host_recs_free(host_recs_t *own);
+bwb_locus *host_loci(const sam_reads_t *rd, size_t n, const host_tables_t *T); /* -B: the locus record of every placement record, with all cores (malloc'ed) */
+/* -J: the join record of every read, with all cores (malloc'ed).  sub: one byte per item, not zero for a suboptimal one; NULL: from the reads'
+ * hits - read r's are hits[hit_off[r] ..) - an item is suboptimal when its hit's score is greater than the first hit's (align.c:771-779) */
+bwb_join *host_joins(const sam_reads_t *rd, size_t n, const host_tables_t *T, int max_mm, const uint8_t *sub, const bwb_aln *hits, const uint64_t *hit_off);
+void sam_reads_set_lift(sam_reads_t *rd, const lift_set_t *ls);     /* -R's records into the carrier, whose lift_n is its number of reads (NULL: as placed) */
+void sam_reads_set_md(sam_reads_t *rd, const md_set_t *ms);          /* -D's (NULL: no tags) */
+/* the four stages in order, as the options ask; rd gains the records, own what has to be freed.  sub / hits / hit_off: host_joins's; log: the lines of -R and -D */
+void host_chain(sam_reads_t *rd, size_t n, const host_tables_t *T, const map_opts_t *opts, const md_text_t *text, const uint8_t *sub, const bwb_aln *hits, const uint64_t *hit_off, int log, host_recs_t *own);
+/* the tail, when the SAM file is complete: the host's rules of -A and -I on the same records, the calls of -G from both tables, each file written and its log line */
+void host_tail(host_outs_t *out, const sam_reads_t *rd, size_t n, const host_tables_t *T, const md_text_t *text);
 
 /* The OpenMP teams of the host stages of `align` / `aln2sam` (base encoding, .aln serialisation, SAM text) have at most 32 threads unless
  * OMP_NUM_THREADS says otherwise: on the GPU box (2 x 64 cores, 256 hardware threads) a team of 256 - every hardware thread spinning in

@@ -61,67 +61,50 @@ static int aln2sam_usage(void) {
 	printf("         A    <counts.tsv>: the allele counts of `bwbble map -A`, from the host's rule (default: no counts)\n         I    <indels.tsv>, with -B: the read support per indel bubble of `bwbble map -I`, from the host's rule (default: no table)\n         G    <calls.tsv>: the genotype calls of `bwbble map -G`, from the host's rule (default: no calls)\n         q    with -G: the error phred, 4..93 (default: 20)\n         d    with -G: the minimum depth, 1..2147483647 (default: 1)\n         w    with -I or -G: the anchor, 1..255 (default: 1)\n         a    with -A, -I or -G: the least MAPQ that counts, 0..255 (default: 0)\n\n");
 	return 1;
 }
-/* -a's argument: 0..255, anything else is refused; and -a without -A */
-static int mapq_option(const char *arg) {
-	char *end;
-	const long v = strtol(arg, &end, 10);
-	if (end == arg || *end || v < 0 || v > 255) { printf("Error: -a takes a MAPQ of 0..255, not %s\n", arg); exit(1); }
-	return (int)v;
-}
-static void pile_option_check(const char *countsFname, const char *indelFname, const char *genoFname, int min_mapq) {
-	if (countsFname || indelFname || genoFname || min_mapq < 0) return;
-	printf("Error: -a needs -A <counts.tsv>, -I <indels.tsv> or -G <calls.tsv>\n");
-	exit(1);
-}
-/* -w's argument: 1..255, anything else is refused; -I without -B; and -w without -I */
-static int anchor_option(const char *arg) {
-	char *end;
-	const long v = strtol(arg, &end, 10);
-	if (end == arg || *end || v < 1 || v > 255) { printf("Error: -w takes an anchor of 1..255, not %s\n", arg); exit(1); }
-	return (int)v;
-}
-static void indel_option_check(const char *indelFname, int anchor, const char *bubbleFname, const char *genoFname) {
-	if (indelFname && !bubbleFname) { printf("Error: -I needs -B <bubble.data>\n"); exit(1); }
-	if (!indelFname && !genoFname && anchor > 0) { printf("Error: -w needs -I <indels.tsv> or -G <calls.tsv>\n"); exit(1); }
-}
-/* -q's argument: 4..93; -d's: 1..2^31 - 1; anything else is refused; and either without -G (0: not given) */
-static int err_option(const char *arg) {
-	char *end;
-	const long v = strtol(arg, &end, 10);
-	if (end == arg || *end || v < 4 || v > 93) { printf("Error: -q takes an error phred of 4..93, not %s\n", arg); exit(1); }
-	return (int)v;
-}
-static int64_t depth_option(const char *arg) {
+/* a number option's argument: lo..hi, anything else is refused with the flag's own message */
+static long long range_option(const char *arg, long long lo, long long hi, const char *refusal) {
 	char *end;
 	const long long v = strtoll(arg, &end, 10);
-	if (end == arg || *end || v < 1 || v > 2147483647ll) { printf("Error: -d takes a minimum depth of 1..2147483647, not %s\n", arg); exit(1); }
-	return (int64_t)v;
-}
-static void geno_option_check(const char *genoFname, int geno_err, int64_t geno_depth) {
-	if (genoFname) return;
-	if (geno_err) { printf("Error: -q needs -G <calls.tsv>\n"); exit(1); }
-	if (geno_depth) { printf("Error: -d needs -G <calls.tsv>\n"); exit(1); }
-}
-/* -X's argument: 1..255, anything else is refused */
-static int alt_option(const char *arg) {
-	char *end;
-	const long v = strtol(arg, &end, 10);
-	if (*arg == 0 || *end != 0 || v < 1 || v > 255) { printf("Error: -X takes a number from 1 to 255 (got '%s')\n", arg); exit(1); }
-	return (int)v;
+	if (end == arg || *end || v < lo || v > hi) { printf(refusal, arg); exit(1); }
+	return v;
 }
 
-/* -J needs the items of -X and the table of -B: without either nothing is written */
-static void join_option_check(int join, int max_alt, const char *bubbleFname) {
-	if (!join || (max_alt && bubbleFname)) return;
-	printf("Error: -J needs %s%s%s\n", max_alt ? "" : "-X <N>", max_alt || bubbleFname ? "" : " and ", bubbleFname ? "" : "-B <bubble.data>");
-	exit(1);
+/* the options of the result stream that `map`, `aln2sam` and `places2sam` share (bwb_host.h: map_opts_t): the record before any is given, and
+ * one option letter with its argument into it; 0 = not one of them */
+static const map_opts_t MAP_OPTS_NONE = { .max_mm = 6 /* (aln2sam's default, mg-aligner/main.c:142) */, .min_mapq = -1 /* (no -a) */ };
+static int map_option(int c, const char *arg, map_opts_t *o) {
+	switch (c) {
+	case 'Q': o->max_mm = atoi(arg); return 1; /* (aln2sam spells it -n) */
+	case 'X': o->max_alt = (int)range_option(arg, 1, 255, "Error: -X takes a number from 1 to 255 (got '%s')\n"); return 1;
+	case 'B': o->bubbleFname = arg; return 1;
+	case 'J': o->join = 1; return 1;
+	case 'R': o->lift = 1; return 1;
+	case 'D': o->md = 1; return 1;
+	case 'A': o->countsFname = arg; return 1;
+	case 'a': o->min_mapq = (int)range_option(arg, 0, 255, "Error: -a takes a MAPQ of 0..255, not %s\n"); return 1;
+	case 'I': o->indelFname = arg; return 1;
+	case 'w': o->anchor = (int)range_option(arg, 1, 255, "Error: -w takes an anchor of 1..255, not %s\n"); return 1;
+	case 'G': o->genoFname = arg; return 1;
+	case 'q': o->geno_err = (int)range_option(arg, 4, 93, "Error: -q takes an error phred of 4..93, not %s\n"); return 1;
+	case 'd': o->geno_depth = range_option(arg, 1, 2147483647ll, "Error: -d takes a minimum depth of 1..2147483647, not %s\n"); return 1;
+	}
+	return 0;
 }
 
-/* -R needs the table of -B */
-static void lift_option_check(int lift, const char *bubbleFname) {
-	if (!lift || bubbleFname) return;
-	printf("Error: -R needs -B <bubble.data>\n");
-	exit(1);
+/* what one flag needs of another, in this order: -J, -R, -a, -I / -w, -q / -d; then the defaults of what was not given */
+static void map_opts_finish(map_opts_t *o) {
+	const char *B = o->bubbleFname;
+	if (o->join && !(o->max_alt && B)) { printf("Error: -J needs %s%s%s\n", o->max_alt ? "" : "-X <N>", o->max_alt || B ? "" : " and ", B ? "" : "-B <bubble.data>"); exit(1); }
+	if (o->lift && !B) { printf("Error: -R needs -B <bubble.data>\n"); exit(1); }
+	if (o->min_mapq >= 0 && !o->countsFname && !o->indelFname && !o->genoFname) { printf("Error: -a needs -A <counts.tsv>, -I <indels.tsv> or -G <calls.tsv>\n"); exit(1); }
+	if (o->indelFname && !B) { printf("Error: -I needs -B <bubble.data>\n"); exit(1); }
+	if (o->anchor && !o->indelFname && !o->genoFname) { printf("Error: -w needs -I <indels.tsv> or -G <calls.tsv>\n"); exit(1); }
+	if (o->geno_err && !o->genoFname) { printf("Error: -q needs -G <calls.tsv>\n"); exit(1); }
+	if (o->geno_depth && !o->genoFname) { printf("Error: -d needs -G <calls.tsv>\n"); exit(1); }
+	if (o->min_mapq < 0) o->min_mapq = 0;
+	if (!o->anchor) o->anchor = 1;
+	if (!o->geno_err) o->geno_err = 20;
+	if (!o->geno_depth) o->geno_depth = 1;
 }
 
 /* the options `align` and `map` share; 0 = not one of them */
@@ -170,36 +153,16 @@ int main(int argc, char *argv[]) {
 		if (argc < 5) { map_usage(); exit(1); }
 		aln_params_t params;
 		set_default_aln_params(&params);
-		int c, n_gpus = 1, max_mm = 6, max_alt = 0, join = 0, lift = 0, md = 0; /* (aln2sam's default, mg-aligner/main.c:142) */
-		const char *bubbleFname = NULL, *countsFname = NULL, *indelFname = NULL, *genoFname = NULL;
-		int min_mapq = -1, anchor = 0, geno_err = 0; /* (-1: no -a; 0: no -w, no -q) */
-		int64_t geno_depth = 0; /* (0: no -d) */
+		int c, n_gpus = 1;
+		map_opts_t o = MAP_OPTS_NONE;
 		while ((c = getopt(argc - 1, argv + 1, "M:O:E:n:k:o:e:l:m:t:g:SPQ:X:B:JRDA:a:I:w:G:q:d:")) >= 0) {
-			if (align_option(c, &params, &n_gpus)) continue;
-			if (c == 'Q') { max_mm = atoi(optarg); continue; }
-			if (c == 'X') { max_alt = alt_option(optarg); continue; }
-			if (c == 'B') { bubbleFname = optarg; continue; }
-			if (c == 'J') { join = 1; continue; }
-			if (c == 'R') { lift = 1; continue; }
-			if (c == 'D') { md = 1; continue; }
-			if (c == 'A') { countsFname = optarg; continue; }
-			if (c == 'a') { min_mapq = mapq_option(optarg); continue; }
-			if (c == 'I') { indelFname = optarg; continue; }
-			if (c == 'w') { anchor = anchor_option(optarg); continue; }
-			if (c == 'G') { genoFname = optarg; continue; }
-			if (c == 'q') { geno_err = err_option(optarg); continue; }
-			if (c == 'd') { geno_depth = depth_option(optarg); continue; }
+			if (align_option(c, &params, &n_gpus) || map_option(c, optarg, &o)) continue;
 			if (c == '?') { map_usage(); return 1; }
 			return 1;
 		}
 		if (argc - 1 - optind < 3) { map_usage(); exit(1); }
-		join_option_check(join, max_alt, bubbleFname);
-		lift_option_check(lift, bubbleFname);
-		pile_option_check(countsFname, indelFname, genoFname, min_mapq);
-		indel_option_check(indelFname, anchor, bubbleFname, genoFname);
-		geno_option_check(genoFname, geno_err, geno_depth);
-		map_reads(argv[optind + 1], argv[optind + 2], argv[optind + 3], &params, max_mm, max_alt, bubbleFname, join, lift, md, countsFname, min_mapq < 0 ? 0 : min_mapq, indelFname, anchor ? anchor : 1,
-		          genoFname, geno_err ? geno_err : 20, geno_depth ? geno_depth : 1, n_gpus);
+		map_opts_finish(&o);
+		map_reads(argv[optind + 1], argv[optind + 2], argv[optind + 3], &params, &o, n_gpus);
 	} else if (strcmp(argv[1], "places2sam") == 0) {
 		/* developer command (CPU only, used by the tests): placement records (bwb_place, include/bwbble_hip.h) from a file -> SAM text */
 		/* (a sixth argument: u64 alt_off[n + 1] followed by the bwb_alt records - the X tags of `map -X`) */
@@ -207,30 +170,19 @@ int main(int argc, char *argv[]) {
 		 * the items file then ends with one byte per item, not zero for a suboptimal one; `-R` behind them: RNAME, POS and CIGAR of `map -R`, from the
 		 * host's rule; `-D` behind that: the tags NM / MD of `map -D`, from the host's rule; `-A <counts.tsv>` and `-a <MAPQ>` behind that: the allele
 		 * counts of `map -A`, from the host's rule) */
+		/* (the flags only in this order, each at most once) */
 		char **a = argv + 2;
-		int na = argc - 2, join = 0, lift = 0, md = 0;
-		const char *bubbleFname = NULL, *countsFname = NULL, *indelFname = NULL, *genoFname = NULL;
-		int min_mapq = -1, anchor = 0, geno_err = 0;
-		int64_t geno_depth = 0;
-		if (na >= 2 && strcmp(a[0], "-B") == 0) { bubbleFname = a[1]; a += 2; na -= 2; }
-		if (na >= 1 && strcmp(a[0], "-J") == 0) { join = 1; a++; na--; }
-		if (na >= 1 && strcmp(a[0], "-R") == 0) { lift = 1; a++; na--; }
-		if (na >= 1 && strcmp(a[0], "-D") == 0) { md = 1; a++; na--; }
-		if (na >= 2 && strcmp(a[0], "-A") == 0) { countsFname = a[1]; a += 2; na -= 2; }
-		if (na >= 2 && strcmp(a[0], "-a") == 0) { min_mapq = mapq_option(a[1]); a += 2; na -= 2; }
-		if (na >= 2 && strcmp(a[0], "-I") == 0) { indelFname = a[1]; a += 2; na -= 2; }
-		if (na >= 2 && strcmp(a[0], "-w") == 0) { anchor = anchor_option(a[1]); a += 2; na -= 2; }
-		if (na >= 2 && strcmp(a[0], "-G") == 0) { genoFname = a[1]; a += 2; na -= 2; }
-		if (na >= 2 && strcmp(a[0], "-q") == 0) { geno_err = err_option(a[1]); a += 2; na -= 2; }
-		if (na >= 2 && strcmp(a[0], "-d") == 0) { geno_depth = depth_option(a[1]); a += 2; na -= 2; }
+		int na = argc - 2;
+		map_opts_t o = MAP_OPTS_NONE;
+		for (const char *f = "B:JRDA:a:I:w:G:q:d:"; *f; f++) {
+			const int arg = f[1] == ':';
+			if (na > arg && a[0][0] == '-' && a[0][1] == *f && !a[0][2]) { map_option(*f, arg ? a[1] : NULL, &o); a += 1 + arg; na -= 1 + arg; }
+			f += arg;
+		}
 		if (na < 4) { printf("Usage: bwbble places2sam [-B <bubble.data>] [-J] [-R] [-D] [-A <counts.tsv>] [-a <MAPQ>] [-I <indels.tsv>] [-w <anchor>] [-G <calls.tsv>] [-q <err>] [-d <depth>] <seq_fasta> <reads_fastq> <places_bin> <out_sam> [<alts_bin>] \n"); exit(1); }
-		join_option_check(join, na >= 5, bubbleFname);
-		lift_option_check(lift, bubbleFname);
-		pile_option_check(countsFname, indelFname, genoFname, min_mapq);
-		indel_option_check(indelFname, anchor, bubbleFname, genoFname);
-		geno_option_check(genoFname, geno_err, geno_depth);
-		places2sam(a[0], a[1], a[2], a[3], na >= 5 ? a[4] : NULL, bubbleFname, join, lift, md, countsFname, min_mapq < 0 ? 0 : min_mapq, indelFname, anchor ? anchor : 1, genoFname, geno_err ? geno_err : 20,
-		           geno_depth ? geno_depth : 1);
+		o.max_alt = na >= 5; /* (-J needs the items file, as it needs -X elsewhere) */
+		map_opts_finish(&o);
+		places2sam(a[0], a[1], a[2], a[3], na >= 5 ? a[4] : NULL, &o);
 	} else if (strcmp(argv[1], "sampad") == 0) {
 		if (argc < 5) { printf("Usage: bwbble sampad <bubble.data> <in_sam> <out_sam> \n"); exit(1); }
 		sam_pad(argv[2], argv[3], argv[4]);
@@ -246,39 +198,20 @@ int main(int argc, char *argv[]) {
 		free(seq); free(refFname); free(annFname);
 	} else if (strcmp(argv[1], "aln2sam") == 0) {
 		if (argc < 6) { aln2sam_usage(); exit(1); }
-		int is_multiref = 1, max_diff = 6, n_gpus = 1, max_alt = 0, join = 0, lift = 0, md = 0, c;
-		const char *bubbleFname = NULL, *countsFname = NULL, *indelFname = NULL, *genoFname = NULL;
-		int min_mapq = -1, anchor = 0, geno_err = 0;
-		int64_t geno_depth = 0;
+		int is_multiref = 1, n_gpus = 1, c;
+		map_opts_t o = MAP_OPTS_NONE;
 		while ((c = getopt(argc - 1, argv + 1, "n:g:SX:B:JRDA:a:I:w:G:q:d:")) >= 0) {
+			if (map_option(c == 'n' ? 'Q' : c, optarg, &o)) continue;
 			switch (c) {
-			case 'X': max_alt = alt_option(optarg); break;
-			case 'B': bubbleFname = optarg; break;
-			case 'J': join = 1; break;
-			case 'R': lift = 1; break;
-			case 'D': md = 1; break;
-			case 'A': countsFname = optarg; break;
-			case 'a': min_mapq = mapq_option(optarg); break;
-			case 'I': indelFname = optarg; break;
-			case 'w': anchor = anchor_option(optarg); break;
-			case 'G': genoFname = optarg; break;
-			case 'q': geno_err = err_option(optarg); break;
-			case 'd': geno_depth = depth_option(optarg); break;
 			case 'S': is_multiref = 0; break;
-			case 'n': max_diff = atoi(optarg); break;
 			case 'g': n_gpus = atoi(optarg); break;
 			case '?': printf("Unknown option \n"); break;
 			default: return 1;
 			}
 		}
 		if (argc - 1 - optind < 4) { aln2sam_usage(); exit(1); }
-		join_option_check(join, max_alt, bubbleFname);
-		lift_option_check(lift, bubbleFname);
-		pile_option_check(countsFname, indelFname, genoFname, min_mapq);
-		indel_option_check(indelFname, anchor, bubbleFname, genoFname);
-		geno_option_check(genoFname, geno_err, geno_depth);
-		alns2sam(argv[optind + 1], argv[optind + 2], argv[optind + 3], argv[optind + 4], is_multiref, max_diff, n_gpus, max_alt, bubbleFname, join, lift, md, countsFname, min_mapq < 0 ? 0 : min_mapq, indelFname, anchor ? anchor : 1,
-		         genoFname, geno_err ? geno_err : 20, geno_depth ? geno_depth : 1);
+		map_opts_finish(&o);
+		alns2sam(argv[optind + 1], argv[optind + 2], argv[optind + 3], argv[optind + 4], is_multiref, n_gpus, &o);
 	} else if (strcmp(argv[1], "dumpreads") == 0) {
 		/* developer command (CPU only, used by the tests): what fastq2reads made of a FASTQ - per read "name<TAB>codes<TAB>quality" */
 		if (argc < 4) { printf("Usage: bwbble dumpreads <reads_fastq> <out_tsv> [chunk_reads [text]] \n"); exit(1); }

@@ -226,41 +226,27 @@ static void *locate_worker(void *arg) {
 	return NULL;
 }
 
-/* -B on the host (aln2sam, places2sam): the locus record of every placement record, with all cores */
-static bwb_locus *host_loci(const bwb_place *pl, size_t n, const fasta_annotations_t *ann, int ann_sorted, const int32_t *bubble_of, const bubble_table_t *bub) {
-	bwb_locus *loci = (bwb_locus *)malloc((n ? n : 1) * sizeof(bwb_locus));
-#pragma omp parallel for schedule(static) num_threads(bwb_host_team())
-	for (long r = 0; r < (long)n; r++) locus_resolve(&pl[r], ann, ann_sorted, bubble_of, bub, &loci[r]);
-	return loci;
+/* the carrier of a whole file's reads (aln2sam, places2sam): the records so far; host_chain adds the rest */
+static sam_reads_t sam_reads_of(const reads_t *reads, size_t n, const bwb_place *pl, const uint64_t *alt_off, const bwb_alt *alts) {
+	return (sam_reads_t){ .pl = pl, .seq = reads->seq, .stride = reads->stride, .len = reads->len, .text = reads->raw,
+	                      .name_off = reads->name_off, .qual_off = reads->qual_off, .name_len = reads->name_len, .first = 0, .alt_off = alt_off, .alts = alts, .lift_n = n };
 }
 
-/* -J on the host (aln2sam, places2sam): the join record of every read, with all cores */
-static bwb_join *host_joins(const bwb_place *pl, const bwb_locus *loci, const uint64_t *alt_off, const bwb_alt *alts, const uint8_t *alt_sub, size_t n, const fasta_annotations_t *ann,
-                            int ann_sorted, const int32_t *bubble_of, const int32_t *chrom_of, const bubble_table_t *bub, int max_mm) {
-	bwb_join *joins = (bwb_join *)malloc((n ? n : 1) * sizeof(bwb_join));
-#pragma omp parallel for schedule(static) num_threads(bwb_host_team())
-	for (long r = 0; r < (long)n; r++)
-		join_resolve(&pl[r], &loci[r], alts + alt_off[r], alt_sub + alt_off[r], alt_off[r + 1] - alt_off[r], ann, ann_sorted, bubble_of, chrom_of, bub, max_mm, &joins[r]);
-	return joins;
-}
-
-void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int max_diff, int n_gpus, int max_alt, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor, const char *genoFname, int geno_err, int64_t geno_depth) {
+void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFname, int is_multiref, int n_gpus, const map_opts_t *o) {
 	(void)is_multiref;
 	printf("**** BWBBLE Alignment Evaluation/SAM File Generation ****\n");
-	pile_t *pile = countsFname || genoFname ? pile_open(countsFname, min_mapq) : NULL; /* -A (a path that cannot be written stops the run before anything is loaded); -G: the table without a file */
-	indel_t *indel = indelFname || (genoFname && bubbleFname) ? indel_open(indelFname, min_mapq, anchor) : NULL; /* -I (main.c: only with -B; the same); -G with -B: the table without a file */
-	geno_t *geno = genoFname ? geno_open(genoFname, geno_err, geno_depth) : NULL; /* -G (the same) */
-	md_text_t *text = md || pile ? md_text_open_for(fastaFname, 0, md ? "-D" : countsFname ? "-A" : "-G") : NULL; /* -D (a missing .ref, or one of another size than the .ann says, stops the run before anything is loaded or created) */
+	const int max_alt = o->max_alt;
+	host_outs_t out;
+	host_outs_open(&out, o);
+	md_text_t *text = host_text_open(fastaFname, o, &out, 0); /* (before anything is loaded or created) */
 	size_t Ln = strlen(fastaFname) + 8;
 	char *bwtFname = (char *)malloc(Ln), *annFname = (char *)malloc(Ln);
 	snprintf(bwtFname, Ln, "%s.bwt", fastaFname);
 	snprintf(annFname, Ln, "%s.ann", fastaFname);
 	bwt_t *BWT = load_bwt(bwtFname, 1);
 	fasta_annotations_t *ann = annf2ann(annFname);
-	bubble_table_t *bub = bubbleFname ? load_bubbles(bubbleFname) : NULL; /* (refused tables stop the run before the SAM file exists) */
-	int32_t *bubble_of = bub ? ann_bubble_of(ann, bub) : NULL;
-	if (lift) lift_check_table(bub); /* -R (main.c: only with -B) */
-	int32_t *chrom_of = join || lift || indel ? bubble_chrom_of(ann, bubble_of, bub, join ? "-J" : lift ? "-R" : indelFname ? "-I" : "-G") : NULL; /* -J (main.c: only with -X and -B), -R */
+	host_tables_t T;
+	host_tables_load(&T, ann, o, out.indel != NULL);
 	alns_batch_t *alns = alnsf2alns_bin(alnsFname);
 	reads_t *reads = fastq2reads(readsFname);
 	FILE *sam = fopen(samFname, "w");
@@ -326,25 +312,11 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 	bwb_place *pl = (bwb_place *)malloc((n ? n : 1) * sizeof(bwb_place));
 #pragma omp parallel for schedule(static) num_threads(bwb_host_team())
 	for (long r = 0; r < (long)n; r++)
-		place_from_alns(alns->alns + alns->aln_off[r], alns->aln_off[r + 1] - alns->aln_off[r], ref_pos[r], BWT->length, max_diff, &pl[r]);
-	const int ann_sorted = sam_ann_sorted(ann);
-	bwb_locus *loci = bub ? host_loci(pl, n, ann, ann_sorted, bubble_of, bub) : NULL;
-	uint8_t *alt_sub = NULL; /* -J: an item is suboptimal when its hit's score is greater than the first hit's (align.c:771-779) */
-	if (join) {
-		alt_sub = (uint8_t *)malloc(n_alt ? n_alt : 1);
-		for (size_t r = 0; r < n; r++)
-			for (uint64_t q = alt_off[r]; q < alt_off[r + 1]; q++) alt_sub[q] = alns->alns[alns->aln_off[r] + alts[q].hit].score > alns->alns[alns->aln_off[r]].score;
-	}
-	bwb_join *joins = join ? host_joins(pl, loci, alt_off, alts, alt_sub, n, ann, ann_sorted, bubble_of, chrom_of, bub, max_diff) : NULL;
-	lift_set_t *ls = lift ? lift_host(pl, loci, n, alt_off, alts, ann, ann_sorted, bubble_of, chrom_of, bub) : NULL;
-	if (ls) printf("placements lifted to chromosome coordinates on the host: %llu  not liftable %llu\n", (unsigned long long)ls->n_lifted, (unsigned long long)ls->n_unliftable);
-	md_set_t *ms = md ? md_host(pl, n, reads->seq, reads->stride, reads->len, ls ? ls->kind : NULL, ls ? ls->off : NULL, ls ? ls->recs : NULL, ann, text) : NULL;
-	if (ms) printf("NM and MD against the text on the host: reads %llu  too long %llu  MD bytes %llu\n", (unsigned long long)ms->n_ok, (unsigned long long)ms->n_too_long, (unsigned long long)ms->off[n]);
-	const sam_reads_t rd = { .pl = pl, .seq = reads->seq, .stride = reads->stride, .len = reads->len, .text = reads->raw,
-	                         .name_off = reads->name_off, .qual_off = reads->qual_off, .name_len = reads->name_len, .first = 0,
-	                         .alt_off = alt_off, .alts = alts, .loci = loci, .bubbles = bub, .joins = joins,
-	                         .lift_kind = ls ? ls->kind : NULL, .lift_off = ls ? ls->off : NULL, .lift_recs = ls ? ls->recs : NULL, .lift_n = n,
-	                         .md = ms ? ms->recs : NULL, .md_off = ms ? ms->off : NULL, .md_text = ms ? ms->text : NULL };
+		place_from_alns(alns->alns + alns->aln_off[r], alns->aln_off[r + 1] - alns->aln_off[r], ref_pos[r], BWT->length, o->max_mm, &pl[r]);
+	const int ann_sorted = T.ann_sorted;
+	sam_reads_t rd = sam_reads_of(reads, n, pl, alt_off, alts);
+	host_recs_t own;
+	host_chain(&rd, n, &T, o, text, NULL, alns->alns, alns->aln_off, 1, &own); /* (-J: an item's suboptimal byte from the hits' scores) */
 	/* The text: blocks of reads are formatted into memory by all cores and written in order (round 5: one thread's fprintf calls were
 	 * the wall time of aln2sam on a 10 M-read file, not the SA lookups). */
 	const size_t BLK = SAM_BLOCK_READS;
@@ -369,49 +341,24 @@ void alns2sam(char *fastaFname, char *readsFname, char *alnsFname, char *samFnam
 	free(rows); free(pos); free(which); free(ref_pos);
 	free(bwtFname); free(annFname);
 	fclose(sam);
-	if (pile) { /* -A: the host's rule on the same records, written when the SAM file is complete */
-		pile_set_text(pile, text, 1);
-		pile_host(pile, pl, n, reads->seq, reads->stride, reads->len, ls ? ls->kind : NULL, ls ? ls->off : NULL, ls ? ls->recs : NULL, joins, ann);
-	}
-	if (pile && pile->f) {
-		const unsigned long long lines = pile_write(pile, ann);
-		printf("allele counts at the text's IUPAC sites on the host: sites %llu  reads counted %llu  adds %llu  sites written %llu\n", (unsigned long long)pile->n_sites, (unsigned long long)pile->reads, (unsigned long long)pile->adds, lines);
-	}
-	if (indel) { /* -I: the host's rule on the same records (the printed CIGAR, with or without -R), written when the SAM file is complete */
-		indel_set_table(indel, bub, chrom_of);
-		indel_host(indel, pl, loci, n, reads->len, joins);
-	}
-	if (indel && indel->f) {
-		const unsigned long long lines = indel_write(indel);
-		printf("read support per indel bubble on the host: anchor %d  eligible bubbles %llu  refused and skipped %llu  reads counted %llu  adds %llu  candidates %llu  lines written %llu\n", indel->anchor,
-		       (unsigned long long)indel->n_tab, (unsigned long long)indel->n_refused, (unsigned long long)indel->reads, (unsigned long long)indel->adds, (unsigned long long)indel->cands, lines);
-	}
-	if (geno) { /* -G: the calls from the two tables, written last */
-		geno_host(geno, pile, indel);
-		const unsigned long long sites = geno->n_sites, bubs = geno->n_bubs, lines = geno_write(geno, ann, bub);
-		printf("genotype calls on the host: error phred %d  minimum depth %lld  sites called %llu  bubbles called %llu  lines written %llu\n", geno->err, (long long)geno->min_depth, sites, bubs, lines);
-	}
-	free(pl); free(alt_off); free(alts); free(loci); free(bubble_of); free_bubbles(bub);
-	free(alt_sub); free(joins); free(chrom_of); lift_free(ls); md_free(ms); pile_free(pile); indel_free(indel); geno_free(geno); md_text_free(text);
+	host_tail(&out, &rd, n, &T, text);
+	free(pl); free(alt_off); free(alts);
+	host_recs_free(&own); host_tables_free(&T); host_outs_free(&out); md_text_free(text);
 	free_bwt(BWT); free_reads(reads); free_alns_batch(alns); free_ann(ann);
 }
 
-/* developer command (CPU only, for the tests): raw bwb_place records from a file through sam_format_reads - the formatter `map` uses, on a
- * machine without a GPU (bubbleFname: -B, the loci from the host resolver; join: -J, the join records from the host's rule; lift: -R, the
- * lift records from the host's rule; md: -D, NM and MD from the host's rule) */
-void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const char *bubbleFname, int join, int lift, int md, const char *countsFname, int min_mapq, const char *indelFname, int anchor, const char *genoFname, int geno_err, int64_t geno_depth) {
-	pile_t *pile = countsFname || genoFname ? pile_open(countsFname, min_mapq) : NULL; /* -A; -G: the table without a file */
-	indel_t *indel = indelFname || (genoFname && bubbleFname) ? indel_open(indelFname, min_mapq, anchor) : NULL; /* -I (main.c: only with -B); -G with -B: the table without a file */
-	geno_t *geno = genoFname ? geno_open(genoFname, geno_err, geno_depth) : NULL; /* -G */
+/* developer command (CPU only, for the tests): raw bwb_place records from a file through the host's chain and sam_format_reads - the formatter
+ * `map` uses, on a machine without a GPU */
+void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *samFname, char *altsFname, const map_opts_t *o) {
+	host_outs_t out;
+	host_outs_open(&out, o);
 	size_t Ln = strlen(fastaFname) + 8;
 	char *annFname = (char *)malloc(Ln);
 	snprintf(annFname, Ln, "%s.ann", fastaFname);
 	fasta_annotations_t *ann = annf2ann(annFname);
-	bubble_table_t *bub = bubbleFname ? load_bubbles(bubbleFname) : NULL;
-	int32_t *bubble_of = bub ? ann_bubble_of(ann, bub) : NULL;
-	if (lift) lift_check_table(bub); /* -R (main.c: only with -B) */
-	int32_t *chrom_of = join || lift || indel ? bubble_chrom_of(ann, bubble_of, bub, join ? "-J" : lift ? "-R" : indelFname ? "-I" : "-G") : NULL; /* -J (main.c: only with -B and an items file), -R */
-	md_text_t *text = md || pile ? md_text_open_for(fastaFname, 0, md ? "-D" : countsFname ? "-A" : "-G") : NULL; /* -D, -A, -G */
+	host_tables_t T;
+	host_tables_load(&T, ann, o, out.indel != NULL);
+	md_text_t *text = host_text_open(fastaFname, o, &out, 0);
 	reads_t *reads = fastq2reads(readsFname);
 	FILE *pf = fopen(placesFname, "rb");
 	if (!pf) { perror(placesFname); bwb_die("places2sam: Cannot open the placements file: %s!", placesFname); }
@@ -431,7 +378,7 @@ void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *sam
 		for (size_t r = 0; r < n; r++) if (alt_off[r + 1] < alt_off[r]) bwb_die("places2sam: %s: the offsets do not ascend", altsFname);
 		alts = (bwb_alt *)malloc((alt_off[n] ? alt_off[n] : 1) * sizeof(bwb_alt));
 		if (alt_off[0] != 0 || fread(alts, sizeof(bwb_alt), alt_off[n], af) != alt_off[n]) bwb_die("places2sam: %s does not hold the records its offsets name", altsFname);
-		if (join) {
+		if (o->join) {
 			alt_sub = (uint8_t *)malloc(alt_off[n] ? alt_off[n] : 1);
 			if (fread(alt_sub, 1, alt_off[n], af) != alt_off[n]) bwb_die("places2sam: %s does not hold one suboptimal byte per item behind its records (-J)", altsFname);
 		}
@@ -440,47 +387,19 @@ void places2sam(char *fastaFname, char *readsFname, char *placesFname, char *sam
 	FILE *sam = fopen(samFname, "w");
 	if (!sam) { perror(samFname); bwb_die("places2sam: Cannot open SAM file: %s!", samFname); }
 	sam_write_header(sam, ann);
-	const int ann_sorted = sam_ann_sorted(ann);
-	bwb_locus *loci = bub ? host_loci(pl, n, ann, ann_sorted, bubble_of, bub) : NULL;
-	bwb_join *joins = join ? host_joins(pl, loci, alt_off, alts, alt_sub, n, ann, ann_sorted, bubble_of, chrom_of, bub, 6) : NULL; /* (aln2sam's default -n: the records carry no max_mm) */
-	lift_set_t *ls = lift ? lift_host(pl, loci, n, alt_off, alts, ann, ann_sorted, bubble_of, chrom_of, bub) : NULL;
-	md_set_t *ms = md ? md_host(pl, n, reads->seq, reads->stride, reads->len, ls ? ls->kind : NULL, ls ? ls->off : NULL, ls ? ls->recs : NULL, ann, text) : NULL;
-	const sam_reads_t rd = { .pl = pl, .seq = reads->seq, .stride = reads->stride, .len = reads->len, .text = reads->raw,
-	                         .name_off = reads->name_off, .qual_off = reads->qual_off, .name_len = reads->name_len, .first = 0,
-	                         .alt_off = alt_off, .alts = alts, .loci = loci, .bubbles = bub, .joins = joins,
-	                         .lift_kind = ls ? ls->kind : NULL, .lift_off = ls ? ls->off : NULL, .lift_recs = ls ? ls->recs : NULL, .lift_n = n,
-	                         .md = ms ? ms->recs : NULL, .md_off = ms ? ms->off : NULL, .md_text = ms ? ms->text : NULL };
+	sam_reads_t rd = sam_reads_of(reads, n, pl, alt_off, alts);
+	host_recs_t own;
+	host_chain(&rd, n, &T, o, text, alt_sub, NULL, NULL, 0, &own);
 	for (size_t r0 = 0; r0 < n; r0 += SAM_BLOCK_READS) {
 		size_t len = 0;
-		char *buf = sam_format_reads(&rd, r0, r0 + SAM_BLOCK_READS < n ? r0 + SAM_BLOCK_READS : n, ann, ann_sorted, &len);
+		char *buf = sam_format_reads(&rd, r0, r0 + SAM_BLOCK_READS < n ? r0 + SAM_BLOCK_READS : n, ann, T.ann_sorted, &len);
 		if (len && fwrite(buf, 1, len, sam) != len) bwb_die("places2sam: Cannot write to the SAM file: %s!", samFname);
 		free(buf);
 	}
 	printf("Processed %zu reads.\n", n);
 	fclose(sam);
-	if (pile) { /* -A: the host's rule, written when the SAM file is complete */
-		pile_set_text(pile, text, 1);
-		pile_host(pile, pl, n, reads->seq, reads->stride, reads->len, ls ? ls->kind : NULL, ls ? ls->off : NULL, ls ? ls->recs : NULL, joins, ann);
-	}
-	if (pile && pile->f) {
-		const unsigned long long lines = pile_write(pile, ann);
-		printf("allele counts at the text's IUPAC sites on the host: sites %llu  reads counted %llu  adds %llu  sites written %llu\n", (unsigned long long)pile->n_sites, (unsigned long long)pile->reads, (unsigned long long)pile->adds, lines);
-	}
-	if (indel) { /* -I: the host's rule on the same records (the printed CIGAR, with or without -R), written when the SAM file is complete */
-		indel_set_table(indel, bub, chrom_of);
-		indel_host(indel, pl, loci, n, reads->len, joins);
-	}
-	if (indel && indel->f) {
-		const unsigned long long lines = indel_write(indel);
-		printf("read support per indel bubble on the host: anchor %d  eligible bubbles %llu  refused and skipped %llu  reads counted %llu  adds %llu  candidates %llu  lines written %llu\n", indel->anchor,
-		       (unsigned long long)indel->n_tab, (unsigned long long)indel->n_refused, (unsigned long long)indel->reads, (unsigned long long)indel->adds, (unsigned long long)indel->cands, lines);
-	}
-	if (geno) { /* -G: the calls from the two tables, written last */
-		geno_host(geno, pile, indel);
-		const unsigned long long sites = geno->n_sites, bubs = geno->n_bubs, lines = geno_write(geno, ann, bub);
-		printf("genotype calls on the host: error phred %d  minimum depth %lld  sites called %llu  bubbles called %llu  lines written %llu\n", geno->err, (long long)geno->min_depth, sites, bubs, lines);
-	}
-	free(pl); free(annFname); free(alt_off); free(alts); free(loci); free(bubble_of); free_bubbles(bub);
-	free(alt_sub); free(joins); free(chrom_of); lift_free(ls); md_free(ms); pile_free(pile); indel_free(indel); geno_free(geno); md_text_free(text);
+	host_tail(&out, &rd, n, &T, text);
+	free(pl); free(annFname); free(alt_off); free(alts); free(alt_sub);
+	host_recs_free(&own); host_tables_free(&T); host_outs_free(&out); md_text_free(text);
 	free_reads(reads); free_ann(ann);
 }
