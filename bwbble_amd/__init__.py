@@ -31,6 +31,8 @@ EXPORTS = [
     "bwb_hip_pile_begin", "bwb_hip_slot_pile", "bwb_hip_batch_pile", "bwb_hip_pile_records", "bwb_hip_pile_counts", "bwb_hip_pile_reset", "bwb_hip_pile_site_of", "bwb_hip_pile_stats",
     "bwb_hip_indel_begin", "bwb_hip_slot_indel", "bwb_hip_batch_indel", "bwb_hip_indel_records", "bwb_hip_indel_counts", "bwb_hip_indel_reset", "bwb_hip_indel_stats",
     "bwb_hip_geno_begin", "bwb_hip_pile_put", "bwb_hip_indel_put", "bwb_hip_geno_sites", "bwb_hip_geno_bubbles", "bwb_hip_geno_stats",
+    "bwb_hip_pileq_begin", "bwb_hip_slot_quals", "bwb_hip_slot_pile_q", "bwb_hip_batch_pile_q", "bwb_hip_pile_records_q", "bwb_hip_pileq_sums", "bwb_hip_pileq_put", "bwb_hip_pileq_stats",
+    "bwb_hip_geno_sites_q",
 ]
 ABI_VERSION = 3  # BWB_HIP_ABI_VERSION (include/bwbble_hip.h)
 MAX_SLOTS = 8  # BWB_MAX_SLOTS
@@ -88,7 +90,9 @@ LIFT_NONE, LIFT_LIFTED, LIFT_UNLIFTABLE = 0, 1, 2
 # bwb_geno_site / bwb_geno_bubble (include/bwbble_hip.h): the called sites' and bubbles' records of the geno family
 GENO_SITE_DTYPE = np.dtype([("pos", "<u8"), ("site", "<u8"), ("n", "<u4", (4,)), ("code", "u1"), ("n_geno", "u1"), ("gt", "u1"), ("gq", "u1"), ("reserved", "<u4"), ("pl", "<u4", (6,))])
 GENO_BUBBLE_DTYPE = np.dtype([("bubble", "<u4"), ("n", "<u4", (4,)), ("gt", "u1"), ("gq", "u1"), ("reserved", "<u2"), ("pl", "<u4", (3,)), ("pad", "<u4", (3,))])
-assert GENO_SITE_DTYPE.itemsize == 64 and GENO_BUBBLE_DTYPE.itemsize == 48
+# bwb_geno_site_q: the site's record by the weighted rule (-Y), then its four quality sums
+GENO_SITE_Q_DTYPE = np.dtype(GENO_SITE_DTYPE.descr + [("qs", "<u4", (4,))])
+assert GENO_SITE_DTYPE.itemsize == 64 and GENO_BUBBLE_DTYPE.itemsize == 48 and GENO_SITE_Q_DTYPE.itemsize == 80 and GENO_SITE_Q_DTYPE.fields["qs"][1] == 64
 MD_DTYPE = np.dtype([("nm", "<u4"), ("md_len", "<u2"), ("kind", "u1"), ("reserved", "u1")])
 assert MD_DTYPE.itemsize == 8
 MD_NONE, MD_OK, MD_TOO_LONG, MD_MAX_SPAN = 0, 1, 2, 4096
@@ -189,6 +193,15 @@ def lib():
         L.bwb_hip_geno_sites.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.bwb_hip_geno_bubbles.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.bwb_hip_geno_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.bwb_hip_pileq_begin.argtypes = [C.c_void_p, C.c_int]
+        L.bwb_hip_slot_quals.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32]
+        L.bwb_hip_slot_pile_q.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+        L.bwb_hip_batch_pile_q.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+        L.bwb_hip_pile_records_q.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.bwb_hip_pileq_sums.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        L.bwb_hip_pileq_put.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        L.bwb_hip_pileq_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.bwb_hip_geno_sites_q.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
 
@@ -647,8 +660,8 @@ class Context:
         _chk(lib().bwb_hip_batch_pile(self._h, max_mm, max_alt, int(bool(lifted)), int(bool(joined)), min_mapq, C.byref(n)))
         return n.value
 
-    def pile_records(self, seqs, lens, places, kinds=None, lift_off=None, words=None, mapq=None, min_mapq=0):
-        """the same kernel on reads and records of the caller's, laid out as for md_records; mapq: one value per read in place of the records' own"""
+    @staticmethod
+    def _pile_record_arrays(seqs, lens, places, kinds, lift_off, words, mapq):
         seqs, lens = _read_arrays(seqs, lens)
         places = np.ascontiguousarray(places, dtype=PLACE_DTYPE)
         if len(places) != len(lens):
@@ -665,6 +678,11 @@ class Context:
             mapq = np.ascontiguousarray(mapq, dtype=np.uint8)
             if len(mapq) != len(lens):
                 raise ValueError("one MAPQ per read")
+        return seqs, lens, places, lift, mapq, (kinds, lift_off, words)  # (the last: kept alive behind the pointers in `lift`)
+
+    def pile_records(self, seqs, lens, places, kinds=None, lift_off=None, words=None, mapq=None, min_mapq=0):
+        """the same kernel on reads and records of the caller's, laid out as for md_records; mapq: one value per read in place of the records' own"""
+        seqs, lens, places, lift, mapq, _keep = self._pile_record_arrays(seqs, lens, places, kinds, lift_off, words, mapq)
         _chk(lib().bwb_hip_pile_records(self._h, seqs.ctypes.data, lens.ctypes.data, seqs.shape[1], places.ctypes.data, len(lens), *lift,
                                         mapq.ctypes.data if mapq is not None else None, min_mapq))
 
@@ -689,6 +707,59 @@ class Context:
     def pile_stats(self):
         """(reads counted, adds, kernel ms) of the last pile call that launched"""
         return self._count_steps_ms(lib().bwb_hip_pile_stats)
+
+    # -- base qualities in the pile (-b / -Y): a minimum base quality, and device-resident quality sums beside the counters (needs pile_begin and
+    #    pileq_begin; the slot forms slot_quals behind the slot's upload) --
+    def pileq_begin(self, weighted=False):
+        """the slots keep quality bytes from now on; weighted: zeroed quality sums, n_sites x (A, C, G, T).  After pile_begin, before the first upload"""
+        _chk(lib().bwb_hip_pileq_begin(self._h, int(bool(weighted))))
+
+    def slot_quals(self, slot, quals, stride=None):
+        """the quality bytes of the slot's reads, (n_reads, stride) uint8 laid out like the upload's seqs (stride None: the array's)"""
+        quals = np.ascontiguousarray(quals, dtype=np.uint8)
+        if quals.ndim != 2:
+            raise ValueError("quals must be (n_reads, stride) uint8")
+        _chk(lib().bwb_hip_slot_quals(self._h, slot, quals.ctypes.data, max(quals.shape[1], 1) if stride is None else stride))
+
+    def slot_pile_q(self, slot, max_mm=6, max_alt=5, lifted=False, joined=False, min_mapq=0, min_baseq=0, err_cap=0):
+        """slot_pile with the slot's qualities: bases below min_baseq are dropped; err_cap 4..93 also adds min(max(Q, 4), err_cap) to the sums"""
+        n = C.c_uint64()
+        _chk(lib().bwb_hip_slot_pile_q(self._h, slot, max_mm, max_alt, int(bool(lifted)), int(bool(joined)), min_mapq, min_baseq, err_cap, C.byref(n)))
+        return n.value
+
+    def batch_pile_q(self, max_mm=6, max_alt=5, lifted=False, joined=False, min_mapq=0, min_baseq=0, err_cap=0):
+        """the same for the one-batch interface (after run() / align(); slot_quals(0, ...) behind the upload)"""
+        n = C.c_uint64()
+        _chk(lib().bwb_hip_batch_pile_q(self._h, max_mm, max_alt, int(bool(lifted)), int(bool(joined)), min_mapq, min_baseq, err_cap, C.byref(n)))
+        return n.value
+
+    def pile_records_q(self, seqs, quals, lens, places, kinds=None, lift_off=None, words=None, mapq=None, min_mapq=0, min_baseq=0, err_cap=0):
+        """pile_records with the reads' quality bytes, laid out like seqs"""
+        seqs, lens, places, lift, mapq, _keep = self._pile_record_arrays(seqs, lens, places, kinds, lift_off, words, mapq)
+        quals = np.ascontiguousarray(quals, dtype=np.uint8)
+        if quals.shape != seqs.shape:
+            raise ValueError("quals must have the shape of seqs")
+        _chk(lib().bwb_hip_pile_records_q(self._h, seqs.ctypes.data, quals.ctypes.data, lens.ctypes.data, seqs.shape[1], places.ctypes.data, len(lens), *lift,
+                                          mapq.ctypes.data if mapq is not None else None, min_mapq, min_baseq, err_cap))
+
+    def pileq_sums(self, first=0, n=None, n_sites=None):
+        """the quality sums of the sites first .. first + n - 1 as an (n, 4) uint32 array: A, C, G, T (n None: up to n_sites)"""
+        if n is None:
+            n = n_sites - first
+        out = np.zeros((n, 4), dtype=np.uint32)
+        _chk(lib().bwb_hip_pileq_sums(self._h, first, n, out.ctypes.data))
+        return out
+
+    def pileq_put(self, first, sums):
+        """overwrites the quality sums of the sites first .. with an (n, 4) uint32 array: A, C, G, T"""
+        sums = np.ascontiguousarray(sums, dtype=np.uint32).reshape(-1, 4)
+        _chk(lib().bwb_hip_pileq_put(self._h, first, len(sums), sums.ctypes.data))
+
+    def pileq_stats(self):
+        """(reads counted, adds, bases dropped by min_baseq, kernel ms) of the last pile_q call that launched"""
+        r, a, d, ms = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_double()
+        _chk(lib().bwb_hip_pileq_stats(self._h, C.byref(r), C.byref(a), C.byref(d), C.byref(ms)))
+        return r.value, a.value, d.value, ms.value
 
     # -- ref / alt read support per indel bubble (-I): device-resident counters, n_bub x (ref, alt, ref_gapped, alt_gapped), summed over every
     #    indel call (needs set_loci, set_bubble_chrom and indel_begin; the slot forms set_sa) --
@@ -762,6 +833,10 @@ class Context:
     def geno_sites(self, first, n, err=20, min_depth=1):
         """the records (GENO_SITE_DTYPE, a copy) of the called sites among first .. first + n - 1, in site order"""
         return self._geno(lib().bwb_hip_geno_sites, GENO_SITE_DTYPE, first, n, err, min_depth)
+
+    def geno_sites_q(self, first, n, err=20, min_depth=1):
+        """the same by the weighted rule, from the counters and the quality sums (GENO_SITE_Q_DTYPE; needs pileq_begin(weighted) before geno_begin)"""
+        return self._geno(lib().bwb_hip_geno_sites_q, GENO_SITE_Q_DTYPE, first, n, err, min_depth)
 
     def geno_bubbles(self, first, n, err=20, min_depth=1):
         """the records (GENO_BUBBLE_DTYPE, a copy) of the called bubbles among first .. first + n - 1, in bubble order"""

@@ -163,6 +163,10 @@ struct Slot {
 	std::vector<uint64_t> h_aln_off;
 	std::vector<bwb_aln> h_alns;
 	Event ev_up;
+	DevMem d_quals; PinMem h_quals; /* bwb_hip_slot_quals: one quality byte per base of the resident reads, strided like d_reads */
+	Event ev_quals;
+	uint32_t up_stride = 0;         /* the caller's stride at slot_upload (slot_quals takes the same) */
+	bool quals_set = false;         /* this upload's qualities are there; cleared by slot_upload */
 	bool calcd_queued = false;    /* kl_calc_d of this batch has been queued ahead of its submit, on the context's second kernel stream (calcd_ahead) */
 	Event ev_calcd;
 	uint64_t launch = 0;          /* sequence number of the slice that was fed from this slot */
@@ -224,6 +228,9 @@ struct bwb_hip_ctx {
 	PinMem h_pile_stats;
 	bool pile_on = false; uint64_t pile_sites = 0; /* pile_begin has run on this text; its sites */
 	double pile_ms = 0; uint64_t pile_reads = 0, pile_adds = 0; /* the last pile call that launched */
+	DevMem d_qsum, d_pileq_stats; PinMem h_pileq_stats; /* k_pile_q: the n_sites x 4 quality sums (weighted only), three sums of one launch (bwb_hip_pileq_begin) */
+	bool pileq_on = false, pileq_weighted = false;      /* pileq_begin has run behind this pile_begin: the slots keep quality bytes; qsum exists */
+	double pileq_ms = 0; uint64_t pileq_reads = 0, pileq_adds = 0, pileq_dropped = 0; /* the last pile_q call that launched */
 	std::vector<bwb_bubble> loci_bubbles; std::vector<int32_t> chrom_of; /* the host's copies of set_loci's bubble table and set_bubble_chrom's records (bwb_hip_indel_begin) */
 	DevMem d_indel_tab, d_indel_elig, d_indel_counts, d_indel_stats; /* k_indel: the eligible bubbles sorted by (chrom_of, lo, bubble), one byte per bubble, the n_bub x 4 counters, three sums of one launch */
 	PinMem h_indel_stats;
@@ -231,6 +238,7 @@ struct bwb_hip_ctx {
 	double indel_ms = 0; uint64_t indel_reads = 0, indel_adds = 0, indel_cands = 0; /* the last indel call that launched */
 	DevMem d_geno_cnt, d_geno_word, d_geno_off, d_geno_bsum, d_geno_sites, d_geno_bubs; /* the geno kernels: per entry of a piece the called flag, the site's word and the scan; the called records */
 	PinMem h_geno_sites, h_geno_bubs, h_geno_n;
+	bool geno_q = false;                /* geno_begin came behind a weighted pileq_begin: the site records' buffers hold 80-byte bwb_geno_site_q */
 	bool geno_on = false, geno_bub = false; uint32_t geno_piece = 0, geno_piece_bub = 0; /* geno_begin has run on this site index (and on this bubble table) */
 	double geno_ms = 0; uint64_t geno_sites_called = 0, geno_bubs_called = 0; /* the last geno_sites / geno_bubbles call: its kernels' time; the entries each called last */
 	bool force_slices = false;          /* BWB_FORCE_SLICES: the one-batch API parks and resumes too (tests) */
@@ -517,7 +525,7 @@ static int ensure_pool(bwb_hip_ctx *c) {
 	const size_t isz = c->pos32 ? 8 : 16;
 	const size_t cls1 = (size_t)std::max(1, c->num_cu / 2) * LANE_BLOCK * (2 * 8192 * isz + 1024 * sizeof(bwb_aln)), cls2 = (size_t)LANE_BLOCK * (2 * ((size_t)1 << 20) * isz + 65536 * sizeof(bwb_aln));
 	size_t slot_bytes = 0;
-	for (const Slot &s : c->slots) slot_bytes = std::max(slot_bytes, s.d_reads.bytes + s.d_dbuf.bytes + s.d_log.bytes + (size_t)s.n_reads * sizeof(bwb_aln));
+	for (const Slot &s : c->slots) slot_bytes = std::max(slot_bytes, s.d_reads.bytes + s.d_quals.bytes + s.d_dbuf.bytes + s.d_log.bytes + (size_t)s.n_reads * sizeof(bwb_aln));
 	/* (every slot still to come like the largest so far: a stream needs them all - the heaviest reads of a batch take several slices'
 	 * time, DESIGN.md section 2.3 - and 8 x 3 GB is little next to the pool) */
 	size_t more_slots = 0; /* slots that have no buffers yet (a caller that uploads every slot before the first submit - bench.py - has none left) */
@@ -770,6 +778,8 @@ extern "C" int bwb_hip_slot_upload(bwb_hip_ctx *c, int si, const bwb_params *p, 
 	const size_t nr = s.n_tot ? s.n_tot : 1;
 	HIPCHK(s.d_reads.reserve(nr * s.stride));
 	HIPCHK(s.d_lens.reserve(nr * 2));
+	if (c->pileq_on) HIPCHK(s.d_quals.reserve(nr * s.stride)); /* (here, so that ensure_pool counts it with the slot's other buffers) */
+	s.up_stride = stride; s.quals_set = false;
 	HIPCHK(s.d_dbuf.reserve(nr * s.dstride));
 	HIPCHK(s.d_status.reserve(nr));
 	HIPCHK(s.d_worklist.reserve(nr * 4));
@@ -2195,6 +2205,7 @@ extern "C" int bwb_hip_set_text(bwb_hip_ctx *c, const uint8_t *codes, uint64_t n
 	for (auto &s : c->slots) s.stage.text_replaced();
 	c->pile_on = false; c->pile_sites = 0; /* (the site index and the counters were this text's) */
 	c->d_site_base.release(); c->d_counts.release();
+	c->pileq_on = false; c->pileq_weighted = false; c->d_qsum.release();
 	c->geno_on = false; c->geno_bub = false;
 	const uint64_t CH = 1ull << BWB_TEXT_CHUNK_SHIFT, n_words = (n_fwd + 31) / 32;
 	HIPCHK(c->d_text.alloc((size_t)n_words * 16));
@@ -2355,6 +2366,7 @@ extern "C" int bwb_hip_pile_begin(bwb_hip_ctx *c, uint64_t *n_sites) {
 	HIPCHK(hipSetDevice(c->device));
 	HIPCHK(hipStreamSynchronize(c->rstream)); /* (a pile kernel of an earlier call may still add to the counters that are replaced) */
 	c->pile_on = false; c->pile_sites = 0;
+	c->pileq_on = false; c->pileq_weighted = false; c->d_qsum.release(); /* (pileq_begin comes behind its pile_begin) */
 	c->geno_on = false; c->geno_bub = false; /* (the calls were for this index and these counters) */
 	const unsigned nblk = blocks_of(n_words);
 	DevMem d_bsum, d_total;
@@ -2466,6 +2478,7 @@ extern "C" int bwb_hip_pile_records(bwb_hip_ctx *c, const uint8_t *reads_fwd, co
  * of either need: the buffer, its entries, whether its *_begin has run, and the words of the messages. */
 struct CounterTable { const DevMem &buf; uint64_t entries; bool on; const char *missing, *unit; };
 static CounterTable site_counters(const bwb_hip_ctx *c) { return { c->d_counts, c->pile_sites, c->pile_on, "no site index and counters (bwb_hip_pile_begin)", "sites" }; }
+static CounterTable qsum_counters(const bwb_hip_ctx *c) { return { c->d_qsum, c->pile_sites, c->pile_on && c->pileq_weighted, "no quality sums (bwb_hip_pileq_begin with weighted != 0)", "sites" }; }
 static CounterTable bubble_counters(const bwb_hip_ctx *c) { return { c->d_indel_counts, c->loci_nbub, c->indel_on, "no bubble table and counters (bwb_hip_indel_begin)", "bubbles" }; }
 /* n entries from `first` on, device to host or host to device (pageable memory of the caller: waits for the copy) */
 static int counters_copy(bwb_hip_ctx *c, const char *who, const CounterTable &t, uint64_t first, uint64_t n, const void *host, hipMemcpyKind kind) {
@@ -2493,7 +2506,8 @@ extern "C" int bwb_hip_pile_counts(bwb_hip_ctx *c, uint64_t first, uint64_t n, u
 
 extern "C" int bwb_hip_pile_reset(bwb_hip_ctx *c) {
 	if (!c) return fail(BWB_E_ARG, "pile_reset: null context");
-	return counters_reset(c, "pile_reset", site_counters(c));
+	RC(counters_reset(c, "pile_reset", site_counters(c)));
+	return c->pileq_weighted ? counters_reset(c, "pile_reset", qsum_counters(c)) : BWB_OK;
 }
 
 extern "C" int bwb_hip_pile_site_of(bwb_hip_ctx *c, const uint64_t *pos, size_t n, int64_t *site) {
@@ -2520,6 +2534,151 @@ extern "C" int bwb_hip_pile_stats(bwb_hip_ctx *c, uint64_t *reads, uint64_t *add
 	if (reads) *reads = c->pile_reads;
 	if (adds) *adds = c->pile_adds;
 	if (kernel_ms) *kernel_ms = c->pile_ms;
+	return BWB_OK;
+}
+
+/* ---- the pile with base qualities (k_pile_q): a minimum base quality, and the quality sums the weighted calls need ----------------------------- */
+extern "C" int bwb_hip_pileq_begin(bwb_hip_ctx *c, int weighted) {
+	if (!c) return fail(BWB_E_ARG, "pileq_begin: null context");
+	if (!c->pile_on) return fail(BWB_E_STATE, "pileq_begin: no site index and counters (bwb_hip_pile_begin)");
+	HIPCHK(hipSetDevice(c->device));
+	HIPCHK(hipStreamSynchronize(c->rstream)); /* (a kernel of an earlier call may still add to the sums that are replaced) */
+	c->pileq_on = false; c->pileq_weighted = false;
+	c->d_qsum.release();
+	if (weighted) {
+		HIPCHK(c->d_qsum.alloc((size_t)c->pile_sites * 16));
+		if (c->pile_sites) HIPCHK(hipMemsetAsync(c->d_qsum.p, 0, (size_t)c->pile_sites * 16, c->rstream));
+	}
+	HIPCHK(c->d_pileq_stats.alloc(24));
+	HIPCHK(c->h_pileq_stats.reserve(24));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	c->pileq_on = true; c->pileq_weighted = weighted != 0;
+	c->pileq_ms = 0; c->pileq_reads = 0; c->pileq_adds = 0; c->pileq_dropped = 0;
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_slot_quals(bwb_hip_ctx *c, int si, const uint8_t *quals, uint32_t stride) {
+	if (!c || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_quals: bad argument");
+	if (!c->pileq_on) return fail(BWB_E_STATE, "slot_quals: no quality buffers (bwb_hip_pileq_begin)");
+	Slot &s = c->slots[si];
+	if (!s.uploaded) return fail(BWB_E_STATE, "slot_quals: the slot has no upload");
+	if (stride != s.up_stride) return fail(BWB_E_ARG, "slot_quals: the stride is " + std::to_string(stride) + ", the upload's " + std::to_string(s.up_stride));
+	if (s.n_reads && !quals) return fail(BWB_E_ARG, "slot_quals: null argument");
+	HIPCHK(hipSetDevice(c->device));
+	const size_t bytes = (size_t)s.n_reads * s.stride;
+	HIPCHK(s.ev_quals.create());
+	HIPCHK(hipEventSynchronize(s.ev_quals.e)); /* (the slot's previous copy has left the staging buffer; an event never recorded is complete) */
+	HIPCHK(s.d_quals.reserve(bytes)); /* (slot_upload sized it when pileq_begin came first) */
+	HIPCHK(s.h_quals.reserve(bytes));
+	uint8_t *hq = s.h_quals.as<uint8_t>();
+	/* (the slot's stride is the upload's clamped to its longest read: the bytes behind it belong to no base) */
+	if (s.stride == stride) memcpy(hq, quals, bytes);
+	else for (uint32_t i = 0; i < s.n_reads; i++) memcpy(hq + (size_t)i * s.stride, quals + (size_t)i * stride, s.stride);
+	if (bytes) HIPCHK(hipMemcpyAsync(s.d_quals.p, hq, bytes, hipMemcpyHostToDevice, c->cstream));
+	HIPCHK(hipEventRecord(s.ev_quals.e, c->cstream));
+	s.quals_set = true;
+	return BWB_OK;
+}
+
+static int pileq_args(bwb_hip_ctx *c, const char *who, int min_baseq, int err_cap) {
+	if (min_baseq < 0 || min_baseq > 93) return fail(BWB_E_ARG, std::string(who) + ": min_baseq must be 0..93");
+	if (err_cap != 0 && (err_cap < 4 || err_cap > 93)) return fail(BWB_E_ARG, std::string(who) + ": err_cap must be 0 or 4..93");
+	if (!c->pile_on) return fail(BWB_E_STATE, std::string(who) + ": no site index and counters (bwb_hip_pile_begin)");
+	if (!c->pileq_on) return fail(BWB_E_STATE, std::string(who) + ": no quality buffers (bwb_hip_pileq_begin)");
+	if (err_cap && !c->pileq_weighted) return fail(BWB_E_STATE, std::string(who) + ": no quality sums (bwb_hip_pileq_begin with weighted != 0)");
+	return BWB_OK;
+}
+
+/* pile_launch with k_pile_q: d_quals beside d_reads; sets pileq_ms / pileq_reads / pileq_adds / pileq_dropped.  What comes back is the 24 bytes of
+ * the three sums. */
+static int pileq_launch(bwb_hip_ctx *c, const uint8_t *d_reads, const uint8_t *d_quals, const uint16_t *d_lens, uint32_t stride, const uint4 *d_places, uint32_t n, const uint8_t *d_kind,
+                        const uint64_t *d_loff, const uint4 *d_lrecs, const uint8_t *d_mapq, uint32_t mapq_stride, int min_mapq, int min_baseq, int err_cap) {
+	if (!n) return BWB_OK; /* (nothing launched: the figures of the last launch stay) */
+	const uint32_t n_seq = d_kind ? c->loci_nseq : 0u;
+	HIPCHK(hipMemsetAsync(c->d_pileq_stats.p, 0, 24, c->rstream));
+	Timed t(c, c->rstream);
+	RC(t.begin());
+	hipLaunchKernelGGL(k_pile_q, dim3(lane_grid(c, n)), dim3(BWB_BLOCK), 0, c->rstream, d_reads, d_quals, d_lens, stride, d_places, n, d_kind, d_loff, d_lrecs, c->d_lstart.as<uint64_t>(), n_seq,
+	                   c->d_text.as<uint4>(), c->text_n, d_mapq, mapq_stride, (uint32_t)min_mapq, (uint32_t)min_baseq, (uint32_t)err_cap, c->d_site_base.as<uint32_t>(),
+	                   c->d_counts.as<uint32_t>(), c->d_qsum.as<uint32_t>(), c->d_pileq_stats.as<unsigned long long>());
+	HIPCHK(hipGetLastError());
+	RC(t.end());
+	HIPCHK(hipMemcpyAsync(c->h_pileq_stats.p, c->d_pileq_stats.p, 24, hipMemcpyDeviceToHost, c->rstream));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	float ms = 0;
+	RC(t.ms(&ms));
+	c->pileq_ms = ms;
+	c->pileq_reads = c->h_pileq_stats.as<uint64_t>()[0];
+	c->pileq_adds = c->h_pileq_stats.as<uint64_t>()[1];
+	c->pileq_dropped = c->h_pileq_stats.as<uint64_t>()[2];
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_slot_pile_q(bwb_hip_ctx *c, int si, int max_mm, int max_alt, int lifted, int joined, int min_mapq, int min_baseq, int err_cap, uint64_t *reads_counted) {
+	if (!c || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_pile_q: bad argument");
+	RC(pileq_args(c, "slot_pile_q", min_baseq, err_cap));
+	RC(pile_ready(c, "slot_pile_q", max_alt, lifted, joined, min_mapq));
+	if (reads_counted) *reads_counted = 0;
+	RC(ensure_place(c, si, max_mm));
+	Slot &s = c->slots[si];
+	if (s.stage.piled) return BWB_OK; /* (a submission is counted once, by slot_pile or by slot_pile_q) */
+	if (!s.quals_set) return fail(BWB_E_STATE, "slot_pile_q: the slot's upload has no qualities (bwb_hip_slot_quals)");
+	if (lifted) RC(ensure_lift(c, si, max_mm, max_alt));
+	if (joined) RC(ensure_join(c, si, max_mm, max_alt));
+	const uint32_t n = s.n_reads; /* (not n_tot: a carried read that rides along behind the batch's reads has no record) */
+	if (n) {
+		HIPCHK(hipStreamWaitEvent(c->rstream, s.ev_up.e, 0));    /* (the slot's reads and */
+		HIPCHK(hipStreamWaitEvent(c->rstream, s.ev_quals.e, 0)); /* qualities, uploaded on the copy stream) */
+		RC(pileq_launch(c, s.d_reads.as<uint8_t>(), s.d_quals.as<uint8_t>(), s.d_lens.as<uint16_t>(), s.stride, s.d_place.as<uint4>(), n, lifted ? s.lift.d_kind.as<uint8_t>() : nullptr,
+		                s.lift.d_off.as<uint64_t>(), s.lift.d_recs.as<uint4>(), joined ? s.d_join.as<uint8_t>() + offsetof(bwb_join, mapq) : nullptr, (uint32_t)sizeof(bwb_join), min_mapq,
+		                min_baseq, err_cap));
+		if (reads_counted) *reads_counted = c->pileq_reads;
+	}
+	s.stage.piled = true;
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_batch_pile_q(bwb_hip_ctx *c, int max_mm, int max_alt, int lifted, int joined, int min_mapq, int min_baseq, int err_cap, uint64_t *reads_counted) {
+	if (!c) return fail(BWB_E_ARG, "batch_pile_q: null context");
+	RC(pileq_args(c, "batch_pile_q", min_baseq, err_cap));
+	RC(pile_ready(c, "batch_pile_q", max_alt, lifted, joined, min_mapq));
+	RC(batch_ready(c, "batch_pile_q"));
+	return bwb_hip_slot_pile_q(c, 0, max_mm, max_alt, lifted, joined, min_mapq, min_baseq, err_cap, reads_counted);
+}
+
+/* the kernel on reads, qualities and records of the caller's instead of a slot's (for parity tests); needs no slot_quals */
+extern "C" int bwb_hip_pile_records_q(bwb_hip_ctx *c, const uint8_t *reads_fwd, const uint8_t *quals, const uint16_t *lens, uint32_t stride, const bwb_place *places, uint32_t n,
+                                      const uint8_t *kinds, const uint64_t *lift_off, const bwb_lift *lift_recs, const uint8_t *mapq, int min_mapq, int min_baseq, int err_cap) {
+	if (!c || (n && (!reads_fwd || !quals || !lens || !places)) || n > 0x7FFFFFFFu || stride < 1 || stride > 255) return fail(BWB_E_ARG, "pile_records_q: bad argument");
+	if ((kinds != nullptr) != (lift_off != nullptr)) return fail(BWB_E_ARG, "pile_records_q: the lift kinds and offsets come together");
+	if (min_mapq < 0 || min_mapq > 255) return fail(BWB_E_ARG, "pile_records_q: min_mapq must be 0..255");
+	RC(pileq_args(c, "pile_records_q", min_baseq, err_cap));
+	StagedReads in;
+	DevMem d_mapq, d_quals; /* (d_mapq stays NULL without a MAPQ array, and without reads) */
+	RC(stage_reads(c, "pile_records_q", reads_fwd, lens, stride, places, n, kinds, lift_off, lift_recs, in));
+	RC(stage_in(c, d_quals, quals, (size_t)n * stride));
+	if (mapq && n) RC(stage_in(c, d_mapq, mapq, (size_t)n));
+	HIPCHK(hipStreamSynchronize(c->rstream));
+	return pileq_launch(c, in.reads.as<uint8_t>(), d_quals.as<uint8_t>(), in.lens.as<uint16_t>(), stride, in.places.as<uint4>(), n, in.kind.as<uint8_t>(), in.loff.as<uint64_t>(),
+	                    in.lrecs.as<uint4>(), d_mapq.as<uint8_t>(), 1u, min_mapq, min_baseq, err_cap);
+}
+
+extern "C" int bwb_hip_pileq_sums(bwb_hip_ctx *c, uint64_t first, uint64_t n, uint32_t *out) {
+	if (!c) return fail(BWB_E_ARG, "pileq_sums: null argument");
+	return counters_copy(c, "pileq_sums", qsum_counters(c), first, n, out, hipMemcpyDeviceToHost);
+}
+extern "C" int bwb_hip_pileq_put(bwb_hip_ctx *c, uint64_t first, uint64_t n, const uint32_t *sums) {
+	if (!c) return fail(BWB_E_ARG, "pileq_put: null argument");
+	return counters_copy(c, "pileq_put", qsum_counters(c), first, n, sums, hipMemcpyHostToDevice);
+}
+
+/* the last pile_q call that launched: reads counted, adds made, bases dropped by min_baseq, and the kernel's HIP-event time */
+extern "C" int bwb_hip_pileq_stats(bwb_hip_ctx *c, uint64_t *reads, uint64_t *adds, uint64_t *dropped, double *kernel_ms) {
+	if (!c) return fail(BWB_E_ARG, "pileq_stats: null context");
+	if (reads) *reads = c->pileq_reads;
+	if (adds) *adds = c->pileq_adds;
+	if (dropped) *dropped = c->pileq_dropped;
+	if (kernel_ms) *kernel_ms = c->pileq_ms;
 	return BWB_OK;
 }
 
@@ -2671,6 +2830,7 @@ extern "C" int bwb_hip_indel_stats(bwb_hip_ctx *c, uint64_t *reads, uint64_t *ad
 /* ---- genotype calls at IUPAC sites and indel bubbles (k_geno_count, k_geno_emit, k_geno_bubbles) ------------------------------------------- */
 static_assert(sizeof(bwb_geno_site) == 64 && offsetof(bwb_geno_site, n) == 16 && offsetof(bwb_geno_site, code) == 32 && offsetof(bwb_geno_site, pl) == 40, "k_geno_emit writes this layout");
 static_assert(sizeof(bwb_geno_bubble) == 48 && offsetof(bwb_geno_bubble, gt) == 20 && offsetof(bwb_geno_bubble, pl) == 24, "k_geno_bubbles writes this layout");
+static_assert(sizeof(bwb_geno_site_q) == 80 && offsetof(bwb_geno_site_q, qs) == 64, "k_geno_emit_q writes this layout");
 extern "C" int bwb_hip_geno_begin(bwb_hip_ctx *c, uint32_t piece) {
 	if (!c) return fail(BWB_E_ARG, "geno_begin: null context");
 	if (piece < 1 || piece > (1u << 24)) return fail(BWB_E_ARG, "geno_begin: the piece must be 1..2^24");
@@ -2682,8 +2842,10 @@ extern "C" int bwb_hip_geno_begin(bwb_hip_ctx *c, uint32_t piece) {
 	HIPCHK(c->d_geno_word.alloc((size_t)piece * 4));
 	HIPCHK(c->d_geno_off.alloc(((size_t)piece + 1) * 8));
 	HIPCHK(c->d_geno_bsum.alloc((size_t)blocks_of(piece) * 8));
-	HIPCHK(c->d_geno_sites.alloc((size_t)piece * sizeof(bwb_geno_site)));
-	HIPCHK(c->h_geno_sites.reserve((size_t)piece * sizeof(bwb_geno_site)));
+	c->geno_q = c->pileq_on && c->pileq_weighted;
+	const size_t site_rec = c->geno_q ? sizeof(bwb_geno_site_q) : sizeof(bwb_geno_site);
+	HIPCHK(c->d_geno_sites.alloc((size_t)piece * site_rec));
+	HIPCHK(c->h_geno_sites.reserve((size_t)piece * site_rec));
 	HIPCHK(c->h_geno_n.reserve(8));
 	c->geno_piece = piece;
 	if (c->indel_on) {
@@ -2731,11 +2893,12 @@ static int geno_fetch(bwb_hip_ctx *c, Timed &t, uint32_t n, const void *d_recs, 
 	return BWB_OK;
 }
 
-extern "C" int bwb_hip_geno_sites(bwb_hip_ctx *c, uint64_t first, uint64_t n, int err, int64_t min_depth, const bwb_geno_site **out, uint64_t *n_out) {
-	if (!c || !out || !n_out) return fail(BWB_E_ARG, "geno_sites: null argument");
-	if (!c->geno_on || !c->pile_on) return fail(BWB_E_STATE, "geno_sites: no scratch and output (bwb_hip_geno_begin)");
-	RC(geno_args(c, "geno_sites", first, n, err, min_depth, c->pile_sites, c->geno_piece));
-	*out = c->h_geno_sites.as<bwb_geno_site>(); *n_out = 0;
+/* the sites' calls, by the existing rule (64-byte records) or - weighted - by the quality sums (80-byte records), into h_geno_sites */
+static int geno_sites_run(bwb_hip_ctx *c, const char *who, bool weighted, uint64_t first, uint64_t n, int err, int64_t min_depth, uint64_t *n_out) {
+	if (!c->geno_on || !c->pile_on) return fail(BWB_E_STATE, std::string(who) + ": no scratch and output (bwb_hip_geno_begin)");
+	if (weighted && !(c->pileq_on && c->pileq_weighted && c->geno_q)) return fail(BWB_E_STATE, std::string(who) + ": no quality sums before geno_begin (bwb_hip_pileq_begin with weighted != 0)");
+	RC(geno_args(c, who, first, n, err, min_depth, c->pile_sites, c->geno_piece));
+	*n_out = 0;
 	if (!n) return BWB_OK; /* (nothing launched: the figures of the last launch stay) */
 	HIPCHK(hipSetDevice(c->device));
 	const uint64_t n_words64 = (c->text_n + 31) / 32;
@@ -2746,12 +2909,31 @@ extern "C" int bwb_hip_geno_sites(bwb_hip_ctx *c, uint64_t first, uint64_t n, in
 	hipLaunchKernelGGL(k_geno_count, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, c->d_text.as<uint4>(), c->d_site_base.as<uint32_t>(), n_words, ceil_log2(n_words64), c->d_counts.as<uint4>(), first, nn,
 	                   (uint64_t)min_depth, c->d_geno_cnt.as<uint32_t>(), c->d_geno_word.as<uint32_t>());
 	geno_scan(c, nn);
-	hipLaunchKernelGGL(k_geno_emit, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, c->d_text.as<uint4>(), c->d_site_base.as<uint32_t>(), n_words, c->d_counts.as<uint4>(), first, nn,
-	                   (uint64_t)min_depth, (uint32_t)err, c->d_geno_cnt.as<uint32_t>(), c->d_geno_word.as<uint32_t>(), c->d_geno_off.as<uint64_t>(), c->d_geno_sites.as<uint4>());
+	if (weighted)
+		hipLaunchKernelGGL(k_geno_emit_q, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, c->d_text.as<uint4>(), c->d_site_base.as<uint32_t>(), n_words, c->d_counts.as<uint4>(), c->d_qsum.as<uint4>(),
+		                   first, nn, c->d_geno_cnt.as<uint32_t>(), c->d_geno_word.as<uint32_t>(), c->d_geno_off.as<uint64_t>(), c->d_geno_sites.as<uint4>());
+	else
+		hipLaunchKernelGGL(k_geno_emit, dim3(grid), dim3(BWB_BLOCK), 0, c->rstream, c->d_text.as<uint4>(), c->d_site_base.as<uint32_t>(), n_words, c->d_counts.as<uint4>(), first, nn,
+		                   (uint64_t)min_depth, (uint32_t)err, c->d_geno_cnt.as<uint32_t>(), c->d_geno_word.as<uint32_t>(), c->d_geno_off.as<uint64_t>(), c->d_geno_sites.as<uint4>());
 	HIPCHK(hipGetLastError());
 	RC(t.end());
-	RC(geno_fetch(c, t, nn, c->d_geno_sites.p, c->h_geno_sites.p, sizeof(bwb_geno_site), n_out));
+	RC(geno_fetch(c, t, nn, c->d_geno_sites.p, c->h_geno_sites.p, weighted ? sizeof(bwb_geno_site_q) : sizeof(bwb_geno_site), n_out));
 	c->geno_sites_called = *n_out;
+	return BWB_OK;
+}
+
+extern "C" int bwb_hip_geno_sites(bwb_hip_ctx *c, uint64_t first, uint64_t n, int err, int64_t min_depth, const bwb_geno_site **out, uint64_t *n_out) {
+	if (!c || !out || !n_out) return fail(BWB_E_ARG, "geno_sites: null argument");
+	RC(geno_sites_run(c, "geno_sites", false, first, n, err, min_depth, n_out));
+	*out = c->h_geno_sites.as<bwb_geno_site>();
+	return BWB_OK;
+}
+
+/* the weighted calls: err is checked like geno_sites' (the sums were capped by the pile's err_cap; the rule itself no longer needs E) */
+extern "C" int bwb_hip_geno_sites_q(bwb_hip_ctx *c, uint64_t first, uint64_t n, int err, int64_t min_depth, const bwb_geno_site_q **out, uint64_t *n_out) {
+	if (!c || !out || !n_out) return fail(BWB_E_ARG, "geno_sites_q: null argument");
+	RC(geno_sites_run(c, "geno_sites_q", true, first, n, err, min_depth, n_out));
+	*out = c->h_geno_sites.as<bwb_geno_site_q>();
 	return BWB_OK;
 }
 

@@ -13,6 +13,7 @@
  *   k_text_pack, k_md_count, k_md   the forward text at 4 bits per character, and a read's NM and MD text against it (`bwbble map -D`)
  *   k_site_count, k_site_add, k_site_of, k_pile   the rank structure over the text's IUPAC sites, and the reads' allele counts at them (`bwbble map -A`)
  *   k_indel                      ref / alt read support per indel bubble, against a sorted table of the eligible bubbles (`bwbble map -I`)
+ *   k_pile_q, k_geno_emit_q      the allele counts with a minimum base quality and the quality sums, and the genotype calls weighted by them (`bwbble map -b / -Y`)
  * The alignment kernels themselves (kl_calc_d, kl_search: one read per lane) are in bwb_lane.h.
  */
 #pragma once
@@ -1140,6 +1141,89 @@ __global__ __launch_bounds__(BWB_BLOCK) void k_pile(const uint8_t *reads, const 
 	}
 }
 
+/* k_pile_q (`map -b / -Y`): k_pile with the base qualities - the rule is in include/bwbble_hip.h (bwb_hip_pileq_begin).  The same lanes, md_read,
+ * checks and walk; quals holds one byte per base in FASTQ order, strided like the reads, and a base's byte is the one at the read base's own
+ * index (len - 1 - ri on the reverse strand), loaded only when the base falls on a site and is no N.  Q = 0 below '!', else min(byte - 33, 93).
+ * A base with Q < min_baseq is dropped: no add, counted in `dropped`.  err_cap != 0 (4..93, then qsum is a table like counts): the base also adds
+ * min(max(Q, 4), err_cap) to qsum at the counter's index.  Both adds are relaxed agent-scope atomics.  Reads, adds and dropped bases go to
+ * stats[0..2] once per block.  Bounds as in k_pile; the quality byte's index is the read base's. */
+#define PILEQ_MAX_Q 93u
+#define PILEQ_MIN_W 4u
+struct PileWalkQ {
+	const uint4 *text; uint64_t cur; uint4 w; uint32_t mask;
+	const uint32_t *site_base; uint32_t *counts, *qsum;
+	const uint8_t *seq, *qual; uint32_t len; bool reverse;
+	uint32_t min_baseq, err_cap;
+	uint32_t ri, adds, dropped; uint64_t tp;
+	__device__ __forceinline__ void step(uint32_t op, uint32_t count) { /* op: 0 M, 1 I, 2 D, 4 S */
+		if (op == 0u) {
+			for (uint32_t k = 0; k < count; k++, ri++, tp++) {
+				const uint64_t wi = tp >> 5;
+				if (wi != cur) { w = text[wi]; cur = wi; mask = site_mask32(w); }
+				const uint32_t at = (uint32_t)tp & 31u;
+				if (!((mask >> at) & 1u)) continue;
+				const uint32_t idx = reverse ? len - 1u - ri : ri;
+				const uint32_t c = seq[idx];
+				if (c > 3u) continue; /* a read N */
+				const uint32_t qc = qual[idx];
+				const uint32_t Q = qc < 33u ? 0u : (qc - 33u > PILEQ_MAX_Q ? PILEQ_MAX_Q : qc - 33u);
+				if (Q < min_baseq) { dropped++; continue; }
+				const uint32_t b = reverse ? 3u - c : c; /* A0 G1 C2 T3 as printed */
+				const uint32_t col = (b == 1u || b == 2u) ? 3u - b : b; /* A C G T */
+				const uint64_t site = (uint64_t)site_base[wi] + (uint32_t)__popc(mask & ((1u << at) - 1u));
+				__hip_atomic_fetch_add(counts + site * 4u + col, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+				if (err_cap) {
+					const uint32_t lo = Q < PILEQ_MIN_W ? PILEQ_MIN_W : Q;
+					__hip_atomic_fetch_add(qsum + site * 4u + col, lo > err_cap ? err_cap : lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+				}
+				adds++;
+			}
+		} else if (op == 2u) tp += count;
+		else ri += count;
+	}
+};
+__global__ __launch_bounds__(BWB_BLOCK) void k_pile_q(const uint8_t *reads, const uint8_t *quals, const uint16_t *lens, uint32_t stride, const uint4 *places, uint32_t n_reads,
+                                                       const uint8_t *lift_kind, const uint64_t *lift_off, const uint4 *lift_recs, const uint64_t *lstart, uint32_t n_seq,
+                                                       const uint4 *text, uint64_t n_fwd, const uint8_t *mapq, uint32_t mapq_stride, uint32_t min_mapq, uint32_t min_baseq,
+                                                       uint32_t err_cap, const uint32_t *site_base, uint32_t *counts, uint32_t *qsum, unsigned long long *stats) {
+	__shared__ unsigned long long s_sum[3][BWB_BLOCK / 64];
+	const uint32_t gstride = gridDim.x * BWB_BLOCK;
+	unsigned long long my_reads = 0, my_adds = 0, my_drop = 0;
+	for (uint32_t q = blockIdx.x * BWB_BLOCK + threadIdx.x; q < n_reads; q += gstride) {
+		const MdRead v = md_read(q, places, lift_kind, lift_off, lift_recs, lstart, n_seq);
+		const uint32_t len = lens[q];
+		if (!(v.mapped && len <= 255u && len <= stride)) continue;
+		const uint32_t mq = mapq ? mapq[(size_t)q * mapq_stride] : (places[(size_t)q * 3 + 1].x >> 16) & 0xFFu;
+		if (mq < min_mapq) continue;
+		uint64_t span = 0, on_read = 0;
+		if (v.lifted) for (uint32_t i = 0; i < v.n_ops; i++) { const uint32_t op = md_rec_op(v.rec, i); if ((op & 15u) == 0u || (op & 15u) == 2u) span += op >> 4; if ((op & 15u) != 2u) on_read += op >> 4; }
+		else for (uint32_t t = 0; t < v.alen; t++) { const uint32_t op = lift_op_at(v.runs, v.alen, v.reverse, t); span += op != 1u; on_read += op != 2u; }
+		if (span > MD_MAX_SPAN || v.start < 0 || (uint64_t)v.start > n_fwd || span > n_fwd - (uint64_t)v.start || on_read != len) continue;
+		PileWalkQ m;
+		m.text = text; m.cur = ~0ull; m.w = make_uint4(0u, 0u, 0u, 0u); m.mask = 0u;
+		m.site_base = site_base; m.counts = counts; m.qsum = qsum;
+		m.seq = reads + (size_t)q * stride; m.qual = quals + (size_t)q * stride; m.len = len; m.reverse = v.reverse;
+		m.min_baseq = min_baseq; m.err_cap = err_cap;
+		m.ri = 0; m.adds = 0; m.dropped = 0; m.tp = (uint64_t)v.start;
+		if (v.lifted) for (uint32_t i = 0; i < v.n_ops; i++) { const uint32_t op = md_rec_op(v.rec, i); m.step(op & 15u, op >> 4); }
+		else for (uint32_t t = 0; t < v.alen; t++) m.step(lift_op_at(v.runs, v.alen, v.reverse, t), 1u);
+		my_reads++; my_adds += m.adds; my_drop += m.dropped;
+	}
+	/* (every thread of the block gets here: the loop has no barrier inside) */
+#pragma unroll
+	for (int d = 32; d > 0; d >>= 1) { my_reads += __shfl_down(my_reads, d); my_adds += __shfl_down(my_adds, d); my_drop += __shfl_down(my_drop, d); }
+	if ((threadIdx.x & 63) == 0) { s_sum[0][threadIdx.x >> 6] = my_reads; s_sum[1][threadIdx.x >> 6] = my_adds; s_sum[2][threadIdx.x >> 6] = my_drop; }
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		unsigned long long r = 0, a = 0, x = 0;
+#pragma unroll
+		for (int k = 0; k < BWB_BLOCK / 64; k++) { r += s_sum[0][k]; a += s_sum[1][k]; x += s_sum[2][k]; }
+		if (r) atomicAdd(stats, r);
+		if (a) atomicAdd(stats + 1, a);
+		if (x) atomicAdd(stats + 2, x);
+	}
+}
+
 /* ---- ref / alt read support per indel bubble (`map -I`) --------------------------------------------------------------------------------
  * The rule is in include/bwbble_hip.h (bwb_hip_indel_begin).  k_indel: one lane per READ, grid-strided, over the placement records of k_place
  * and the locus records of k_locus.  A read's printed CIGAR is walked one text position at a time (lift_op_at: at most 8 gap runs compared per
@@ -1271,6 +1355,31 @@ __device__ __forceinline__ GenoCall geno_rule(uint64_t n0, uint64_t n1, uint64_t
 	for (uint32_t j = 0; j < 6; j++) { const uint64_t d = raw[j] - best; g.pl[j] = j < ng ? (d > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)d) : 0u; }
 	return g;
 }
+/* the weighted rule (`map -Y`, bwb_hip_pileq_begin): s0, s1, s2 the alleles' qsum columns, S the sum of all four; GT, GQ and the PLs from the raw
+ * costs as in geno_rule.  (The selection is repeated here, not shared: sharing it through a helper changed k_geno_emit's instructions, and
+ * every kernel from before -Y stays as it was.) */
+__device__ __forceinline__ GenoCall geno_rule_q(uint64_t n0, uint64_t n1, uint64_t n2, uint64_t s0, uint64_t s1, uint64_t s2, uint32_t k, uint64_t S) {
+	uint64_t raw[6];
+	raw[0] = S - s0;
+	raw[1] = GENO_HET * (n0 + n1) + (S - s0 - s1);
+	raw[2] = S - s1;
+	raw[3] = GENO_HET * (n0 + n2) + (S - s0 - s2);
+	raw[4] = GENO_HET * (n1 + n2) + (S - s1 - s2);
+	raw[5] = S - s2;
+	const uint32_t ng = k == 3u ? 6u : 3u;
+	uint32_t gt = 0;
+	uint64_t best = raw[0];
+#pragma unroll
+	for (uint32_t j = 1; j < 6; j++) { const bool lower = j < ng && raw[j] < best; gt = lower ? j : gt; best = lower ? raw[j] : best; }
+	uint64_t second = ~0ull;
+#pragma unroll
+	for (uint32_t j = 0; j < 6; j++) { const bool in = j < ng && j != gt && raw[j] - best < second; second = in ? raw[j] - best : second; }
+	GenoCall g;
+	g.gt = gt; g.gq = second > 99ull ? 99u : (uint32_t)second;
+#pragma unroll
+	for (uint32_t j = 0; j < 6; j++) { const uint64_t d = raw[j] - best; g.pl[j] = j < ng ? (d > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)d) : 0u; }
+	return g;
+}
 /* Site s (< n_sites, checked by the caller) -> its word: the last w with site_base[w] <= s, by `trips` halving steps for every lane (2^trips >=
  * n_words, a kernel argument: selects, no divergent while; site_base[] does not descend and site_base[0] = 0).  The lanes of a wave hold 64
  * consecutive sites, which lie in a handful of neighbouring words: all but the last few steps load the same address in every lane, one
@@ -1348,6 +1457,44 @@ __global__ __launch_bounds__(BWB_BLOCK) void k_geno_emit(const uint4 *text, cons
 		dst[1] = c;
 		dst[2] = make_uint4(code | (k == 3u ? 6u : 3u) << 8 | g.gt << 16 | g.gq << 24, 0u, g.pl[0], g.pl[1]);
 		dst[3] = make_uint4(g.pl[2], g.pl[3], g.pl[4], g.pl[5]);
+	}
+}
+/* k_geno_emit_q (`map -Y`): k_geno_emit behind the same k_geno_count and scan, with the weighted rule - the site's four qsum words in one 16-byte
+ * load beside its counters - and the 80-byte bwb_geno_site_q record at out[off[i]] (off[i] < n: the output holds n records of 80 bytes): the 64
+ * bytes of bwb_geno_site, then the four qsum words, as five 16-byte stores. */
+__global__ __launch_bounds__(BWB_BLOCK) void k_geno_emit_q(const uint4 *text, const uint32_t *site_base, uint32_t n_words, const uint4 *counts, const uint4 *qsum, uint64_t first, uint32_t n,
+                                                            const uint32_t *cnt, const uint32_t *word, const uint64_t *off, uint4 *out) {
+	const uint32_t gstride = gridDim.x * BWB_BLOCK;
+	for (uint32_t i = blockIdx.x * BWB_BLOCK + threadIdx.x; i < n; i += gstride) {
+		if (!cnt[i]) continue;
+		const uint64_t s = first + i, o = off[i];
+		const uint32_t w = word[i];
+		if (w >= n_words || o >= (uint64_t)n) continue; /* (k_geno_count wrote both: never) */
+		uint32_t code;
+		const uint64_t r = s - (uint64_t)site_base[w];
+		const uint32_t at = geno_char(text[w], r < 32u ? (uint32_t)r : 32u, &code) & 31u; /* (k_geno_count found it below 32) */
+		const uint32_t mem = (uint32_t)(GENO_MEMBERS >> (4u * code)) & 15u;
+		const uint4 c = counts[s], qs = qsum[s];
+		const uint64_t S = (uint64_t)qs.x + qs.y + qs.z + qs.w;
+		uint64_t a[3] = { 0, 0, 0 }, e[3] = { 0, 0, 0 };
+		uint32_t k = 0;
+#pragma unroll
+		for (uint32_t col = 0; col < 4; col++) {
+			const uint32_t v = col == 0u ? c.x : col == 1u ? c.y : col == 2u ? c.z : c.w;
+			const uint32_t u = col == 0u ? qs.x : col == 1u ? qs.y : col == 2u ? qs.z : qs.w;
+			const bool in = (mem >> col) & 1u;
+			a[0] = in && k == 0u ? v : a[0]; a[1] = in && k == 1u ? v : a[1]; a[2] = in && k == 2u ? v : a[2];
+			e[0] = in && k == 0u ? u : e[0]; e[1] = in && k == 1u ? u : e[1]; e[2] = in && k == 2u ? u : e[2];
+			k += in ? 1u : 0u;
+		}
+		const GenoCall g = geno_rule_q(a[0], a[1], a[2], e[0], e[1], e[2], k, S);
+		const uint64_t pos = (uint64_t)w * 32u + at;
+		uint4 *dst = out + o * 5u;
+		dst[0] = make_uint4((uint32_t)pos, (uint32_t)(pos >> 32), (uint32_t)s, (uint32_t)(s >> 32));
+		dst[1] = c;
+		dst[2] = make_uint4(code | (k == 3u ? 6u : 3u) << 8 | g.gt << 16 | g.gq << 24, 0u, g.pl[0], g.pl[1]);
+		dst[3] = make_uint4(g.pl[2], g.pl[3], g.pl[4], g.pl[5]);
+		dst[4] = qs;
 	}
 }
 /* k_geno_bubbles: one lane per bubble of [first, first + n) (first + n <= n_bub, checked by the caller), grid-strided.  off NULL, the count pass:

@@ -55,6 +55,7 @@ typedef struct {
 	md_text_t *text;          /* -D, -A (NULL: neither): the forward text of <seq_fasta>.ref */
 	int md;                   /* -D: the tags NM:i / MD:Z against the text */
 	pile_t *pile;             /* -A (NULL: no counts): the allele counts at the text's IUPAC sites; on the GPU unless pile_on_host */
+	int pile_q;               /* -b above 0 or -Y: the pile reads the base qualities - on the GPU k_pile_q on the slot's quality bytes, and with -Y the sums of the weighted calls */
 	int pile_on_host;         /* -A with the host's lift or join records (-R / -J on an .ann that is not ascending and disjoint): the host's rule */
 	indel_t *indel;           /* -I (NULL: no table): the read support per indel bubble; needs bub and chrom_of; on the GPU when gpu_loci, else the host's rule */
 	geno_t *geno;             /* -G (NULL: no calls): the genotype calls from both tables - pile is there then, and with bub indel; each half on the GPU where its counters are */
@@ -94,6 +95,7 @@ typedef struct {
 	double lift_ms; unsigned long long lift_lifted, lift_unliftable, lift_bytes; /* map -R: k_lift_count + scan + k_lift, summed over the chunks; what came back for them */
 	double md_ms, text_s; unsigned long long md_reads, md_bytes, md_back; /* map -D: k_md_count + scan + k_md, summed over the chunks; set_text's seconds; reads tagged, MD bytes, what came back */
 	double pile_ms, pile_begin_s, pile_fetch_s; unsigned long long pile_reads, pile_adds; /* map -A: k_pile, summed over the chunks; pile_begin's and the final read-back's seconds; reads counted, adds */
+	double quals_s; unsigned long long quals_bytes, pile_dropped; /* map -b / -Y: packing and staging the chunks' quality lines, their bytes; the bases -b dropped */
 	double indel_ms, indel_begin_s, indel_fetch_s; unsigned long long indel_reads, indel_adds, indel_cands; /* map -I: k_indel, summed over the chunks; indel_begin's and the final read-back's seconds; reads counted, adds, candidates */
 } worker_t;
 
@@ -250,12 +252,16 @@ static void stage_md(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c, sam_re
 static void stage_pile(worker_t *w, bwb_hip_ctx *ctx, int slot, chunk_t *c, sam_reads_t *rd) {
 	const map_t *m = w->pp->map;
 	if (!m->pile_on_host) {
-		uint64_t nr = 0, na = 0; double ms = 0;
-		gpu_ok(bwb_hip_slot_pile(ctx, slot, m->max_mm, m->max_alt, m->lift, m->join, m->pile->min_mapq, &nr), "map_reads", w->gpu);
-		if (c->n) { bwb_hip_pile_stats(ctx, NULL, &na, &ms); w->pile_ms += ms; w->pile_reads += nr; w->pile_adds += na; } /* (a chunk without reads launches nothing) */
+		uint64_t nr = 0, na = 0, nd = 0; double ms = 0;
+		if (m->pile_q) gpu_ok(bwb_hip_slot_pile_q(ctx, slot, m->max_mm, m->max_alt, m->lift, m->join, m->pile->min_mapq, m->pile->min_baseq, m->pile->err_cap, &nr), "map_reads", w->gpu);
+		else gpu_ok(bwb_hip_slot_pile(ctx, slot, m->max_mm, m->max_alt, m->lift, m->join, m->pile->min_mapq, &nr), "map_reads", w->gpu);
+		if (c->n) { /* (a chunk without reads launches nothing) */
+			if (m->pile_q) bwb_hip_pileq_stats(ctx, NULL, &na, &nd, &ms); else bwb_hip_pile_stats(ctx, NULL, &na, &ms);
+			w->pile_ms += ms; w->pile_reads += nr; w->pile_adds += na; w->pile_dropped += nd;
+		}
 	} else {
 		pthread_mutex_lock(&w->pp->mu); /* (pile_host adds with the whole team: one worker at a time) */
-		pile_host(m->pile, rd->pl, c->n, rd->seq, rd->stride, rd->len, rd->lift_kind, rd->lift_off, rd->lift_recs, rd->joins, m->T.ann);
+		pile_host_q(m->pile, rd->pl, c->n, rd->seq, rd->stride, rd->len, rd->text, rd->qual_off, rd->lift_kind, rd->lift_off, rd->lift_recs, rd->joins, m->T.ann);
 		pthread_mutex_unlock(&w->pp->mu);
 	}
 }
@@ -397,9 +403,26 @@ static void worker_map_setup(worker_t *w, bwb_hip_ctx *ctx, double tq, int dbg) 
 		w->pile_begin_s = wall() - t0;
 		if (n_sites != m->pile->n_sites) bwb_die("map_reads: GPU %d counts %llu IUPAC sites in the text, the host's scan of the .ref %llu", w->device, (unsigned long long)n_sites, (unsigned long long)m->pile->n_sites);
 	}
+	/* -b / -Y: from here on every slot keeps its reads' quality bytes; -Y: the quality sums (16 bytes per site) beside the counters.  Before geno_begin,
+	 * which then sizes its output for the 80-byte records */
+	if (pile_gpu && m->pile_q) gpu_ok(bwb_hip_pileq_begin(ctx, m->pile->err_cap != 0), "map_reads", w->device);
 	/* -G: the scratch and the pinned output of one piece of calls (92 bytes per site of the piece, 48 more per bubble), in every context - which worker
 	 * finishes last is not known yet */
 	if (m->geno && pile_gpu) gpu_ok(bwb_hip_geno_begin(ctx, geno_piece(m)), "map_reads", w->device);
+}
+
+/* map -b / -Y: the chunk's quality lines packed like its reads - one byte per base in FASTQ order, the chunk's stride per read - and handed to the
+ * slot behind its upload (the library stages them: the buffer is free at once) */
+static void slot_quals_up(worker_t *w, bwb_hip_ctx *ctx, int slot, const chunk_t *c) {
+	const double t0 = wall();
+	const size_t stride = c->fq.stride;
+	uint8_t *q = (uint8_t *)calloc((size_t)c->fq.n * stride + 1, 1);
+	if (!q) bwb_die("map_reads: no memory for the qualities of %u reads", c->fq.n);
+#pragma omp parallel for schedule(static) num_threads(bwb_host_team())
+	for (long r = 0; r < (long)c->fq.n; r++) memcpy(q + (size_t)r * stride, c->fq.text + c->fq.qual_off[r], c->fq.len[r] <= stride ? c->fq.len[r] : stride);
+	gpu_ok(bwb_hip_slot_quals(ctx, slot, q, c->fq.stride), "map_reads", w->device);
+	free(q);
+	w->quals_s += wall() - t0; w->quals_bytes += (unsigned long long)c->fq.n * stride;
 }
 
 /* The stream.  Chunks go through the slots of the context: while the search slice of chunk j runs, chunk j+1 is already uploaded and queued
@@ -429,6 +452,7 @@ static void worker_stream(worker_t *w, bwb_hip_ctx *ctx, double tq, int dbg) {
 		const int slot = (int)(j % NS);
 		if (j >= NS && retired + NS <= j) { hand_over(w, ctx, slot, in_slot[slot]); retired++; } /* the slot's previous chunk: NS - 1 slices stay queued while the host waits */
 		gpu_ok(bwb_hip_slot_upload(ctx, slot, w->params, c->fq.seq, c->fq.len, c->fq.n, c->fq.stride, c->carry, c->carry_len), "align_reads_inexact_gpu", w->device);
+		if (pp->map && pp->map->pile_q && !pp->map->pile_on_host) slot_quals_up(w, ctx, slot, c);
 		if (j == 0) { /* the first chunk is staged, scratch and pool exist: now the index must be complete */
 			gpu_ok(bwb_hip_ctx_index_wait(ctx, &w->t_ctx), "align_reads_inexact_gpu", w->device);
 			uint64_t pb = 0;
@@ -450,15 +474,16 @@ static void worker_stream(worker_t *w, bwb_hip_ctx *ctx, double tq, int dbg) {
 
 /* map -A, -I: the stream has ended and every chunk of this worker is retired - its counters (bubbles: those of -I's n bubbles, else those of
  * -A's n sites) come back in bounded pieces and are summed on the host; returns the pieces */
-static uint64_t counters_back(worker_t *w, bwb_hip_ctx *ctx, int bubbles, uint64_t n) {
+enum { BACK_SITES, BACK_BUBBLES, BACK_QSUMS }; /* -A's counters, -I's, -Y's quality sums */
+static uint64_t counters_back(worker_t *w, bwb_hip_ctx *ctx, int which, uint64_t n) {
 	pipe_t *pp = w->pp;
 	const uint64_t PIECE = count_piece();
 	uint32_t *buf = (uint32_t *)malloc((size_t)(n < PIECE ? n : PIECE) * 16 + 16);
 	uint64_t turns = 0, ns;
 	for (uint64_t s0 = 0; (ns = piece_at(s0, n, PIECE)); s0 += ns, turns++) {
-		gpu_ok(bubbles ? bwb_hip_indel_counts(ctx, s0, ns, buf) : bwb_hip_pile_counts(ctx, s0, ns, buf), "map_reads", w->device);
+		gpu_ok(which == BACK_BUBBLES ? bwb_hip_indel_counts(ctx, s0, ns, buf) : which == BACK_QSUMS ? bwb_hip_pileq_sums(ctx, s0, ns, buf) : bwb_hip_pile_counts(ctx, s0, ns, buf), "map_reads", w->device);
 		pthread_mutex_lock(&pp->mu);
-		if (bubbles) indel_add(pp->map->indel, s0, ns, buf); else pile_add(pp->map->pile, s0, ns, buf);
+		if (which == BACK_BUBBLES) indel_add(pp->map->indel, s0, ns, buf); else if (which == BACK_QSUMS) pile_add_q(pp->map->pile, s0, ns, buf); else pile_add(pp->map->pile, s0, ns, buf);
 		pthread_mutex_unlock(&pp->mu);
 	}
 	free(buf);
@@ -468,13 +493,14 @@ static void worker_map_counters(worker_t *w, bwb_hip_ctx *ctx, int dbg) {
 	const map_t *m = w->pp->map;
 	if (m->pile && !m->pile_on_host) {
 		const double t0 = wall();
-		const uint64_t turns = counters_back(w, ctx, 0, m->pile->n_sites);
+		uint64_t turns = counters_back(w, ctx, BACK_SITES, m->pile->n_sites);
+		if (m->pile->err_cap) turns += counters_back(w, ctx, BACK_QSUMS, m->pile->n_sites); /* -Y: the quality sums beside them */
 		w->pile_fetch_s = wall() - t0;
 		if (dbg) fprintf(stderr, "[bwb host] worker %d: the counters of %llu sites read back in %llu pieces\n", w->gpu, (unsigned long long)m->pile->n_sites, (unsigned long long)turns);
 	}
 	if (m->indel && m->gpu_loci) {
 		const double t0 = wall();
-		const uint64_t turns = counters_back(w, ctx, 1, (uint64_t)m->T.bub->n);
+		const uint64_t turns = counters_back(w, ctx, BACK_BUBBLES, (uint64_t)m->T.bub->n);
 		w->indel_fetch_s = wall() - t0;
 		if (dbg) fprintf(stderr, "[bwb host] worker %d: the counters of %llu bubbles read back in %llu pieces\n", w->gpu, (unsigned long long)m->T.bub->n, (unsigned long long)turns);
 	}
@@ -498,6 +524,8 @@ static void worker_map_genotypes(worker_t *w, bwb_hip_ctx *ctx, int dbg) {
 	if (pp->n_workers > 1) {
 		for (uint64_t s0 = 0; (ns = piece_at(s0, n_sites, PIECE)); s0 += ns, G->put_pieces++)
 			gpu_ok(bwb_hip_pile_put(ctx, s0, ns, m->pile->counts + s0 * 4), "map_reads", w->device);
+		for (uint64_t s0 = 0; G->weighted && (ns = piece_at(s0, n_sites, PIECE)); s0 += ns, G->put_pieces++)
+			gpu_ok(bwb_hip_pileq_put(ctx, s0, ns, m->pile->qsum + s0 * 4), "map_reads", w->device);
 		for (uint64_t s0 = 0; (ns = piece_at(s0, n_bub, PIECE)); s0 += ns, G->put_pieces++)
 			gpu_ok(bwb_hip_indel_put(ctx, s0, ns, m->indel->counts + s0 * 4), "map_reads", w->device);
 	}
@@ -505,11 +533,12 @@ static void worker_map_genotypes(worker_t *w, bwb_hip_ctx *ctx, int dbg) {
 	t0 = wall();
 	double ms = 0;
 	for (uint64_t s0 = 0; (ns = piece_at(s0, n_sites, GP)); s0 += ns, G->pieces++) {
-		const bwb_geno_site *recs = NULL; uint64_t k = 0;
-		gpu_ok(bwb_hip_geno_sites(ctx, s0, ns, G->err, G->min_depth, &recs, &k), "map_reads", w->device);
+		const bwb_geno_site *recs = NULL; const bwb_geno_site_q *recs_q = NULL; uint64_t k = 0;
+		if (G->weighted) gpu_ok(bwb_hip_geno_sites_q(ctx, s0, ns, G->err, G->min_depth, &recs_q, &k), "map_reads", w->device);
+		else gpu_ok(bwb_hip_geno_sites(ctx, s0, ns, G->err, G->min_depth, &recs, &k), "map_reads", w->device);
 		bwb_hip_geno_stats(ctx, NULL, NULL, &ms);
 		G->kernel_ms += ms;
-		geno_take_sites(G, recs, k);
+		if (G->weighted) geno_take_sites_q(G, recs_q, k); else geno_take_sites(G, recs, k);
 	}
 	for (uint64_t s0 = 0; (ns = piece_at(s0, n_bub, GP)); s0 += ns, G->pieces++) {
 		const bwb_geno_bubble *recs = NULL; uint64_t k = 0;
@@ -565,6 +594,7 @@ static void fold_worker(worker_t *t, const worker_t *w) {
 	max_of(&t->lift_ms, w->lift_ms); t->lift_lifted += w->lift_lifted; t->lift_unliftable += w->lift_unliftable; t->lift_bytes += w->lift_bytes;
 	max_of(&t->md_ms, w->md_ms); max_of(&t->text_s, w->text_s); t->md_reads += w->md_reads; t->md_bytes += w->md_bytes; t->md_back += w->md_back;
 	max_of(&t->pile_ms, w->pile_ms); max_of(&t->pile_begin_s, w->pile_begin_s); max_of(&t->pile_fetch_s, w->pile_fetch_s); t->pile_reads += w->pile_reads; t->pile_adds += w->pile_adds;
+	max_of(&t->quals_s, w->quals_s); t->quals_bytes += w->quals_bytes; t->pile_dropped += w->pile_dropped;
 	max_of(&t->indel_ms, w->indel_ms); max_of(&t->indel_begin_s, w->indel_begin_s); max_of(&t->indel_fetch_s, w->indel_fetch_s);
 	t->indel_reads += w->indel_reads; t->indel_adds += w->indel_adds; t->indel_cands += w->indel_cands;
 }
@@ -588,6 +618,9 @@ static void print_map_summary(const map_t *map, const worker_t *t, uint64_t n_re
 		       (unsigned long long)map->pile->n_sites, t->pile_reads, t->pile_adds, t->pile_ms, (unsigned long long)((map->text->n_fwd + 31) / 32 * 4 + map->pile->n_sites * 16), t->pile_begin_s, t->pile_fetch_s);
 	else if (map->pile) printf("allele counts at the text's IUPAC sites on the host (the .ann records are not ascending and disjoint): sites %llu  reads counted %llu  adds %llu\n",
 		                   (unsigned long long)map->pile->n_sites, (unsigned long long)map->pile->reads, (unsigned long long)map->pile->adds);
+	if (map->pile && !map->pile_on_host && map->pile_q)
+		printf("base qualities in the counts on the GPU (k_pile_q): minimum %d  bases dropped %llu  quality sums %s  quality bytes to the slots %llu, packed and staged in %.3f s\n",
+		       map->pile->min_baseq, t->pile_dropped, map->pile->err_cap ? "kept (-Y)" : "not kept", t->quals_bytes, t->quals_s);
 	if (map->indel && map->gpu_loci)
 		printf("read support per indel bubble on the GPU: anchor %d  eligible bubbles %llu  refused and skipped %llu  reads counted %llu  adds %llu  candidates %llu  k_indel %.3f ms  table and counters %llu bytes, sorted in %.3f s, resident in %.3f s  counters read back in %.3f s\n",
 		       map->indel->anchor, (unsigned long long)map->indel->n_tab, (unsigned long long)map->indel->n_refused, t->indel_reads, t->indel_adds, t->indel_cands, t->indel_ms,
@@ -598,7 +631,7 @@ static void print_map_summary(const map_t *map, const worker_t *t, uint64_t n_re
 		printf("genotype calls on the GPU (worker %d): error phred %d  minimum depth %lld  sites called %llu%s  bubbles called %llu  kernels %.3f ms  pieces %llu  bytes to the host %llu  tables put back in %llu pieces, %.3f s  called in %.3f s\n",
 		       map->geno->worker, map->geno->err, (long long)map->geno->min_depth, (unsigned long long)map->geno->n_sites, map->indel && !map->gpu_loci ? " (the bubbles follow on the host)" : "",
 		       (unsigned long long)map->geno->n_bubs, map->geno->kernel_ms, (unsigned long long)map->geno->pieces,
-		       (unsigned long long)(map->geno->n_sites * sizeof(bwb_geno_site) + map->geno->n_bubs * sizeof(bwb_geno_bubble) + map->geno->pieces * 8), (unsigned long long)map->geno->put_pieces, map->geno->put_s, map->geno->call_s);
+		       (unsigned long long)(map->geno->n_sites * (map->geno->weighted ? sizeof(bwb_geno_site_q) : sizeof(bwb_geno_site)) + map->geno->n_bubs * sizeof(bwb_geno_bubble) + map->geno->pieces * 8), (unsigned long long)map->geno->put_pieces, map->geno->put_s, map->geno->call_s);
 	if (map->max_alt)
 		printf("other placements on the GPU (-X %d): items %llu (%.3f per read)  rank-block visits %llu  kernels %.3f ms\n", map->max_alt, t->alt_items,
 		       n_reads ? (double)t->alt_items / (double)n_reads : 0.0, t->alt_steps, t->alt_ms);
@@ -794,7 +827,7 @@ int map_reads(char *fastaFname, char *readsFname, char *samFname, aln_params_t *
 	sam_write_header(sam, ann);
 	const map_t m = { .max_mm = o->max_mm, .max_alt = o->max_alt, .T = { .ann = ann, .ann_sorted = sam_ann_sorted(ann), .bub = bub, .bubble_of = bubble_of, .chrom_of = chrom_of },
 	                  .gpu_loci = gpu_loci, .rec_start = rec_start, .rec_end = rec_end, .join = join, .lift = lift, .text = text,
-	                  .md = o->md, .pile = pile, .pile_on_host = pile && bub && !gpu_loci && (lift || join), .indel = indel, .geno = geno };
+	                  .md = o->md, .pile = pile, .pile_on_host = pile && bub && !gpu_loci && (lift || join), .pile_q = pile && (pile->min_baseq || pile->err_cap), .indel = indel, .geno = geno };
 
 	t = wall();
 	printf("BWBBLE Inexact Alignment (MI355X)...\n");

@@ -135,6 +135,8 @@ typedef struct {
 	int min_mapq;                /* -a: the least MAPQ that -A, -I and -G count, 0..255 (-1 until finished: not given, then 0) */
 	const char *indelFname;      /* -I: the file of the read support per indel bubble (NULL: no table); needs -B */
 	int anchor;                  /* -w: the flank bases a read must cover on either side for -I and -G, 1..255 (0 until finished: not given, then 1) */
+	int min_baseq;               /* -b: the least base quality that -A and -G count, 0..93 (-1 until finished: not given, then 0) */
+	int weighted;                /* -Y: the genotype calls of -G weighted by the base qualities, the column QS; needs -G */
 	const char *genoFname;       /* -G: the file of the genotype calls from both tables (NULL: no calls) */
 	int geno_err;                /* -q: the error phred of -G, 4..93 (0 until finished: not given, then 20) */
 	int64_t geno_depth;          /* -d: the minimum depth of a call of -G, 1..2^31 - 1 (0 until finished: not given, then 1) */
@@ -230,12 +232,17 @@ typedef struct pile {
 	char *fname; FILE *f; int min_mapq;                               /* the counts file, open since before anything was loaded (NULL: none, a table in memory only); -a */
 	const md_text_t *text; uint64_t n_sites; uint32_t *base;          /* the text, its sites, and - for pile_host - the sites below every 32 characters */
 	uint32_t *counts; uint64_t reads, adds;                           /* n_sites x (A, C, G, T), wrapping; what pile_host has counted */
+	int min_baseq, err_cap;                                           /* -b: the least base quality that counts, 0..93; -Y: -q's E, the cap of a base's weight (0: no -Y), set before pile_set_text */
+	uint32_t *qsum; uint64_t dropped;                                 /* -Y (NULL: none): n_sites x (A, C, G, T) quality sums, wrapping; the bases -b has dropped in pile_host */
 } pile_t;
 pile_t *pile_open(const char *countsFname, int min_mapq);             /* a path that cannot be written stops the run; until pile_write has finished, a run that exits leaves no file */
 void pile_set_text(pile_t *p, const md_text_t *t, int index);         /* counts the sites of the text in memory and makes the zeroed table; index: also what pile_host needs */
 uint64_t pile_host(pile_t *p, const bwb_place *pl, size_t n, const uint8_t *seq, uint32_t stride, const uint16_t *len, const uint8_t *lift_kind, const uint64_t *lift_off,
                    const bwb_lift *lift_recs, const bwb_join *joins, const fasta_annotations_t *ann); /* kernel k_pile on the host: adds into the table, returns the reads counted (joins NULL: the placements' MAPQ) */
+uint64_t pile_host_q(pile_t *p, const bwb_place *pl, size_t n, const uint8_t *seq, uint32_t stride, const uint16_t *len, const char *qtext, const size_t *qual_off,
+                     const uint8_t *lift_kind, const uint64_t *lift_off, const bwb_lift *lift_recs, const bwb_join *joins, const fasta_annotations_t *ann); /* the same with the qualities, kernel k_pile_q on the host: read r's quality line is qtext + qual_off[r] (read only with -b above 0 or -Y) */
 void pile_add(pile_t *p, uint64_t first, uint64_t n, const uint32_t *counts); /* adds a context's counters of n sites from `first` (bwb_hip_pile_counts) */
+void pile_add_q(pile_t *p, uint64_t first, uint64_t n, const uint32_t *sums); /* the same for its quality sums (bwb_hip_pileq_sums) */
 uint64_t pile_write(pile_t *p, const fasta_annotations_t *ann);       /* the header line and one line per site with a counter that is not zero; closes the file; returns the lines */
 void pile_free(pile_t *p);
 
@@ -260,12 +267,15 @@ void indel_free(indel_t *p);
 typedef struct geno {
 	char *fname; FILE *f; int err; int64_t min_depth;                  /* the calls file, open since before anything was loaded (NULL: none, records in memory only); -q; -d */
 	bwb_geno_site *sites; uint64_t n_sites, cap_sites;                /* the called sites' records, in site order */
+	int weighted; uint32_t *qs;                                       /* -Y: the weighted rule and the column QS; the sites' quality sums, four per record of `sites` */
 	bwb_geno_bubble *bubs; uint64_t n_bubs, cap_bubs;                 /* the called bubbles' records, in bubble order */
 	int worker; uint64_t pieces, put_pieces; double kernel_ms, put_s, call_s; /* map: the worker that called, its geno_sites / geno_bubbles calls, its pile_put / indel_put calls, the kernels' time summed, the seconds of both */
 } geno_t;
 geno_t *geno_open(const char *genoFname, int err, int64_t min_depth); /* a path that cannot be written stops the run; until geno_write has finished, a run that exits leaves no file */
 void geno_rule(const uint32_t *n, unsigned k, uint64_t depth, unsigned err, uint8_t *gt, uint8_t *gq, uint32_t *pl /* 6 */); /* the rule from the k = 2 or 3 alleles' counts and the depth */
+void geno_rule_q(const uint32_t *n, const uint32_t *s, unsigned k, uint64_t S, uint8_t *gt, uint8_t *gq, uint32_t *pl /* 6 */); /* -Y: the weighted rule from the alleles' counts and quality sums and the sum of all four columns */
 void geno_take_sites(geno_t *g, const bwb_geno_site *recs, uint64_t n); /* keeps a piece's records for the writer (bwb_hip_geno_sites) */
+void geno_take_sites_q(geno_t *g, const bwb_geno_site_q *recs, uint64_t n); /* -Y: the same with the records' quality sums (bwb_hip_geno_sites_q) */
 void geno_take_bubbles(geno_t *g, const bwb_geno_bubble *recs, uint64_t n); /* (bwb_hip_geno_bubbles) */
 void geno_host(geno_t *g, const pile_t *pile, const indel_t *indel);  /* the geno kernels on the host: the same records from the host's tables (either may be NULL) */
 uint64_t geno_write(geno_t *g, const fasta_annotations_t *ann, const bubble_table_t *bub); /* the header line, the called sites, the called bubbles (bub NULL: none); closes the file; returns the lines */

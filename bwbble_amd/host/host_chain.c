@@ -11,6 +11,8 @@ void host_outs_open(host_outs_t *out, const map_opts_t *o) {
 	out->pile = o->countsFname || o->genoFname ? pile_open(o->countsFname, o->min_mapq) : NULL; /* -A; -G: the table without a file */
 	out->indel = o->indelFname || (o->genoFname && o->bubbleFname) ? indel_open(o->indelFname, o->min_mapq, o->anchor) : NULL; /* -I (main.c: only with -B); -G with -B: the table without a file */
 	out->geno = o->genoFname ? geno_open(o->genoFname, o->geno_err, o->geno_depth) : NULL; /* -G */
+	if (out->pile) { out->pile->min_baseq = o->min_baseq; out->pile->err_cap = o->weighted ? o->geno_err : 0; } /* -b; -Y: the quality sums beside the counters */
+	if (out->geno) out->geno->weighted = o->weighted; /* -Y (main.c: only with -G) */
 }
 void host_outs_free(host_outs_t *out) { pile_free(out->pile); indel_free(out->indel); geno_free(out->geno); }
 
@@ -79,7 +81,8 @@ void host_tail(host_outs_t *out, const sam_reads_t *rd, size_t n, const host_tab
 	geno_t *geno = out->geno;
 	if (pile) { /* -A: the host's rule on the same records */
 		pile_set_text(pile, text, 1);
-		pile_host(pile, rd->pl, n, rd->seq, rd->stride, rd->len, rd->lift_kind, rd->lift_off, rd->lift_recs, rd->joins, T->ann);
+		pile_host_q(pile, rd->pl, n, rd->seq, rd->stride, rd->len, rd->text, rd->qual_off, rd->lift_kind, rd->lift_off, rd->lift_recs, rd->joins, T->ann);
+		if (pile->min_baseq || pile->err_cap) printf("base qualities in the counts on the host: minimum %d  bases dropped %llu  quality sums %s\n", pile->min_baseq, (unsigned long long)pile->dropped, pile->err_cap ? "kept (-Y)" : "not kept");
 	}
 	if (pile && pile->f) {
 		const unsigned long long lines = pile_write(pile, T->ann);

@@ -1,7 +1,8 @@
 /* main.c - `bwbble` command line, same commands and flags as the reference (mg-aligner/main.c:38-160),
  * plus -g <n_gpus> on align / aln2sam, `map` = align + aln2sam in one pass, and `sampad` = mg-ref/sam_pad (-B on map / aln2sam: the same
  * tags without a second pass; -J, -R, -D, -A, -I and -G, the project's own: placements counted by locus, written in chromosome coordinates, the tags
- * NM:i / MD:Z against the text, the allele counts at the text's IUPAC sites, the read support per indel bubble, and the genotype calls from both). */
+ * NM:i / MD:Z against the text, the allele counts at the text's IUPAC sites, the read support per indel bubble, and the genotype calls from both;
+ * -b and -Y: the base qualities in the counts and the calls). */
 #define _GNU_SOURCE
 #include <getopt.h>
 #include <time.h>
@@ -32,7 +33,7 @@ static int align_usage(void) {
 }
 
 static int map_usage(void) {
-	printf("Usage: bwbble map [align options] [-Q <int>] [-X <int>] [-B <bubble.data>] [-J] [-R] [-D] [-A <counts.tsv> [-a <int>]] [-I <indels.tsv> [-w <int>]] [-G <calls.tsv> [-q <int>] [-d <int>]] [-g <gpus>] <seq_fasta> <reads_fastq> <out_sam> \n");
+	printf("Usage: bwbble map [align options] [-Q <int>] [-X <int>] [-B <bubble.data>] [-J] [-R] [-D] [-A <counts.tsv> [-a <int>]] [-I <indels.tsv> [-w <int>]] [-G <calls.tsv> [-q <int>] [-d <int>]] [-b <int>] [-Y] [-g <gpus>] <seq_fasta> <reads_fastq> <out_sam> \n");
 	printf("         writes the SAM file that `bwbble align [align options]` followed by `bwbble aln2sam [-n <Q>] [-X <N>]` writes, without the .aln file\n");
 	printf("Options: the options of align, and\n");
 	printf("         Q    the mismatch count at which a unique hit gets MAPQ 25 (aln2sam's -n; default: 6)\n");
@@ -47,18 +48,20 @@ static int map_usage(void) {
 	printf("         q    with -G: the error phred, the cost of a base a genotype does not carry, 4..93 (default: 20)\n");
 	printf("         d    with -G: the minimum depth of a call, 1..2147483647 (default: 1)\n");
 	printf("         w    with -I or -G: the anchor, the flank bases a read must cover on either side, 1..255 (default: 1)\n");
-	printf("         a    with -A, -I or -G: only reads with MAPQ >= a count, 0..255 (default: 0)\n\n");
+	printf("         a    with -A, -I or -G: only reads with MAPQ >= a count, 0..255 (default: 0)\n");
+	printf("         b    with -A or -G: only read bases with a quality of at least b count at a site, 0..93, from the QUAL byte SAM prints under the base; the numbers of -A and the calls of -G are those of the filtered counts; -I is not affected, its rule looks at the CIGAR's ops, not at bases (default: 0)\n");
+	printf("         Y    with -G: the calls at the IUPAC sites weigh every counted base by its quality q = min(max(Q, 4), E), E being -q: a genotype pays q for a base it does not carry instead of E; the calls file gains a last column QS, the alleles' quality sums on S lines and `.` on I lines - bubbles are called as without -Y, from -I's counters (default: every base costs E)\n\n");
 	return 1;
 }
 static int aln2sam_usage(void) {
-	printf("Usage: bwbble aln2sam [-S, -n, -g, -X, -B, -J, -R, -D, -A, -a, -I, -w, -G, -q, -d] <seq_fasta> <reads_fastq> <alns_aln> <out_sam> \n");
+	printf("Usage: bwbble aln2sam [-S, -n, -g, -X, -B, -J, -R, -D, -A, -a, -I, -w, -G, -q, -d, -b, -Y] <seq_fasta> <reads_fastq> <alns_aln> <out_sam> \n");
 	printf("Options: n    the mismatch count at which a unique hit gets MAPQ 25 (default: 6)\n         g    number of GPUs for the SA lookups (default: 1)\n");
 	printf("         X    1..255: the tags X0:i / X1:i / XA:Z: of `bwbble map -X` (default: no tags)\n");
 	printf("         B    the bubble table (bubble.data): the tags bC:Z: / bP:Z: of `bwbble map -B` (default: no tags)\n");
 	printf("         J    with -X and -B: MAPQ and the tag bJ:i: of `bwbble map -J` (default: every placement counts)\n");
 	printf("         R    with -B: RNAME, POS and CIGAR in chromosome coordinates and the tag bO:Z: of `bwbble map -R` (default: bubble coordinates)\n");
 	printf("         D    the tags NM:i: / MD:Z: of `bwbble map -D`, against the text of <seq_fasta>.ref (default: no tags)\n");
-	printf("         A    <counts.tsv>: the allele counts of `bwbble map -A`, from the host's rule (default: no counts)\n         I    <indels.tsv>, with -B: the read support per indel bubble of `bwbble map -I`, from the host's rule (default: no table)\n         G    <calls.tsv>: the genotype calls of `bwbble map -G`, from the host's rule (default: no calls)\n         q    with -G: the error phred, 4..93 (default: 20)\n         d    with -G: the minimum depth, 1..2147483647 (default: 1)\n         w    with -I or -G: the anchor, 1..255 (default: 1)\n         a    with -A, -I or -G: the least MAPQ that counts, 0..255 (default: 0)\n\n");
+	printf("         A    <counts.tsv>: the allele counts of `bwbble map -A`, from the host's rule (default: no counts)\n         I    <indels.tsv>, with -B: the read support per indel bubble of `bwbble map -I`, from the host's rule (default: no table)\n         G    <calls.tsv>: the genotype calls of `bwbble map -G`, from the host's rule (default: no calls)\n         q    with -G: the error phred, 4..93 (default: 20)\n         d    with -G: the minimum depth, 1..2147483647 (default: 1)\n         w    with -I or -G: the anchor, 1..255 (default: 1)\n         a    with -A, -I or -G: the least MAPQ that counts, 0..255 (default: 0)\n         b    with -A or -G: the least base quality that counts at a site, 0..93; -I is not affected (default: 0)\n         Y    with -G: the calls of `bwbble map -Y`, weighted by the base qualities, and the column QS (default: every base costs -q)\n\n");
 	return 1;
 }
 /* a number option's argument: lo..hi, anything else is refused with the flag's own message */
@@ -71,7 +74,7 @@ static long long range_option(const char *arg, long long lo, long long hi, const
 
 /* the options of the result stream that `map`, `aln2sam` and `places2sam` share (bwb_host.h: map_opts_t): the record before any is given, and
  * one option letter with its argument into it; 0 = not one of them */
-static const map_opts_t MAP_OPTS_NONE = { .max_mm = 6 /* (aln2sam's default, mg-aligner/main.c:142) */, .min_mapq = -1 /* (no -a) */ };
+static const map_opts_t MAP_OPTS_NONE = { .max_mm = 6 /* (aln2sam's default, mg-aligner/main.c:142) */, .min_mapq = -1 /* (no -a) */, .min_baseq = -1 /* (no -b) */ };
 static int map_option(int c, const char *arg, map_opts_t *o) {
 	switch (c) {
 	case 'Q': o->max_mm = atoi(arg); return 1; /* (aln2sam spells it -n) */
@@ -86,12 +89,14 @@ static int map_option(int c, const char *arg, map_opts_t *o) {
 	case 'w': o->anchor = (int)range_option(arg, 1, 255, "Error: -w takes an anchor of 1..255, not %s\n"); return 1;
 	case 'G': o->genoFname = arg; return 1;
 	case 'q': o->geno_err = (int)range_option(arg, 4, 93, "Error: -q takes an error phred of 4..93, not %s\n"); return 1;
+	case 'b': o->min_baseq = (int)range_option(arg, 0, 93, "Error: -b takes a base quality of 0..93, not %s\n"); return 1;
+	case 'Y': o->weighted = 1; return 1;
 	case 'd': o->geno_depth = range_option(arg, 1, 2147483647ll, "Error: -d takes a minimum depth of 1..2147483647, not %s\n"); return 1;
 	}
 	return 0;
 }
 
-/* what one flag needs of another, in this order: -J, -R, -a, -I / -w, -q / -d; then the defaults of what was not given */
+/* what one flag needs of another, in this order: -J, -R, -a, -I / -w, -q / -d, -b, -Y; then the defaults of what was not given */
 static void map_opts_finish(map_opts_t *o) {
 	const char *B = o->bubbleFname;
 	if (o->join && !(o->max_alt && B)) { printf("Error: -J needs %s%s%s\n", o->max_alt ? "" : "-X <N>", o->max_alt || B ? "" : " and ", B ? "" : "-B <bubble.data>"); exit(1); }
@@ -101,7 +106,10 @@ static void map_opts_finish(map_opts_t *o) {
 	if (o->anchor && !o->indelFname && !o->genoFname) { printf("Error: -w needs -I <indels.tsv> or -G <calls.tsv>\n"); exit(1); }
 	if (o->geno_err && !o->genoFname) { printf("Error: -q needs -G <calls.tsv>\n"); exit(1); }
 	if (o->geno_depth && !o->genoFname) { printf("Error: -d needs -G <calls.tsv>\n"); exit(1); }
+	if (o->min_baseq >= 0 && !o->countsFname && !o->genoFname) { printf("Error: -b needs -A <counts.tsv> or -G <calls.tsv>\n"); exit(1); }
+	if (o->weighted && !o->genoFname) { printf("Error: -Y needs -G <calls.tsv>\n"); exit(1); }
 	if (o->min_mapq < 0) o->min_mapq = 0;
+	if (o->min_baseq < 0) o->min_baseq = 0;
 	if (!o->anchor) o->anchor = 1;
 	if (!o->geno_err) o->geno_err = 20;
 	if (!o->geno_depth) o->geno_depth = 1;
@@ -155,7 +163,7 @@ int main(int argc, char *argv[]) {
 		set_default_aln_params(&params);
 		int c, n_gpus = 1;
 		map_opts_t o = MAP_OPTS_NONE;
-		while ((c = getopt(argc - 1, argv + 1, "M:O:E:n:k:o:e:l:m:t:g:SPQ:X:B:JRDA:a:I:w:G:q:d:")) >= 0) {
+		while ((c = getopt(argc - 1, argv + 1, "M:O:E:n:k:o:e:l:m:t:g:SPQ:X:B:JRDA:a:I:w:G:q:d:b:Y")) >= 0) {
 			if (align_option(c, &params, &n_gpus) || map_option(c, optarg, &o)) continue;
 			if (c == '?') { map_usage(); return 1; }
 			return 1;
@@ -169,17 +177,17 @@ int main(int argc, char *argv[]) {
 		/* (a leading `-B <bubble.data>`: the tags of `map -B`, the loci from the host resolver; `-J` behind it: MAPQ and the tag of `map -J`,
 		 * the items file then ends with one byte per item, not zero for a suboptimal one; `-R` behind them: RNAME, POS and CIGAR of `map -R`, from the
 		 * host's rule; `-D` behind that: the tags NM / MD of `map -D`, from the host's rule; `-A <counts.tsv>` and `-a <MAPQ>` behind that: the allele
-		 * counts of `map -A`, from the host's rule) */
+		 * counts of `map -A`, from the host's rule; `-I`, `-w`, `-G`, `-q`, `-d` and last `-b <m>` and `-Y`: the tables and calls of the flags of `map`) */
 		/* (the flags only in this order, each at most once) */
 		char **a = argv + 2;
 		int na = argc - 2;
 		map_opts_t o = MAP_OPTS_NONE;
-		for (const char *f = "B:JRDA:a:I:w:G:q:d:"; *f; f++) {
+		for (const char *f = "B:JRDA:a:I:w:G:q:d:b:Y"; *f; f++) {
 			const int arg = f[1] == ':';
 			if (na > arg && a[0][0] == '-' && a[0][1] == *f && !a[0][2]) { map_option(*f, arg ? a[1] : NULL, &o); a += 1 + arg; na -= 1 + arg; }
 			f += arg;
 		}
-		if (na < 4) { printf("Usage: bwbble places2sam [-B <bubble.data>] [-J] [-R] [-D] [-A <counts.tsv>] [-a <MAPQ>] [-I <indels.tsv>] [-w <anchor>] [-G <calls.tsv>] [-q <err>] [-d <depth>] <seq_fasta> <reads_fastq> <places_bin> <out_sam> [<alts_bin>] \n"); exit(1); }
+		if (na < 4) { printf("Usage: bwbble places2sam [-B <bubble.data>] [-J] [-R] [-D] [-A <counts.tsv>] [-a <MAPQ>] [-I <indels.tsv>] [-w <anchor>] [-G <calls.tsv>] [-q <err>] [-d <depth>] [-b <baseq>] [-Y] <seq_fasta> <reads_fastq> <places_bin> <out_sam> [<alts_bin>] \n"); exit(1); }
 		o.max_alt = na >= 5; /* (-J needs the items file, as it needs -X elsewhere) */
 		map_opts_finish(&o);
 		places2sam(a[0], a[1], a[2], a[3], na >= 5 ? a[4] : NULL, &o);
@@ -200,7 +208,7 @@ int main(int argc, char *argv[]) {
 		if (argc < 6) { aln2sam_usage(); exit(1); }
 		int is_multiref = 1, n_gpus = 1, c;
 		map_opts_t o = MAP_OPTS_NONE;
-		while ((c = getopt(argc - 1, argv + 1, "n:g:SX:B:JRDA:a:I:w:G:q:d:")) >= 0) {
+		while ((c = getopt(argc - 1, argv + 1, "n:g:SX:B:JRDA:a:I:w:G:q:d:b:Y")) >= 0) {
 			if (map_option(c == 'n' ? 'Q' : c, optarg, &o)) continue;
 			switch (c) {
 			case 'S': is_multiref = 0; break;

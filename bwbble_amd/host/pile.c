@@ -6,6 +6,8 @@
  * reads laid out the way md_host takes them (aln2sam, places2sam, and map with the host's lift or join records).  The table lives here either
  * way: n_sites x (A, C, G, T) uint32 counters that wrap, sites numbered in text order.  pile_write enumerates the sites by scanning the text's
  * bytes - no site list travels from the device - and writes one line per site with a counter that is not zero.
+ * -b / -Y (include/bwbble_hip.h: bwb_hip_pileq_begin): min_baseq drops the bases below it, and with err_cap a second table of the same shape,
+ * qsum, takes min(max(Q, 4), err_cap) for every base counted; the qualities are the FASTQ's lines, byte i under read base i.
  * The counts file is opened before anything is loaded, so that a path that cannot be written stops the run there; a run that ends through
  * bwb_die (exit) before pile_write has finished leaves no counts file behind.
  */
@@ -54,7 +56,8 @@ void pile_set_text(pile_t *p, const md_text_t *t, int index) {
 	if (n > 0xFFFFFFFFull) bwb_die("-A: the text has %llu IUPAC sites, more than 2^32 - 1", (unsigned long long)n);
 	p->n_sites = n;
 	p->counts = (uint32_t *)calloc(n ? (size_t)n * 4 : 1, sizeof(uint32_t));
-	if (!p->counts) bwb_die("-A: no memory for the counters of %llu sites", (unsigned long long)n);
+	if (p->err_cap) p->qsum = (uint32_t *)calloc(n ? (size_t)n * 4 : 1, sizeof(uint32_t)); /* -Y */
+	if (!p->counts || (p->err_cap && !p->qsum)) bwb_die("-A: no memory for the counters of %llu sites", (unsigned long long)n);
 }
 
 /* the site number of a site's position (pile_host; needs the index of pile_set_text) */
@@ -64,14 +67,19 @@ static inline uint64_t pile_site(const pile_t *p, uint64_t i) {
 	return s;
 }
 
-/* The rule on a set of reads, laid out as for md_host; joins NULL: MAPQ is the placement's.  Adds into the table with all cores (the adds
- * commute); returns the reads counted and adds the adds to p->adds. */
-uint64_t pile_host(pile_t *p, const bwb_place *pl, size_t n, const uint8_t *seq, uint32_t stride, const uint16_t *len, const uint8_t *lift_kind, const uint64_t *lift_off,
-                   const bwb_lift *lift_recs, const bwb_join *joins, const fasta_annotations_t *ann) {
+/* The rule on a set of reads, laid out as for md_host; joins NULL: MAPQ is the placement's; read r's quality line is qtext + qual_off[r] (only
+ * read with -b above 0 or -Y).  Adds into the table with all cores (the adds commute); returns the reads counted and adds the adds to p->adds,
+ * the bases -b dropped to p->dropped. */
+uint64_t pile_host_q(pile_t *p, const bwb_place *pl, size_t n, const uint8_t *seq, uint32_t stride, const uint16_t *len, const char *qtext, const size_t *qual_off,
+                     const uint8_t *lift_kind, const uint64_t *lift_off, const bwb_lift *lift_recs, const bwb_join *joins, const fasta_annotations_t *ann) {
+	const unsigned min_baseq = (unsigned)p->min_baseq, err_cap = (unsigned)p->err_cap;
+	const int with_q = min_baseq || err_cap;
+	if (with_q && !(qtext && qual_off)) bwb_die("-b / -Y: the reads carry no qualities");
+	uint64_t dropped = 0;
 	const uint8_t *text = p->text->codes;
 	const uint64_t n_fwd = p->text->n_fwd;
 	uint64_t reads = 0, adds = 0;
-#pragma omp parallel for schedule(static) reduction(+ : reads, adds) num_threads(bwb_host_team())
+#pragma omp parallel for schedule(static) reduction(+ : reads, adds, dropped) num_threads(bwb_host_team())
 	for (long r = 0; r < (long)n; r++) {
 		if (!(pl[r].flags & BWB_PLACE_MAPPED) || len[r] > 255 || len[r] > stride) continue;
 		if ((int)(joins ? joins[r].mapq : pl[r].mapq) < p->min_mapq) continue;
@@ -94,6 +102,7 @@ uint64_t pile_host(pile_t *p, const bwb_place *pl, size_t n, const uint8_t *seq,
 		}
 		if (span > BWB_MD_MAX_SPAN || start < 0 || (uint64_t)start > n_fwd || span > n_fwd - (uint64_t)start || on_read != len[r]) continue;
 		const uint8_t *s = seq + (size_t)r * stride;
+		const uint8_t *ql = with_q ? (const uint8_t *)qtext + qual_off[r] : NULL;
 		unsigned ri = 0;
 		uint64_t tp = (uint64_t)start;
 		for (unsigned i = 0; i < n_ops; i++) {
@@ -101,13 +110,25 @@ uint64_t pile_host(pile_t *p, const bwb_place *pl, size_t n, const uint8_t *seq,
 			if (op == BWB_LIFT_M) {
 				for (unsigned k = 0; k < count; k++, ri++, tp++) {
 					if (!((PILE_SITE_CODES >> (text[tp] & 15u)) & 1u)) continue;
-					const unsigned raw = reverse ? s[len[r] - 1 - ri] : s[ri];
+					const unsigned idx = reverse ? len[r] - 1u - ri : ri;
+					const unsigned raw = s[idx];
 					if (raw > 3) continue; /* a read N */
+					unsigned Q = 0;
+					if (with_q) {
+						Q = ql[idx] < 33 ? 0u : (ql[idx] - 33u > 93u ? 93u : ql[idx] - 33u);
+						if (Q < min_baseq) { dropped++; continue; }
+					}
 					const unsigned b = reverse ? 3u - raw : raw; /* A0 G1 C2 T3 as SAM prints it */
 					const unsigned col = (b == 1 || b == 2) ? 3u - b : b; /* A C G T */
 					uint32_t *dst = p->counts + pile_site(p, tp) * 4 + col;
 #pragma omp atomic
 					*dst += 1u;
+					if (err_cap) {
+						uint32_t *qd = p->qsum + (dst - p->counts);
+						const uint32_t q = Q < 4 ? 4u : Q > err_cap ? err_cap : Q;
+#pragma omp atomic
+						*qd += q;
+					}
 					adds++;
 				}
 			} else if (op == BWB_LIFT_D) tp += count;
@@ -115,14 +136,26 @@ uint64_t pile_host(pile_t *p, const bwb_place *pl, size_t n, const uint8_t *seq,
 		}
 		reads++;
 	}
-	p->reads += reads; p->adds += adds;
+	p->reads += reads; p->adds += adds; p->dropped += dropped;
 	return reads;
+}
+
+/* the rule without qualities (a table without -b and -Y) */
+uint64_t pile_host(pile_t *p, const bwb_place *pl, size_t n, const uint8_t *seq, uint32_t stride, const uint16_t *len, const uint8_t *lift_kind, const uint64_t *lift_off,
+                   const bwb_lift *lift_recs, const bwb_join *joins, const fasta_annotations_t *ann) {
+	return pile_host_q(p, pl, n, seq, stride, len, NULL, NULL, lift_kind, lift_off, lift_recs, joins, ann);
 }
 
 /* a worker's counters of the sites first .. first + n - 1 (bwb_hip_pile_counts), added into the table */
 void pile_add(pile_t *p, uint64_t first, uint64_t n, const uint32_t *counts) {
 	uint32_t *dst = p->counts + first * 4;
 	for (uint64_t k = 0; k < n * 4; k++) dst[k] += counts[k];
+}
+
+/* a worker's quality sums of the same sites (bwb_hip_pileq_sums) */
+void pile_add_q(pile_t *p, uint64_t first, uint64_t n, const uint32_t *sums) {
+	uint32_t *dst = p->qsum + first * 4;
+	for (uint64_t k = 0; k < n * 4; k++) dst[k] += sums[k];
 }
 
 typedef struct { uint64_t start; int rec; } pile_rec_t;
@@ -167,5 +200,5 @@ void pile_free(pile_t *p) {
 	if (!p) return;
 	if (p->f) fclose(p->f);
 	if (p->fname && pile_unfinished == p->fname) { remove(p->fname); pile_unfinished = NULL; }
-	free(p->fname); free(p->base); free(p->counts); free(p);
+	free(p->fname); free(p->base); free(p->counts); free(p->qsum); free(p);
 }

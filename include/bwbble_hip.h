@@ -509,7 +509,7 @@ int bwb_hip_pile_stats(bwb_hip_ctx *ctx, uint64_t *reads, uint64_t *adds, double
  *             record is classed against b's own window only: alt += 1 when clean, alt_gapped += 1 when gapped.  A read on a non-bubble record
  *             c is classed against the window of EVERY eligible bubble with chrom_of == c: ref += 1 or ref_gapped += 1.  Mismatches under M
  *             do not matter.
- * Not here: other bubbles' sites inside a bubble record's flanks, XA items, base qualities, genotypes, left-alignment (a read that fits both
+ * Not here: other bubbles' sites inside a bubble record's flanks, XA items, base qualities (the rule looks at ops, not at bases: -b and -Y below do not change it), genotypes, left-alignment (a read that fits both
  * alleles equally well counts for whichever placement is its primary).
  * The adds are integer and commute: the table does not depend on chunking, slot order, parked reads or the number of contexts whose tables are
  * summed.  Kernel k_indel: one lane per read behind k_place / k_locus / the join kernels on the result stream; a read on a chromosome bisects
@@ -557,7 +557,7 @@ int bwb_hip_indel_stats(bwb_hip_ctx *ctx, uint64_t *reads, uint64_t *adds, uint6
  *               alt, the clean counts; other = ref_gapped + alt_gapped, depth = n_R + n_V + other, both in 64 bits.  Called when depth >= d, by
  *               the same formulas over R/R, R/V, V/V.  Bubbles that share a site are called each on its own, biallelic, with the shared ref count,
  *               exactly as the indel family counts them.
- * Which reads count is entirely the pile and indel families' rule; nothing here walks a read.  Not here: base qualities, priors, multi-allelic
+ * Which reads count is entirely the pile and indel families' rule; nothing here walks a read.  Base qualities: bwb_hip_pileq_begin, below.  Not here: priors, multi-allelic
  * indel sites, XA items, left-alignment, and VCF itself - the text has no reference allele to put in REF.
  * Kernels: k_geno_count (one lane per site of a range: the inverse of the site index - the site's word by bisection over the one uint32 per word,
  * its character as the r-th set bit of the word's site mask - and the four counters in one 16-byte load), the scan of the alt family, k_geno_emit
@@ -597,6 +597,61 @@ int bwb_hip_geno_bubbles(bwb_hip_ctx *ctx, uint64_t first, uint64_t n, int err, 
 /* the entries the last geno_sites and the last geno_bubbles call that launched have called, and the HIP-event time of the kernels of whichever
  * of the two launched last (any pointer may be NULL) */
 int bwb_hip_geno_stats(bwb_hip_ctx *ctx, uint64_t *sites_called, uint64_t *bubbles_called, double *kernel_ms);
+
+/* Base qualities in the allele counts and the genotype calls (`bwbble map -b <m>` and `-Y`): a minimum base quality for the pile family, and a
+ * quality-weighted rule beside the geno family's.  Nobody can apply either afterwards, for the reasons the two families give.  The rule - stated
+ * here once; the kernels, host/pile.c + host/geno.c and tests/pileq_model.py implement it and agree bit for bit.  Integer arithmetic only.
+ *   quality     the quality of a read base is taken from the QUAL byte SAM prints under it: for the read base at index i of the read as uploaded
+ *               (i = ri on the forward strand, len - 1 - ri on the reverse one - the index k_pile uses for the base) it is byte i of the FASTQ's
+ *               quality line.  For a byte c, Q = 0 when c < 33, else min(c - 33, 93).  I and S ops consume quality bytes as they consume bases.
+ *   -b m        m = min_baseq, 0..93.  Everything of the pile family's rule stands - which reads count, which ops are walked, from where, which
+ *               column, -a, -J's MAPQ, -R's walk - with one more condition: an M base on a site adds to counts[site][column] only when Q >= m.
+ *               The indel family is not affected: its rule looks at ops, not at bases.
+ *   -Y          err_cap = E, the geno family's error phred, 4..93.  A second table beside the counters, qsum[site][A|C|G|T], uint32, wrapping
+ *               modulo 2^32: every base that adds 1 to a counter (after -b) adds q = min(max(Q, 4), E) to qsum in the same column; q lies in
+ *               4..E.  The floor of 4 is E's own lower bound: a base costs a homozygous genotype that lacks it no less than H = 3, its cost
+ *               under a heterozygous one that carries it.
+ *   calls       for a site with the alleles a0 < a1 (< a2): n_i and depth as in the geno family, s_i the qsum column of a_i, S the sum of all
+ *               four qsum columns in 64 bits;
+ *                 raw(x,x) = S - s_x          raw(x,y) = H (n_x + n_y) + (S - s_x - s_y)          in uint64
+ *               and GT, GQ, PL and CALLED (depth >= d) from raw exactly as there.  When every counted base has Q >= E, s_x = E n_x and the
+ *               calls are the geno family's, number for number.  Bubbles have no per-base evidence: they are called by the geno family's rule.
+ * Not here: quality-aware indel support, base qualities capped by MAPQ, the qualities of XA items, priors, VCF.
+ * Kernels: k_pile_q beside k_pile (the same lanes and walk; the quality byte is loaded only when a base falls on a site, as the read base is;
+ * relaxed agent-scope atomic adds to counts and qsum) and k_geno_emit_q beside k_geno_emit (behind the same k_geno_count and scan; counters and
+ * sums in one 16-byte load each).  (Added without a version change: no structure or existing entry point changed.) */
+typedef struct {
+	bwb_geno_site site;     /* as from bwb_hip_geno_sites, GT / GQ / PL by the weighted rule */
+	uint32_t qs[4];         /* the quality sums: A, C, G, T */
+} bwb_geno_site_q;          /* 80 bytes */
+/* After pile_begin (BWB_E_STATE without) and before the first slot_upload sizes the pool: from now on every slot keeps n_reads x stride quality
+ * bytes beside its reads, and - weighted != 0 - allocates and zeroes the n_sites x 4 quality sums.  A later pile_begin or set_text forgets it. */
+int bwb_hip_pileq_begin(bwb_hip_ctx *ctx, int weighted);
+/* The quality bytes of the slot's resident reads, laid out like slot_upload's reads_fwd (one byte per base in FASTQ order, `stride` bytes per read):
+ * staged and copied on the copy stream; the caller's buffer is free on return.  After the slot's slot_upload and before its pile call; the slot's
+ * next slot_upload forgets them.  BWB_E_STATE without pileq_begin or on a slot without an upload; BWB_E_ARG when stride is not the upload's. */
+int bwb_hip_slot_quals(bwb_hip_ctx *ctx, int slot, const uint8_t *quals, uint32_t stride);
+/* slot_pile's chain - slot_place, slot_lift, slot_join or their cached records - then k_pile_q.  err_cap == 0: unweighted (counts only); 4..93:
+ * weighted with that E, which needs pileq_begin(weighted != 0).  A SUBMISSION IS PILED ONCE: slot_pile and slot_pile_q share the flag.  slot_pile's
+ * errors, and BWB_E_ARG for min_baseq outside 0..93 or err_cap outside {0, 4..93}; BWB_E_STATE without pileq_begin, for err_cap != 0 without the
+ * sums, and without the slot's qualities; the context stays usable after each.  batch_pile_q is the one-batch form (slot 0 after batch_run). */
+int bwb_hip_slot_pile_q(bwb_hip_ctx *ctx, int slot, int max_mm, int max_alt, int lifted, int joined, int min_mapq, int min_baseq, int err_cap, uint64_t *reads_counted);
+int bwb_hip_batch_pile_q(bwb_hip_ctx *ctx, int max_mm, int max_alt, int lifted, int joined, int min_mapq, int min_baseq, int err_cap, uint64_t *reads_counted);
+/* pile_records with the reads' quality bytes (laid out like reads_fwd), min_baseq and err_cap: accumulates into the counters and the sums. */
+int bwb_hip_pile_records_q(bwb_hip_ctx *ctx, const uint8_t *reads_fwd, const uint8_t *quals, const uint16_t *lens, uint32_t stride, const bwb_place *places, uint32_t n,
+                           const uint8_t *kinds, const uint64_t *lift_off, const bwb_lift *lift_recs, const uint8_t *mapq, int min_mapq, int min_baseq, int err_cap);
+/* The mirrors of pile_counts and pile_put for the 4 n quality sums of the sites first .. first + n - 1, with their argument checks; BWB_E_STATE
+ * without a weighted pileq_begin.  pile_reset zeroes the sums with the counters. */
+int bwb_hip_pileq_sums(bwb_hip_ctx *ctx, uint64_t first, uint64_t n, uint32_t *out);
+int bwb_hip_pileq_put(bwb_hip_ctx *ctx, uint64_t first, uint64_t n, const uint32_t *sums);
+/* the last pile_q call on the context that launched the kernel: reads counted, adds made, bases dropped by min_baseq, and the kernel's HIP-event
+ * time (any pointer may be NULL) */
+int bwb_hip_pileq_stats(bwb_hip_ctx *ctx, uint64_t *reads, uint64_t *adds, uint64_t *dropped, double *kernel_ms);
+/* geno_sites by the weighted rule, from the counters and the sums: geno_begin's piece - a geno_begin that comes after pileq_begin(weighted != 0)
+ * sizes scratch and output for the 80-byte records -, the same pinned-output discipline (*out shares geno_sites' memory), geno_stats as there.
+ * err is checked as there; the sums carry it from the pile's err_cap.  geno_sites' errors, and BWB_E_STATE without a weighted pileq_begin before
+ * geno_begin. */
+int bwb_hip_geno_sites_q(bwb_hip_ctx *ctx, uint64_t first, uint64_t n, int err, int64_t min_depth, const bwb_geno_site_q **out, uint64_t *n_out);
 
 #ifdef __cplusplus
 }
