@@ -617,9 +617,9 @@ class Context:
         _chk(lib().bwb_hip_batch_md(self._h, max_mm, max_alt, int(bool(lifted)), *[C.byref(x) for x in p], C.byref(n)))
         return self._md(p, n.value)
 
-    def md_records(self, seqs, lens, places, kinds=None, lift_off=None, words=None):
-        """the same kernels on reads and placement records of the caller's; kinds / lift_off / words: every read's lift kind and the 16-byte words
-        of the lifted ones' records, laid out as slot_lift() returns them for its primaries"""
+    @staticmethod
+    def _record_arrays(seqs, lens, places, kinds, lift_off, words, mapq):
+        """the arrays and pointers of the *_records calls (md_records: mapq None), checked"""
         seqs, lens = _read_arrays(seqs, lens)
         places = np.ascontiguousarray(places, dtype=PLACE_DTYPE)
         if len(places) != len(lens):
@@ -632,6 +632,16 @@ class Context:
             if len(kinds) != len(lens) or len(lift_off) != len(lens) + 1 or len(words) != int(lift_off[-1]):
                 raise ValueError("kinds must have one entry per read, lift_off one more, words one row per 16-byte word")
             lift = [kinds.ctypes.data, lift_off.ctypes.data, words.ctypes.data]
+        if mapq is not None:
+            mapq = np.ascontiguousarray(mapq, dtype=np.uint8)
+            if len(mapq) != len(lens):
+                raise ValueError("one MAPQ per read")
+        return seqs, lens, places, lift, mapq, (kinds, lift_off, words)  # (the last: kept alive behind the pointers in `lift`)
+
+    def md_records(self, seqs, lens, places, kinds=None, lift_off=None, words=None):
+        """the same kernels on reads and placement records of the caller's; kinds / lift_off / words: every read's lift kind and the 16-byte words
+        of the lifted ones' records, laid out as slot_lift() returns them for its primaries"""
+        seqs, lens, places, lift, _mapq, _keep = self._record_arrays(seqs, lens, places, kinds, lift_off, words, None)
         p = [C.c_void_p() for _ in range(3)]
         _chk(lib().bwb_hip_md_records(self._h, seqs.ctypes.data, lens.ctypes.data, seqs.shape[1], places.ctypes.data, len(lens), *lift, *[C.byref(x) for x in p]))
         return self._md(p, len(lens))
@@ -660,29 +670,9 @@ class Context:
         _chk(lib().bwb_hip_batch_pile(self._h, max_mm, max_alt, int(bool(lifted)), int(bool(joined)), min_mapq, C.byref(n)))
         return n.value
 
-    @staticmethod
-    def _pile_record_arrays(seqs, lens, places, kinds, lift_off, words, mapq):
-        seqs, lens = _read_arrays(seqs, lens)
-        places = np.ascontiguousarray(places, dtype=PLACE_DTYPE)
-        if len(places) != len(lens):
-            raise ValueError("one placement record per read")
-        lift = [None, None, None]
-        if kinds is not None:
-            kinds = np.ascontiguousarray(kinds, dtype=np.uint8)
-            lift_off = np.ascontiguousarray(lift_off, dtype=np.uint64)
-            words = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, 4)
-            if len(kinds) != len(lens) or len(lift_off) != len(lens) + 1 or len(words) != int(lift_off[-1]):
-                raise ValueError("kinds must have one entry per read, lift_off one more, words one row per 16-byte word")
-            lift = [kinds.ctypes.data, lift_off.ctypes.data, words.ctypes.data]
-        if mapq is not None:
-            mapq = np.ascontiguousarray(mapq, dtype=np.uint8)
-            if len(mapq) != len(lens):
-                raise ValueError("one MAPQ per read")
-        return seqs, lens, places, lift, mapq, (kinds, lift_off, words)  # (the last: kept alive behind the pointers in `lift`)
-
     def pile_records(self, seqs, lens, places, kinds=None, lift_off=None, words=None, mapq=None, min_mapq=0):
         """the same kernel on reads and records of the caller's, laid out as for md_records; mapq: one value per read in place of the records' own"""
-        seqs, lens, places, lift, mapq, _keep = self._pile_record_arrays(seqs, lens, places, kinds, lift_off, words, mapq)
+        seqs, lens, places, lift, mapq, _keep = self._record_arrays(seqs, lens, places, kinds, lift_off, words, mapq)
         _chk(lib().bwb_hip_pile_records(self._h, seqs.ctypes.data, lens.ctypes.data, seqs.shape[1], places.ctypes.data, len(lens), *lift,
                                         mapq.ctypes.data if mapq is not None else None, min_mapq))
 
@@ -735,7 +725,7 @@ class Context:
 
     def pile_records_q(self, seqs, quals, lens, places, kinds=None, lift_off=None, words=None, mapq=None, min_mapq=0, min_baseq=0, err_cap=0):
         """pile_records with the reads' quality bytes, laid out like seqs"""
-        seqs, lens, places, lift, mapq, _keep = self._pile_record_arrays(seqs, lens, places, kinds, lift_off, words, mapq)
+        seqs, lens, places, lift, mapq, _keep = self._record_arrays(seqs, lens, places, kinds, lift_off, words, mapq)
         quals = np.ascontiguousarray(quals, dtype=np.uint8)
         if quals.shape != seqs.shape:
             raise ValueError("quals must have the shape of seqs")

@@ -113,6 +113,14 @@ struct MdBufs {
 	PinMem h_recs, h_off, h_text;
 };
 
+/* a pile kernel's block of 64-bit sums (k_pile: reads, adds; k_pile_q: and the bases dropped), and the figures of its last call that launched */
+struct PileFigures {
+	DevMem d_stats; PinMem h_stats;
+	double ms = 0; uint64_t reads = 0, adds = 0, dropped = 0;
+	int begin(size_t bytes) { HIPCHK(d_stats.alloc(bytes)); HIPCHK(h_stats.reserve(bytes)); return BWB_OK; }
+	void zero() { ms = 0; reads = adds = dropped = 0; }
+};
+
 /* per-lane scratch of one class (class 0 = every resident lane, classes 1/2 = fewer lanes with larger lists) */
 struct ScratchClass {
 	DevMem mem;
@@ -224,13 +232,11 @@ struct bwb_hip_ctx {
 	DevMem d_text; uint64_t text_n = 0;           /* k_md_count / k_md: the forward text at 4 bits per character (bwb_hip_set_text; 0: none) */
 	MdBufs md_rec;                                /* bwb_hip_md_records */
 	double md_ms = 0; uint64_t md_reads = 0, md_bytes = 0; /* the last md call */
-	DevMem d_site_base, d_counts, d_pile_stats;   /* k_pile: the sites below every 16-byte word of the text, the n_sites x 4 counters, reads and adds of one launch (bwb_hip_pile_begin) */
-	PinMem h_pile_stats;
+	DevMem d_site_base, d_counts;                 /* k_pile: the sites below every 16-byte word of the text, the n_sites x 4 counters (bwb_hip_pile_begin) */
 	bool pile_on = false; uint64_t pile_sites = 0; /* pile_begin has run on this text; its sites */
-	double pile_ms = 0; uint64_t pile_reads = 0, pile_adds = 0; /* the last pile call that launched */
-	DevMem d_qsum, d_pileq_stats; PinMem h_pileq_stats; /* k_pile_q: the n_sites x 4 quality sums (weighted only), three sums of one launch (bwb_hip_pileq_begin) */
-	bool pileq_on = false, pileq_weighted = false;      /* pileq_begin has run behind this pile_begin: the slots keep quality bytes; qsum exists */
-	double pileq_ms = 0; uint64_t pileq_reads = 0, pileq_adds = 0, pileq_dropped = 0; /* the last pile_q call that launched */
+	DevMem d_qsum;                                /* k_pile_q: the n_sites x 4 quality sums (weighted only; bwb_hip_pileq_begin) */
+	bool pileq_on = false, pileq_weighted = false; /* pileq_begin has run behind this pile_begin: the slots keep quality bytes; qsum exists */
+	PileFigures pile_fig, pileq_fig;              /* the last plain pile call that launched (k_pile: 2 sums), the last pile_q call that launched (k_pile_q: 3) */
 	std::vector<bwb_bubble> loci_bubbles; std::vector<int32_t> chrom_of; /* the host's copies of set_loci's bubble table and set_bubble_chrom's records (bwb_hip_indel_begin) */
 	DevMem d_indel_tab, d_indel_elig, d_indel_counts, d_indel_stats; /* k_indel: the eligible bubbles sorted by (chrom_of, lo, bubble), one byte per bubble, the n_bub x 4 counters, three sums of one launch */
 	PinMem h_indel_stats;
@@ -2383,38 +2389,48 @@ extern "C" int bwb_hip_pile_begin(bwb_hip_ctx *c, uint64_t *n_sites) {
 	if (total > 0xFFFFFFFFull) { c->d_site_base.release(); return fail(BWB_E_ARG, "pile_begin: the text has more than 2^32 - 1 sites"); }
 	HIPCHK(c->d_counts.alloc((size_t)total * 16));
 	if (total) HIPCHK(hipMemsetAsync(c->d_counts.p, 0, (size_t)total * 16, c->rstream));
-	HIPCHK(c->d_pile_stats.alloc(16));
-	HIPCHK(c->h_pile_stats.reserve(16));
+	RC(c->pile_fig.begin(16));
 	HIPCHK(hipStreamSynchronize(c->rstream));
 	c->pile_on = true; c->pile_sites = total;
-	c->pile_ms = 0; c->pile_reads = 0; c->pile_adds = 0;
+	c->pile_fig.zero();
 	*n_sites = total;
 	return BWB_OK;
 }
 
-/* k_pile over n reads (reads, lengths, placement records, - d_kind NULL: none - lift records and - d_mapq NULL: the placement's own - one MAPQ
- * byte every mapq_stride bytes, all device memory) into the context's counters; sets pile_ms / pile_reads / pile_adds.  On the result stream,
- * behind the kernels that wrote the records; the grid of the md kernels, for their reason (a lane's walk is a chain of dependent loads).  What
- * comes back is the 16 bytes of the two sums. */
+/* the quality part of a pile call (k_pile_q); a null pointer to it is the plain form (k_pile) */
+struct PileQuals { const uint8_t *d_quals; int min_baseq, err_cap; };
+
+/* k_pile - with q, k_pile_q - over n reads (reads, lengths, placement records, - d_kind NULL: none - lift records and - d_mapq NULL: the placement's
+ * own - one MAPQ byte every mapq_stride bytes, all device memory) into the context's counters; sets the figures of its form, pile_fig or pileq_fig.
+ * On the result stream, behind the kernels that wrote the records; the grid of the md kernels, for their reason (a lane's walk is a chain of
+ * dependent loads).  What comes back is the 16 bytes of the two sums, or the 24 of the three. */
 static int pile_launch(bwb_hip_ctx *c, const uint8_t *d_reads, const uint16_t *d_lens, uint32_t stride, const uint4 *d_places, uint32_t n, const uint8_t *d_kind, const uint64_t *d_loff,
-                       const uint4 *d_lrecs, const uint8_t *d_mapq, uint32_t mapq_stride, int min_mapq) {
+                       const uint4 *d_lrecs, const uint8_t *d_mapq, uint32_t mapq_stride, int min_mapq, const PileQuals *q) {
 	if (!n) return BWB_OK; /* (nothing launched: the figures of the last launch stay) */
+	PileFigures &f = q ? c->pileq_fig : c->pile_fig;
+	const size_t bytes = q ? 24 : 16;
 	const uint32_t n_seq = d_kind ? c->loci_nseq : 0u;
-	HIPCHK(hipMemsetAsync(c->d_pile_stats.p, 0, 16, c->rstream));
+	HIPCHK(hipMemsetAsync(f.d_stats.p, 0, bytes, c->rstream));
 	Timed t(c, c->rstream);
 	RC(t.begin());
-	hipLaunchKernelGGL(k_pile, dim3(lane_grid(c, n)), dim3(BWB_BLOCK), 0, c->rstream, d_reads, d_lens, stride, d_places, n, d_kind, d_loff, d_lrecs, c->d_lstart.as<uint64_t>(), n_seq,
-	                   c->d_text.as<uint4>(), c->text_n, d_mapq, mapq_stride, (uint32_t)min_mapq, c->d_site_base.as<uint32_t>(), c->d_counts.as<uint32_t>(),
-	                   c->d_pile_stats.as<unsigned long long>());
+	if (q)
+		hipLaunchKernelGGL(k_pile_q, dim3(lane_grid(c, n)), dim3(BWB_BLOCK), 0, c->rstream, d_reads, q->d_quals, d_lens, stride, d_places, n, d_kind, d_loff, d_lrecs, c->d_lstart.as<uint64_t>(), n_seq,
+		                   c->d_text.as<uint4>(), c->text_n, d_mapq, mapq_stride, (uint32_t)min_mapq, (uint32_t)q->min_baseq, (uint32_t)q->err_cap, c->d_site_base.as<uint32_t>(),
+		                   c->d_counts.as<uint32_t>(), c->d_qsum.as<uint32_t>(), f.d_stats.as<unsigned long long>());
+	else
+		hipLaunchKernelGGL(k_pile, dim3(lane_grid(c, n)), dim3(BWB_BLOCK), 0, c->rstream, d_reads, d_lens, stride, d_places, n, d_kind, d_loff, d_lrecs, c->d_lstart.as<uint64_t>(), n_seq,
+		                   c->d_text.as<uint4>(), c->text_n, d_mapq, mapq_stride, (uint32_t)min_mapq, c->d_site_base.as<uint32_t>(), c->d_counts.as<uint32_t>(),
+		                   f.d_stats.as<unsigned long long>());
 	HIPCHK(hipGetLastError());
 	RC(t.end());
-	HIPCHK(hipMemcpyAsync(c->h_pile_stats.p, c->d_pile_stats.p, 16, hipMemcpyDeviceToHost, c->rstream));
+	HIPCHK(hipMemcpyAsync(f.h_stats.p, f.d_stats.p, bytes, hipMemcpyDeviceToHost, c->rstream));
 	HIPCHK(hipStreamSynchronize(c->rstream));
 	float ms = 0;
 	RC(t.ms(&ms));
-	c->pile_ms = ms;
-	c->pile_reads = c->h_pile_stats.as<uint64_t>()[0];
-	c->pile_adds = c->h_pile_stats.as<uint64_t>()[1];
+	f.ms = ms;
+	f.reads = f.h_stats.as<uint64_t>()[0];
+	f.adds = f.h_stats.as<uint64_t>()[1];
+	f.dropped = q ? f.h_stats.as<uint64_t>()[2] : 0;
 	return BWB_OK;
 }
 
@@ -2431,24 +2447,41 @@ static int pile_ready(bwb_hip_ctx *c, const char *who, int max_alt, int lifted, 
 	return BWB_OK;
 }
 
-extern "C" int bwb_hip_slot_pile(bwb_hip_ctx *c, int si, int max_mm, int max_alt, int lifted, int joined, int min_mapq, uint64_t *reads_counted) {
-	if (!c || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_pile: bad argument");
-	RC(pile_ready(c, "slot_pile", max_alt, lifted, joined, min_mapq));
+static int pileq_args(bwb_hip_ctx *c, const char *who, int min_baseq, int err_cap) {
+	if (min_baseq < 0 || min_baseq > 93) return fail(BWB_E_ARG, std::string(who) + ": min_baseq must be 0..93");
+	if (err_cap != 0 && (err_cap < 4 || err_cap > 93)) return fail(BWB_E_ARG, std::string(who) + ": err_cap must be 0 or 4..93");
+	if (!c->pile_on) return fail(BWB_E_STATE, std::string(who) + ": no site index and counters (bwb_hip_pile_begin)");
+	if (!c->pileq_on) return fail(BWB_E_STATE, std::string(who) + ": no quality buffers (bwb_hip_pileq_begin)");
+	if (err_cap && !c->pileq_weighted) return fail(BWB_E_STATE, std::string(who) + ": no quality sums (bwb_hip_pileq_begin with weighted != 0)");
+	return BWB_OK;
+}
+
+/* bwb_hip_slot_pile and, with q (its d_quals is set here, to the slot's), bwb_hip_slot_pile_q */
+static int slot_pile(bwb_hip_ctx *c, const char *who, int si, int max_mm, int max_alt, int lifted, int joined, int min_mapq, PileQuals *q, uint64_t *reads_counted) {
+	if (!c || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, std::string(who) + ": bad argument");
+	if (q) RC(pileq_args(c, who, q->min_baseq, q->err_cap));
+	RC(pile_ready(c, who, max_alt, lifted, joined, min_mapq));
 	if (reads_counted) *reads_counted = 0;
 	RC(ensure_place(c, si, max_mm));
 	Slot &s = c->slots[si];
-	if (s.stage.piled) return BWB_OK; /* (a submission is counted once) */
+	if (s.stage.piled) return BWB_OK; /* (a submission is counted once, by slot_pile or by slot_pile_q) */
+	if (q && !s.quals_set) return fail(BWB_E_STATE, std::string(who) + ": the slot's upload has no qualities (bwb_hip_slot_quals)");
 	if (lifted) RC(ensure_lift(c, si, max_mm, max_alt));
 	if (joined) RC(ensure_join(c, si, max_mm, max_alt));
 	const uint32_t n = s.n_reads; /* (not n_tot: a carried read that rides along behind the batch's reads has no record) */
 	if (n) {
-		HIPCHK(hipStreamWaitEvent(c->rstream, s.ev_up.e, 0)); /* (the slot's reads, uploaded on the copy stream) */
+		HIPCHK(hipStreamWaitEvent(c->rstream, s.ev_up.e, 0)); /* (the slot's reads and, with q, its qualities, uploaded on the copy stream) */
+		if (q) { HIPCHK(hipStreamWaitEvent(c->rstream, s.ev_quals.e, 0)); q->d_quals = s.d_quals.as<uint8_t>(); }
 		RC(pile_launch(c, s.d_reads.as<uint8_t>(), s.d_lens.as<uint16_t>(), s.stride, s.d_place.as<uint4>(), n, lifted ? s.lift.d_kind.as<uint8_t>() : nullptr,
-		               s.lift.d_off.as<uint64_t>(), s.lift.d_recs.as<uint4>(), joined ? s.d_join.as<uint8_t>() + offsetof(bwb_join, mapq) : nullptr, (uint32_t)sizeof(bwb_join), min_mapq));
-		if (reads_counted) *reads_counted = c->pile_reads;
+		               s.lift.d_off.as<uint64_t>(), s.lift.d_recs.as<uint4>(), joined ? s.d_join.as<uint8_t>() + offsetof(bwb_join, mapq) : nullptr, (uint32_t)sizeof(bwb_join), min_mapq, q));
+		if (reads_counted) *reads_counted = (q ? c->pileq_fig : c->pile_fig).reads;
 	}
 	s.stage.piled = true;
 	return BWB_OK;
+}
+
+extern "C" int bwb_hip_slot_pile(bwb_hip_ctx *c, int si, int max_mm, int max_alt, int lifted, int joined, int min_mapq, uint64_t *reads_counted) {
+	return slot_pile(c, "slot_pile", si, max_mm, max_alt, lifted, joined, min_mapq, nullptr, reads_counted);
 }
 
 extern "C" int bwb_hip_batch_pile(bwb_hip_ctx *c, int max_mm, int max_alt, int lifted, int joined, int min_mapq, uint64_t *reads_counted) {
@@ -2458,20 +2491,28 @@ extern "C" int bwb_hip_batch_pile(bwb_hip_ctx *c, int max_mm, int max_alt, int l
 	return bwb_hip_slot_pile(c, 0, max_mm, max_alt, lifted, joined, min_mapq, reads_counted);
 }
 
-/* the kernel on reads and records of the caller's instead of a slot's (for parity tests) */
-extern "C" int bwb_hip_pile_records(bwb_hip_ctx *c, const uint8_t *reads_fwd, const uint16_t *lens, uint32_t stride, const bwb_place *places, uint32_t n, const uint8_t *kinds,
-                                    const uint64_t *lift_off, const bwb_lift *lift_recs, const uint8_t *mapq, int min_mapq) {
-	if (!c || (n && (!reads_fwd || !lens || !places)) || n > 0x7FFFFFFFu || stride < 1 || stride > 255) return fail(BWB_E_ARG, "pile_records: bad argument");
-	if ((kinds != nullptr) != (lift_off != nullptr)) return fail(BWB_E_ARG, "pile_records: the lift kinds and offsets come together");
-	if (min_mapq < 0 || min_mapq > 255) return fail(BWB_E_ARG, "pile_records: min_mapq must be 0..255");
-	if (!c->pile_on) return fail(BWB_E_STATE, "pile_records: no site index and counters (bwb_hip_pile_begin)");
+/* the kernel on reads and records of the caller's instead of a slot's (for parity tests): bwb_hip_pile_records and, with q and the caller's quality
+ * bytes (staged here: its d_quals is set to them; needs no slot_quals), bwb_hip_pile_records_q */
+static int pile_records(bwb_hip_ctx *c, const char *who, const uint8_t *reads_fwd, const uint8_t *quals, const uint16_t *lens, uint32_t stride, const bwb_place *places, uint32_t n,
+                        const uint8_t *kinds, const uint64_t *lift_off, const bwb_lift *lift_recs, const uint8_t *mapq, int min_mapq, PileQuals *q) {
+	if (!c || (n && (!reads_fwd || (q && !quals) || !lens || !places)) || n > 0x7FFFFFFFu || stride < 1 || stride > 255) return fail(BWB_E_ARG, std::string(who) + ": bad argument");
+	if ((kinds != nullptr) != (lift_off != nullptr)) return fail(BWB_E_ARG, std::string(who) + ": the lift kinds and offsets come together");
+	if (min_mapq < 0 || min_mapq > 255) return fail(BWB_E_ARG, std::string(who) + ": min_mapq must be 0..255");
+	if (q) RC(pileq_args(c, who, q->min_baseq, q->err_cap));
+	else if (!c->pile_on) return fail(BWB_E_STATE, std::string(who) + ": no site index and counters (bwb_hip_pile_begin)");
 	StagedReads in;
-	DevMem d_mapq; /* (stays NULL without a MAPQ array, and without reads) */
-	RC(stage_reads(c, "pile_records", reads_fwd, lens, stride, places, n, kinds, lift_off, lift_recs, in));
+	DevMem d_mapq, d_quals; /* (d_mapq stays NULL without a MAPQ array, and without reads) */
+	RC(stage_reads(c, who, reads_fwd, lens, stride, places, n, kinds, lift_off, lift_recs, in));
+	if (q) { RC(stage_in(c, d_quals, quals, (size_t)n * stride)); q->d_quals = d_quals.as<uint8_t>(); }
 	if (mapq && n) RC(stage_in(c, d_mapq, mapq, (size_t)n));
 	HIPCHK(hipStreamSynchronize(c->rstream));
 	return pile_launch(c, in.reads.as<uint8_t>(), in.lens.as<uint16_t>(), stride, in.places.as<uint4>(), n, in.kind.as<uint8_t>(), in.loff.as<uint64_t>(), in.lrecs.as<uint4>(),
-	                   d_mapq.as<uint8_t>(), 1u, min_mapq);
+	                   d_mapq.as<uint8_t>(), 1u, min_mapq, q);
+}
+
+extern "C" int bwb_hip_pile_records(bwb_hip_ctx *c, const uint8_t *reads_fwd, const uint16_t *lens, uint32_t stride, const bwb_place *places, uint32_t n, const uint8_t *kinds,
+                                    const uint64_t *lift_off, const bwb_lift *lift_recs, const uint8_t *mapq, int min_mapq) {
+	return pile_records(c, "pile_records", reads_fwd, nullptr, lens, stride, places, n, kinds, lift_off, lift_recs, mapq, min_mapq, nullptr);
 }
 
 /* The two counter tables, four 32-bit counters per entry: the sites' (pile_begin) and the bubbles' (indel_begin).  What the counts / put / reset calls
@@ -2531,9 +2572,9 @@ extern "C" int bwb_hip_pile_site_of(bwb_hip_ctx *c, const uint64_t *pos, size_t 
 /* the last pile call that launched: reads counted, adds made, and the kernel's HIP-event time */
 extern "C" int bwb_hip_pile_stats(bwb_hip_ctx *c, uint64_t *reads, uint64_t *adds, double *kernel_ms) {
 	if (!c) return fail(BWB_E_ARG, "pile_stats: null context");
-	if (reads) *reads = c->pile_reads;
-	if (adds) *adds = c->pile_adds;
-	if (kernel_ms) *kernel_ms = c->pile_ms;
+	if (reads) *reads = c->pile_fig.reads;
+	if (adds) *adds = c->pile_fig.adds;
+	if (kernel_ms) *kernel_ms = c->pile_fig.ms;
 	return BWB_OK;
 }
 
@@ -2549,11 +2590,10 @@ extern "C" int bwb_hip_pileq_begin(bwb_hip_ctx *c, int weighted) {
 		HIPCHK(c->d_qsum.alloc((size_t)c->pile_sites * 16));
 		if (c->pile_sites) HIPCHK(hipMemsetAsync(c->d_qsum.p, 0, (size_t)c->pile_sites * 16, c->rstream));
 	}
-	HIPCHK(c->d_pileq_stats.alloc(24));
-	HIPCHK(c->h_pileq_stats.reserve(24));
+	RC(c->pileq_fig.begin(24));
 	HIPCHK(hipStreamSynchronize(c->rstream));
 	c->pileq_on = true; c->pileq_weighted = weighted != 0;
-	c->pileq_ms = 0; c->pileq_reads = 0; c->pileq_adds = 0; c->pileq_dropped = 0;
+	c->pileq_fig.zero();
 	return BWB_OK;
 }
 
@@ -2580,62 +2620,9 @@ extern "C" int bwb_hip_slot_quals(bwb_hip_ctx *c, int si, const uint8_t *quals, 
 	return BWB_OK;
 }
 
-static int pileq_args(bwb_hip_ctx *c, const char *who, int min_baseq, int err_cap) {
-	if (min_baseq < 0 || min_baseq > 93) return fail(BWB_E_ARG, std::string(who) + ": min_baseq must be 0..93");
-	if (err_cap != 0 && (err_cap < 4 || err_cap > 93)) return fail(BWB_E_ARG, std::string(who) + ": err_cap must be 0 or 4..93");
-	if (!c->pile_on) return fail(BWB_E_STATE, std::string(who) + ": no site index and counters (bwb_hip_pile_begin)");
-	if (!c->pileq_on) return fail(BWB_E_STATE, std::string(who) + ": no quality buffers (bwb_hip_pileq_begin)");
-	if (err_cap && !c->pileq_weighted) return fail(BWB_E_STATE, std::string(who) + ": no quality sums (bwb_hip_pileq_begin with weighted != 0)");
-	return BWB_OK;
-}
-
-/* pile_launch with k_pile_q: d_quals beside d_reads; sets pileq_ms / pileq_reads / pileq_adds / pileq_dropped.  What comes back is the 24 bytes of
- * the three sums. */
-static int pileq_launch(bwb_hip_ctx *c, const uint8_t *d_reads, const uint8_t *d_quals, const uint16_t *d_lens, uint32_t stride, const uint4 *d_places, uint32_t n, const uint8_t *d_kind,
-                        const uint64_t *d_loff, const uint4 *d_lrecs, const uint8_t *d_mapq, uint32_t mapq_stride, int min_mapq, int min_baseq, int err_cap) {
-	if (!n) return BWB_OK; /* (nothing launched: the figures of the last launch stay) */
-	const uint32_t n_seq = d_kind ? c->loci_nseq : 0u;
-	HIPCHK(hipMemsetAsync(c->d_pileq_stats.p, 0, 24, c->rstream));
-	Timed t(c, c->rstream);
-	RC(t.begin());
-	hipLaunchKernelGGL(k_pile_q, dim3(lane_grid(c, n)), dim3(BWB_BLOCK), 0, c->rstream, d_reads, d_quals, d_lens, stride, d_places, n, d_kind, d_loff, d_lrecs, c->d_lstart.as<uint64_t>(), n_seq,
-	                   c->d_text.as<uint4>(), c->text_n, d_mapq, mapq_stride, (uint32_t)min_mapq, (uint32_t)min_baseq, (uint32_t)err_cap, c->d_site_base.as<uint32_t>(),
-	                   c->d_counts.as<uint32_t>(), c->d_qsum.as<uint32_t>(), c->d_pileq_stats.as<unsigned long long>());
-	HIPCHK(hipGetLastError());
-	RC(t.end());
-	HIPCHK(hipMemcpyAsync(c->h_pileq_stats.p, c->d_pileq_stats.p, 24, hipMemcpyDeviceToHost, c->rstream));
-	HIPCHK(hipStreamSynchronize(c->rstream));
-	float ms = 0;
-	RC(t.ms(&ms));
-	c->pileq_ms = ms;
-	c->pileq_reads = c->h_pileq_stats.as<uint64_t>()[0];
-	c->pileq_adds = c->h_pileq_stats.as<uint64_t>()[1];
-	c->pileq_dropped = c->h_pileq_stats.as<uint64_t>()[2];
-	return BWB_OK;
-}
-
 extern "C" int bwb_hip_slot_pile_q(bwb_hip_ctx *c, int si, int max_mm, int max_alt, int lifted, int joined, int min_mapq, int min_baseq, int err_cap, uint64_t *reads_counted) {
-	if (!c || si < 0 || si >= BWB_MAX_SLOTS) return fail(BWB_E_ARG, "slot_pile_q: bad argument");
-	RC(pileq_args(c, "slot_pile_q", min_baseq, err_cap));
-	RC(pile_ready(c, "slot_pile_q", max_alt, lifted, joined, min_mapq));
-	if (reads_counted) *reads_counted = 0;
-	RC(ensure_place(c, si, max_mm));
-	Slot &s = c->slots[si];
-	if (s.stage.piled) return BWB_OK; /* (a submission is counted once, by slot_pile or by slot_pile_q) */
-	if (!s.quals_set) return fail(BWB_E_STATE, "slot_pile_q: the slot's upload has no qualities (bwb_hip_slot_quals)");
-	if (lifted) RC(ensure_lift(c, si, max_mm, max_alt));
-	if (joined) RC(ensure_join(c, si, max_mm, max_alt));
-	const uint32_t n = s.n_reads; /* (not n_tot: a carried read that rides along behind the batch's reads has no record) */
-	if (n) {
-		HIPCHK(hipStreamWaitEvent(c->rstream, s.ev_up.e, 0));    /* (the slot's reads and */
-		HIPCHK(hipStreamWaitEvent(c->rstream, s.ev_quals.e, 0)); /* qualities, uploaded on the copy stream) */
-		RC(pileq_launch(c, s.d_reads.as<uint8_t>(), s.d_quals.as<uint8_t>(), s.d_lens.as<uint16_t>(), s.stride, s.d_place.as<uint4>(), n, lifted ? s.lift.d_kind.as<uint8_t>() : nullptr,
-		                s.lift.d_off.as<uint64_t>(), s.lift.d_recs.as<uint4>(), joined ? s.d_join.as<uint8_t>() + offsetof(bwb_join, mapq) : nullptr, (uint32_t)sizeof(bwb_join), min_mapq,
-		                min_baseq, err_cap));
-		if (reads_counted) *reads_counted = c->pileq_reads;
-	}
-	s.stage.piled = true;
-	return BWB_OK;
+	PileQuals q = { nullptr, min_baseq, err_cap };
+	return slot_pile(c, "slot_pile_q", si, max_mm, max_alt, lifted, joined, min_mapq, &q, reads_counted);
 }
 
 extern "C" int bwb_hip_batch_pile_q(bwb_hip_ctx *c, int max_mm, int max_alt, int lifted, int joined, int min_mapq, int min_baseq, int err_cap, uint64_t *reads_counted) {
@@ -2646,21 +2633,10 @@ extern "C" int bwb_hip_batch_pile_q(bwb_hip_ctx *c, int max_mm, int max_alt, int
 	return bwb_hip_slot_pile_q(c, 0, max_mm, max_alt, lifted, joined, min_mapq, min_baseq, err_cap, reads_counted);
 }
 
-/* the kernel on reads, qualities and records of the caller's instead of a slot's (for parity tests); needs no slot_quals */
 extern "C" int bwb_hip_pile_records_q(bwb_hip_ctx *c, const uint8_t *reads_fwd, const uint8_t *quals, const uint16_t *lens, uint32_t stride, const bwb_place *places, uint32_t n,
                                       const uint8_t *kinds, const uint64_t *lift_off, const bwb_lift *lift_recs, const uint8_t *mapq, int min_mapq, int min_baseq, int err_cap) {
-	if (!c || (n && (!reads_fwd || !quals || !lens || !places)) || n > 0x7FFFFFFFu || stride < 1 || stride > 255) return fail(BWB_E_ARG, "pile_records_q: bad argument");
-	if ((kinds != nullptr) != (lift_off != nullptr)) return fail(BWB_E_ARG, "pile_records_q: the lift kinds and offsets come together");
-	if (min_mapq < 0 || min_mapq > 255) return fail(BWB_E_ARG, "pile_records_q: min_mapq must be 0..255");
-	RC(pileq_args(c, "pile_records_q", min_baseq, err_cap));
-	StagedReads in;
-	DevMem d_mapq, d_quals; /* (d_mapq stays NULL without a MAPQ array, and without reads) */
-	RC(stage_reads(c, "pile_records_q", reads_fwd, lens, stride, places, n, kinds, lift_off, lift_recs, in));
-	RC(stage_in(c, d_quals, quals, (size_t)n * stride));
-	if (mapq && n) RC(stage_in(c, d_mapq, mapq, (size_t)n));
-	HIPCHK(hipStreamSynchronize(c->rstream));
-	return pileq_launch(c, in.reads.as<uint8_t>(), d_quals.as<uint8_t>(), in.lens.as<uint16_t>(), stride, in.places.as<uint4>(), n, in.kind.as<uint8_t>(), in.loff.as<uint64_t>(),
-	                    in.lrecs.as<uint4>(), d_mapq.as<uint8_t>(), 1u, min_mapq, min_baseq, err_cap);
+	PileQuals q = { nullptr, min_baseq, err_cap };
+	return pile_records(c, "pile_records_q", reads_fwd, quals, lens, stride, places, n, kinds, lift_off, lift_recs, mapq, min_mapq, &q);
 }
 
 extern "C" int bwb_hip_pileq_sums(bwb_hip_ctx *c, uint64_t first, uint64_t n, uint32_t *out) {
@@ -2675,10 +2651,10 @@ extern "C" int bwb_hip_pileq_put(bwb_hip_ctx *c, uint64_t first, uint64_t n, con
 /* the last pile_q call that launched: reads counted, adds made, bases dropped by min_baseq, and the kernel's HIP-event time */
 extern "C" int bwb_hip_pileq_stats(bwb_hip_ctx *c, uint64_t *reads, uint64_t *adds, uint64_t *dropped, double *kernel_ms) {
 	if (!c) return fail(BWB_E_ARG, "pileq_stats: null context");
-	if (reads) *reads = c->pileq_reads;
-	if (adds) *adds = c->pileq_adds;
-	if (dropped) *dropped = c->pileq_dropped;
-	if (kernel_ms) *kernel_ms = c->pileq_ms;
+	if (reads) *reads = c->pileq_fig.reads;
+	if (adds) *adds = c->pileq_fig.adds;
+	if (dropped) *dropped = c->pileq_fig.dropped;
+	if (kernel_ms) *kernel_ms = c->pileq_fig.ms;
 	return BWB_OK;
 }
 

@@ -970,9 +970,26 @@ __device__ __forceinline__ MdRead md_read(uint32_t q, const uint4 *places, const
 __device__ __forceinline__ uint32_t md_rec_op(const uint4 *rec, uint32_t i) {
 	return ((const uint32_t *)(rec + 1))[i];
 }
-__device__ __forceinline__ void md_walk(MdWalk &m, const MdRead &v) {
-	if (v.lifted) for (uint32_t i = 0; i < v.n_ops; i++) { const uint32_t op = md_rec_op(v.rec, i); m.step(op & 15u, op >> 4); }
-	else for (uint32_t t = 0; t < v.alen; t++) m.step(lift_op_at(v.runs, v.alen, v.reverse, t), 1u);
+/* the read's ops in order, f(op, count): the words of its lift record, or its printed CIGAR one text position at a time */
+template <typename F> __device__ __forceinline__ void md_ops(const MdRead &v, F &&f) {
+	if (v.lifted) for (uint32_t i = 0; i < v.n_ops; i++) { const uint32_t op = md_rec_op(v.rec, i); f(op & 15u, op >> 4); }
+	else for (uint32_t t = 0; t < v.alen; t++) f(lift_op_at(v.runs, v.alen, v.reverse, t), 1u);
+}
+/* the walker's step (MdWalk, PileWalk<Q>) over the read's ops */
+template <typename W> __device__ __forceinline__ void md_walk(W &m, const MdRead &v) {
+	md_ops(v, [&](uint32_t op, uint32_t count) { m.step(op, count); });
+}
+/* May read v be walked?  The gate of every kernel that walks (k_md_count writes the kind, k_md walks the reads it left MD_OK, the pile kernels
+ * count exactly those): a mapped read of at most 255 bases that fits the slot's stride, whose ops - the span on the text and the read bases they
+ * consume - stay within MD_MAX_SPAN, within [0, n_fwd) from the start, and consume the read exactly.  Nothing of the text or the read is fetched
+ * here; a read that is not MD_OK has none of either fetched by anybody. */
+__device__ __forceinline__ uint32_t md_gate(const MdRead &v, uint32_t len, uint32_t stride, uint64_t n_fwd) {
+	if (!(v.mapped && len <= 255u && len <= stride)) return MD_NONE;
+	uint64_t span = 0, on_read = 0;
+	md_ops(v, [&](uint32_t op, uint32_t count) { if (op == 0u || op == 2u) span += count; if (op != 2u) on_read += count; });
+	/* (the kind as two selects, not a return per kind: that form cost the pile kernels registers) */
+	const bool fits = v.start >= 0 && (uint64_t)v.start <= n_fwd && span <= n_fwd - (uint64_t)v.start && on_read == len;
+	return span > MD_MAX_SPAN ? MD_TOO_LONG : fits ? MD_OK : MD_NONE;
 }
 __device__ __forceinline__ MdWalk md_begin(const uint4 *text, const uint8_t *seq, uint32_t len, const MdRead &v, char *dst, uint32_t cap) {
 	MdWalk m;
@@ -989,19 +1006,13 @@ __global__ __launch_bounds__(BWB_BLOCK) void k_md_count(const uint8_t *reads, co
 	for (uint32_t q = blockIdx.x * BWB_BLOCK + threadIdx.x; q < n_reads; q += gstride) {
 		const MdRead v = md_read(q, places, lift_kind, lift_off, lift_recs, lstart, n_seq);
 		const uint32_t len = lens[q];
-		uint32_t kind = MD_NONE, nm = 0, bytes = 0;
-		if (v.mapped && len <= 255u && len <= stride) {
-			/* the span on the text and the read bases the ops consume */
-			uint64_t span = 0, on_read = 0;
-			if (v.lifted) for (uint32_t i = 0; i < v.n_ops; i++) { const uint32_t op = md_rec_op(v.rec, i); if ((op & 15u) == 0u || (op & 15u) == 2u) span += op >> 4; if ((op & 15u) != 2u) on_read += op >> 4; }
-			else for (uint32_t t = 0; t < v.alen; t++) { const uint32_t op = lift_op_at(v.runs, v.alen, v.reverse, t); span += op != 1u; on_read += op != 2u; }
-			if (span > MD_MAX_SPAN) kind = MD_TOO_LONG;
-			else if (v.start >= 0 && (uint64_t)v.start <= n_fwd && span <= n_fwd - (uint64_t)v.start && on_read == len) {
-				MdWalk m = md_begin(text, reads + (size_t)q * stride, len, v, nullptr, 0u);
-				md_walk(m, v);
-				m.number(m.run);
-				kind = MD_OK; nm = m.mm + m.gaps; bytes = m.n;
-			}
+		const uint32_t kind = md_gate(v, len, stride, n_fwd);
+		uint32_t nm = 0, bytes = 0;
+		if (kind == MD_OK) {
+			MdWalk m = md_begin(text, reads + (size_t)q * stride, len, v, nullptr, 0u);
+			md_walk(m, v);
+			m.number(m.run);
+			nm = m.mm + m.gaps; bytes = m.n;
 		}
 		recs[q] = make_uint2(nm, bytes | (kind << 16));
 		md_len[q] = bytes;
@@ -1069,91 +1080,57 @@ __global__ __launch_bounds__(BWB_BLOCK) void k_site_of(const uint4 *text, const 
 	}
 }
 
-/* k_pile: one lane per READ, grid-strided; the walk of k_md_count - md_read, the same ops from the same start, the same span and length checks,
- * the text in 16-byte words held in registers - with one add where k_md compares: for every M base that lies on a site and is A, C, G or T,
- * counts[site * 4 + column] += 1, the columns A, C, G, T by the letter SAM prints.  The site mask is computed once per word held; site_base[] is
- * loaded only when a base falls on a site, and the read base only then.  A read counts when its kind would be BWB_MD_OK and its MAPQ - the
- * placement's, or mapq[q * mapq_stride] (the join record's, or the caller's override) - is at least min_mapq.  The adds are relaxed, agent-scope
- * atomics to scattered counters (a site sees about as many adds per run as the coverage: no aggregation ahead of them); the reads counted and
- * the adds made are summed over the block - shuffles, then LDS - and added to stats[0] / stats[1] once per block.  Every text position fetched
- * lies in [0, n_fwd), every read base in [0, len), every site number below n_sites (the index was built from this text). */
-struct PileWalk {
-	const uint4 *text; uint64_t cur; uint4 w; uint32_t mask;  /* the packed text, the word held and its site mask */
-	const uint32_t *site_base; uint32_t *counts;
-	const uint8_t *seq; uint32_t len; bool reverse;
-	uint32_t ri, adds; uint64_t tp;
-	__device__ __forceinline__ void step(uint32_t op, uint32_t count) { /* op: 0 M, 1 I, 2 D, 4 S */
-		if (op == 0u) {
-			for (uint32_t k = 0; k < count; k++, ri++, tp++) {
-				const uint64_t wi = tp >> 5;
-				if (wi != cur) { w = text[wi]; cur = wi; mask = site_mask32(w); }
-				const uint32_t at = (uint32_t)tp & 31u;
-				if (!((mask >> at) & 1u)) continue;
-				const uint32_t c = reverse ? seq[len - 1u - ri] : seq[ri];
-				if (c > 3u) continue; /* a read N */
-				const uint32_t b = reverse ? 3u - c : c; /* A0 G1 C2 T3 as printed */
-				const uint32_t col = (b == 1u || b == 2u) ? 3u - b : b; /* A C G T */
-				const uint64_t site = (uint64_t)site_base[wi] + (uint32_t)__popc(mask & ((1u << at) - 1u));
-				__hip_atomic_fetch_add(counts + site * 4u + col, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-				adds++;
-			}
-		} else if (op == 2u) tp += count;
-		else ri += count;
-	}
-};
-__global__ __launch_bounds__(BWB_BLOCK) void k_pile(const uint8_t *reads, const uint16_t *lens, uint32_t stride, const uint4 *places, uint32_t n_reads, const uint8_t *lift_kind,
-                                                     const uint64_t *lift_off, const uint4 *lift_recs, const uint64_t *lstart, uint32_t n_seq, const uint4 *text, uint64_t n_fwd,
-                                                     const uint8_t *mapq, uint32_t mapq_stride, uint32_t min_mapq, const uint32_t *site_base, uint32_t *counts,
-                                                     unsigned long long *stats) {
-	__shared__ unsigned long long s_sum[2][BWB_BLOCK / 64];
-	const uint32_t gstride = gridDim.x * BWB_BLOCK;
-	unsigned long long my_reads = 0, my_adds = 0;
-	for (uint32_t q = blockIdx.x * BWB_BLOCK + threadIdx.x; q < n_reads; q += gstride) {
-		const MdRead v = md_read(q, places, lift_kind, lift_off, lift_recs, lstart, n_seq);
-		const uint32_t len = lens[q];
-		if (!(v.mapped && len <= 255u && len <= stride)) continue;
-		const uint32_t mq = mapq ? mapq[(size_t)q * mapq_stride] : (places[(size_t)q * 3 + 1].x >> 16) & 0xFFu;
-		if (mq < min_mapq) continue;
-		uint64_t span = 0, on_read = 0;
-		if (v.lifted) for (uint32_t i = 0; i < v.n_ops; i++) { const uint32_t op = md_rec_op(v.rec, i); if ((op & 15u) == 0u || (op & 15u) == 2u) span += op >> 4; if ((op & 15u) != 2u) on_read += op >> 4; }
-		else for (uint32_t t = 0; t < v.alen; t++) { const uint32_t op = lift_op_at(v.runs, v.alen, v.reverse, t); span += op != 1u; on_read += op != 2u; }
-		if (span > MD_MAX_SPAN || v.start < 0 || (uint64_t)v.start > n_fwd || span > n_fwd - (uint64_t)v.start || on_read != len) continue;
-		PileWalk m;
-		m.text = text; m.cur = ~0ull; m.w = make_uint4(0u, 0u, 0u, 0u); m.mask = 0u;
-		m.site_base = site_base; m.counts = counts;
-		m.seq = reads + (size_t)q * stride; m.len = len; m.reverse = v.reverse;
-		m.ri = 0; m.adds = 0; m.tp = (uint64_t)v.start;
-		if (v.lifted) for (uint32_t i = 0; i < v.n_ops; i++) { const uint32_t op = md_rec_op(v.rec, i); m.step(op & 15u, op >> 4); }
-		else for (uint32_t t = 0; t < v.alen; t++) m.step(lift_op_at(v.runs, v.alen, v.reverse, t), 1u);
-		my_reads++; my_adds += m.adds;
-	}
-	/* (every thread of the block gets here: the loop has no barrier inside) */
+/* The block's sums of N per-lane figures, added to stats[0 .. N) once per block: shuffles over the wave's 64 lanes, the waves' sums through LDS
+ * (N * BWB_BLOCK / 64 * 8 bytes), then thread 0 adds what is not zero.  EVERY thread of the block must get here - there is a barrier inside -,
+ * so the callers' loops have no barrier, return or break past it: they fall through to this call. */
+template <int N> __device__ __forceinline__ void block_sums_to(unsigned long long (&mine)[N], unsigned long long *stats) {
+	__shared__ unsigned long long s_sum[N][BWB_BLOCK / 64];
 #pragma unroll
-	for (int d = 32; d > 0; d >>= 1) { my_reads += __shfl_down(my_reads, d); my_adds += __shfl_down(my_adds, d); }
-	if ((threadIdx.x & 63) == 0) { s_sum[0][threadIdx.x >> 6] = my_reads; s_sum[1][threadIdx.x >> 6] = my_adds; }
+	for (int d = 32; d > 0; d >>= 1) {
+#pragma unroll
+		for (int k = 0; k < N; k++) mine[k] += __shfl_down(mine[k], d);
+	}
+	if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+		for (int k = 0; k < N; k++) s_sum[k][threadIdx.x >> 6] = mine[k];
+	}
 	__syncthreads();
 	if (threadIdx.x == 0) {
-		unsigned long long r = 0, a = 0;
+		unsigned long long sum[N];
 #pragma unroll
-		for (int k = 0; k < BWB_BLOCK / 64; k++) { r += s_sum[0][k]; a += s_sum[1][k]; }
-		if (r) atomicAdd(stats, r);
-		if (a) atomicAdd(stats + 1, a);
+		for (int k = 0; k < N; k++) sum[k] = 0;
+#pragma unroll
+		for (int i = 0; i < BWB_BLOCK / 64; i++) {
+#pragma unroll
+			for (int k = 0; k < N; k++) sum[k] += s_sum[k][i];
+		}
+#pragma unroll
+		for (int k = 0; k < N; k++) if (sum[k]) atomicAdd(stats + k, sum[k]);
 	}
 }
 
-/* k_pile_q (`map -b / -Y`): k_pile with the base qualities - the rule is in include/bwbble_hip.h (bwb_hip_pileq_begin).  The same lanes, md_read,
- * checks and walk; quals holds one byte per base in FASTQ order, strided like the reads, and a base's byte is the one at the read base's own
- * index (len - 1 - ri on the reverse strand), loaded only when the base falls on a site and is no N.  Q = 0 below '!', else min(byte - 33, 93).
- * A base with Q < min_baseq is dropped: no add, counted in `dropped`.  err_cap != 0 (4..93, then qsum is a table like counts): the base also adds
- * min(max(Q, 4), err_cap) to qsum at the counter's index.  Both adds are relaxed agent-scope atomics.  Reads, adds and dropped bases go to
- * stats[0..2] once per block.  Bounds as in k_pile; the quality byte's index is the read base's. */
+/* k_pile, k_pile_q: one lane per READ, grid-strided; the walk of k_md_count - md_read, md_gate, the same ops from the same start, the text in
+ * 16-byte words held in registers - with one add where k_md compares: for every M base that lies on a site and is A, C, G or T,
+ * counts[site * 4 + column] += 1, the columns A, C, G, T by the letter SAM prints.  The site mask is computed once per word held; site_base[] is
+ * loaded only when a base falls on a site, and the read base only then.  A read counts when its kind is BWB_MD_OK (md_gate) and its MAPQ - the
+ * placement's, or mapq[q * mapq_stride] (the join record's, or the caller's override) - is at least min_mapq; the MAPQ is tested ahead of the
+ * gate, so a filtered read costs no op decoding.  The adds are relaxed, agent-scope atomics to scattered counters (a site sees about as many
+ * adds per run as the coverage: no aggregation ahead of them); the reads counted and the adds made go to stats[0] / stats[1] once per block
+ * (block_sums_to).  Every text position fetched lies in [0, n_fwd), every read base in [0, len), every site number below n_sites (the index was
+ * built from this text).
+ * Q, k_pile_q (`map -b / -Y`): with the base qualities - the rule is in include/bwbble_hip.h (bwb_hip_pileq_begin).  quals holds one byte per
+ * base in FASTQ order, strided like the reads, and a base's byte is the one at the read base's own index (len - 1 - ri on the reverse strand),
+ * loaded only when the base falls on a site and is no N.  Q = 0 below '!', else min(byte - 33, 93).  A base with Q < min_baseq is dropped: no
+ * add, counted in `dropped`, which goes to stats[2].  err_cap != 0 (4..93, then qsum is a table like counts): the base also adds
+ * min(max(Q, 4), err_cap) to qsum at the counter's index, the same kind of atomic.  Q is a template argument and the two kernels two entry
+ * points, not a flag read at run time: k_pile keeps its registers (69 VGPRs, 7 waves per SIMD; k_pile_q 74 and 6). */
 #define PILEQ_MAX_Q 93u
 #define PILEQ_MIN_W 4u
-struct PileWalkQ {
-	const uint4 *text; uint64_t cur; uint4 w; uint32_t mask;
+template <bool Q> struct PileWalk {
+	const uint4 *text; uint64_t cur; uint4 w; uint32_t mask;  /* the packed text, the word held and its site mask */
 	const uint32_t *site_base; uint32_t *counts, *qsum;
 	const uint8_t *seq, *qual; uint32_t len; bool reverse;
-	uint32_t min_baseq, err_cap;
+	uint32_t min_baseq, err_cap;                              /* (qsum, qual and these two: Q only) */
 	uint32_t ri, adds, dropped; uint64_t tp;
 	__device__ __forceinline__ void step(uint32_t op, uint32_t count) { /* op: 0 M, 1 I, 2 D, 4 S */
 		if (op == 0u) {
@@ -1165,16 +1142,21 @@ struct PileWalkQ {
 				const uint32_t idx = reverse ? len - 1u - ri : ri;
 				const uint32_t c = seq[idx];
 				if (c > 3u) continue; /* a read N */
-				const uint32_t qc = qual[idx];
-				const uint32_t Q = qc < 33u ? 0u : (qc - 33u > PILEQ_MAX_Q ? PILEQ_MAX_Q : qc - 33u);
-				if (Q < min_baseq) { dropped++; continue; }
+				uint32_t qv = 0;
+				if constexpr (Q) {
+					const uint32_t qc = qual[idx];
+					qv = qc < 33u ? 0u : (qc - 33u > PILEQ_MAX_Q ? PILEQ_MAX_Q : qc - 33u);
+					if (qv < min_baseq) { dropped++; continue; }
+				}
 				const uint32_t b = reverse ? 3u - c : c; /* A0 G1 C2 T3 as printed */
 				const uint32_t col = (b == 1u || b == 2u) ? 3u - b : b; /* A C G T */
 				const uint64_t site = (uint64_t)site_base[wi] + (uint32_t)__popc(mask & ((1u << at) - 1u));
 				__hip_atomic_fetch_add(counts + site * 4u + col, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-				if (err_cap) {
-					const uint32_t lo = Q < PILEQ_MIN_W ? PILEQ_MIN_W : Q;
-					__hip_atomic_fetch_add(qsum + site * 4u + col, lo > err_cap ? err_cap : lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+				if constexpr (Q) {
+					if (err_cap) {
+						const uint32_t lo = qv < PILEQ_MIN_W ? PILEQ_MIN_W : qv;
+						__hip_atomic_fetch_add(qsum + site * 4u + col, lo > err_cap ? err_cap : lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+					}
 				}
 				adds++;
 			}
@@ -1182,46 +1164,43 @@ struct PileWalkQ {
 		else ri += count;
 	}
 };
+template <bool Q> __device__ __forceinline__ void pile_body(const uint8_t *reads, const uint8_t *quals, const uint16_t *lens, uint32_t stride, const uint4 *places, uint32_t n_reads,
+                                                            const uint8_t *lift_kind, const uint64_t *lift_off, const uint4 *lift_recs, const uint64_t *lstart, uint32_t n_seq,
+                                                            const uint4 *text, uint64_t n_fwd, const uint8_t *mapq, uint32_t mapq_stride, uint32_t min_mapq, uint32_t min_baseq,
+                                                            uint32_t err_cap, const uint32_t *site_base, uint32_t *counts, uint32_t *qsum, unsigned long long *stats) {
+	const uint32_t gstride = gridDim.x * BWB_BLOCK;
+	unsigned long long mine[Q ? 3 : 2] = {}; /* reads, adds, and with Q the bases dropped */
+	for (uint32_t q = blockIdx.x * BWB_BLOCK + threadIdx.x; q < n_reads; q += gstride) {
+		const MdRead v = md_read(q, places, lift_kind, lift_off, lift_recs, lstart, n_seq);
+		const uint32_t mq = mapq ? mapq[(size_t)q * mapq_stride] : (places[(size_t)q * 3 + 1].x >> 16) & 0xFFu;
+		if (mq < min_mapq) continue;
+		const uint32_t len = lens[q];
+		if (md_gate(v, len, stride, n_fwd) != MD_OK) continue;
+		PileWalk<Q> m;
+		m.text = text; m.cur = ~0ull; m.w = make_uint4(0u, 0u, 0u, 0u); m.mask = 0u;
+		m.site_base = site_base; m.counts = counts; m.qsum = qsum;
+		m.seq = reads + (size_t)q * stride; m.qual = Q ? quals + (size_t)q * stride : nullptr; m.len = len; m.reverse = v.reverse;
+		m.min_baseq = min_baseq; m.err_cap = err_cap;
+		m.ri = 0; m.adds = 0; m.dropped = 0; m.tp = (uint64_t)v.start;
+		md_walk(m, v);
+		mine[0]++; mine[1] += m.adds;
+		if constexpr (Q) mine[2] += m.dropped;
+	}
+	block_sums_to(mine, stats);
+}
+__global__ __launch_bounds__(BWB_BLOCK) void k_pile(const uint8_t *reads, const uint16_t *lens, uint32_t stride, const uint4 *places, uint32_t n_reads, const uint8_t *lift_kind,
+                                                     const uint64_t *lift_off, const uint4 *lift_recs, const uint64_t *lstart, uint32_t n_seq, const uint4 *text, uint64_t n_fwd,
+                                                     const uint8_t *mapq, uint32_t mapq_stride, uint32_t min_mapq, const uint32_t *site_base, uint32_t *counts,
+                                                     unsigned long long *stats) {
+	pile_body<false>(reads, nullptr, lens, stride, places, n_reads, lift_kind, lift_off, lift_recs, lstart, n_seq, text, n_fwd, mapq, mapq_stride, min_mapq, 0u, 0u, site_base, counts, nullptr,
+	                 stats);
+}
 __global__ __launch_bounds__(BWB_BLOCK) void k_pile_q(const uint8_t *reads, const uint8_t *quals, const uint16_t *lens, uint32_t stride, const uint4 *places, uint32_t n_reads,
                                                        const uint8_t *lift_kind, const uint64_t *lift_off, const uint4 *lift_recs, const uint64_t *lstart, uint32_t n_seq,
                                                        const uint4 *text, uint64_t n_fwd, const uint8_t *mapq, uint32_t mapq_stride, uint32_t min_mapq, uint32_t min_baseq,
                                                        uint32_t err_cap, const uint32_t *site_base, uint32_t *counts, uint32_t *qsum, unsigned long long *stats) {
-	__shared__ unsigned long long s_sum[3][BWB_BLOCK / 64];
-	const uint32_t gstride = gridDim.x * BWB_BLOCK;
-	unsigned long long my_reads = 0, my_adds = 0, my_drop = 0;
-	for (uint32_t q = blockIdx.x * BWB_BLOCK + threadIdx.x; q < n_reads; q += gstride) {
-		const MdRead v = md_read(q, places, lift_kind, lift_off, lift_recs, lstart, n_seq);
-		const uint32_t len = lens[q];
-		if (!(v.mapped && len <= 255u && len <= stride)) continue;
-		const uint32_t mq = mapq ? mapq[(size_t)q * mapq_stride] : (places[(size_t)q * 3 + 1].x >> 16) & 0xFFu;
-		if (mq < min_mapq) continue;
-		uint64_t span = 0, on_read = 0;
-		if (v.lifted) for (uint32_t i = 0; i < v.n_ops; i++) { const uint32_t op = md_rec_op(v.rec, i); if ((op & 15u) == 0u || (op & 15u) == 2u) span += op >> 4; if ((op & 15u) != 2u) on_read += op >> 4; }
-		else for (uint32_t t = 0; t < v.alen; t++) { const uint32_t op = lift_op_at(v.runs, v.alen, v.reverse, t); span += op != 1u; on_read += op != 2u; }
-		if (span > MD_MAX_SPAN || v.start < 0 || (uint64_t)v.start > n_fwd || span > n_fwd - (uint64_t)v.start || on_read != len) continue;
-		PileWalkQ m;
-		m.text = text; m.cur = ~0ull; m.w = make_uint4(0u, 0u, 0u, 0u); m.mask = 0u;
-		m.site_base = site_base; m.counts = counts; m.qsum = qsum;
-		m.seq = reads + (size_t)q * stride; m.qual = quals + (size_t)q * stride; m.len = len; m.reverse = v.reverse;
-		m.min_baseq = min_baseq; m.err_cap = err_cap;
-		m.ri = 0; m.adds = 0; m.dropped = 0; m.tp = (uint64_t)v.start;
-		if (v.lifted) for (uint32_t i = 0; i < v.n_ops; i++) { const uint32_t op = md_rec_op(v.rec, i); m.step(op & 15u, op >> 4); }
-		else for (uint32_t t = 0; t < v.alen; t++) m.step(lift_op_at(v.runs, v.alen, v.reverse, t), 1u);
-		my_reads++; my_adds += m.adds; my_drop += m.dropped;
-	}
-	/* (every thread of the block gets here: the loop has no barrier inside) */
-#pragma unroll
-	for (int d = 32; d > 0; d >>= 1) { my_reads += __shfl_down(my_reads, d); my_adds += __shfl_down(my_adds, d); my_drop += __shfl_down(my_drop, d); }
-	if ((threadIdx.x & 63) == 0) { s_sum[0][threadIdx.x >> 6] = my_reads; s_sum[1][threadIdx.x >> 6] = my_adds; s_sum[2][threadIdx.x >> 6] = my_drop; }
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		unsigned long long r = 0, a = 0, x = 0;
-#pragma unroll
-		for (int k = 0; k < BWB_BLOCK / 64; k++) { r += s_sum[0][k]; a += s_sum[1][k]; x += s_sum[2][k]; }
-		if (r) atomicAdd(stats, r);
-		if (a) atomicAdd(stats + 1, a);
-		if (x) atomicAdd(stats + 2, x);
-	}
+	pile_body<true>(reads, quals, lens, stride, places, n_reads, lift_kind, lift_off, lift_recs, lstart, n_seq, text, n_fwd, mapq, mapq_stride, min_mapq, min_baseq, err_cap, site_base, counts,
+	                qsum, stats);
 }
 
 /* ---- ref / alt read support per indel bubble (`map -I`) --------------------------------------------------------------------------------
@@ -1233,8 +1212,8 @@ __global__ __launch_bounds__(BWB_BLOCK) void k_pile_q(const uint8_t *reads, cons
  * M), `trips` steps for every lane (2^trips > n_tab, a kernel argument: selects, no divergent while), and walks on while the entry's c is its
  * own and lo does not exceed its last M: the loop is bounded by the table alone.  An entry whose hi = C + w - 1 (from bub[]) lies behind the
  * last M is skipped.  The adds are relaxed, agent-scope atomics into counts[bubble * 4 + ref 0 | alt 1 | ref_gapped 2 | alt_gapped 3]; reads
- * counted, adds made and candidates examined are summed over the block - shuffles, then LDS - into stats[0..2] once per block.  Every index is
- * bounded: tab[] below n_tab, a locus record's bubble below the table's size (bwb_hip_set_loci checked bubble_of), an entry's bubble likewise. */
+ * counted, adds made and candidates examined go to stats[0..2] once per block (block_sums_to).  Every index is bounded: tab[] below n_tab, a
+ * locus record's bubble below the table's size (bwb_hip_set_loci checked bubble_of), an entry's bubble likewise. */
 struct IndelRead { int64_t pos1; bool reverse; uint32_t alen; uint4 runs; };
 /* 0 not covering, 1 clean, 2 gapped (lo < hi: a window is at least two positions wide) */
 __device__ __forceinline__ uint32_t indel_class(const IndelRead &v, int64_t lo, int64_t hi) {
@@ -1254,7 +1233,6 @@ __device__ __forceinline__ uint32_t indel_class(const IndelRead &v, int64_t lo, 
 __global__ __launch_bounds__(BWB_BLOCK) void k_indel(const uint4 *places, const uint4 *loci, uint32_t n_reads, const uint16_t *lens, const uint8_t *mapq, uint32_t mapq_stride,
                                                       uint32_t min_mapq, const uint64_t *bub, const uint8_t *elig, uint32_t anchor, const uint4 *tab, uint32_t n_tab, uint32_t trips,
                                                       uint32_t *counts, unsigned long long *stats) {
-	__shared__ unsigned long long s_sum[3][BWB_BLOCK / 64];
 	const uint32_t gstride = gridDim.x * BWB_BLOCK;
 	unsigned long long my_reads = 0, my_adds = 0, my_cand = 0;
 	for (uint32_t q = blockIdx.x * BWB_BLOCK + threadIdx.x; q < n_reads; q += gstride) {
@@ -1310,19 +1288,8 @@ __global__ __launch_bounds__(BWB_BLOCK) void k_indel(const uint4 *places, const 
 			if (cls) { __hip_atomic_fetch_add(counts + (size_t)k.w * 4 + (cls == 1u ? 0u : 2u), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); my_adds++; }
 		}
 	}
-	/* (every thread of the block gets here: the loop has no barrier inside) */
-#pragma unroll
-	for (int d = 32; d > 0; d >>= 1) { my_reads += __shfl_down(my_reads, d); my_adds += __shfl_down(my_adds, d); my_cand += __shfl_down(my_cand, d); }
-	if ((threadIdx.x & 63) == 0) { s_sum[0][threadIdx.x >> 6] = my_reads; s_sum[1][threadIdx.x >> 6] = my_adds; s_sum[2][threadIdx.x >> 6] = my_cand; }
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		unsigned long long r = 0, a = 0, k = 0;
-#pragma unroll
-		for (int i = 0; i < BWB_BLOCK / 64; i++) { r += s_sum[0][i]; a += s_sum[1][i]; k += s_sum[2][i]; }
-		if (r) atomicAdd(stats, r);
-		if (a) atomicAdd(stats + 1, a);
-		if (k) atomicAdd(stats + 2, k);
-	}
+	unsigned long long mine[3] = { my_reads, my_adds, my_cand };
+	block_sums_to(mine, stats); /* (every thread of the block gets here: the loop has no barrier inside) */
 }
 
 /* ---- genotype calls at IUPAC sites and indel bubbles (`map -G`) ---------------------------------------------------------------------------
@@ -1422,12 +1389,15 @@ __global__ __launch_bounds__(BWB_BLOCK) void k_geno_count(const uint4 *text, con
 		cnt[i] = at < 32u && (uint64_t)c.x + c.y + c.z + c.w >= min_depth ? 1u : 0u;
 	}
 }
-/* k_geno_emit: the same lanes; a called site makes its call and writes its 64-byte bwb_geno_site record at out[off[i]] (off[i] < off[n] <= n: the
- * output holds n records) as four 16-byte vector stores back to back.  The called lanes of a wave write neighbouring records, so the wave's four
- * stores fill the same run of whole 64-byte lines, which L2 combines: no transpose through LDS (1.05 M sites, 787 k records: 0.09 ms for the
- * count pass, the scan and this kernel together). */
-__global__ __launch_bounds__(BWB_BLOCK) void k_geno_emit(const uint4 *text, const uint32_t *site_base, uint32_t n_words, const uint4 *counts, uint64_t first, uint32_t n, uint64_t min_depth,
-                                                          uint32_t err, const uint32_t *cnt, const uint32_t *word, const uint64_t *off, uint4 *out) {
+/* k_geno_emit, k_geno_emit_q: the same lanes; a called site makes its call and writes its 64-byte bwb_geno_site record at out[off[i]] (off[i] <
+ * off[n] <= n: the output holds n records) as four 16-byte vector stores back to back.  The called lanes of a wave write neighbouring records, so
+ * the wave's stores fill the same run of whole 64-byte lines, which L2 combines: no transpose through LDS (1.05 M sites, 787 k records: 0.09 ms
+ * for the count pass, the scan and this kernel together).
+ * Q, k_geno_emit_q (`map -Y`): behind the same k_geno_count and scan, with the weighted rule - the site's four qsum words in one 16-byte load
+ * beside its counters - and the 80-byte bwb_geno_site_q record (the output holds n records of 80 bytes): the 64 bytes of bwb_geno_site, then the
+ * four qsum words, as five 16-byte stores. */
+template <bool Q> __device__ __forceinline__ void geno_emit_body(const uint4 *text, const uint32_t *site_base, uint32_t n_words, const uint4 *counts, const uint4 *qsum, uint64_t first,
+                                                                 uint32_t n, uint32_t err, const uint32_t *cnt, const uint32_t *word, const uint64_t *off, uint4 *out) {
 	const uint32_t gstride = gridDim.x * BWB_BLOCK;
 	for (uint32_t i = blockIdx.x * BWB_BLOCK + threadIdx.x; i < n; i += gstride) {
 		if (!cnt[i]) continue;
@@ -1439,63 +1409,41 @@ __global__ __launch_bounds__(BWB_BLOCK) void k_geno_emit(const uint4 *text, cons
 		const uint32_t at = geno_char(text[w], r < 32u ? (uint32_t)r : 32u, &code) & 31u; /* (k_geno_count found it below 32) */
 		const uint32_t mem = (uint32_t)(GENO_MEMBERS >> (4u * code)) & 15u;
 		const uint4 c = counts[s];
-		const uint64_t depth = (uint64_t)c.x + c.y + c.z + c.w;
-		/* the members in column order: the counters of the set bits of mem, lowest first (two or three of them) */
-		uint64_t a[3] = { 0, 0, 0 };
-		uint32_t k = 0;
-#pragma unroll
-		for (uint32_t col = 0; col < 4; col++) {
-			const uint32_t v = col == 0u ? c.x : col == 1u ? c.y : col == 2u ? c.z : c.w;
-			const bool in = (mem >> col) & 1u;
-			a[0] = in && k == 0u ? v : a[0]; a[1] = in && k == 1u ? v : a[1]; a[2] = in && k == 2u ? v : a[2];
-			k += in ? 1u : 0u;
-		}
-		const GenoCall g = geno_rule(a[0], a[1], a[2], k, depth, err);
-		const uint64_t pos = (uint64_t)w * 32u + at;
-		uint4 *dst = out + o * 4u;
-		dst[0] = make_uint4((uint32_t)pos, (uint32_t)(pos >> 32), (uint32_t)s, (uint32_t)(s >> 32));
-		dst[1] = c;
-		dst[2] = make_uint4(code | (k == 3u ? 6u : 3u) << 8 | g.gt << 16 | g.gq << 24, 0u, g.pl[0], g.pl[1]);
-		dst[3] = make_uint4(g.pl[2], g.pl[3], g.pl[4], g.pl[5]);
-	}
-}
-/* k_geno_emit_q (`map -Y`): k_geno_emit behind the same k_geno_count and scan, with the weighted rule - the site's four qsum words in one 16-byte
- * load beside its counters - and the 80-byte bwb_geno_site_q record at out[off[i]] (off[i] < n: the output holds n records of 80 bytes): the 64
- * bytes of bwb_geno_site, then the four qsum words, as five 16-byte stores. */
-__global__ __launch_bounds__(BWB_BLOCK) void k_geno_emit_q(const uint4 *text, const uint32_t *site_base, uint32_t n_words, const uint4 *counts, const uint4 *qsum, uint64_t first, uint32_t n,
-                                                            const uint32_t *cnt, const uint32_t *word, const uint64_t *off, uint4 *out) {
-	const uint32_t gstride = gridDim.x * BWB_BLOCK;
-	for (uint32_t i = blockIdx.x * BWB_BLOCK + threadIdx.x; i < n; i += gstride) {
-		if (!cnt[i]) continue;
-		const uint64_t s = first + i, o = off[i];
-		const uint32_t w = word[i];
-		if (w >= n_words || o >= (uint64_t)n) continue; /* (k_geno_count wrote both: never) */
-		uint32_t code;
-		const uint64_t r = s - (uint64_t)site_base[w];
-		const uint32_t at = geno_char(text[w], r < 32u ? (uint32_t)r : 32u, &code) & 31u; /* (k_geno_count found it below 32) */
-		const uint32_t mem = (uint32_t)(GENO_MEMBERS >> (4u * code)) & 15u;
-		const uint4 c = counts[s], qs = qsum[s];
-		const uint64_t S = (uint64_t)qs.x + qs.y + qs.z + qs.w;
+		uint4 qs = make_uint4(0u, 0u, 0u, 0u);
+		if constexpr (Q) qs = qsum[s];
+		/* the members in column order: the counters (with Q: and the quality sums) of the set bits of mem, lowest first (two or three of them) */
 		uint64_t a[3] = { 0, 0, 0 }, e[3] = { 0, 0, 0 };
 		uint32_t k = 0;
 #pragma unroll
 		for (uint32_t col = 0; col < 4; col++) {
 			const uint32_t v = col == 0u ? c.x : col == 1u ? c.y : col == 2u ? c.z : c.w;
-			const uint32_t u = col == 0u ? qs.x : col == 1u ? qs.y : col == 2u ? qs.z : qs.w;
 			const bool in = (mem >> col) & 1u;
 			a[0] = in && k == 0u ? v : a[0]; a[1] = in && k == 1u ? v : a[1]; a[2] = in && k == 2u ? v : a[2];
-			e[0] = in && k == 0u ? u : e[0]; e[1] = in && k == 1u ? u : e[1]; e[2] = in && k == 2u ? u : e[2];
+			if constexpr (Q) {
+				const uint32_t u = col == 0u ? qs.x : col == 1u ? qs.y : col == 2u ? qs.z : qs.w;
+				e[0] = in && k == 0u ? u : e[0]; e[1] = in && k == 1u ? u : e[1]; e[2] = in && k == 2u ? u : e[2];
+			}
 			k += in ? 1u : 0u;
 		}
-		const GenoCall g = geno_rule_q(a[0], a[1], a[2], e[0], e[1], e[2], k, S);
+		GenoCall g;
+		if constexpr (Q) g = geno_rule_q(a[0], a[1], a[2], e[0], e[1], e[2], k, (uint64_t)qs.x + qs.y + qs.z + qs.w);
+		else g = geno_rule(a[0], a[1], a[2], k, (uint64_t)c.x + c.y + c.z + c.w, err);
 		const uint64_t pos = (uint64_t)w * 32u + at;
-		uint4 *dst = out + o * 5u;
+		uint4 *dst = out + o * (Q ? 5u : 4u);
 		dst[0] = make_uint4((uint32_t)pos, (uint32_t)(pos >> 32), (uint32_t)s, (uint32_t)(s >> 32));
 		dst[1] = c;
 		dst[2] = make_uint4(code | (k == 3u ? 6u : 3u) << 8 | g.gt << 16 | g.gq << 24, 0u, g.pl[0], g.pl[1]);
 		dst[3] = make_uint4(g.pl[2], g.pl[3], g.pl[4], g.pl[5]);
-		dst[4] = qs;
+		if constexpr (Q) dst[4] = qs;
 	}
+}
+__global__ __launch_bounds__(BWB_BLOCK) void k_geno_emit(const uint4 *text, const uint32_t *site_base, uint32_t n_words, const uint4 *counts, uint64_t first, uint32_t n, uint64_t min_depth,
+                                                          uint32_t err, const uint32_t *cnt, const uint32_t *word, const uint64_t *off, uint4 *out) {
+	geno_emit_body<false>(text, site_base, n_words, counts, nullptr, first, n, err, cnt, word, off, out);
+}
+__global__ __launch_bounds__(BWB_BLOCK) void k_geno_emit_q(const uint4 *text, const uint32_t *site_base, uint32_t n_words, const uint4 *counts, const uint4 *qsum, uint64_t first, uint32_t n,
+                                                            const uint32_t *cnt, const uint32_t *word, const uint64_t *off, uint4 *out) {
+	geno_emit_body<true>(text, site_base, n_words, counts, qsum, first, n, 0u, cnt, word, off, out);
 }
 /* k_geno_bubbles: one lane per bubble of [first, first + n) (first + n <= n_bub, checked by the caller), grid-strided.  off NULL, the count pass:
  * cnt[i] = 1 when the bubble is eligible (elig[], one byte per bubble from bwb_hip_indel_begin) and depth = ref + alt + ref_gapped + alt_gapped >=

@@ -223,6 +223,92 @@ def test_pile_records_strides_over_twice_the_lanes_of_the_grid(ctx, text, inject
     assert np.array_equal(counts_of(ctx), want * np.uint32(times)) and ctx.pile_stats()[:2] == (reads * times, adds * times)
 
 
+def test_md_pile_and_pile_q_walk_the_same_reads_at_the_edges_of_the_gate(built, golden, text, ctx, injected):
+    """k_md_count, k_pile and k_pile_q share one gate (md_gate): the reads md_records calls MD_OK are the reads pile_records and pile_records_q
+    count.  The injected reads of 1..255 bases and the lifted ones, plus records on every edge of the gate, each on both strands: a span of
+    MD_MAX_SPAN and one more, the last text character reached and passed by one, ops that consume one base less and one more than the read has,
+    lift headers with 0 and 21 ops, a record number that is the table's size, a lift record one word short of its ops, an unmapped read.  All
+    of the refused ones are refused before a text or read byte is fetched: the header's fields and the ops' sums alone decide."""
+    import pileq_model
+    from test_gpu_md import read_for
+    rows, seqs, lens, places, kinds, lrecs = injected
+    keep = [r for r, ((start, cig, seq, lops), _) in enumerate(rows) if lops is not None or (start == 600 and cig == f"{len(seq)}M")]
+    assert {1, 255} <= set(lens[keep].tolist()) and (kinds[keep] == bw.LIFT_LIFTED).any() and (kinds[keep] == 0).any()
+    n, h, rng, span = len(text), ctx.starts[1], np.random.default_rng(9), bw.MD_MAX_SPAN
+    m50 = [(50, "M")]
+    edges = [("unmapped", (300, "50M", read_for(text, 300, m50, rng), None)),
+             ("span 4096", (100, None, "ACGT" * 5, [(10, M), (span - 20, D), (10, M)])),
+             ("span 4097", (100, None, "ACGT" * 5, [(10, M), (span - 19, D), (10, M)])),
+             ("ends at the text's end", (n - 50, "50M", read_for(text, n - 50, m50, rng), None)),
+             ("ends one past it", (n - 49, "50M", "ACGT" * 12 + "AC", None)),
+             ("lifted, ends at the text's end", (n - 40, None, read_for(text, n - 40, [(10, "M"), (20, "D"), (10, "M")], rng), [(10, M), (20, D), (10, M)])),
+             ("lifted, ends one past it", (n - 39, None, "ACGT" * 5, [(10, M), (20, D), (10, M)])),
+             ("ops one base short", (300, "49M", "ACGT" * 12 + "AC", None)),
+             ("ops one base over", (300, "51M", "ACGT" * 12 + "AC", None)),
+             ("lifted, ops one base short", (300, None, "ACGT" * 12 + "AC", [(49, M)])),
+             ("lifted, ops one base over", (300, None, "ACGT" * 12 + "AC", [(51, M)])),
+             ("header with no op", (300, None, "ACGT" * 5, [])),
+             ("header with 21 ops", (300, None, read_for(text, 300, [(42, "M")], rng), [(2, M)] * 21)),
+             ("record number n_seq", (300, None, read_for(text, 300, m50, rng), [(50, M)])),
+             ("lifted, as it should be", (h + 300, None, read_for(text, h + 300, m50, rng), [(20, M), (30, M)])),
+             ("one word short", (300, None, read_for(text, 300, m50, rng), [(10, M)] * 5))]
+    names = [name for name, _ in edges for _ in (False, True)]
+    _, e_seqs, e_lens, e_places, e_kinds, e_lrecs = records(ctx, text, [c for _, c in edges])
+    e_places["flags"] |= bw.PLACE_MAPPED  # (records() leaves a few unmapped by their row number: here the one that says so is)
+    seqs, lens, places = np.concatenate([seqs[keep], e_seqs]), np.concatenate([lens[keep], e_lens]), np.concatenate([places[keep], e_places])
+    kinds, lrecs = np.concatenate([kinds[keep], e_kinds]), [lrecs[r] for r in keep] + e_lrecs
+    at = {name: [len(keep) + i for i, nm in enumerate(names) if nm == name] for name in dict(edges)}
+    assert len(lens) < 100 and all(len(v) == 2 for v in at.values())
+    for r in at["record number n_seq"]:
+        lrecs[r] = (lrecs[r][0], 2, lrecs[r][2])
+    for r in at["unmapped"]:
+        places["flags"][r] = 0
+    k_arr, off, words = md_model.pack_lift(kinds, lrecs)
+    for r in sorted(at["one word short"], reverse=True):  # (three words each: the header and five ops; the last is taken away)
+        assert int(off[r + 1] - off[r]) == 3
+        words = np.delete(words, int(off[r + 1]) - 1, axis=0)
+        off[r + 1:] -= 1
+    assert int(off[-1]) == len(words)
+    # what the model is told: a lift record that does not fit its own words, has no or too many ops or names no record of the table is walked by nobody
+    nobody = at["header with 21 ops"] + at["record number n_seq"] + at["one word short"] + at["header with no op"]
+    told = places.copy()
+    told["flags"][nobody] = 0
+    want = md_model.expected_records(text, seqs, lens, told, kinds, lrecs, ctx.starts)
+    c = bw.Context(os.path.join(golden, "toy.fa.bwt"))
+    try:
+        c.set_text(pile_model.codes(text))
+        n_sites = c.pile_begin()
+        c.pileq_begin()
+        c.set_loci(np.array([0, h], dtype=np.uint64), np.array([h - 1, n - 1], dtype=np.uint64), np.array([-1, -1], dtype=np.int32), np.zeros(0, dtype=bw.BUBBLE_DTYPE))
+        got = c.md_records(seqs, lens, places, k_arr, off, words)
+        assert md_model.compare_records(got, want) is None, md_model.compare_records(got, want)
+        kind = got[0]["kind"]
+        ok = np.flatnonzero(kind == bw.MD_OK)
+        for name, rs in at.items():
+            expect = bw.MD_TOO_LONG if name == "span 4097" else bw.MD_OK if name in ("ends at the text's end", "lifted, ends at the text's end", "lifted, as it should be") else bw.MD_NONE
+            assert kind[rs].tolist() == [expect, expect], (name, kind[rs])
+        assert len(ok) > 20 and len(lens) - len(ok) >= 30
+        # the model over exactly the reads of kind MD_OK: it counts every one of them, and the kernels count those and no other
+        sub = (seqs[ok], lens[ok], places[ok], kinds[ok], [lrecs[r] for r in ok], ctx.starts)
+        counts, reads, adds = pile_model.expected_counts(text, *sub)
+        assert reads == len(ok) and adds > 100
+        c.pile_records(seqs, lens, places, k_arr, off, words, min_mapq=0)
+        assert c.pile_stats()[:2] == (len(ok), adds) and np.array_equal(c.pile_counts(0, n_sites), counts)
+        quals = np.full(seqs.shape, ord("I"), dtype=np.uint8)
+        counts_q, _, reads_q, adds_q, dropped = pileq_model.expected_q(text, seqs[ok], quals[ok], *sub[1:])
+        assert (reads_q, adds_q, dropped) == (len(ok), adds, 0) and np.array_equal(counts_q, counts)
+        c.pile_reset()
+        c.pile_records_q(seqs, quals, lens, places, k_arr, off, words, min_mapq=0)
+        assert c.pileq_stats()[:3] == (len(ok), adds, 0) and np.array_equal(c.pile_counts(0, n_sites), counts)
+        assert c.pile_stats()[:2] == (len(ok), adds)  # (the plain form's figures: its own last launch)
+        # the context is usable afterwards
+        c.pile_reset()
+        c.pile_records(seqs[ok], lens[ok], places[ok], *md_model.pack_lift(kinds[ok], sub[4]))
+        assert c.pile_stats()[:2] == (len(ok), adds) and np.array_equal(c.pile_counts(0, n_sites), counts)
+    finally:
+        c.close()
+
+
 @pytest.mark.parametrize("lib", ["product", "testlib"])
 def test_pile_and_slot_pile_equal_the_model_fed_the_oracles_hits(built, pad_text, lib):
     """a text uploaded in two chunks by the test build, its site index at every position; the pad_bub reads in one batch - plain, lifted, joined -

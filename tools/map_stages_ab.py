@@ -2,10 +2,11 @@
 """`bwbble map` with every result-stream stage (-X 5 -B -J -R -D -A -I -G) on the 3.3 M-character fixture of tests/mid_model.py, this tree's build
 against another build's - the parent commit's -, alternating, two runs each: the log lines of the stages with their counts, the kernel times each
 line reports, and the bytes of the SAM and the three tables.  With `trace`: one more run per build under rocprofv3 --kernel-trace --stats, and the
-kernel call counts by name compared.  The fixture (genome, index, .ref, bubble table, reads: the CPU half of mid_model.build) is made in <dir>
+kernel call counts by name compared.  With `q`: -b 20 -Y on the command line too (the fixture's reads carry quality lines), and the log line of
+k_pile_q among the stage lines.  The fixture (genome, index, .ref, bubble table, reads: the CPU half of mid_model.build) is made in <dir>
 unless it is there already, so it can be prepared on a machine without a GPU.
 usage: tools/map_stages_ab.py <dir> prepare
-       tools/map_stages_ab.py <dir> <the other build's bwbble_amd/bin> [trace]      (profiles/stage_fold.txt is one run's output)"""
+       tools/map_stages_ab.py <dir> <the other build's bwbble_amd/bin> [q] [trace]  (profiles/stage_fold.txt, profiles/pile_fold.txt: one run's output each)"""
 import csv
 import glob
 import hashlib
@@ -21,6 +22,7 @@ import mid_model
 
 STAGES = ("placements on the GPU", "other placements on the GPU", "placements joined by locus", "placements lifted", "NM and MD", "allele counts at", "read support per indel bubble on",
           "genotype calls on the GPU")
+STAGE_Q = "base qualities in the counts on the GPU (k_pile_q)"
 TIME = re.compile(r"\b(kernels?|k_pile|k_indel) (\d+\.\d+) ms")
 
 
@@ -54,6 +56,11 @@ def main():
     out = {e: os.path.join(d, "out." + e) for e in ("sam", "a.tsv", "i.tsv", "g.tsv")}
     args = ["map"] + mid_model.ALIGN + ["-X", "5", "-B", data, "-J", "-R", "-D", "-A", out["a.tsv"], "-a", str(mid_model.MIN_MAPQ), "-I", out["i.tsv"], "-w", str(mid_model.ANCHOR),
                                         "-G", out["g.tsv"], fa, fq, out["sam"]]
+    opts = sys.argv[3:]
+    stages = STAGES
+    if "q" in opts:
+        args[1:1] = ["-b", "20", "-Y"]
+        stages += (STAGE_Q,)
     builds = {"parent": os.path.join(sys.argv[2], "bwbble"), "this": bw.HOST_BIN}
     counts, files, times = {}, {}, {}
     for run in range(2):
@@ -62,8 +69,8 @@ def main():
             if r.returncode != 0:
                 print(name, "FAILED", r.returncode, r.stdout[-2000:])
                 return 1
-            lines = [ln for ln in r.stdout.split("\n") if ln.startswith(STAGES)]
-            print(f"--- {name}, run {run + 1}: {len(lines)} of {len(STAGES)} stage lines")
+            lines = [ln for ln in r.stdout.split("\n") if ln.startswith(stages)]
+            print(f"--- {name}, run {run + 1}: {len(lines)} of {len(stages)} stage lines")
             print("\n".join(lines))
             counts.setdefault(name, set()).add("\n".join(re.sub(r"\d+\.\d+", "#", ln) for ln in lines))  # (every figure that is not a time or a rate is an integer)
             files.setdefault(name, set()).add(" ".join(f"{e} {os.path.getsize(p)} bytes {digest(p)}" for e, p in out.items()))
@@ -75,7 +82,7 @@ def main():
         lo, hi = min(t["parent"]), max(t["parent"])
         print(f"{stage:24s} kernel ms  parent {t['parent'][0]:.3f} {t['parent'][1]:.3f}  this {t['this'][0]:.3f} {t['this'][1]:.3f}  "
               f"{'within' if all(lo <= v <= hi for v in t['this']) else 'OUTSIDE'} the parent's spread")
-    if sys.argv[3:] == ["trace"]:
+    if "trace" in opts:
         calls = {}
         for name, exe in builds.items():
             td = os.path.join(d, "trace_" + name)
